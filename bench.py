@@ -14,7 +14,9 @@ process for 512 length-128 backbones per GPU (1000 replays of the per-timestep
 hipGraph), state + history resident in HBM, Philox noise generated in the update
 kernel, then (N > 1) the single RCCL gather of the final angles to rank 0.
 Inputs (x_T, lengths, weights, tables) are resident in HBM before the timed
-region starts.  Nothing is skipped or cached between passes.
+region starts.  Nothing is skipped or cached between passes.  --dump-outputs DIR writes what the last timed
+pass returned (final angles, a seeded sample of the history) as DIR/*.npy: the inputs depend on the arguments
+alone, so two builds of the project compare output by output.
 
 The JSON line also carries
   roofline      the dominant kernel (the fused q|k|v projection + attention kernel, seq_attn16.hip; the q|k|v GEMM where that does not run):
@@ -225,6 +227,32 @@ def measure_traffic(kernel_substr, args):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_BYTES = 60 << 20  # under 64 MB in either unit, .npy headers included
+
+
+def dump_outputs(d, final, hist):
+    """--dump-outputs: what the last timed pass handed back, as float32 .npy files of at most DUMP_BYTES in all.
+    final_angles [B*N, L, 6]: the final states (gathered over the N ranks); history_sample [T, k, L, 6]: rank 0's history at every
+    timestep for k of its B sequences, a fixed seeded choice (all of them when they fit).  The inputs depend on the arguments only,
+    so two builds run with the same arguments compare file by file."""
+    os.makedirs(d, exist_ok=True)
+    room = DUMP_BYTES
+    for name, x, dim in (("final_angles", final, 0), ("history_sample", hist, 1)):
+        if x is None:
+            continue
+        n = x.shape[dim]
+        k = min(n, room // (x.numel() // n * 4))
+        if k == 0:
+            continue
+        if k < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+            x = x.index_select(dim, torch.from_numpy(idx).to(x.device))
+        a = x.float().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), a)
+        room -= a.nbytes
+        print(f"bench.py: {name} {list(a.shape)} -> {d}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -248,6 +276,9 @@ def main():
     ap.add_argument("--precision", default=None, choices=["f32", "f16x3"], help="GEMM arithmetic (default: library default)")
     ap.add_argument("--no-exact-f32", action="store_true",
                     help="skip the extra single pass in exact-fp32 MFMA mode that is reported next to the headline (N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB "
+                         "in all): final_angles, and history_sample (a fixed, seeded choice of sequences of the history)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -307,8 +338,8 @@ def main():
                                             full_history=not args.no_history)
             final = out[-1] if not args.no_history else out
             if world > 1:
-                return fdist.gather_final(final.contiguous(), counts)
-            return final
+                final = fdist.gather_final(final.contiguous(), counts)
+            return final, (None if args.no_history else out)
 
     def sync_all():
         torch.cuda.synchronize(dev)
@@ -326,9 +357,9 @@ def main():
     if sampler:
         sampler.start()
     t0 = time.perf_counter()
-    last = None
+    last = last_hist = None
     for k in range(args.steps):
-        last = one_pass(k)
+        last, last_hist = one_pass(k)
     sync_all()
     elapsed = time.perf_counter() - t0
     telemetry = sampler.stop() if sampler else None
@@ -340,6 +371,8 @@ def main():
     if rank == 0:
         assert last is not None and tuple(last.shape) == (B * world, L, 6)
         assert torch.isfinite(last).all() and float(last.abs().max()) <= 3.1415927 + 1e-5
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, last_hist)
 
     # per-kernel stats measured inside the timed region
     kernels = {}

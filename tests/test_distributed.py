@@ -103,14 +103,19 @@ def _stub_fd_sample(h, x0, lens, t_start, zs, seed, seq_offset, out, full_histor
 def _run_sample(mode, gather="rank0", sweep=(5, 14), n=3, final_only=True, offset=None):
     import numpy as np
     from foldingdiff_amd import datasets, sampling
+    # also called in the pytest process itself: the stub must not outlive the call (the GPU tests run later in the same process)
+    saved = sampling._run_fd_sample, sampling.NOISE_MODE
     sampling._run_fd_sample = _stub_fd_sample
     sampling.NOISE_MODE = mode
-    ds = datasets.NoisedAnglesDataset(
-        datasets.AnglesEmptyDataset("canonical-full-angles", pad=32, mean_offset=None if offset is None else np.asarray(offset)),
-        timesteps=4, beta_schedule="cosine")
-    torch.manual_seed(11)
-    model = _StubModel()
-    res = sampling.sample(model, ds, n=n, sweep_lengths=sweep, batch_size=16, final_only=final_only, gather=gather)
+    try:
+        ds = datasets.NoisedAnglesDataset(
+            datasets.AnglesEmptyDataset("canonical-full-angles", pad=32, mean_offset=None if offset is None else np.asarray(offset)),
+            timesteps=4, beta_schedule="cosine")
+        torch.manual_seed(11)
+        model = _StubModel()
+        res = sampling.sample(model, ds, n=n, sweep_lengths=sweep, batch_size=16, final_only=final_only, gather=gather)
+    finally:
+        sampling._run_fd_sample, sampling.NOISE_MODE = saved
     return res, model.opts
 
 
