@@ -18,13 +18,21 @@ region starts.  Nothing is skipped or cached between passes.  --dump-outputs DIR
 pass returned (final angles, a seeded sample of the history) as DIR/*.npy: the inputs depend on the arguments
 alone, so two builds of the project compare output by output.
 
-The JSON line also carries
+A plain run does only what the headline needs: set up, warm up, time the steps, dump (if asked) and print the JSON line.  Its
+line also carries what the timed region measured on the way: per-kernel launch times, the roofline and whole-step figures built
+from them, the shader clock and socket power.  Everything that takes runs of its own is behind --full (N = 1 only; each leg has a
+--no-* switch there): roofline.traffic (two rocprofv3 child passes), exact_f32_mode, extras.* and cpu_baseline.
+
+The JSON line carries
   roofline      the dominant kernel (the fused q|k|v projection + attention kernel, seq_attn16.hip; the q|k|v GEMM where that does not run):
                 algorithmic FLOPs per launch /
                 average launch duration measured live with hipEvents inside the timed
                 region (every 100th timestep is launched eagerly with an event pair per
                 kernel instead of replaying the graph), against the dense MFMA peak of the instruction
                 actually used (fp16: 2500 TFLOP/s in the default f16x3 mode, fp32: 157.3 in --precision f32).
+                --full adds .traffic, its HBM bytes per launch from rocprofv3 counters (two child passes of this script).
+and, with --full only,
+  exact_f32_mode  one pass of the same workload with every contraction on v_mfma_f32_32x32x2_f32.
   cpu_baseline  the reference CPU path (oracle restatement, "port") timed on this box's
                 host cores over a bounded sample of the same workload.
   extras.c5     one pass of BASELINE config C5 (L = 512, batch 128, max_position_embeddings = 512).
@@ -202,8 +210,7 @@ def measure_traffic(kernel_substr, args):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [prof, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--timesteps", "3", "--profile-every", "0", "--no-cpu-baseline",
-                   "--no-exact-f32", "--no-c5-extra", "--no-user-paths", "--no-traffic"]
+                   os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--timesteps", "3", "--profile-every", "0"]  # (a plain run)
             if args.precision:
                 cmd += ["--precision", args.precision]
             env = dict(os.environ, FDMI_NO_GRAPH="1", TMPDIR="/tmp")
@@ -263,19 +270,22 @@ def main():
                          "max_position_embeddings 512 (long-chain stress)")
     ap.add_argument("--batch", type=int, default=None, help="sequences per GPU (default: the configuration's)")
     ap.add_argument("--length", type=int, default=None)
-    ap.add_argument("--no-c5-extra", action="store_true", help="skip the extra BASELINE C5 pass reported in extras (N=1, c2 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs that take runs of their own (N=1): roofline.traffic, exact_f32_mode, "
+                         "extras (C5, C3, host entry, small batch, NeRF) and cpu_baseline; the --no-* switches skip single legs")
+    ap.add_argument("--no-c5-extra", action="store_true", help="skip the extra BASELINE C5 pass reported in extras (--full, N=1, c2 only)")
     ap.add_argument("--no-user-paths", action="store_true",
-                    help="skip extras.c3 (sampling.sample on the manuscript sweep, both noise modes) and extras.host_entry (N=1, c2 only)")
+                    help="skip extras.c3 (sampling.sample on the manuscript sweep, both noise modes) and extras.host_entry (--full, N=1, c2 only)")
     ap.add_argument("--timesteps", type=int, default=1000)
     ap.add_argument("--profile-every", type=int, default=100)
     ap.add_argument("--no-history", action="store_true", help="do not keep the [T,B,L,F] history in HBM")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip cpu_baseline (--full, N=1)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic (N=1 only)")
+                    help="skip the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic (--full, N=1 only)")
     ap.add_argument("--fuse-ln", type=int, default=-1, help="-1 auto (fused with f16x3), 0 off, 1 on")
     ap.add_argument("--precision", default=None, choices=["f32", "f16x3"], help="GEMM arithmetic (default: library default)")
     ap.add_argument("--no-exact-f32", action="store_true",
-                    help="skip the extra single pass in exact-fp32 MFMA mode that is reported next to the headline (N=1 only)")
+                    help="skip the extra single pass in exact-fp32 MFMA mode that is reported next to the headline (--full, N=1 only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB "
                          "in all): final_angles, and history_sample (a fixed, seeded choice of sequences of the history)")
@@ -423,8 +433,8 @@ def main():
     sub = "gemm_img_kernel<5" if model.precision == "f16x3" else "gemm_f32_kernel"
     if dom_name in KDESC:
         sub, dom_kernel = KDESC[dom_name]
-    traffic, traffic_note = None, "not measured (--no-traffic, N > 1 or another shape)"
-    if world == 1 and not args.no_traffic and (B, L) == (512, 128) and dom:
+    traffic, traffic_note = None, "not measured (measured by --full at N=1, C2, without --no-traffic)"
+    if args.full and world == 1 and not args.no_traffic and (B, L) == (512, 128) and dom:
         traffic, traffic_note = measure_traffic(sub, args)
     roofline = None
     if dom:
@@ -487,7 +497,7 @@ def main():
                             for k in ("embed_ln_time", "head_update_wrap") if k in kernels},
         "dist": {"backend": dist.get_backend() if world > 1 else None, "world_size": dist.get_world_size() if world > 1 else 1},
     }
-    if world == 1 and model.precision != "f32" and not args.no_exact_f32 and L <= 128:
+    if args.full and world == 1 and model.precision != "f32" and not args.no_exact_f32 and L <= 128:
         # the same workload with every contraction on v_mfma_f32_32x32x2_f32 (bitwise-fp32 products), one pass
         model.set_precision("f32")
         model.prepare(betas)
@@ -501,7 +511,7 @@ def main():
         result["exact_f32_mode"] = {"value": B / dt, "unit": "backbones/s", "ms_per_step": dt * 1e3,
                                     "frac_of_f32_mfma_peak": (B / dt) * flop_per_backbone / 1e12 / PEAK_F32_MFMA_TFLOPS,
                                     "note": "FD_PREC_F32: all GEMM/attention products on v_mfma_f32_32x32x2_f32, 1 timed pass"}
-    if world == 1 and args.config == "c2" and not args.no_c5_extra:
+    if args.full and world == 1 and args.config == "c2" and not args.no_c5_extra:
         # BASELINE config C5 (L = 512 long-chain stress, batch 128, max_position_embeddings = 512): one timed pass
         m5 = modelling.BertForDiffusionBase(modelling.BertConfig(**dict(RELEASED, max_position_embeddings=512)), [True] * 6).to(dev)
         m5.set_precision(pinfo_key)
@@ -521,7 +531,7 @@ def main():
                                    "ms_per_timestep": dt5 / T * 1e3, "passes": 1,
                                    "algorithmic_tflops": 128 / dt5 * flops_per_token(512) * 512 * T / 1e12}}
         del m5
-    if world == 1 and args.config == "c2" and not args.no_user_paths and (B, L) == (512, 128):
+    if args.full and world == 1 and args.config == "c2" and not args.no_user_paths and (B, L) == (512, 128):
         # what users call.  (a) BASELINE C3, the reference's own published setting (README.md:100-103, bin/sample.py defaults):
         # sampling.sample(n=10, sweep_lengths=(50, 128), batch_size=512) -- 780 backbones in two chunks, packed rows --
         # with on-device Philox noise and in the DEFAULT mode (the reference's torch.randn order, streamed from the host).
@@ -614,7 +624,7 @@ def main():
         assert len(coords) == 780 and all(np.isfinite(c).all() for c in coords)
         extras["nerf"] = {"metric": "ms for the 780 backbones of C3 (lengths 50..127), angles -> N/CA/C coordinates, host arrays in / out (fd_nerf)",
                           "ms": round(dtn * 1e3, 3), "backbones_per_s": round(780 / dtn, 1)}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(B, L, T, shape)
     print(json.dumps(result), flush=True)
     if world > 1:

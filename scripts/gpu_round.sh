@@ -16,13 +16,13 @@ timeout 1200 python -m pytest tests -q -m gpu --durations=8 -p no:cacheprovider 
 echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 | tee $OUT/smoke.log
 echo "== bench"
-timeout 900 python bench.py --steps ${BENCH_STEPS:-1} --warmup 1 ${BENCH_ARGS:-} 2>&1 | tail -3 | tee $OUT/bench.log
+timeout 900 python bench.py --full --steps ${BENCH_STEPS:-1} --warmup 1 ${BENCH_ARGS:-} 2>&1 | tail -3 | tee $OUT/bench.log
 smi after-bench | tee -a $OUT/smi.log
 if [ -n "${BENCH2_ARGS:-}" ]; then
-  env ${BENCH2_ENV:-X=1} timeout 600 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 $BENCH2_ARGS 2>&1 | tail -1 | tee $OUT/bench2.log
+  env ${BENCH2_ENV:-X=1} timeout 600 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 $BENCH2_ARGS 2>&1 | tail -1 | tee $OUT/bench2.log
 fi
 if [ -n "${BENCH3_ARGS:-}" ]; then
-  env ${BENCH3_ENV:-X=1} timeout 600 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 $BENCH3_ARGS 2>&1 | tail -1 | tee $OUT/bench3.log
+  env ${BENCH3_ENV:-X=1} timeout 600 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 $BENCH3_ARGS 2>&1 | tail -1 | tee $OUT/bench3.log
 fi
 if [ "${WITH_PROF:-1}" = "1" ]; then
   echo "== rocprofv3 kernel-trace --stats (same command as the bench, T=${PROF_T:-200})"

@@ -55,3 +55,23 @@ def test_bench_dumps_the_last_timed_pass(gpu, tmp_path):
     assert np.isfinite(hist).all() and np.array_equal(hist[-1], fin)
     for f, v in dumps[0].items():
         assert np.array_equal(v, dumps[1][f]), f
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_extra_legs_to_full(gpu):
+    """At the headline's shape (C2, one GPU) a plain run prints the headline and what its timed region measured, and nothing that
+    takes runs of its own; --full adds exact_f32_mode and the extras.  (T = 200: the small-batch leg starts at t = 199.)"""
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--timesteps", "200"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-traffic"])):
+        r = subprocess.run(cmd + extra, cwd=REPO, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["metric"] == "backbones/sec (L=128, T=200, bs=512)" and line["unit"] == "backbones/s" and line["higher_is_better"]
+        assert line["steps"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["kernels"] and line["roofline"]["achieved"] > 0 and line["roofline"]["traffic"] is None
+    assert not {"exact_f32_mode", "extras", "cpu_baseline"} & set(plain)
+    assert full["exact_f32_mode"]["value"] > 0 and "cpu_baseline" not in full
+    assert sorted(full["extras"]) == ["c3", "c5", "host_entry", "nerf", "small_batch"]
