@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""
+Partially noise PDB structures and reconstruct them with a trained model on MI355X -- stand-in for the reference's
+bin/partial_noise_reconstruct.py (same positional arguments and flags).
+
+The structures are read and featurised by foldingdiff_amd.structures (one device launch for all files), forward-noised
+to t = --timesteps and denoised again on the device, and every reconstruction is scored with the backbone RMSD after
+optimal superposition (Angstrom, lower is better).  The output JSON holds
+
+    {"timesteps": T, "model": DIR, "rmsd": {file: RMSD of NeRF(reconstruction) to NeRF(original angles)},
+     "rmsd_coord": {file: RMSD of NeRF(reconstruction) to the file's own backbone}}
+
+in place of the reference's "tmscores": the TM-score needs the external TM-align binary, which is not part of this
+package.  The model must be a local directory (no hub download): training_args.json, config.json, models/ and
+training_mean_offset.npy.  Files the parser rejects (several models, a residue without N / CA / C, angles out of
+range) or that are shorter than the model's min_seq_len are left out of the output.
+"""
+import argparse
+import json
+import logging
+import os
+import sys
+from pathlib import Path
+from typing import Collection, Dict, Tuple
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from foldingdiff_amd import datasets, modelling, sampling, structures  # noqa: E402
+
+
+def load_dataset(pdb_files: Collection[str], model_dir: Path) -> datasets.NoisedAnglesDataset:
+    """The reference's load_dataset: the clean dataset class of the model's feature set, padded and filtered like its
+    training data, centred with the training means, wrapped in the model's noise schedule."""
+    logging.info(f"Loading dataset from {len(pdb_files)} pdb files")
+    with open(model_dir / "training_args.json") as source:
+        training_args = json.load(source)
+    key = training_args["angles_definitions"]
+    if key not in structures.DATASETS:
+        raise NotImplementedError(f"angles_definitions={key!r}: only the canonical angle feature sets are supported")
+    dset = structures.DATASETS[key](
+        pdbs=list(pdb_files),
+        split=None,
+        pad=training_args["max_seq_len"],
+        min_length=training_args.get("min_seq_len", 0),   # bin/train.py's default
+        trim_strategy="leftalign",
+        zero_center=True,  # the offset is replaced by the training one just below
+    )
+    dset.set_masked_means(np.load(model_dir / "training_mean_offset.npy"))
+    return datasets.NoisedAnglesDataset(
+        dset,
+        dset_key="angles",
+        timesteps=training_args["timesteps"],
+        beta_schedule=training_args["variance_schedule"],
+        nonangular_variance=1.0,
+        angular_variance=training_args["variance_scale"],
+    )
+
+
+def build_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument("pdb_files", nargs="+", help="PDB files to reconstruct (.pdb or .pdb.gz)")
+    parser.add_argument("output_json", type=str, help="Output JSON file")
+    parser.add_argument("-t", "--timesteps", type=int, default=800, help="Timesteps of noise to add (default: 800)")
+    parser.add_argument("-m", "--model", type=str, required=True, help="Local model directory")
+    parser.add_argument("-d", "--device", type=int, default=0, help="GPU to use (default: 0)")
+    return parser
+
+
+def get_reconstruction_error(pdb_files: Collection[str], timesteps: int, model: str,
+                             device: int = 0) -> Tuple[Dict[str, float], Dict[str, float]]:
+    """(RMSD to the original angles' backbone, RMSD to the file's backbone) per file that entered the dataset."""
+    assert os.path.isdir(model), f"Model path {model} is not a local directory"
+    dset = load_dataset(pdb_files, Path(model))
+    net = modelling.BertForDiffusionBase.from_dir(model).to(torch.device(f"cuda:{device}"))
+    scores, coord_scores = sampling.get_reconstruction_error(net, dset=dset, noise_timesteps=timesteps,
+                                                             scorer=structures.RmsdScorer(device=device))
+    files = dset.filenames   # the dataset's (shuffled) order, which the scores follow
+    logging.info(f"Reconstruction RMSD from t={timesteps}: {np.min(scores):.3f}-{np.max(scores):.3f} A")
+    return ({f: float(s) for f, s in zip(files, scores)}, {f: float(s) for f, s in zip(files, coord_scores)})
+
+
+def main():
+    args = build_parser().parse_args()
+    rmsd, rmsd_coord = get_reconstruction_error(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device)
+    with open(args.output_json, "w") as sink:
+        json.dump({"timesteps": args.timesteps, "model": args.model, "rmsd": rmsd, "rmsd_coord": rmsd_coord}, sink, indent=4)
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.INFO)
+    main()

@@ -22,6 +22,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import nerf
+from .structures import canonical_distances_and_dihedrals, extract_backbone_coords  # noqa: F401  (the reference's import path)
 
 _ATOMS = (("N", "N"), ("CA", "C"), ("C", "C"))  # (atom name, element) per residue, in chain order
 

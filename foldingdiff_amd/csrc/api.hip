@@ -1060,6 +1060,55 @@ int check_lens(const int32_t* lens, int B, int L) {
   return FD_OK;
 }
 
+// chains / pairs packed back to back: offsets[c] = lens[0] + ... + lens[c-1]; *total = the sum of all lengths
+static int check_packed(const int32_t* offsets, const int32_t* lens, int n, long long limit, long long* total) {
+  long long sum = 0;
+  for (int c = 0; c < n; ++c) sum += lens[c] > 0 ? lens[c] : 0;
+  if (sum > limit) return fail(FD_E_UNSUPPORTED, "%lld entries in total, at most %lld", sum, limit);
+  long long at = 0;
+  for (int c = 0; c < n; ++c) {
+    if (lens[c] < 1) return fail(FD_E_INVALID, "lens[%d]=%d must be >= 1", c, lens[c]);
+    if (offsets[c] < 0 || (long long)offsets[c] + lens[c] > sum)
+      return fail(FD_E_INVALID, "offsets[%d]=%d (length %d) outside the buffer of %lld entries", c, offsets[c], lens[c], sum);
+    if (offsets[c] != at)
+      return fail(FD_E_INVALID, "offsets[%d]=%d, expected %lld (entries are packed back to back in order)", c, offsets[c], at);
+    at += lens[c];
+  }
+  *total = sum;
+  return FD_OK;
+}
+
+// one synchronous device round trip: inputs up, one launch, the output down (fd_internal_coords, fd_superpose_rmsd)
+template <typename Launch>
+static int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs, void* out,
+                            size_t out_bytes, Launch launch) {
+  HIP_TRY(hipSetDevice(device_id));
+  std::vector<void*> bufs;
+  auto cleanup = [&]() {
+    for (void* p : bufs) (void)hipFree(p);
+  };
+  auto hip = [&](hipError_t e, const char* what) -> int {
+    if (e == hipSuccess) return FD_OK;
+    cleanup();
+    return fail(FD_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+  };
+  for (auto& in : inputs) {
+    void* d = nullptr;
+    if (int rc = hip(hipMalloc(&d, in.second), "hipMalloc")) return rc;
+    bufs.push_back(d);
+    if (int rc = hip(hipMemcpy(d, in.first, in.second, hipMemcpyHostToDevice), "hipMemcpy H2D")) return rc;
+  }
+  void* d_out = nullptr;
+  if (int rc = hip(hipMalloc(&d_out, out_bytes), "hipMalloc")) return rc;
+  bufs.push_back(d_out);
+  launch(bufs);
+  if (int rc = hip(hipGetLastError(), "launch")) return rc;
+  if (int rc = hip(hipDeviceSynchronize(), "hipDeviceSynchronize")) return rc;
+  if (int rc = hip(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy D2H")) return rc;
+  cleanup();
+  return FD_OK;
+}
+
 // the workspace's captured graph still holds the launch sequence the model's options ask for
 static bool graph_current(const fd_model* m, const Workspace& w) {
   return w.graph && w.graph_fuse_ln == m->fuse_ln && w.graph_varlen == m->varlen && w.graph_fuse_attn == m->fuse_attn && w.graph_fuse_ffn == m->fuse_ffn &&
@@ -1837,6 +1886,34 @@ int fd_nerf(int device_id, const float* feats, const int32_t* lens, int B, int L
 #undef N_TRY
   cleanup();
   return FD_OK;
+}
+
+int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens, int n_chains,
+                       float* feats_out) {
+  if (!xyz || !chain_offsets || !chain_lens || !feats_out || n_chains < 1) return fail(FD_E_INVALID, "bad argument");
+  long long n_res = 0;
+  if (int rc = check_packed(chain_offsets, chain_lens, n_chains, 0x7fffffffLL / 9, &n_res)) return rc;
+  const size_t nr = (size_t)n_res, nc = (size_t)n_chains;
+  return device_roundtrip(device_id, {{xyz, nr * 9 * 4}, {chain_offsets, nc * 4}, {chain_lens, nc * 4}}, feats_out, nr * 9 * 4,
+                          [&](const std::vector<void*>& d) {
+                            launch_internal_coords(static_cast<const float*>(d[0]), static_cast<const int*>(d[1]),
+                                                   static_cast<const int*>(d[2]), n_chains, (int)n_res, static_cast<float*>(d[3]),
+                                                   nullptr);
+                          });
+}
+
+int fd_superpose_rmsd(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens, int n_pairs,
+                      double* rmsd_out) {
+  if (!a || !b || !offsets || !lens || !rmsd_out || n_pairs < 1) return fail(FD_E_INVALID, "bad argument");
+  long long n_atoms = 0;
+  if (int rc = check_packed(offsets, lens, n_pairs, 0x7fffffffLL / 3, &n_atoms)) return rc;
+  const size_t na = (size_t)n_atoms, np = (size_t)n_pairs;
+  return device_roundtrip(device_id, {{a, na * 3 * 8}, {b, na * 3 * 8}, {offsets, np * 4}, {lens, np * 4}}, rmsd_out, np * 8,
+                          [&](const std::vector<void*>& d) {
+                            launch_superpose_rmsd(static_cast<const double*>(d[0]), static_cast<const double*>(d[1]),
+                                                  static_cast<const int*>(d[2]), static_cast<const int*>(d[3]), n_pairs,
+                                                  static_cast<double*>(d[4]), nullptr);
+                          });
 }
 
 int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L, const void* lens_dev, const void* item_off_dev,

@@ -94,6 +94,15 @@ struct NerfFeatures {
 void launch_nerf(const float* feats, const int* lens, int B, int L, int F, const NerfFeatures& fx, int center,
                  double* out /* [B][3L][3] */, hipStream_t s);
 
+// The inverse of NeRF (internal_coords.hip): float32 N, CA, C coordinates [n_res][3][3] of chains packed back to back
+// (chain c = residues offsets[c] .. offsets[c] + lens[c] - 1) -> float32 [n_res][9] canonical features, one lane per residue.
+void launch_internal_coords(const float* xyz, const int* offsets, const int* lens, int n_chains, int n_res, float* out,
+                            hipStream_t s);
+// RMSD after optimal superposition of a[k] onto b[k] for atoms offsets[p] .. offsets[p] + lens[p] - 1 of pair p (fp64
+// [n_atoms][3] each), one wave per pair.
+void launch_superpose_rmsd(const double* a, const double* b, const int* offsets, const int* lens, int n_pairs, double* rmsd,
+                           hipStream_t s);
+
 // *t_dev -= 1  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, hipStream_t s);
 

@@ -620,11 +620,15 @@ def get_reconstruction_error(model, dset, noise_timesteps: int = 250, bs: int = 
     """Reference signature + ``scorer``: TM-align (an external binary) and the PDB writer are outside this
     path, so the caller supplies ``scorer(reconst_angles, truth_angles, truth_pdb_file) -> (score,
     score_coord)`` -- the role of the reference's ``_score_angles`` (foldingdiff/sampling.py:266-284).
-    Returns (scores, coord_scores) as the reference does."""
+    A scorer with a ``score_batch(recon, truth, files) -> (scores, coord_scores)`` method (e.g.
+    ``structures.rmsd_scorer``) scores all items in one call.  Returns (scores, coord_scores) as the reference does."""
     if scorer is None:
         raise NotImplementedError("pass scorer=...: TM-score evaluation is not part of the MI355X hot path; "
                                   "use reconstruct() for the angle sets")
     recon, truth, files = reconstruct(model, dset, noise_timesteps=noise_timesteps, bs=bs)
+    if hasattr(scorer, "score_batch"):
+        scores, coord_scores = scorer.score_batch(recon, truth, files)
+        return np.asarray(scores), np.asarray(coord_scores)
     scores, coord_scores = zip(*(scorer(r, t, f) for r, t, f in zip(recon, truth, files)))
     return np.array(scores), np.array(coord_scores)
 

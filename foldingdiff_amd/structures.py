@@ -1,0 +1,393 @@
+"""
+Input side of the package: PDB backbones -> internal coordinates -> datasets, and superposed-RMSD scoring.
+
+The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
+
+* ``canonical_distances_and_dihedrals`` / ``extract_backbone_coords`` (foldingdiff/angles_and_coords.py:30-109,
+  :271-284): the geometry of EVERY parsed file comes from one ``fd_internal_coords`` launch (one lane per residue,
+  fp64), the PDB parsing stays on the host (``read_backbone``);
+* ``CathCanonicalAnglesDataset`` and its angle-only subclasses (foldingdiff/datasets.py:75-566) over a list of files
+  or a directory (``PdbAnglesDataset``), without the pickle cache;
+* the scorer of ``sampling.get_reconstruction_error``: the reference scores with TM-align, an external binary
+  (``_score_angles``, foldingdiff/sampling.py:266-284); ``rmsd_scorer`` scores with the backbone RMSD after optimal
+  superposition (``fd_superpose_rmsd``, one launch per call).
+
+PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PDBFile`` for them):
+
+1. a file with more than one MODEL record is rejected (``None``), as the reference does;
+2. ATOM records are read, plus HETATM records of selenomethionine (MSE); other HETATM records are skipped;
+3. of an atom with alternate locations, the first record in the file is kept;
+4. a residue is identified by (chain, resSeq, iCode); residues are taken in the order they first appear;
+5. each residue contributes its N, CA and C atoms, in that order;
+6. all chains are concatenated in file order (the reference runs ``dihedral_backbone`` over the whole structure, so
+   the geometry across a chain break is computed like any other);
+7. a residue without one of N / CA / C rejects the file (``None``, with a debug log line).  This project's choice:
+   it stands in for biotite's ``BadStructureError``, whose exact trigger is not pinned here.
+"""
+import ctypes as C
+import glob
+import gzip
+import logging
+import os
+from typing import Callable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import pandas as pd
+import torch
+
+from . import _binding, datasets, nerf, utils
+
+EXHAUSTIVE_ANGLES = ["phi", "psi", "omega", "tau", "CA:C:1N", "C:1N:1CA"]
+EXHAUSTIVE_DISTS = ["0C:1N", "N:CA", "CA:C"]
+MINIMAL_ANGLES = ["phi", "psi", "omega"]
+MINIMAL_DISTS: List[str] = []
+
+# fd_internal_coords' output columns
+CANONICAL = datasets.FEATURE_SET_NAMES_TO_FEATURE_NAMES["canonical"]
+# accepted names -> output column (the reference also accepts "N:CA:C" for tau and "C:1N" for 0C:1N)
+_ALIASES = {**{c: c for c in CANONICAL}, "N:CA:C": "tau", "C:1N": "0C:1N"}
+_DIHEDRALS = ("phi", "psi", "omega")
+_BACKBONE = ("N", "CA", "C")
+
+
+# ---------------------------------------------------------------------------------------------------- parsing
+def _open(fname: str):
+    return gzip.open(fname, "rt") if str(fname).endswith(".gz") else open(fname, "rt")
+
+
+def read_backbone(fname: str) -> Optional[Tuple[np.ndarray, List[Tuple[str, str, str]]]]:
+    """N, CA, C coordinates of every residue of a ``.pdb`` / ``.pdb.gz`` file: (float32 [3n, 3], the n residue ids
+    (chain, resSeq, iCode)), or ``None`` for a rejected file.  Rules 1-7 of the module docstring."""
+    n_models = 0
+    atoms = {}       # residue id -> {atom name: xyz}; the first record of an atom wins (alternate locations)
+    order = []       # residue ids in order of first appearance
+    with _open(fname) as fh:
+        for line in fh:
+            rec = line[:6]
+            if rec == "MODEL ":
+                n_models += 1
+                continue
+            if rec != "ATOM  " and not (rec == "HETATM" and line[17:20] == "MSE"):
+                continue
+            name = line[12:16].strip()
+            if name not in _BACKBONE:
+                continue
+            rid = (line[21], line[22:26].strip(), line[26].strip())
+            res = atoms.get(rid)
+            if res is None:
+                res = atoms[rid] = {}
+                order.append(rid)
+            if name not in res:
+                res[name] = (float(line[30:38]), float(line[38:46]), float(line[46:54]))
+    if n_models > 1:
+        logging.debug(f"{fname}: {n_models} models - skipping")
+        return None
+    if not order:
+        logging.debug(f"{fname}: no backbone atoms - skipping")
+        return None
+    for rid in order:
+        missing = [a for a in _BACKBONE if a not in atoms[rid]]
+        if missing:
+            logging.debug(f"{fname}: residue {rid} lacks {missing} - skipping")
+            return None
+    xyz = np.array([atoms[rid][a] for rid in order for a in _BACKBONE], dtype=np.float32)
+    return xyz, order
+
+
+def extract_backbone_coords(fname: str, atoms: Sequence[str] = ("CA",)) -> Optional[np.ndarray]:
+    """float32 coordinates of the chosen backbone atoms of every residue, in file order (N, CA, C within a residue):
+    ``extract_backbone_coords`` (foldingdiff/angles_and_coords.py:271-284), the ``"coords"`` the datasets carry.
+    ``None`` for a file ``read_backbone`` rejects."""
+    bb = read_backbone(fname)
+    if bb is None:
+        return None
+    keep = [k for k, a in enumerate(_BACKBONE) if a in atoms]
+    return bb[0].reshape(-1, 3, 3)[:, keep].reshape(-1, 3)
+
+
+# ---------------------------------------------------------------------------------------------------- featurising
+def internal_coords(chains: Sequence[np.ndarray], device: int = 0) -> List[np.ndarray]:
+    """The nine canonical features (float32 [n_i, 9], columns ``CANONICAL``) of every backbone in ``chains``
+    (each [3 n_i, 3]: N, CA, C per residue), all in one ``fd_internal_coords`` launch."""
+    if not chains:
+        return []
+    lens = np.array([len(c) // 3 for c in chains], dtype=np.int32)
+    for c in chains:
+        assert c.ndim == 2 and c.shape[1] == 3 and len(c) % 3 == 0 and len(c) > 0, f"expected [3n, 3], got {c.shape}"
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+    xyz = np.ascontiguousarray(np.concatenate(chains), dtype=np.float32)
+    out = np.empty((int(lens.sum()), 9), dtype=np.float32)
+    _binding.check(_binding.load().fd_internal_coords(
+        device, xyz.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+        len(chains), out.ctypes.data_as(C.c_void_p)))
+    return [out[o: o + n] for o, n in zip(offsets, lens)]
+
+
+def _columns(distances: Sequence[str], angles: Sequence[str]) -> List[str]:
+    for d in distances:
+        if d not in _ALIASES or _ALIASES[d].count(":") != 1:
+            raise ValueError(f"Unrecognized distance: {d}")
+    for a in angles:
+        if a not in _ALIASES or _ALIASES[a].count(":") == 1:
+            raise ValueError(f"Unrecognized angle: {a}")
+    return list(distances) + list(angles)
+
+
+def _in_range(feats: np.ndarray, angles: Sequence[str], fname: str) -> bool:
+    """The reference's range check (angles_and_coords.py:78-82): the three dihedrals and every requested angle, float32
+    values against float64 pi; NaN padding is ignored."""
+    for a in list(_DIHEDRALS) + [a for a in angles if _ALIASES[a] not in _DIHEDRALS]:
+        v = feats[:, CANONICAL.index(_ALIASES[a])]
+        v = v[~np.isnan(v)]
+        if v.size and not (v.min() >= -np.pi and v.max() <= np.pi):
+            logging.warning(f"Illegal values for {a} in {fname} -- skipping")
+            return False
+    return True
+
+
+def featurize_backbones(fnames: Sequence[str], device: int = 0) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+    """(float32 [n, 9] canonical features, float32 [3n, 3] backbone) per file, ``None`` for a rejected one; the files
+    are parsed on the host, the geometry of all of them is one device launch."""
+    parsed = [read_backbone(f) for f in fnames]
+    ok = [i for i, p in enumerate(parsed) if p is not None]
+    feats = internal_coords([parsed[i][0] for i in ok], device=device)
+    out: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [None] * len(fnames)
+    for i, f in zip(ok, feats):
+        out[i] = (f, parsed[i][0])
+    return out
+
+
+def featurize(fnames: Sequence[str], distances: Sequence[str] = tuple(EXHAUSTIVE_DISTS),
+              angles: Sequence[str] = tuple(EXHAUSTIVE_ANGLES), device: int = 0) -> List[Optional[pd.DataFrame]]:
+    """``canonical_distances_and_dihedrals`` for many files with one ``fd_internal_coords`` call: per file a DataFrame
+    with the columns ``distances + angles`` (float32), or ``None`` if the file is rejected (parser rules 1 and 7) or
+    one of its angles leaves [-pi, pi]."""
+    cols = _columns(distances, angles)
+    out: List[Optional[pd.DataFrame]] = []
+    for fname, r in zip(fnames, featurize_backbones(fnames, device=device)):
+        if r is None or not _in_range(r[0], angles, fname):
+            out.append(None)
+            continue
+        out.append(pd.DataFrame({c: r[0][:, CANONICAL.index(_ALIASES[c])] for c in cols}))
+    return out
+
+
+def canonical_distances_and_dihedrals(fname: str, distances: List[str] = MINIMAL_DISTS,
+                                      angles: List[str] = MINIMAL_ANGLES) -> Optional[pd.DataFrame]:
+    """The reference's single-file form (foldingdiff/angles_and_coords.py:30-109), same signature and defaults."""
+    assert os.path.isfile(fname), fname
+    return featurize([fname], distances=distances, angles=angles)[0]
+
+
+# ---------------------------------------------------------------------------------------------------- datasets
+def _pdb_fnames(pdbs: Union[str, Sequence[str]]) -> List[str]:
+    """A list of files, or the ``*.pdb`` / ``*.pdb.gz`` files of a directory (sorted: the reference takes the
+    filesystem's order, which the seeded shuffle then depends on)."""
+    if isinstance(pdbs, (list, tuple)):
+        for f in pdbs:
+            assert os.path.isfile(f), f"Given file does not exist: {f}"
+        return list(pdbs)
+    assert os.path.isdir(pdbs), f"{pdbs} is neither a list of files nor a directory"
+    fnames = []
+    for ext in (".pdb", ".pdb.gz"):
+        fnames.extend(sorted(glob.glob(os.path.join(pdbs, f"*{ext}"))))
+    assert fnames, f"No PDB files found in {pdbs}"
+    return fnames
+
+
+def _featurize_for_dataset(fnames: Sequence[str]) -> List[Optional[Tuple[pd.DataFrame, np.ndarray]]]:
+    """Default ``featurizer`` of ``PdbAnglesDataset``: (9-column DataFrame, CA coordinates) per file or ``None``
+    (what the reference's ``__compute_featurization`` gets from its two pool maps)."""
+    out = []
+    for fname, r in zip(fnames, featurize_backbones(fnames)):
+        if r is None or not _in_range(r[0], EXHAUSTIVE_ANGLES, fname):
+            out.append(None)
+            continue
+        out.append((pd.DataFrame(r[0], columns=CANONICAL), r[1][1::3].copy()))
+    return out
+
+
+class PdbAnglesDataset:
+    """``CathCanonicalAnglesDataset`` (foldingdiff/datasets.py:75-465) over PDB files: items of the nine canonical
+    features, with the reference's filtering, seeded shuffle and split, zero-centring, padding and item keys.
+
+    ``pdbs``: a list of files or a directory.  ``featurizer(fnames)`` returns per file ``(DataFrame with the columns
+    CANONICAL, float32 [n, 3] CA coordinates)`` or ``None``; the default reads the files and featurises them on the
+    device.  ``trim_strategy``: "leftalign" or "discard" ("randomcrop" is not supported)."""
+
+    feature_names = {"angles": list(CANONICAL)}
+    feature_is_angular = {"angles": list(datasets.FEATURE_SET_NAMES_TO_ANGULARITY["canonical"])}
+
+    def __init__(self, pdbs: Union[str, Sequence[str]], split: Optional[str] = None, pad: int = 512, min_length: int = 40,
+                 trim_strategy: str = "leftalign", zero_center: bool = True,
+                 featurizer: Optional[Callable[[Sequence[str]], list]] = None) -> None:
+        assert pad > min_length
+        if trim_strategy not in ("leftalign", "discard"):
+            raise NotImplementedError(f"trim_strategy={trim_strategy!r}")
+        self.trim_strategy, self.pad, self.min_length = trim_strategy, pad, min_length
+        self.feature_idx = [CANONICAL.index(f) for f in self.feature_names["angles"]]
+        fnames = _pdb_fnames(pdbs)
+        feats = (featurizer or _featurize_for_dataset)(fnames)
+        assert len(feats) == len(fnames)
+        self.structures = [{"angles": r[0], "coords": r[1], "fname": f} for f, r in zip(fnames, feats) if r is not None]
+        for s in self.structures:
+            assert list(s["angles"].columns) == CANONICAL and len(s["coords"]) == len(s["angles"]), s["fname"]
+        if self.min_length:
+            self.structures = [s for s in self.structures if s["angles"].shape[0] >= self.min_length]
+        if self.trim_strategy == "discard":
+            self.structures = [s for s in self.structures if s["angles"].shape[0] <= self.pad]
+        # shuffled even without a split, so that contiguous splits act like random ones (datasets.py:190-208)
+        self.rng = np.random.default_rng(seed=6489)
+        self.rng.shuffle(self.structures)
+        if split is not None:
+            n = len(self.structures)
+            cut = int(n * 0.8)
+            if split == "train":
+                self.structures = self.structures[:cut]
+            elif split == "validation":
+                self.structures = self.structures[cut: cut + int(n * 0.1)]
+            elif split == "test":
+                self.structures = self.structures[cut + int(n * 0.1):]
+            else:
+                raise ValueError(f"Unknown split: {split}")
+        # circular mean of ALL nine columns, the distances included (the reference's quirk); NaN padding ignored
+        self.means = None
+        if zero_center:
+            concat = np.concatenate([s["angles"] for s in self.structures])
+            self.means = np.arctan2(np.nanmean(np.sin(concat), axis=0), np.nanmean(np.cos(concat), axis=0))
+        self.all_lengths = [s["angles"].shape[0] for s in self.structures]
+        self._length_rng = np.random.default_rng(seed=6489)
+
+    @property
+    def filenames(self) -> List[str]:
+        return [s["fname"] for s in self.structures]
+
+    def __len__(self) -> int:
+        return len(self.structures)
+
+    def sample_length(self, n: int = 1) -> Union[int, List[int]]:
+        assert n > 0
+        if n == 1:
+            return self._length_rng.choice(self.all_lengths)
+        return self._length_rng.choice(self.all_lengths, size=n, replace=True).tolist()
+
+    def get_masked_means(self) -> Optional[np.ndarray]:
+        """The means of the features this dataset returns (``None`` without zero-centring)."""
+        return None if self.means is None else np.copy(self.means)[self.feature_idx]
+
+    def set_masked_means(self, mean_values: np.ndarray) -> None:
+        """Overwrite the means of the features this dataset returns, e.g. with a model's training_mean_offset.npy."""
+        if self.means is None:
+            raise NotImplementedError
+        self.means[self.feature_idx] = np.asarray(mean_values).copy()
+
+    def __getitem__(self, index: int, ignore_zero_center: bool = False):
+        if not 0 <= index < len(self):
+            raise IndexError("Index out of range")
+        s = self.structures[index]
+        angles = np.asarray(s["angles"].values)
+        coords = np.asarray(s["coords"])
+        if self.means is not None and not ignore_zero_center:
+            angles = angles - self.means
+            # "angular" = every column whose name does not hold exactly one ':' (datasets.py:405-411)
+            ang = [j for j, c in enumerate(CANONICAL) if c.count(":") != 1]
+            angles[:, ang] = utils.modulo_with_wrapped_range(angles[:, ang], -np.pi, np.pi)
+        angles = np.nan_to_num(angles[:, self.feature_idx], nan=0.0)
+        l = min(self.pad, angles.shape[0])
+        attn_mask = torch.zeros(size=(self.pad,))
+        attn_mask[:l] = 1.0
+        if angles.shape[0] < self.pad:
+            angles = np.pad(angles, ((0, self.pad - angles.shape[0]), (0, 0)), mode="constant", constant_values=0)
+            coords = np.pad(coords, ((0, self.pad - coords.shape[0]), (0, 0)), mode="constant", constant_values=0)
+        else:   # left-align ("discard" has removed the longer ones)
+            angles, coords = angles[: self.pad], coords[: self.pad]
+        return {
+            "angles": torch.from_numpy(np.ascontiguousarray(angles)).float(),
+            "coords": torch.from_numpy(np.ascontiguousarray(coords)).float(),
+            "attn_mask": attn_mask,
+            "position_ids": torch.arange(start=0, end=self.pad, step=1, dtype=torch.long),
+            "lengths": torch.tensor(l, dtype=torch.int64),
+        }
+
+
+class PdbAnglesOnlyDataset(PdbAnglesDataset):
+    """``CathCanonicalAnglesOnlyDataset`` (datasets.py:487-548): the three dihedrals and the three bond angles."""
+    feature_names = {"angles": list(datasets.FEATURE_SET_NAMES_TO_FEATURE_NAMES["canonical-full-angles"])}
+    feature_is_angular = {"angles": list(datasets.FEATURE_SET_NAMES_TO_ANGULARITY["canonical-full-angles"])}
+
+
+class PdbMinimalAnglesDataset(PdbAnglesDataset):
+    """``CathCanonicalMinimalAnglesDataset`` (datasets.py:551-561): phi, psi, omega, tau."""
+    feature_names = {"angles": list(datasets.FEATURE_SET_NAMES_TO_FEATURE_NAMES["canonical-minimal-angles"])}
+    feature_is_angular = {"angles": list(datasets.FEATURE_SET_NAMES_TO_ANGULARITY["canonical-minimal-angles"])}
+
+
+# training_args["angles_definitions"] -> dataset class ("cart-coords" is not supported)
+DATASETS = {"canonical": PdbAnglesDataset, "canonical-full-angles": PdbAnglesOnlyDataset,
+            "canonical-minimal-angles": PdbMinimalAnglesDataset}
+
+
+# ---------------------------------------------------------------------------------------------------- scoring
+def superposed_rmsd(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], device: int = 0) -> np.ndarray:
+    """RMSD of a[i] to b[i] after optimal rotation and translation, for every pair (each [m_i, 3], m_i >= 1), in one
+    ``fd_superpose_rmsd`` call; float64 [len(a_list)]."""
+    assert len(a_list) == len(b_list)
+    if not a_list:
+        return np.zeros((0,), dtype=np.float64)
+    a = [np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in a_list]
+    b = [np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in b_list]
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert x.shape == y.shape and len(x) > 0, f"pair {i}: {x.shape} vs {y.shape}"
+    lens = np.array([len(x) for x in a], dtype=np.int32)
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+    A, B = np.ascontiguousarray(np.concatenate(a)), np.ascontiguousarray(np.concatenate(b))
+    out = np.empty((len(a),), dtype=np.float64)
+    _binding.check(_binding.load().fd_superpose_rmsd(
+        device, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+        lens.ctypes.data_as(C.c_void_p), len(a), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class RmsdScorer:
+    """A ``scorer=`` for ``sampling.get_reconstruction_error``: per item (RMSD of NeRF(reconstruction) to NeRF(truth),
+    RMSD of NeRF(reconstruction) to the backbone of the item's PDB file), in Angstrom after optimal superposition --
+    the reference's ``_score_angles`` (foldingdiff/sampling.py:266-284) with RMSD in place of the TM-score.
+
+    Like the reference, it builds the backbones from the angles exactly as ``reconstruct`` returns them: the training
+    mean offset is NOT added back first.  The feature names follow from the number of columns (9, 6 or 4: the
+    ``canonical*`` sets).  The file's backbone is compared over the residues the item holds (the first ``len`` of
+    them: left-aligned items); an unreadable file scores NaN.  ``score_batch`` scores all items of a call with one NeRF
+    launch and one RMSD launch; ``get_reconstruction_error`` uses it."""
+
+    def __init__(self, device: int = 0):
+        self.device = device
+
+    def __call__(self, reconst_angles, truth_angles, truth_pdb_file: str) -> Tuple[float, float]:
+        s, c = self.score_batch([reconst_angles], [truth_angles], [truth_pdb_file])
+        return float(s[0]), float(c[0])
+
+    def score_batch(self, recon: Sequence, truth: Sequence, files: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+        n = len(recon)
+        assert len(truth) == n == len(files)
+        if n == 0:
+            return np.zeros((0,)), np.zeros((0,))
+        recon = [np.asarray(r, dtype=np.float32) for r in recon]
+        truth = [np.asarray(t, dtype=np.float32) for t in truth]
+        F = recon[0].shape[1]
+        names = [v for k, v in datasets.FEATURE_SET_NAMES_TO_FEATURE_NAMES.items() if k in DATASETS and len(v) == F]
+        assert names, f"no canonical feature set has {F} features"
+        xyz = nerf.build_backbones(recon + truth, names[0], device=self.device)
+        a, b, which = [], [], []
+        for i, f in enumerate(files):
+            a.append(xyz[i]); b.append(xyz[n + i]); which.append(("angles", i))
+            bb = read_backbone(f) if os.path.isfile(f) else None
+            if bb is not None and len(bb[0]) >= len(xyz[i]):
+                a.append(xyz[i]); b.append(bb[0][: len(xyz[i])]); which.append(("coords", i))
+        r = superposed_rmsd(a, b, device=self.device)
+        scores, coord_scores = np.full(n, np.nan), np.full(n, np.nan)
+        for (kind, i), v in zip(which, r):
+            (scores if kind == "angles" else coord_scores)[i] = v
+        return scores, coord_scores
+
+
+rmsd_scorer = RmsdScorer()

@@ -36,7 +36,8 @@ extern "C" {
 /* 3: fd_shift_trim_dev, fd_test_wrap, option "fuse_attn" (round 5) */
 /* 4: fd_fused_attn_supported; option "fuse_attn" takes 2 (the round-5 kernel) and its default kernel no longer promises the bits of
  *    the two-kernel path; option "fuse_ffn" (round 6) */
-#define FDMI_ABI_VERSION 4
+/* 5: fd_internal_coords, fd_superpose_rmsd (coordinates -> internal coordinates, superposed RMSD) */
+#define FDMI_ABI_VERSION 5
 
 enum {
   FD_OK = 0,
@@ -253,6 +254,28 @@ int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, 
  *   coords_out float64 [B][3*L][3]: N, CA, C of each residue; rows of residues >= lens[b] are 0 */
 int fd_nerf(int device_id, const float* feats, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
             int center, double* coords_out);
+
+/* ---- input side: backbone coordinates -> internal coordinates (the inverse of fd_nerf) ----
+ * Replaces canonical_distances_and_dihedrals (foldingdiff/angles_and_coords.py:30-109) with every distance and angle
+ * (EXHAUSTIVE_DISTS + EXHAUSTIVE_ANGLES), for many chains in one launch.
+ *   xyz           float32 [n_res][3][3]: N, CA, C of each residue (host), n_res = sum of chain_lens
+ *   chain_offsets int32[n_chains]: first residue of each chain; chains are packed back to back in order
+ *                 (chain_offsets[0] = 0, chain_offsets[c + 1] = chain_offsets[c] + chain_lens[c])
+ *   chain_lens    int32[n_chains], each >= 1
+ *   feats_out     float32 [n_res][9] in the reference's column order 0C:1N, N:CA, CA:C, phi, psi, omega, tau, CA:C:1N,
+ *                 C:1N:1CA, computed in fp64.  Index shifts and padding are the reference's: phi of a chain's first residue
+ *                 is NaN; on its last residue the three distances are 0 and the six angles NaN; N:CA, CA:C and tau at
+ *                 index i are those of residue i + 1. */
+int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens, int n_chains,
+                       float* feats_out);
+
+/* Backbone RMSD after optimal superposition, the score of a reconstruction against its source structure (in place of
+ * the TM-score of tmalign.run_tmalign that _score_angles computes, foldingdiff/sampling.py:266-284; TM-align is an
+ * external binary).  Pair p = atoms offsets[p] .. offsets[p] + lens[p] - 1 of a and of b (host, float64 [n_atoms][3],
+ * packed back to back like fd_internal_coords' chains, lens >= 1); rmsd_out float64 [n_pairs] = min over rotations R and
+ * translations of sqrt(mean |R a + t - b|^2) (Horn's quaternion method, fp64). */
+int fd_superpose_rmsd(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens, int n_pairs,
+                      double* rmsd_out);
 
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
