@@ -10,8 +10,14 @@ optimal superposition (Angstrom, lower is better).  The output JSON holds
     {"timesteps": T, "model": DIR, "rmsd": {file: RMSD of NeRF(reconstruction) to NeRF(original angles)},
      "rmsd_coord": {file: RMSD of NeRF(reconstruction) to the file's own backbone}}
 
-in place of the reference's "tmscores": the TM-score needs the external TM-align binary, which is not part of this
-package.  The model must be a local directory (no hub download): training_args.json, config.json, models/ and
+With --tmscore the same reconstructions are also scored by TM-score (structures.tm_scorer: CA traces, the published
+TM-score search on the device in place of the external TM-align binary; higher is better, 1 = identical), under the
+reference's key and one for the file's own backbone:
+
+     "tmscores": {file: TM-score of NeRF(reconstruction) to NeRF(original angles)},
+     "tmscores_coord": {file: TM-score of NeRF(reconstruction) to the file's CA atoms, normalised by its length}
+
+The model must be a local directory (no hub download): training_args.json, config.json, models/ and
 training_mean_offset.npy.  Files the parser rejects (several models, a residue without N / CA / C, angles out of
 range) or that are shorter than the model's min_seq_len are left out of the output.
 """
@@ -68,6 +74,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("-t", "--timesteps", type=int, default=800, help="Timesteps of noise to add (default: 800)")
     parser.add_argument("-m", "--model", type=str, required=True, help="Local model directory")
     parser.add_argument("-d", "--device", type=int, default=0, help="GPU to use (default: 0)")
+    parser.add_argument("--tmscore", action="store_true",
+                        help='also write TM-scores ("tmscores", "tmscores_coord") of the same reconstructions')
     return parser
 
 
@@ -84,8 +92,31 @@ def get_reconstruction_error(pdb_files: Collection[str], timesteps: int, model: 
     return ({f: float(s) for f, s in zip(files, scores)}, {f: float(s) for f, s in zip(files, coord_scores)})
 
 
+def get_reconstruction_scores(pdb_files: Collection[str], timesteps: int, model: str,
+                              device: int = 0) -> Dict[str, Dict[str, float]]:
+    """One reconstruction per file, scored by both scorers: {"rmsd", "rmsd_coord", "tmscores", "tmscores_coord"},
+    each {file: score} over the files that entered the dataset."""
+    assert os.path.isdir(model), f"Model path {model} is not a local directory"
+    dset = load_dataset(pdb_files, Path(model))
+    net = modelling.BertForDiffusionBase.from_dir(model).to(torch.device(f"cuda:{device}"))
+    recon, truth, files = sampling.reconstruct(net, dset, noise_timesteps=timesteps)
+    out = {}
+    for key, scorer in (("rmsd", structures.RmsdScorer(device=device)), ("tmscores", structures.TmScorer(device=device))):
+        scores, coord_scores = scorer.score_batch(recon, truth, files)
+        out[key] = {f: float(s) for f, s in zip(files, scores)}
+        out[f"{key}_coord"] = {f: float(s) for f, s in zip(files, coord_scores)}
+    logging.info(f"Reconstruction TM-score from t={timesteps}: {min(out['tmscores'].values()):.3f}-"
+                 f"{max(out['tmscores'].values()):.3f}")
+    return out
+
+
 def main():
     args = build_parser().parse_args()
+    if args.tmscore:
+        scores = get_reconstruction_scores(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device)
+        with open(args.output_json, "w") as sink:
+            json.dump({"timesteps": args.timesteps, "model": args.model, **scores}, sink, indent=4)
+        return
     rmsd, rmsd_coord = get_reconstruction_error(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device)
     with open(args.output_json, "w") as sink:
         json.dump({"timesteps": args.timesteps, "model": args.model, "rmsd": rmsd, "rmsd_coord": rmsd_coord}, sink, indent=4)

@@ -4,12 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fdmi.h"
@@ -1078,10 +1080,12 @@ static int check_packed(const int32_t* offsets, const int32_t* lens, int n, long
   return FD_OK;
 }
 
-// one synchronous device round trip: inputs up, one launch, the output down (fd_internal_coords, fd_superpose_rmsd)
+// one synchronous device round trip: inputs up, one launch, the outputs down; an output with a null host pointer is a
+// device workspace that stays there.  The launch gets the device buffers in order, inputs first, and may return a
+// hipError_t (fd_internal_coords, fd_superpose_rmsd, fd_tm_score)
 template <typename Launch>
-static int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs, void* out,
-                            size_t out_bytes, Launch launch) {
+static int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs,
+                            std::initializer_list<std::pair<void*, size_t>> outputs, Launch launch) {
   HIP_TRY(hipSetDevice(device_id));
   std::vector<void*> bufs;
   auto cleanup = [&]() {
@@ -1098,15 +1102,32 @@ static int device_roundtrip(int device_id, std::initializer_list<std::pair<const
     bufs.push_back(d);
     if (int rc = hip(hipMemcpy(d, in.first, in.second, hipMemcpyHostToDevice), "hipMemcpy H2D")) return rc;
   }
-  void* d_out = nullptr;
-  if (int rc = hip(hipMalloc(&d_out, out_bytes), "hipMalloc")) return rc;
-  bufs.push_back(d_out);
-  launch(bufs);
+  for (auto& out : outputs) {
+    void* d = nullptr;
+    if (int rc = hip(hipMalloc(&d, out.second), "hipMalloc")) return rc;
+    bufs.push_back(d);
+  }
+  if constexpr (std::is_void_v<decltype(launch(bufs))>) {
+    launch(bufs);
+  } else {
+    if (int rc = hip(launch(bufs), "launch")) return rc;
+  }
   if (int rc = hip(hipGetLastError(), "launch")) return rc;
   if (int rc = hip(hipDeviceSynchronize(), "hipDeviceSynchronize")) return rc;
-  if (int rc = hip(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy D2H")) return rc;
+  size_t k = inputs.size();
+  for (auto& out : outputs) {
+    if (out.first)
+      if (int rc = hip(hipMemcpy(out.first, bufs[k], out.second, hipMemcpyDeviceToHost), "hipMemcpy D2H")) return rc;
+    ++k;
+  }
   cleanup();
   return FD_OK;
+}
+
+template <typename Launch>
+static int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs, void* out,
+                            size_t out_bytes, Launch launch) {
+  return device_roundtrip(device_id, inputs, {{out, out_bytes}}, launch);
 }
 
 // the workspace's captured graph still holds the launch sequence the model's options ask for
@@ -1914,6 +1935,55 @@ int fd_superpose_rmsd(int device_id, const double* a, const double* b, const int
                                                   static_cast<const int*>(d[2]), static_cast<const int*>(d[3]), n_pairs,
                                                   static_cast<double*>(d[4]), nullptr);
                           });
+}
+
+int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens,
+                const int32_t* norm_lens, int n_pairs, int stride, double* tm_out, double* transform_out) {
+  if (!a || !b || !offsets || !lens || !tm_out) return fail(FD_E_INVALID, "null argument");
+  if (n_pairs < 1) return fail(FD_E_INVALID, "n_pairs=%d must be >= 1", n_pairs);
+  if (stride < 1) return fail(FD_E_INVALID, "stride=%d must be >= 1", stride);
+  int max_len = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    if (lens[p] < 1 || lens[p] > FDMI_TM_MAX_LEN)
+      return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", p, lens[p], FDMI_TM_MAX_LEN);
+    if (norm_lens && norm_lens[p] < lens[p])
+      return fail(FD_E_INVALID, "norm_lens[%d]=%d is below lens[%d]=%d", p, norm_lens[p], p, lens[p]);
+    max_len = std::max(max_len, (int)lens[p]);
+  }
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_pairs, 0x7fffffffLL / 3, &n_res)) return rc;
+  // finite coordinates within 1e6 A (every squared distance stays far from overflow), and the centroids the kernel
+  // subtracts: the traces are scored in their own centred frames
+  std::vector<double> cent((size_t)n_pairs * 6, 0.0);
+  for (int p = 0; p < n_pairs; ++p) {
+    for (int i = offsets[p]; i < offsets[p] + lens[p]; ++i)
+      for (int d = 0; d < 3; ++d) {
+        const double u = a[(size_t)i * 3 + d], v = b[(size_t)i * 3 + d];
+        if (!(std::fabs(u) <= 1e6) || !(std::fabs(v) <= 1e6))
+          return fail(FD_E_INVALID, "coordinate %d of residue %d (pair %d) is not finite or beyond 1e6: a %g, b %g", d, i,
+                      p, u, v);
+        cent[(size_t)p * 6 + d] += u;
+        cent[(size_t)p * 6 + 3 + d] += v;
+      }
+    for (int d = 0; d < 6; ++d) cent[(size_t)p * 6 + d] /= lens[p];
+  }
+  std::vector<int32_t> chunk_off((size_t)n_pairs + 1);
+  const int n_chunks = tm_chunk_offsets(lens, n_pairs, stride, chunk_off.data());
+  if (n_chunks < 0) return fail(FD_E_UNSUPPORTED, "more than 2^31 - 1 seed workgroups");
+  const size_t na = (size_t)n_res, np = (size_t)n_pairs;
+  std::vector<double> transform(np * 12);
+  return device_roundtrip(
+      device_id,
+      {{a, na * 3 * 8}, {b, na * 3 * 8}, {cent.data(), np * 6 * 8}, {offsets, np * 4}, {lens, np * 4},
+       {norm_lens ? norm_lens : lens, np * 4}, {chunk_off.data(), (np + 1) * 4}},
+      {{nullptr, tm_workspace_bytes(n_chunks)}, {tm_out, np * 8}, {transform_out, np * 12 * 8}},
+      [&](const std::vector<void*>& d) {
+        return launch_tm_score(static_cast<const double*>(d[0]), static_cast<const double*>(d[1]),
+                               static_cast<const double*>(d[2]), static_cast<const int*>(d[3]), static_cast<const int*>(d[4]),
+                               static_cast<const int*>(d[5]), static_cast<const int*>(d[6]), n_pairs, n_chunks, stride,
+                               max_len, static_cast<double*>(d[7]), static_cast<double*>(d[8]), static_cast<double*>(d[9]),
+                               nullptr);
+      });
 }
 
 int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L, const void* lens_dev, const void* item_off_dev,

@@ -102,6 +102,14 @@ void launch_internal_coords(const float* xyz, const int* offsets, const int* len
 // [n_atoms][3] each), one wave per pair.
 void launch_superpose_rmsd(const double* a, const double* b, const int* offsets, const int* lens, int n_pairs, double* rmsd,
                            hipStream_t s);
+// TM-score search (tm_score.hip).  tm_chunk_offsets fills chunk_off[n_pairs + 1] (host: pair p's seeds are workgroups
+// chunk_off[p] .. chunk_off[p + 1] - 1) and returns the number of workgroups, -1 past INT_MAX.  launch_tm_score: cent =
+// [n_pairs][6] centroids of a and b, ws = tm_workspace_bytes(n_chunks), transform_out = [n_pairs][12] (R row-major, t).
+int tm_chunk_offsets(const int* lens, int n_pairs, int stride, int* chunk_off);
+size_t tm_workspace_bytes(int n_chunks);
+hipError_t launch_tm_score(const double* a, const double* b, const double* cent, const int* offsets, const int* lens,
+                           const int* norm_lens, const int* chunk_off, int n_pairs, int n_chunks, int stride, int max_len,
+                           double* ws, double* tm_out, double* transform_out, hipStream_t s);
 
 // *t_dev -= 1  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, hipStream_t s);

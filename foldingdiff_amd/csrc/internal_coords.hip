@@ -15,6 +15,7 @@
 //
 // Both kernels take microseconds next to a sampling run: plain global loads, no LDS.
 #include "fdmi_kernels.h"
+#include "horn_fit.h"
 
 namespace fdmi {
 namespace {
@@ -84,61 +85,6 @@ __device__ __forceinline__ double wave_sum(double v) {
   return __shfl(v, 0, 64);   // lane 0's sum on every lane: all lanes then take the same (bitwise) decisions
 }
 
-// Largest-eigenvalue eigenvector of the symmetric 4x4 A (cyclic Jacobi; every index is a compile-time constant).
-__device__ __forceinline__ void top_eigenvector(double A[4][4], double q[4]) {
-  double V[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) V[r][c] = r == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    double off = 0.0, diag = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      diag += A[p][p] * A[p][p];
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) off += A[p][r] * A[p][r];
-    }
-    if (!(off > 1e-34 * diag)) break;   // |off-diagonal| below 1e-17 of the diagonal (also ends an all-zero matrix)
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) {
-        const double apr = A[p][r];
-        if (apr == 0.0) continue;
-        const double theta = (A[r][r] - A[p][p]) / (2.0 * apr);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {   // A <- A J
-          const double akp = A[k][p], akr = A[k][r];
-          A[k][p] = c * akp - s * akr;
-          A[k][r] = s * akp + c * akr;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {   // A <- J^T A
-          const double apk = A[p][k], ark = A[r][k];
-          A[p][k] = c * apk - s * ark;
-          A[r][k] = s * apk + c * ark;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {   // V <- V J
-          const double vkp = V[k][p], vkr = V[k][r];
-          V[k][p] = c * vkp - s * vkr;
-          V[k][r] = s * vkp + c * vkr;
-        }
-      }
-    }
-  }
-  int best = 0;
-  double lmax = A[0][0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k)
-    if (A[k][k] > lmax) { lmax = A[k][k]; best = k; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = best == 0 ? V[k][0] : best == 1 ? V[k][1] : best == 2 ? V[k][2] : V[k][3];
-}
-
 __global__ void __launch_bounds__(64) superpose_rmsd_kernel(const double* __restrict__ a, const double* __restrict__ b,
                                       const int* __restrict__ offsets, const int* __restrict__ lens,
                                       double* __restrict__ rmsd) {
@@ -169,19 +115,9 @@ __global__ void __launch_bounds__(64) superpose_rmsd_kernel(const double* __rest
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) M[i][j] = wave_sum(M[i][j]);
-  // Horn's quaternion matrix; its top eigenvector q is the rotation taking a onto b
-  const double Sxx = M[0][0], Sxy = M[0][1], Sxz = M[0][2], Syx = M[1][0], Syy = M[1][1], Syz = M[1][2],
-               Szx = M[2][0], Szy = M[2][1], Szz = M[2][2];
-  double H[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
-                    {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
-                    {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
-                    {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
-  double q[4];
-  top_eigenvector(H, q);
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double R[3][3] = {{w * w + x * x - y * y - z * z, 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)},
-                          {2.0 * (x * y + w * z), w * w - x * x + y * y - z * z, 2.0 * (y * z - w * x)},
-                          {2.0 * (x * z - w * y), 2.0 * (y * z + w * x), w * w - x * x - y * y + z * z}};
+  // Horn's quaternion matrix; its top eigenvector is the rotation taking a onto b
+  double R[3][3];
+  horn_rotation(M, R);
   // pass 3: sum |R (a - ca) - (b - cb)|^2
   double e = 0.0;
   for (int k = lane; k < n; k += 64) {

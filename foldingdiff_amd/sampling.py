@@ -620,11 +620,12 @@ def get_reconstruction_error(model, dset, noise_timesteps: int = 250, bs: int = 
     """Reference signature + ``scorer``: TM-align (an external binary) and the PDB writer are outside this
     path, so the caller supplies ``scorer(reconst_angles, truth_angles, truth_pdb_file) -> (score,
     score_coord)`` -- the role of the reference's ``_score_angles`` (foldingdiff/sampling.py:266-284).
-    A scorer with a ``score_batch(recon, truth, files) -> (scores, coord_scores)`` method (e.g.
+    ``structures.tm_scorer`` gives the reference's TM-scores (CA traces, device search); a scorer with a
+    ``score_batch(recon, truth, files) -> (scores, coord_scores)`` method (``structures.tm_scorer``,
     ``structures.rmsd_scorer``) scores all items in one call.  Returns (scores, coord_scores) as the reference does."""
     if scorer is None:
-        raise NotImplementedError("pass scorer=...: TM-score evaluation is not part of the MI355X hot path; "
-                                  "use reconstruct() for the angle sets")
+        raise NotImplementedError("pass scorer=...: structures.tm_scorer for the reference's TM-scores, "
+                                  "structures.rmsd_scorer for RMSDs; use reconstruct() for the angle sets")
     recon, truth, files = reconstruct(model, dset, noise_timesteps=noise_timesteps, bs=bs)
     if hasattr(scorer, "score_batch"):
         scores, coord_scores = scorer.score_batch(recon, truth, files)

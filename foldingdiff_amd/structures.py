@@ -1,5 +1,5 @@
 """
-Input side of the package: PDB backbones -> internal coordinates -> datasets, and superposed-RMSD scoring.
+Input side of the package: PDB backbones -> internal coordinates -> datasets, and TM-score / superposed-RMSD scoring.
 
 The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
 
@@ -8,9 +8,10 @@ The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
   fp64), the PDB parsing stays on the host (``read_backbone``);
 * ``CathCanonicalAnglesDataset`` and its angle-only subclasses (foldingdiff/datasets.py:75-566) over a list of files
   or a directory (``PdbAnglesDataset``), without the pickle cache;
-* the scorer of ``sampling.get_reconstruction_error``: the reference scores with TM-align, an external binary
-  (``_score_angles``, foldingdiff/sampling.py:266-284); ``rmsd_scorer`` scores with the backbone RMSD after optimal
-  superposition (``fd_superpose_rmsd``, one launch per call).
+* the scorers of ``sampling.get_reconstruction_error`` (the reference's ``_score_angles``, foldingdiff/sampling.py:266-284,
+  which runs the external TM-align binary): ``tm_scorer`` scores with the TM-score of the CA traces (``fd_tm_score``,
+  the published TM-score search restated on the device; see ``tm_score``), ``rmsd_scorer`` with the backbone RMSD
+  after optimal superposition (``fd_superpose_rmsd``).  Each scores a whole call with one launch.
 
 PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PDBFile`` for them):
 
@@ -391,3 +392,99 @@ class RmsdScorer:
 
 
 rmsd_scorer = RmsdScorer()
+
+
+def tm_d0(Ln: int) -> float:
+    """The TM-score's distance scale for normalisation length ``Ln``: 1.24 cbrt(Ln - 15) - 1.8 for Ln > 21, else 0.5."""
+    return 1.24 * float(np.cbrt(Ln - 15)) - 1.8 if Ln > 21 else 0.5
+
+
+def tm_score(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], norm_lens: Optional[Sequence[int]] = None,
+             stride: int = 1, device: int = 0, return_transform: bool = False):
+    """TM-score of each residue-paired CA trace pair (a[i], b[i], each [n_i, 3] with 1 <= n_i <= 2048), normalised by
+    ``norm_lens[i]`` (>= n_i; default n_i), in one ``fd_tm_score`` call: float64 [len(a_list)], plus R [n, 3, 3] and
+    t [n, 3] with b ~ a @ R.T + t when ``return_transform`` is set.
+
+    The score is the maximum over superpositions found by the seed-and-extend search of Zhang & Skolnick (2004):
+    seed fragments of lengths n, n/2, n/4, ... and min(n, 4) starting every ``stride`` residues, each extended by
+    repeatedly refitting on the residues within d_cut (DESIGN.md "TM-score" states the rules).  It is not pinned to the
+    TMscore / TMalign binaries; TM-align also searches the residue alignment, so its number is usually the same or
+    higher."""
+    if len(a_list) != len(b_list):
+        raise ValueError(f"{len(a_list)} traces against {len(b_list)}")
+    a = [np.asarray(x, dtype=np.float64) for x in a_list]
+    b = [np.asarray(x, dtype=np.float64) for x in b_list]
+    for i, (x, y) in enumerate(zip(a, b)):
+        if x.ndim != 2 or x.shape[1] != 3 or x.shape != y.shape or not 1 <= len(x) <= 2048:
+            raise ValueError(f"pair {i}: {x.shape} vs {y.shape}; expected two [n, 3] traces with 1 <= n <= 2048")
+    lens = np.array([len(x) for x in a], dtype=np.int32)
+    if norm_lens is None:
+        nl = lens.copy()
+    else:
+        nl = np.asarray(norm_lens, dtype=np.int64).reshape(-1)
+        if nl.shape != lens.shape or (nl < lens).any() or (nl > np.iinfo(np.int32).max).any():
+            raise ValueError(f"norm_lens {nl.tolist()} must hold one length >= n_i per pair (lengths {lens.tolist()})")
+        nl = nl.astype(np.int32)
+    if int(stride) < 1:
+        raise ValueError(f"stride={stride} must be >= 1")
+    n = len(a)
+    out = np.empty((n,), dtype=np.float64)
+    T = np.empty((n, 12), dtype=np.float64)
+    if n == 0:
+        return (out, T[:, :9].reshape(0, 3, 3), T[:, 9:]) if return_transform else out
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+    A, B = np.ascontiguousarray(np.concatenate(a)), np.ascontiguousarray(np.concatenate(b))
+    _binding.check(_binding.load().fd_tm_score(
+        device, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+        lens.ctypes.data_as(C.c_void_p), nl.ctypes.data_as(C.c_void_p), n, int(stride), out.ctypes.data_as(C.c_void_p),
+        T.ctypes.data_as(C.c_void_p)))
+    if return_transform:
+        return out, T[:, :9].reshape(n, 3, 3).copy(), T[:, 9:].copy()
+    return out
+
+
+class TmScorer:
+    """A ``scorer=`` for ``sampling.get_reconstruction_error``: per item (TM-score of NeRF(reconstruction) to
+    NeRF(truth), TM-score of NeRF(reconstruction) to the item's PDB file), over CA atoms -- the two TM-scores of the
+    reference's ``_score_angles`` (foldingdiff/sampling.py:266-284), with ``tm_score``'s search in place of TM-align.
+
+    The first is normalised by the item's length.  The second compares with the first ``len`` CA atoms of the file
+    (left-aligned items) and is normalised by the file's residue count, as TM-align normalises by its second chain;
+    an unreadable file, or one shorter than the item, scores NaN.  Like the reference (and ``RmsdScorer``), the
+    backbones are built from the angles exactly as ``reconstruct`` returns them: the training mean offset is NOT added
+    back first.  ``score_batch`` scores all items of a call with one NeRF launch and one TM-score launch."""
+
+    def __init__(self, device: int = 0, stride: int = 1):
+        self.device, self.stride = device, stride
+
+    def __call__(self, reconst_angles, truth_angles, truth_pdb_file: str) -> Tuple[float, float]:
+        s, c = self.score_batch([reconst_angles], [truth_angles], [truth_pdb_file])
+        return float(s[0]), float(c[0])
+
+    def score_batch(self, recon: Sequence, truth: Sequence, files: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+        n = len(recon)
+        assert len(truth) == n == len(files)
+        if n == 0:
+            return np.zeros((0,)), np.zeros((0,))
+        recon = [np.asarray(r, dtype=np.float32) for r in recon]
+        truth = [np.asarray(t, dtype=np.float32) for t in truth]
+        F = recon[0].shape[1]
+        names = [v for k, v in datasets.FEATURE_SET_NAMES_TO_FEATURE_NAMES.items() if k in DATASETS and len(v) == F]
+        assert names, f"no canonical feature set has {F} features"
+        xyz = nerf.build_backbones(recon + truth, names[0], device=self.device)
+        a, b, norm, which = [], [], [], []
+        for i, f in enumerate(files):
+            ca = xyz[i][1::3]
+            a.append(ca); b.append(xyz[n + i][1::3]); norm.append(len(ca)); which.append(("angles", i))
+            bb = read_backbone(f) if os.path.isfile(f) else None
+            if bb is not None and len(bb[0]) >= len(xyz[i]):
+                file_ca = bb[0][1::3]
+                a.append(ca); b.append(file_ca[: len(ca)]); norm.append(len(file_ca)); which.append(("coords", i))
+        r = tm_score(a, b, norm_lens=norm, stride=self.stride, device=self.device)
+        scores, coord_scores = np.full(n, np.nan), np.full(n, np.nan)
+        for (kind, i), v in zip(which, r):
+            (scores if kind == "angles" else coord_scores)[i] = v
+        return scores, coord_scores
+
+
+tm_scorer = TmScorer()

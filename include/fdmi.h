@@ -37,7 +37,8 @@ extern "C" {
 /* 4: fd_fused_attn_supported; option "fuse_attn" takes 2 (the round-5 kernel) and its default kernel no longer promises the bits of
  *    the two-kernel path; option "fuse_ffn" (round 6) */
 /* 5: fd_internal_coords, fd_superpose_rmsd (coordinates -> internal coordinates, superposed RMSD) */
-#define FDMI_ABI_VERSION 5
+/* 6: fd_tm_score (TM-score of residue-paired CA traces) */
+#define FDMI_ABI_VERSION 6
 
 enum {
   FD_OK = 0,
@@ -276,6 +277,24 @@ int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_off
  * translations of sqrt(mean |R a + t - b|^2) (Horn's quaternion method, fp64). */
 int fd_superpose_rmsd(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens, int n_pairs,
                       double* rmsd_out);
+
+/* Longest chain fd_tm_score takes: both traces of a pair sit in one workgroup's LDS (48 B per residue). */
+#define FDMI_TM_MAX_LEN 2048
+
+/* TM-score of residue-paired CA traces: what tmalign.run_tmalign gives _score_angles (foldingdiff/sampling.py:266-284)
+ * when residue i of one chain corresponds to residue i of the other.  It restates the published seed-and-extend
+ * TM-score search (Zhang & Skolnick 2004; DESIGN.md "TM-score" has the exact rules) in fp64 and is not pinned to the
+ * TMscore / TMalign binaries; TM-align also searches the residue alignment, so its number is usually the same or higher.
+ *   a, b       host float64 [n_res][3] CA traces; pair p = rows offsets[p] .. offsets[p] + lens[p] - 1 of each, packed
+ *              back to back like fd_superpose_rmsd's; 1 <= lens[p] <= FDMI_TM_MAX_LEN; finite, |coordinate| <= 1e6
+ *   norm_lens  int32 [n_pairs] normalisation lengths Ln >= lens[p], or NULL for Ln = lens[p]
+ *   stride     >= 1: seed fragments start every stride residues (1: every start, the published search)
+ *   tm_out     float64 [n_pairs]: max over rotations R and translations t found by the search of
+ *              (1 / Ln) * sum_i 1 / (1 + (|R a_i + t - b_i| / d0)^2), d0 = 1.24 cbrt(Ln - 15) - 1.8 (0.5 for Ln <= 21)
+ *   transform_out  NULL, or float64 [n_pairs][12]: R row-major, then t, with b ~ R a + t at that maximum.
+ * Synchronous; the result does not depend on the other pairs of the call. */
+int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens,
+                const int32_t* norm_lens, int n_pairs, int stride, double* tm_out, double* transform_out);
 
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
