@@ -8,10 +8,17 @@ reference's ``bin/sample.py`` (same flags, same files):
     <outdir>/sampled_pdb/generated_{i}.pdb        N-CA-C backbones built by NeRF on the device (:369, :105-128)
     with --fullhistory: sampled_angles/sample_history/generated_{i}/generated_{i}_timestep_{t}.csv.gz and
                         sampled_pdb/sample_history/generated_{i}/generated_{i}_timestep_{t}.pdb (:371-398)
+    with --psea: plots/ss_cooccurrence_sampled.json  {generated_{i}.pdb: [n_alpha, n_beta]} of the final backbones and
+                 plots/ss_cooccurrence_sampled.pdf   their 2-D histogram, when matplotlib is installed (:456-469)
 
-What is NOT here (outside the sampler path): the matplotlib / astropy plots, secondary-structure
-annotation and the --testcomparison statistics against the CATH test set (they need the dataset pipeline);
---testcomparison therefore raises, --nopsea is accepted and ignored.  The model must be a local directory
+The secondary structures are annotated on the device (structures.count_secondary_structures: P-SEA, in place of
+biotite's annotate_sse) from the coordinates of the backbones just written, without reading the files back.  The step
+is opt-in: the reference runs it unless --nopsea is given, here it runs only with --psea, and without --psea the
+output tree is what it was before the step existed; --nopsea is accepted and changes nothing.
+
+What is NOT here (outside the sampler path): the angle-distribution plots (matplotlib / astropy) and the
+--testcomparison statistics against the CATH test set (they need the dataset pipeline); --testcomparison therefore
+raises.  The model must be a local directory
 (no network): training_args.json, config.json, models/best_by_valid/*.ckpt [, training_mean_offset.npy].
 
 One process per GPU under ``torchrun`` shards every batch over the GPUs (sampling.sample); rank 0 writes the files.
@@ -30,8 +37,8 @@ if REPO not in sys.path:
 import pandas as pd  # noqa: E402
 import torch  # noqa: E402
 
-from foldingdiff_amd import modelling, sampling  # noqa: E402
-from foldingdiff_amd.angles_and_coords import write_preds_pdb_folder  # noqa: E402
+from foldingdiff_amd import modelling, sampling, structures  # noqa: E402
+from foldingdiff_amd.angles_and_coords import coords_as_written, write_preds_pdb_folder  # noqa: E402
 from foldingdiff_amd.datasets import AnglesEmptyDataset, NoisedAnglesDataset  # noqa: E402
 
 # the value the reference's default seed expression (bin/sample.py:34-37) evaluates to
@@ -64,7 +71,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("-b", "--batchsize", type=int, default=512, help="Batch size to use when sampling")
     parser.add_argument("--fullhistory", action="store_true", help="Store full history, not just final structure")
     parser.add_argument("--testcomparison", action="store_true", help="(not available: needs the CATH data pipeline)")
-    parser.add_argument("--nopsea", action="store_true", help="accepted for compatibility; no PSEA step exists here")
+    psea = parser.add_mutually_exclusive_group()
+    psea.add_argument("--psea", action="store_true",
+                      help="count the helices and strands of the sampled backbones (P-SEA on the device) into plots/ss_cooccurrence_sampled.json [.pdf]")
+    psea.add_argument("--nopsea", action="store_true", help="accepted for compatibility: the P-SEA step runs only with --psea")
     parser.add_argument("--seed", type=int, default=SEED, help="Random seed")
     parser.add_argument("--device", type=str, default="cuda:0", help="Device to use")
     return parser
@@ -126,7 +136,8 @@ def main(argv=None) -> None:
         logging.info(f"Writing sampled angles to {sampled_angles_folder}")
         for i, s in enumerate(sampled_dfs):
             s.to_csv(sampled_angles_folder / f"generated_{i}.csv.gz")
-        write_preds_pdb_folder(sampled_dfs, str(outdir / "sampled_pdb"))
+        final_coords = []
+        pdb_files = write_preds_pdb_folder(sampled_dfs, str(outdir / "sampled_pdb"), coords_out=final_coords)
         if args.fullhistory:
             full_history_angles_dir = sampled_angles_folder / "sample_history"
             os.makedirs(full_history_angles_dir)
@@ -140,6 +151,16 @@ def main(argv=None) -> None:
                     snapshot_df.to_csv(ith_angle_dir / f"generated_{i}_timestep_{timestep}.csv.gz")
                 write_preds_pdb_folder(snapshot_dfs, str(full_history_pdb_dir / f"generated_{i}"),
                                        basename_prefix=f"generated_{i}_timestep_")
+        if args.psea:
+            # the reference annotates the files it has just written (make_ss_cooccurrence_plot over sampled_pdb/*.pdb,
+            # bin/sample.py:456-469); the same three-decimal coordinates are taken from memory here
+            plotdir = outdir / "plots"
+            os.makedirs(plotdir, exist_ok=True)
+            kept = [(os.path.basename(f), xyz) for f, xyz in zip(pdb_files, final_coords) if f]
+            device_index = torch.device(args.device).index or 0
+            counts = structures.count_secondary_structures([coords_as_written(xyz[1::3]) for _, xyz in kept], device=device_index)
+            structures.write_ss_cooccurrence([name for name, _ in kept], counts, json_file=str(plotdir / "ss_cooccurrence_sampled.json"),
+                                             outpdf=str(plotdir / "ss_cooccurrence_sampled.pdf"), title="Secondary structure co-occurrence, sampled")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -17,7 +17,7 @@ FD_DEC = {"mlp": 0, "linear": 1}
 FD_PREC_F32 = 0
 FD_PREC_F16X3 = 1
 FD_PREC = {"f32": 0, "f16x3": 1}
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class FdmiError(RuntimeError):
@@ -68,6 +68,7 @@ _SIGNATURES = {
     "fd_internal_coords": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P]),
     "fd_superpose_rmsd": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "fd_tm_score": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "fd_annotate_sse": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P]),
     "fd_shift_trim_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fd_test_wrap": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, _P]),
     "fd_test_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),

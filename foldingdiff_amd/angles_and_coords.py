@@ -87,17 +87,27 @@ def create_new_chain_nerf(out_fname: str, dists_and_angles, angles_to_set: Optio
     return _write_chains([out_fname], [dists_and_angles], angles_to_set, dists_to_set, center_coords, device)[0]
 
 
+def coords_as_written(coords: np.ndarray) -> np.ndarray:
+    """float64 coordinates as a reader of ``write_coords_to_pdb``'s file gets them: three decimals, rounded by the
+    same formatting."""
+    coords = np.asarray(coords, dtype=np.float64)
+    return np.array([float(f"{v:.3f}") for v in coords.ravel()], dtype=np.float64).reshape(coords.shape)
+
+
 def write_preds_pdb_folder(final_sampled: Sequence, outdir: str, basename_prefix: str = "generated_",
-                           threads: Optional[int] = None, device: int = 0) -> List[str]:
+                           threads: Optional[int] = None, device: int = 0, coords_out: Optional[list] = None) -> List[str]:
     """``{outdir}/{basename_prefix}{i}.pdb`` for every sampled chain (bin/sample.py:105-128).  ``threads`` is
-    accepted for signature compatibility; the coordinates come from a single device launch."""
+    accepted for signature compatibility; the coordinates come from a single device launch.  A list given as
+    ``coords_out`` receives, per chain, the [3n, 3] coordinates that were written (``None`` for a chain with NaN)."""
     os.makedirs(outdir, exist_ok=True)
     logging.info(f"Writing sampled angles as PDB files to {outdir}")
     names = [os.path.join(outdir, f"{basename_prefix}{i}.pdb") for i in range(len(final_sampled))]
-    return _write_chains(names, list(final_sampled), None, None, True, device)
+    return _write_chains(names, list(final_sampled), None, None, True, device, coords_out)
 
 
-def _write_chains(fnames, chains, angles_to_set, dists_to_set, center_coords, device):
+def _write_chains(fnames, chains, angles_to_set, dists_to_set, center_coords, device, coords_out=None):
+    if coords_out is not None:
+        coords_out[:] = [None] * len(chains)
     if not chains:
         return []
     groups = {}   # chains sharing a column set go through one fd_nerf call
@@ -114,4 +124,6 @@ def _write_chains(fnames, chains, angles_to_set, dists_to_set, center_coords, de
                 continue
             assert xyz.shape == (3 * len(vals), 3), f"Unexpected shape: {xyz.shape} for input of {len(vals)}"
             written[i] = write_coords_to_pdb(xyz, fnames[i])
+            if coords_out is not None:
+                coords_out[i] = xyz
     return written

@@ -1082,7 +1082,7 @@ static int check_packed(const int32_t* offsets, const int32_t* lens, int n, long
 
 // one synchronous device round trip: inputs up, one launch, the outputs down; an output with a null host pointer is a
 // device workspace that stays there.  The launch gets the device buffers in order, inputs first, and may return a
-// hipError_t (fd_internal_coords, fd_superpose_rmsd, fd_tm_score)
+// hipError_t (fd_internal_coords, fd_superpose_rmsd, fd_tm_score, fd_annotate_sse)
 template <typename Launch>
 static int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs,
                             std::initializer_list<std::pair<void*, size_t>> outputs, Launch launch) {
@@ -1984,6 +1984,31 @@ int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* 
                                max_len, static_cast<double*>(d[7]), static_cast<double*>(d[8]), static_cast<double*>(d[9]),
                                nullptr);
       });
+}
+
+int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                    int8_t* sse_out, int32_t* counts_out) {
+  if (!ca || !offsets || !lens || !sse_out) return fail(FD_E_INVALID, "null argument");
+  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
+  int max_len = 0;
+  for (int c = 0; c < n_chains; ++c) {
+    if (lens[c] < 1 || lens[c] > FDMI_SSE_MAX_LEN)
+      return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", c, lens[c], FDMI_SSE_MAX_LEN);
+    max_len = std::max(max_len, (int)lens[c]);
+  }
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 3, &n_res)) return rc;
+  // finite coordinates within 1e6 A: every squared distance stays far from overflow
+  for (long long k = 0; k < n_res * 3; ++k)
+    if (!(std::fabs(ca[k]) <= 1e6))
+      return fail(FD_E_INVALID, "coordinate %d of residue %lld is not finite or beyond 1e6: %g", (int)(k % 3), k / 3, ca[k]);
+  const size_t na = (size_t)n_res, nc = (size_t)n_chains;
+  return device_roundtrip(device_id, {{ca, na * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}},
+                          {{sse_out, na}, {counts_out, nc * 2 * 4}}, [&](const std::vector<void*>& d) {
+                            launch_psea(static_cast<const double*>(d[0]), static_cast<const int*>(d[1]),
+                                        static_cast<const int*>(d[2]), n_chains, max_len, static_cast<signed char*>(d[3]),
+                                        static_cast<int*>(d[4]), nullptr);
+                          });
 }
 
 int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L, const void* lens_dev, const void* item_off_dev,

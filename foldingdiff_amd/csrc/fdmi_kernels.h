@@ -110,6 +110,11 @@ size_t tm_workspace_bytes(int n_chunks);
 hipError_t launch_tm_score(const double* a, const double* b, const double* cent, const int* offsets, const int* lens,
                            const int* norm_lens, const int* chunk_off, int n_pairs, int n_chunks, int stride, int max_len,
                            double* ws, double* tm_out, double* transform_out, hipStream_t s);
+// P-SEA secondary structure of CA traces (psea.hip), one workgroup per chain: sse_out [sum lens] (0 coil, 1 helix,
+// 2 strand), counts_out [n_chains][2] (runs of helix, runs of strand).  max_len = the longest chain (<= 2048: 29 bytes
+// of LDS per residue).
+void launch_psea(const double* ca, const int* offsets, const int* lens, int n_chains, int max_len, signed char* sse_out,
+                 int* counts_out, hipStream_t s);
 
 // *t_dev -= 1  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, hipStream_t s);

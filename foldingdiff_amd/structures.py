@@ -1,5 +1,6 @@
 """
-Input side of the package: PDB backbones -> internal coordinates -> datasets, and TM-score / superposed-RMSD scoring.
+Input side of the package: PDB backbones -> internal coordinates -> datasets, TM-score / superposed-RMSD scoring, and
+secondary-structure annotation.
 
 The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
 
@@ -11,7 +12,10 @@ The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
 * the scorers of ``sampling.get_reconstruction_error`` (the reference's ``_score_angles``, foldingdiff/sampling.py:266-284,
   which runs the external TM-align binary): ``tm_scorer`` scores with the TM-score of the CA traces (``fd_tm_score``,
   the published TM-score search restated on the device; see ``tm_score``), ``rmsd_scorer`` with the backbone RMSD
-  after optimal superposition (``fd_superpose_rmsd``).  Each scores a whole call with one launch.
+  after optimal superposition (``fd_superpose_rmsd``).  Each scores a whole call with one launch;
+* ``count_structures_in_pdb`` / ``make_ss_cooccurrence_plot`` (bin/annot_secondary_structures.py:64-166), which take
+  the labels from biotite's ``annotate_sse``: ``annotate_sse`` here restates that algorithm (P-SEA) on the device
+  (``fd_annotate_sse``, every chain of a call in one launch), ``ss_cooccurrence`` is the plot function.
 
 PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PDBFile`` for them):
 
@@ -28,6 +32,7 @@ PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PD
 import ctypes as C
 import glob
 import gzip
+import json
 import logging
 import os
 from typing import Callable, List, Optional, Sequence, Tuple, Union
@@ -488,3 +493,128 @@ class TmScorer:
 
 
 tm_scorer = TmScorer()
+
+
+# ---------------------------------------------------------------------------------------------------- secondary structure
+_SSE_LABELS = np.array(["c", "a", "b"])
+
+
+def _annotate(ca_list: Sequence[np.ndarray], device: int) -> Tuple[List[np.ndarray], np.ndarray]:
+    """(int8 labels per chain, int32 [len, 2] counts) of one ``fd_annotate_sse`` call."""
+    ca = [np.asarray(x, dtype=np.float64) for x in ca_list]
+    for i, x in enumerate(ca):
+        if x.ndim != 2 or x.shape[1] != 3 or not 1 <= len(x) <= 2048:
+            raise ValueError(f"chain {i}: {x.shape}; expected an [n, 3] CA trace with 1 <= n <= 2048")
+    n = len(ca)
+    counts = np.zeros((n, 2), dtype=np.int32)
+    if n == 0:
+        return [], counts
+    lens = np.array([len(x) for x in ca], dtype=np.int32)
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+    X = np.ascontiguousarray(np.concatenate(ca))
+    sse = np.empty((len(X),), dtype=np.int8)
+    _binding.check(_binding.load().fd_annotate_sse(
+        device, X.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), n,
+        sse.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+    return [sse[o: o + m] for o, m in zip(offsets, lens)], counts
+
+
+def annotate_sse(ca_list: Sequence[np.ndarray], device: int = 0) -> List[np.ndarray]:
+    """Secondary structure of each CA trace ([n_i, 3], any float dtype, 1 <= n_i <= 2048): a ``'U1'`` array of 'a'
+    (helix), 'b' (strand) and 'c' (coil) per chain, all chains in one ``fd_annotate_sse`` launch.
+
+    The labels are those of the P-SEA algorithm (Labesse et al. 1997) as biotite's ``annotate_sse`` restates it, from
+    CA-CA distances, angles and dihedrals alone (DESIGN.md "Secondary structure (P-SEA)" states the rules).  They are
+    not pinned to biotite."""
+    return [_SSE_LABELS[s] for s in _annotate(ca_list, device)[0]]
+
+
+def count_secondary_structures(ca_list: Sequence[np.ndarray], device: int = 0) -> np.ndarray:
+    """int [len(ca_list), 2]: the number of helices and of strands (maximal runs of 'a' and of 'b' in
+    ``annotate_sse``'s labels) of each CA trace, in one launch."""
+    return _annotate(ca_list, device)[1].astype(np.int64)
+
+
+def _single_chain_ca(fname: str) -> Optional[np.ndarray]:
+    """CA trace of a file for ``count_structures_in_pdb``: ``None`` for a file ``read_backbone`` rejects (more than one
+    model, like the reference; also a residue without N / CA / C, parser rule 7); one chain only, as the reference
+    asserts."""
+    assert os.path.exists(fname), fname
+    bb = read_backbone(fname)
+    if bb is None:
+        return None
+    chains = sorted({rid[0] for rid in bb[1]})
+    assert len(chains) == 1, f"{fname}: chains {chains}, expected one"
+    return bb[0][1::3]
+
+
+def _count_files(fnames: Sequence[str], device: int) -> List[Tuple[int, int]]:
+    traces = [_single_chain_ca(f) for f in fnames]
+    ok = [i for i, t in enumerate(traces) if t is not None]
+    counts = count_secondary_structures([traces[i] for i in ok], device=device)
+    out = [(-1, -1)] * len(fnames)
+    for i, c in zip(ok, counts):
+        out[i] = (int(c[0]), int(c[1]))
+    return out
+
+
+def count_structures_in_pdb(fname: str, backend: str = "psea", device: int = 0) -> Tuple[int, int]:
+    """(# alpha helices, # beta strands) of the single chain in a PDB file, (-1, -1) for a file with several models:
+    ``count_structures_in_pdb`` (bin/annot_secondary_structures.py:64-105) with ``annotate_sse`` above."""
+    if backend != "psea":
+        raise ValueError(f"Unrecognized backend for calculating secondary structures: {backend} (only psea exists here)")
+    return _count_files([fname], device)[0]
+
+
+def write_ss_cooccurrence(names: Sequence[str], counts: Sequence[Sequence[int]], json_file: str = "", outpdf: str = "",
+                          title: str = "Secondary structure co-occurrence", **kwargs) -> None:
+    """The output half of ``make_ss_cooccurrence_plot`` (bin/annot_secondary_structures.py:137-166) for counts already
+    at hand: the JSON ``{name: [n_alpha, n_beta]}`` and the 2-D histogram (``**kwargs`` go to ``hist2d``).  Without
+    matplotlib the plot is skipped with a log line."""
+    counts = [(int(a), int(b)) for a, b in counts]
+    assert len(names) == len(counts)
+    if json_file:
+        logging.info(f"Writing json of ss counts to {json_file}")
+        with open(json_file, "w") as sink:
+            json.dump({k: list(ab) for k, ab in zip(names, counts)}, sink, indent=4)
+    if not outpdf:
+        return
+    if not counts:
+        logging.warning(f"No structures to plot, not writing {outpdf}")
+        return
+    try:
+        from matplotlib.figure import Figure
+    except ImportError as e:
+        logging.warning(f"matplotlib is not available ({e}), not writing {outpdf}")
+        return
+    fig = Figure(dpi=300)
+    ax = fig.subplots()
+    h = ax.hist2d([c[0] for c in counts], [c[1] for c in counts], bins=np.arange(10), density=True, vmin=0.0, **kwargs)
+    ax.set_xlabel(r"Number of $\alpha$ helices", fontsize=12)
+    ax.set_ylabel(r"Number of $\beta$ sheets", fontsize=12)
+    if title:
+        ax.set_title(title.strip(), fontsize=14)
+    cbar = fig.colorbar(h[-1], ax=ax)
+    cbar.ax.set_ylabel("Frequency", fontsize=12)
+    fig.savefig(outpdf, bbox_inches="tight")
+
+
+def ss_cooccurrence(pdb_files: Sequence[str], json_file: str = "", outpdf: str = "", max_seq_len: int = 0,
+                    title: str = "Secondary structure co-occurrence", device: int = 0, **kwargs) -> Tuple[np.ndarray, np.ndarray]:
+    """``make_ss_cooccurrence_plot`` (bin/annot_secondary_structures.py:108-166): helix and strand counts of every
+    file from one ``fd_annotate_sse`` call, files that give (-1, -1) dropped, files of more than ``max_seq_len``
+    residues (when > 0) left out; writes ``json_file`` and ``outpdf`` when named (``write_ss_cooccurrence``) and
+    returns (alpha counts, beta counts).  The JSON pairs each kept file with its own counts (the reference zips the
+    unfiltered file list with the filtered counts)."""
+    pdb_files = list(pdb_files)
+    if max_seq_len > 0:
+        orig_len = len(pdb_files)
+        parsed = [read_backbone(p) for p in pdb_files]
+        pdb_files = [p for p, bb in zip(pdb_files, parsed) if bb is None or len(bb[1]) <= max_seq_len]
+        logging.info(f"Filtering out sequences with more than {max_seq_len} residues: {orig_len} --> {len(pdb_files)}")
+    logging.info(f"Calculating {len(pdb_files)} structures using psea")
+    kept = [(p, c) for p, c in zip(pdb_files, _count_files(pdb_files, device)) if c != (-1, -1)]
+    write_ss_cooccurrence([os.path.basename(p) for p, _ in kept], [c for _, c in kept], json_file=json_file,
+                          outpdf=outpdf, title=title, **kwargs)
+    counts = np.array([c for _, c in kept], dtype=np.int64).reshape(-1, 2)
+    return counts[:, 0], counts[:, 1]

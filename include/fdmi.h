@@ -38,7 +38,8 @@ extern "C" {
  *    the two-kernel path; option "fuse_ffn" (round 6) */
 /* 5: fd_internal_coords, fd_superpose_rmsd (coordinates -> internal coordinates, superposed RMSD) */
 /* 6: fd_tm_score (TM-score of residue-paired CA traces) */
-#define FDMI_ABI_VERSION 6
+/* 7: fd_annotate_sse (P-SEA secondary structure of CA traces) */
+#define FDMI_ABI_VERSION 7
 
 enum {
   FD_OK = 0,
@@ -295,6 +296,20 @@ int fd_superpose_rmsd(int device_id, const double* a, const double* b, const int
  * Synchronous; the result does not depend on the other pairs of the call. */
 int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens,
                 const int32_t* norm_lens, int n_pairs, int stride, double* tm_out, double* transform_out);
+
+/* Longest chain fd_annotate_sse takes: the trace and its per-residue state sit in one workgroup's LDS (29 B per residue). */
+#define FDMI_SSE_MAX_LEN 2048
+
+/* Secondary structure of CA traces: annotate_sse (biotite) as count_structures_in_pdb uses it
+ * (bin/annot_secondary_structures.py:64-105).  It restates the P-SEA algorithm (Labesse et al. 1997; DESIGN.md
+ * "Secondary structure (P-SEA)" has the exact rules) in fp64 and is not pinned to biotite.
+ *   ca          host float64 [n_res][3] CA traces; chain c = rows offsets[c] .. offsets[c] + lens[c] - 1, packed back to
+ *               back like fd_tm_score's; 1 <= lens[c] <= FDMI_SSE_MAX_LEN; finite, |coordinate| <= 1e6
+ *   sse_out     int8 [n_res]: 0 coil ('c'), 1 helix ('a'), 2 strand ('b') per residue
+ *   counts_out  NULL, or int32 [n_chains][2]: the number of maximal runs of helix and of strand labels per chain
+ * Synchronous; the result does not depend on the other chains of the call. */
+int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                    int8_t* sse_out /* [sum lens]: 0 c, 1 a, 2 b */, int32_t* counts_out /* [n_chains][2] or NULL */);
 
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
