@@ -11,11 +11,13 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/fdmi.h"
 #include "fdmi_kernels.h"
+#include "launch_common.h"
 
 using namespace fdmi;
 
@@ -76,6 +78,27 @@ const char* const kClassName[KC_COUNT] = {
     "embed_ln_time", "gemm_qkv", "gemm_v", "attention", "gemm_attn_out", "layernorm_attn", "gemm_ffn_up",
     "gemm_ffn_down", "layernorm_ffn", "gemm_head_dense1", "head_update_wrap", "step_advance", "qkv_attention_fused", "ffn_fused", "attn_out_ffn_fused"};
 
+// The launch sequence of one timestep: every choice between kernels, made once per step (plan_step) from the model's options,
+// the environment overrides and the workspace's shape.  run_step launches from it; a captured graph is current for as long as
+// the plan it was captured with is the plan the options lead to (graph_current).
+struct StepPlan {
+  enum Attn { ATTN_QKV, ATTN_QK_VT, ATTN_FUSED16, ATTN_FUSED32 };  // q | k | v in one launch; q | k + v^T; projection + attention fused:
+                                                                   // seq_attn16.hip (16-row waves) / seq_attn.hip (32-row waves)
+  enum Ffn { FFN_GEMMS, FFN_FUSED, FFN_TAIL };  // two GEMMs; ffn16.hip; ffn16.hip with BertSelfOutput in front of it in the same launch
+  bool img = false;       // the row-image kernels (FD_PREC_F16X3), else the fp32 ones
+  bool fuse_ln = false;   // fp32 path: the LN-fused GEMMs
+  int attn = ATTN_QKV;
+  bool attn_gen = false;  // attention_gen.hip (arbitrary key masks, head sizes 64 / 96 / 128), else attention_img.hip
+  int ffn = FFN_GEMMS;
+  bool split_ln = false;  // d_model > 384: a LayerNorm row does not fit one 384-column tile -- fp32 rows, then the LayerNorm kernel
+  int tail_qk = 0, tail_d = 0, tail_ff = 0;  // GemmImgArgs::tail of the GEMMs of N = 3 d (2 d when v^T is its own launch), d and d_ff
+  bool fused_attn() const { return attn == ATTN_FUSED16 || attn == ATTN_FUSED32; }
+  bool operator==(const StepPlan& o) const {
+    return std::tie(img, fuse_ln, attn, attn_gen, ffn, split_ln, tail_qk, tail_d, tail_ff) ==
+           std::tie(o.img, o.fuse_ln, o.attn, o.attn_gen, o.ffn, o.split_ln, o.tail_qk, o.tail_d, o.tail_ff);
+  }
+};
+
 struct Workspace {
   int B = 0, L = 0;
   float *x = nullptr, *eps = nullptr, *h = nullptr, *qkv = nullptr, *ctx = nullptr, *a = nullptr, *tmp = nullptr,
@@ -93,11 +116,7 @@ struct Workspace {
   unsigned char* kmask = nullptr;  // [B][L] explicit key mask of fd_forward_ex (allocated on first use)
   int* pos_ids = nullptr;          // [B][L] explicit position ids of fd_forward_ex (allocated on first use)
   hipGraphExec_t graph = nullptr;
-  int graph_fuse_ln = -2;  // option value the graph was captured with (-2: none)
-  int graph_varlen = -1;   // ... and the row mode (packed rows launch the slice-capable GEMM instantiation)
-  int graph_fuse_attn = -2;  // ... and the fused projection + attention choice
-  int graph_fuse_ffn = -2;   // ... and the fused feed-forward choice
-  int graph_rows_hint = -1;  // ... and the row count the launch-sequence choices were made for
+  StepPlan graph_plan;  // the launch sequence `graph` was captured with
   uint64_t last_use = 0;
   void release() {
     if (graph) (void)hipGraphExecDestroy(graph);
@@ -111,7 +130,11 @@ struct Workspace {
   }
 };
 
-constexpr long long kStampWords = 5 * 8 * 64 * 6 + 4 * 64 * 8 + 4 * 64 * 16 + 16384 + 8 * 16 * 16;  // (... + ffn16.hip's [8][16][16])  // (+ 32 K floats of register dumps, seq_attn.hip FDMI_SA_DUMP)
+// debug cycle stamps (FDMI_STAMPS=1), one table per kernel family back to back (in 8-byte words): the GEMMs' [5][8][64][6] first
+constexpr long long kStampAttn = 5 * 8 * 64 * 6;                     // attention [4][64][8]
+constexpr long long kStampSeqAttn = kStampAttn + 4 * 64 * 8;          // fused attention [4][64][16] (+ 32 K floats of register dumps, seq_attn.hip FDMI_SA_DUMP)
+constexpr long long kStampFfn = kStampSeqAttn + 4 * 64 * 16 + 16384;  // ffn16.hip's [8][16][16]
+constexpr long long kStampWords = kStampFfn + 8 * 16 * 16;
 
 struct PendingEvent {
   int cls;
@@ -146,8 +169,9 @@ struct fd_model {
   int debug_layer = 0; // layer whose scales fd_debug_read uses
   int split_qkv = 0; // row-image path: 1 = q | k and v^T as two launches even when one would do (A/B, tests)
   int varlen = 0;    // row-image path: only the first lens[b] positions of a sequence are token rows
-  int fuse_attn = -1;  // row-image path: q | k | v projection + attention as ONE kernel per sequence (seq_attn.hip): -1 auto (padded rows of
-                     // 97 .. 128 positions), 0 never, 1 wherever the kernel applies (packed rows too)
+  int fuse_attn = -1;  // row-image path: q | k | v projection + attention as ONE kernel per sequence: -1 auto (seq_attn16.hip for padded rows
+                     // of 97 .. 128 positions in whole rounds of the CUs), 0 never, 1 seq_attn16.hip wherever it applies (any L <= 128, packed
+                     // rows too), 2 seq_attn.hip (32-row waves) wherever it applies (97 .. 128 positions)
   int fuse_ffn = -1;   // row-image path: BertIntermediate + BertOutput as ONE kernel (ffn16.hip): -1 auto (whole rounds of 128-row passes: 2),
                      // 0 never, 1 wherever the kernel applies, 2 with BertSelfOutput in front of it in the same launch
   int rows_hint = 0;   // packed rows: the caller's exact count of token rows of the next calls (sum of the lengths rounded up to 8), or 0 = unknown;
@@ -658,70 +682,95 @@ int harvest(fd_model* m) {
     if (rc_) return rc_;                                  \
   } while (0)
 
-// One reverse-diffusion step = BertForDiffusionBase.forward (modelling.py:384-484) + the
-// p_sample update and wrap (sampling.py:62-75, :119-130), as a fixed kernel sequence.
-void gemm(fd_model* m, int epi, const float* A, const float* W, const float* bias, const float* resid, float* C, int M,
-          int N, int K, hipStream_t s) {
-  (void)m;
-  launch_gemm_f32(epi, A, W, bias, resid, C, M, N, K, s);
+// an attempted launch that did not happen has recorded an empty bracket: drop it
+void prof_drop(fd_model* m, bool on) {
+  if (!on) return;
+  const PendingEvent p = m->pending.back();
+  m->pending.pop_back();
+  m->event_pool.push_back(p.e0);
+  m->event_pool.push_back(p.e1);
 }
 
-int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode);
+// A/B overrides from the environment, read once: FDMI_FUSE_ATTN / FDMI_FUSE_FFN stand in for the options of the same name while
+// those are -1 (auto); FDMI_STAMPS=1 makes the row-image kernels write cycle stamps (fd_model::stamps)
+struct EnvOverrides {
+  int fuse_attn, fuse_ffn;
+  bool stamps;
+};
+const EnvOverrides& env_overrides() {
+  static const EnvOverrides env = [] {
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    return EnvOverrides{num("FDMI_FUSE_ATTN", -1), num("FDMI_FUSE_FFN", -1), num("FDMI_STAMPS", 0) != 0};
+  }();
+  return env;
+}
 
-int run_step(fd_model* m, hipStream_t s, const StepMode& mode) {
-  if (m->ws.img) return run_step_img(m, s, mode);
-  const fd_config& c = m->cfg;
-  Workspace& w = m->ws;
-  const int B = w.B, L = w.L, M = B * L, d = c.d_model, ff = c.d_ff, F = c.n_features;
-  const bool fuse_ln = m->fuse_ln > 0;  // fp32 path: the LN-fused fp32 GEMM is slower than GEMM + LayerNorm, off unless asked for
-  PROF(KC_EMBED, launch_embed(w.x, m->w_in, m->b_in, m->pos_emb, m->emb_g, m->emb_b, c.ln_eps, m->time_table, w.t_dev,
-                              w.h, B, L, F, d, s));
-  for (int li = 0; li < c.n_layers; ++li) {
-    const LayerDev& lw = m->layers[li];
-    PROF(KC_GEMM_QKV, gemm(m, EPI_BIAS, w.h, lw.wqkv, lw.bqkv, nullptr, w.qkv, M, 3 * d, d, s));
-    bool ok = true;
-    PROF(KC_ATTN, ok = launch_attention_f32(w.qkv, lw.demb, w.lens, w.ctx, B, L, c.n_heads, c.max_pos, s,
-                                            c.pos_type == FD_POS_RELATIVE_KEY_QUERY));
-    if (!ok) return fail(FD_E_UNSUPPORTED, "attention: sequence length %d not supported by the fp32 kernel (max 128)", L);
-    bool fused = false;
-    if (fuse_ln)
-      PROF(KC_GEMM_OUT, fused = launch_gemm_f32_ln(w.ctx, lw.wo, lw.bo, w.h, lw.ln1g, lw.ln1b, c.ln_eps, w.a, M, d, d, s));
-    if (!fused) {
-      if (fuse_ln && mode.profile) {  // the attempted launch recorded an empty bracket; drop it
-        PendingEvent p = m->pending.back();
-        m->pending.pop_back();
-        m->event_pool.push_back(p.e0);
-        m->event_pool.push_back(p.e1);
-      }
-      PROF(KC_GEMM_OUT, gemm(m, EPI_BIAS_RESID, w.ctx, lw.wo, lw.bo, w.h, w.tmp, M, d, d, s));
-      PROF(KC_LN1, launch_layernorm(w.tmp, lw.ln1g, lw.ln1b, c.ln_eps, w.a, M, d, s));
-    }
-    PROF(KC_GEMM_UP, gemm(m, EPI_BIAS_GELU, w.a, lw.wi, lw.bi, nullptr, w.g, M, ff, d, s));
-    fused = false;
-    if (fuse_ln)
-      PROF(KC_GEMM_DOWN, fused = launch_gemm_f32_ln(w.g, lw.wd, lw.bd, w.a, lw.ln2g, lw.ln2b, c.ln_eps, w.h, M, d, ff, s));
-    if (!fused) {
-      if (fuse_ln && mode.profile) {
-        PendingEvent p = m->pending.back();
-        m->pending.pop_back();
-        m->event_pool.push_back(p.e0);
-        m->event_pool.push_back(p.e1);
-      }
-      PROF(KC_GEMM_DOWN, gemm(m, EPI_BIAS_RESID, w.g, lw.wd, lw.bd, w.a, w.tmp, M, d, ff, s));
-      PROF(KC_LN2, launch_layernorm(w.tmp, lw.ln2g, lw.ln2b, c.ln_eps, w.h, M, d, s));
-    }
+// Which kernels make up a timestep on workspace `w` (the model's device is current).  key_mask: fd_forward_ex's arbitrary key mask.
+// The weight images every layer has are asked of layer 0 (fd_finalize uploads the same set for every layer).
+StepPlan plan_step(const fd_model* m, const Workspace& w, bool key_mask) {
+  StepPlan p;
+  p.img = w.img;
+  if (!p.img) {
+    p.fuse_ln = m->fuse_ln > 0;  // fp32 path: the LN-fused fp32 GEMM is slower than GEMM + LayerNorm, off unless asked for
+    return p;
   }
+  const fd_config& c = m->cfg;
+  const LayerDev& lw = m->layers[0];
+  const EnvOverrides& env = env_overrides();
+  const int B = w.B, L = w.L, d = c.d_model, max_rows = w.cap, ncu = cu_count();
+  // the fused kernels are persistent, one workgroup per CU: do `items` of their work fill whole rounds of the CUs?  (512 on 256 CUs
+  // are two full rounds, 300 would leave the second round four-fifths empty and 8 would run on 8 CUs)
+  auto whole_rounds = [&](int items) {
+    const int rounds = (items + ncu - 1) / ncu;
+    return (double)items >= 0.94 * (double)rounds * ncu;
+  };
+  const bool fits_u32 = (size_t)w.cap * d * 4 < (1ull << 32) - 65536;  // (the fused kernels address the row images with 32-bit offsets)
+  // q | k | v projection + attention as ONE kernel per sequence: q, k and v never reach HBM.  fuse_attn: 1 = seq_attn16.hip (16-row
+  // waves, two per SIMD; any L <= 128, padded or packed rows), 2 = seq_attn.hip (round 5: 32-row waves, 96 < L <= 128), 0 = never.
+  // auto: seq_attn16.hip for padded rows of 97..128 positions when the batch (one workgroup = one sequence at a time) fills whole rounds.
+  // Measured (profiles/r06_seq_attn16_notes.log): packed rows of BASELINE C3's first chunk (B 512, lengths 50..101) are a tie with
+  // the two-kernel path (5.29 against 5.25 ms per step), its second chunk (B 268) and batches of a few sequences lose.
+  // (auto never reaches seq_attn.hip: its range and its upload condition are subsets of seq_attn16.hip's)
+  const int fuse_attn = m->fuse_attn >= 0 ? m->fuse_attn : env.fuse_attn;
+  const bool attn_auto = !m->varlen && L > 96 && whole_rounds(B);
+  const bool fused_ok = fuse_attn != 0 && (fuse_attn > 0 || attn_auto) && !key_mask && !m->split_qkv && fits_u32;
+  if (fused_ok && fuse_attn != 2 && lw.wsa16_i.p && seq_attn16_supported(d, c.n_heads, L, c.max_pos)) p.attn = StepPlan::ATTN_FUSED16;
+  else if (fused_ok && fuse_attn == 2 && lw.wsa_i.p && seq_attn_supported(d, c.n_heads, L, c.max_pos)) p.attn = StepPlan::ATTN_FUSED32;
+  // else q | k | v in one launch (the three column tiles of a row panel run side by side on one XCD: h is read from HBM once), or q | k + v^T
+  else p.attn = lw.wqkv_i.p && !m->split_qkv ? StepPlan::ATTN_QKV : StepPlan::ATTN_QK_VT;
+  // an arbitrary key mask: the general kernel (the tuned one builds its schedule on prefix masks); so do head sizes 64 / 96 / 128
+  p.attn_gen = key_mask || head_dim(c) != 32;
+  // BertIntermediate + BertOutput as ONE kernel (ffn16.hip): the 2 d wide intermediate never reaches HBM.  fuse_ffn 2 (and auto):
+  // BertSelfOutput (attention.output.dense + residual + LayerNorm) in front of it in the same launch, its output on chip too.  Passes
+  // of 128 rows: auto = the passes fill whole rounds (315 would leave the second round a quarter full where the tile GEMMs deal 6 + 1
+  // column tiles per pass).  Packed rows: by the caller's row count when it gave one -- the bound B * ceil8(L) overstates ragged batches
+  const int fuse_ffn = m->fuse_ffn >= 0 ? m->fuse_ffn : env.fuse_ffn;
+  const int rows_known = m->varlen && m->rows_hint > 0 && m->rows_hint <= max_rows ? m->rows_hint : max_rows;
+  const bool fused_ffn = fuse_ffn != 0 && (fuse_ffn > 0 || whole_rounds((rows_known + 127) / 128)) && lw.wff_i.p &&
+                         ffn16_supported(d, c.d_ff) && fits_u32;
+  p.ffn = !fused_ffn ? StepPlan::FFN_GEMMS : (fuse_ffn != 1 && lw.wtail_i.p && d <= 384) ? StepPlan::FFN_TAIL : StepPlan::FFN_FUSED;
+  p.split_ln = d > 384;
+  // do the tiles of an N-column GEMM over this workspace fill whole rounds of the launch's workgroups?  Padded rows: the row count
+  // is the workspace's capacity, known here; packed rows (sampling.sample): data dependent -> the slice-capable instantiation
+  auto tail_for = [&](int N) {
+    if (m->varlen) return 1;
+    const int ntiles = (max_rows / 128) * ((N + 383) / 384);
+    return ntiles % gemm_img_grid(max_rows, N) != 0 ? 1 : 0;
+  };
+  if (!p.fused_attn()) p.tail_qk = tail_for(p.attn == StepPlan::ATTN_QKV ? 3 * d : 2 * d);
+  p.tail_d = tail_for(d);
+  if (p.ffn == StepPlan::FFN_GEMMS) p.tail_ff = tail_for(c.d_ff);
+  return p;
+}
+
+// the arguments of the head + p_sample update launch that both paths share (the caller adds the head's input)
+UpdateArgs fill_update(const fd_model* m, const Workspace& w, const StepMode& mode) {
   UpdateArgs u;
   memset(&u, 0, sizeof u);
-  if (c.decoder == FD_DEC_MLP) {
-    PROF(KC_GEMM_HEAD, gemm(m, EPI_BIAS_GELU, w.h, m->hd_w1, m->hd_b1, nullptr, w.g, M, d, d, s));
-    u.g = w.g;
+  if (m->cfg.decoder == FD_DEC_MLP) {
     u.gamma = m->hd_g;
     u.beta = m->hd_b;
     u.do_ln = 1;
-  } else {
-    u.g = w.h;
-    u.do_ln = 0;
   }
   u.w2 = m->hd_w2;
   u.b2 = m->hd_b2;
@@ -729,27 +778,71 @@ int run_step(fd_model* m, hipStream_t s, const StepMode& mode) {
   u.coef = m->coef;
   u.t_dev = w.t_dev;
   u.T = m->T;
-  u.M = M;
-  u.L = L;
-  u.F = F;
-  u.d = d;
+  u.M = w.B * w.L;
+  u.L = w.L;
+  u.F = m->cfg.n_features;
+  u.d = m->cfg.d_model;
   u.ln_eps = 1e-12f;  // AnglesPredictor(eps=1e-12)  (modelling.py:187,199)
   u.angle_mask = mode.no_wrap ? 0u : m->angle_mask;
-  if (mode.forward_only) {
-    u.eps_out = w.eps;
-    u.x_out = nullptr;
-  } else {
-    u.eps_out = w.eps;
+  u.eps_out = w.eps;
+  if (!mode.forward_only) {
     u.x_out = w.x;
     if (mode.use_dyn) {
       u.dyn = w.dyn;
     } else {
       u.noise = mode.noise;
-      u.noise_stride = 0;
       u.t_start = mode.t_start;
     }
   }
-  if (mode.use_dyn) u.noise_stride = (long long)M * F;
+  if (mode.use_dyn) u.noise_stride = (long long)u.M * u.F;
+  return u;
+}
+
+int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode, const StepPlan& plan);
+
+// One reverse-diffusion step = BertForDiffusionBase.forward (modelling.py:384-484) + the
+// p_sample update and wrap (sampling.py:62-75, :119-130), as a fixed kernel sequence.
+int run_step(fd_model* m, hipStream_t s, const StepMode& mode) {
+  const StepPlan plan = plan_step(m, m->ws, mode.kmask != nullptr);
+  if (plan.img) return run_step_img(m, s, mode, plan);
+  const fd_config& c = m->cfg;
+  Workspace& w = m->ws;
+  const int B = w.B, L = w.L, M = B * L, d = c.d_model, ff = c.d_ff, F = c.n_features;
+  PROF(KC_EMBED, launch_embed(w.x, m->w_in, m->b_in, m->pos_emb, m->emb_g, m->emb_b, c.ln_eps, m->time_table, w.t_dev,
+                              w.h, B, L, F, d, s));
+  for (int li = 0; li < c.n_layers; ++li) {
+    const LayerDev& lw = m->layers[li];
+    PROF(KC_GEMM_QKV, launch_gemm_f32(EPI_BIAS, w.h, lw.wqkv, lw.bqkv, nullptr, w.qkv, M, 3 * d, d, s));
+    bool ok = true;
+    PROF(KC_ATTN, ok = launch_attention_f32(w.qkv, lw.demb, w.lens, w.ctx, B, L, c.n_heads, c.max_pos, s,
+                                            c.pos_type == FD_POS_RELATIVE_KEY_QUERY));
+    if (!ok) return fail(FD_E_UNSUPPORTED, "attention: sequence length %d not supported by the fp32 kernel (max 128)", L);
+    bool fused = false;  // (the LN-fused GEMM refuses the shapes it is not built for: GEMM + LayerNorm then)
+    if (plan.fuse_ln) {
+      PROF(KC_GEMM_OUT, fused = launch_gemm_f32_ln(w.ctx, lw.wo, lw.bo, w.h, lw.ln1g, lw.ln1b, c.ln_eps, w.a, M, d, d, s));
+      if (!fused) prof_drop(m, mode.profile);
+    }
+    if (!fused) {
+      PROF(KC_GEMM_OUT, launch_gemm_f32(EPI_BIAS_RESID, w.ctx, lw.wo, lw.bo, w.h, w.tmp, M, d, d, s));
+      PROF(KC_LN1, launch_layernorm(w.tmp, lw.ln1g, lw.ln1b, c.ln_eps, w.a, M, d, s));
+    }
+    PROF(KC_GEMM_UP, launch_gemm_f32(EPI_BIAS_GELU, w.a, lw.wi, lw.bi, nullptr, w.g, M, ff, d, s));
+    fused = false;
+    if (plan.fuse_ln) {
+      PROF(KC_GEMM_DOWN, fused = launch_gemm_f32_ln(w.g, lw.wd, lw.bd, w.a, lw.ln2g, lw.ln2b, c.ln_eps, w.h, M, d, ff, s));
+      if (!fused) prof_drop(m, mode.profile);
+    }
+    if (!fused) {
+      PROF(KC_GEMM_DOWN, launch_gemm_f32(EPI_BIAS_RESID, w.g, lw.wd, lw.bd, w.a, w.tmp, M, d, ff, s));
+      PROF(KC_LN2, launch_layernorm(w.tmp, lw.ln2g, lw.ln2b, c.ln_eps, w.h, M, d, s));
+    }
+  }
+  UpdateArgs u = fill_update(m, w, mode);
+  u.g = w.h;
+  if (c.decoder == FD_DEC_MLP) {
+    PROF(KC_GEMM_HEAD, launch_gemm_f32(EPI_BIAS_GELU, w.h, m->hd_w1, m->hd_b1, nullptr, w.g, M, d, d, s));
+    u.g = w.g;
+  }
   PROF(KC_HEAD_UPDATE, launch_head_update(u, s));
   if (mode.advance) PROF(KC_ADVANCE, launch_step_advance(w.t_dev, s));
   HIP_TRY(hipGetLastError());
@@ -759,13 +852,19 @@ int run_step(fd_model* m, hipStream_t s, const StepMode& mode) {
 
 // The same step on the row-image kernels (FD_PREC_F16X3): 6 launches per layer (QK, V^T, attention, attn-out + LN,
 // FFN-up + GELU, FFN-down + LN), every activation an fp16 hi|lo image, no separate step-advance launch.
-int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode) {
-  int launches = 0;
-#define DBG_STOP() do { if (m->debug_stop > 0 && ++launches >= m->debug_stop) { HIP_TRY(hipGetLastError()); return FD_OK; } } while (0)
+int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode, const StepPlan& plan) {
   const fd_config& c = m->cfg;
   Workspace& w = m->ws;
   const int B = w.B, L = w.L, d = c.d_model, ff = c.d_ff, F = c.n_features, H = sub_heads(c);  // H: 32-column sub-heads (= heads at head size 32)
   const int max_rows = w.cap;
+  // debug_stop counts in launches of the unfused sequence, so that a value means the same place under every plan: a fused launch
+  // takes the slots of the launches it stands for (fused attention two, fused feed-forward two, with BertSelfOutput in front three)
+  int slots = 0;
+  auto stop_after = [&](int n) { return m->debug_stop > 0 && (slots += n) >= m->debug_stop; };
+  auto done = [&]() -> int {
+    HIP_TRY(hipGetLastError());
+    return FD_OK;
+  };
   {
     EmbedImgArgs e;
     memset(&e, 0, sizeof e);
@@ -774,20 +873,13 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode) {
     e.h = w.himg; e.L = L; e.F = F; e.d = d; e.eps = c.ln_eps; e.out_scale = m->layers[0].s_h;
     e.pos_ids = mode.pos_ids;
     PROF(KC_EMBED, launch_embed_img(e, max_rows, s));
-      DBG_STOP();
+    if (stop_after(1)) return done();
   }
-  static const bool want_stamps = [] { const char* e = getenv("FDMI_STAMPS"); return e && atoi(e) != 0; }();
-  if (want_stamps && !m->stamps) {
+  if (env_overrides().stamps && !m->stamps) {
     HIP_TRY(hipMalloc((void**)&m->stamps, kStampWords * 8));
     HIP_TRY(hipMemset(m->stamps, 0, kStampWords * 8));
   }
-  // do the tiles of an N-column GEMM over this workspace fill whole rounds of the launch's workgroups?  Padded rows: the row count
-  // is the workspace's capacity, known here; packed rows (sampling.sample): data dependent -> the slice-capable instantiation
-  auto tail_for = [&](int N) {
-    if (m->varlen) return 1;
-    const int ntiles = (max_rows / 128) * ((N + 383) / 384);
-    return ntiles % gemm_img_grid(max_rows, N) != 0 ? 1 : 0;
-  };
+  auto stamps_at = [&](long long word) { return m->stamps ? m->stamps + word : nullptr; };
   auto base = [&]() {
     GemmImgArgs g;
     memset(&g, 0, sizeof g);
@@ -798,30 +890,25 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode) {
     g.eps = c.ln_eps;
     return g;
   };
+  // a d_model wide GEMM with residual + LayerNorm behind it: in its epilogue, or (a LayerNorm row does not fit one 384-column tile)
+  // as fp32 rows and the LayerNorm kernel
+  auto gemm_ln = [&](GemmImgArgs& g, int kc_gemm, int kc_ln) -> int {
+    g.N = d;
+    g.tail = plan.tail_d;
+    if (!plan.split_ln) {
+      PROF(kc_gemm, launch_gemm_img(EPI_IMG_LN, g, max_rows, s));
+      return FD_OK;
+    }
+    g.out_f32 = w.tmp;
+    PROF(kc_gemm, launch_gemm_img(EPI_IMG_BIAS, g, max_rows, s));
+    PROF(kc_ln, launch_ln_f32_img(w.tmp, g.gamma, g.beta, c.ln_eps, w.dims, g.out, d, g.out_scale, max_rows, s));
+    return FD_OK;
+  };
   for (int li = 0; li < c.n_layers; ++li) {
     const LayerDev& lw = m->layers[li];
     const float s_next = li + 1 < c.n_layers ? m->layers[li + 1].s_h : m->s_hfinal;
-    // q | k | v projection + attention as ONE kernel per sequence: q, k and v never reach HBM.  fuse_attn: 1 = seq_attn16.hip (16-row
-    // waves, two per SIMD; any L <= 128, padded or packed rows), 2 = seq_attn.hip (round 5: 32-row waves, 96 < L <= 128), 0 = never
-    static const int fuse_attn_env = [] { const char* e = getenv("FDMI_FUSE_ATTN"); return e ? atoi(e) : -1; }();
-    const int fuse_attn = m->fuse_attn >= 0 ? m->fuse_attn : fuse_attn_env;
-    // auto: padded rows of 97..128 positions when the batch fills whole rounds of the CUs (one workgroup = one sequence at a time: 512
-    // sequences on 256 CUs are two full rounds, 300 would leave the second round four-fifths empty and 8 sequences would run on 8 CUs).
-    // Measured (profiles/r06_seq_attn16_notes.log): packed rows of BASELINE C3's first chunk (B 512, lengths 50..101) are a tie with
-    // the two-kernel path (5.29 against 5.25 ms per step), its second chunk (B 268) and batches of a few sequences lose.
-    bool fused_auto = !m->varlen && L > 96;
-    if (fused_auto) {
-      const int ncu = gemm_img_grid(1 << 30, 384);  // (= the CU count, rounded down to whole XCDs)
-      const int rounds = (B + ncu - 1) / ncu;
-      fused_auto = (double)B >= 0.94 * (double)rounds * ncu;
-    }
-    const bool fused_ok = fuse_attn != 0 && (fuse_attn > 0 || fused_auto) && !mode.kmask && !m->split_qkv &&
-                          (size_t)w.cap * d * 4 < (1ull << 32) - 65536;
-    const bool fused16 = fused_ok && fuse_attn != 2 && lw.wsa16_i.p && seq_attn16_supported(d, c.n_heads, L, c.max_pos);
-    const bool fused32 = fused_ok && !fused16 && (fuse_attn == 2 || fuse_attn < 0) && lw.wsa_i.p && (fuse_attn == 2 || !m->varlen) &&
-                         seq_attn_supported(d, c.n_heads, L, c.max_pos);
-    const bool fused_attn = fused16 || fused32;
-    if (fused_attn) {
+    if (plan.fused_attn()) {
+      const bool fused16 = plan.attn == StepPlan::ATTN_FUSED16;
       SeqAttnArgs a;
       memset(&a, 0, sizeof a);
       a.himg = w.himg; a.himg_bytes = (unsigned)((size_t)w.cap * d * 4);
@@ -833,48 +920,38 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode) {
       a.acc_scale = 1.0f / (lw.s_h * wsa.scale);
       a.q_scale = lw.s_q; a.k_scale = lw.s_k; a.v_scale = lw.s_v; a.ctx_scale = lw.s_v;
       a.r_scale = lw.s_k / lw.demb_s.scale;
-      a.stamps = m->stamps ? m->stamps + 5 * 8 * 64 * 6 + 4 * 64 * 8 : nullptr;
-      if (fused16) {
-        bool launched = false;
-        PROF(KC_SEQ_ATTN, launched = launch_seq_attn16(a, s));
-        if (!launched) return fail(FD_E_HIP, "the fused projection + attention kernel could not be launched (%d bytes of LDS per workgroup)", 160256);
-      } else {
-        bool launched = false;
-        PROF(KC_SEQ_ATTN, launched = launch_seq_attn(a, s));
-        if (!launched) return fail(FD_E_HIP, "the 32-row fused projection + attention kernel could not be launched (%d bytes of LDS per workgroup)", 160 * 1024);
-      }
-      DBG_STOP();
-      DBG_STOP();  // (two launches of the other path: debug_stop counts stay comparable)
-    } else if (lw.wqkv_i.p && !m->split_qkv) {
-      // q | k | v in one launch: the three column tiles of a row panel run side by side on one XCD (h is read from HBM once)
-      GemmImgArgs g = base();
-      g.A = w.himg; g.W = static_cast<const unsigned char*>(lw.wqkv_i.p); g.bias = lw.bqkv;
-      g.qbuf = w.qbuf; g.kbuf = w.kbuf; g.vbuf = w.vbuf; g.N = 3 * d; g.K = d;
-      g.acc_scale = 1.0f / (lw.s_h * lw.wqkv_i.scale); g.q_scale = lw.s_q; g.k_scale = lw.s_k; g.v_scale = lw.s_v;
-      g.tail = tail_for(g.N);
-      PROF(KC_GEMM_QKV, launch_gemm_img(EPI_IMG_QKV, g, max_rows, s));
-      DBG_STOP();
+      a.stamps = stamps_at(kStampSeqAttn);
+      bool launched = false;
+      PROF(KC_SEQ_ATTN, launched = fused16 ? launch_seq_attn16(a, s) : launch_seq_attn(a, s));
+      if (!launched)
+        return fused16 ? fail(FD_E_HIP, "the fused projection + attention kernel could not be launched (%d bytes of LDS per workgroup)", 160256)
+                       : fail(FD_E_HIP, "the 32-row fused projection + attention kernel could not be launched (%d bytes of LDS per workgroup)", 160 * 1024);
+      if (stop_after(2)) return done();
     } else {
-      {
+      if (plan.attn == StepPlan::ATTN_QKV) {
+        GemmImgArgs g = base();
+        g.A = w.himg; g.W = static_cast<const unsigned char*>(lw.wqkv_i.p); g.bias = lw.bqkv;
+        g.qbuf = w.qbuf; g.kbuf = w.kbuf; g.vbuf = w.vbuf; g.N = 3 * d; g.K = d;
+        g.acc_scale = 1.0f / (lw.s_h * lw.wqkv_i.scale); g.q_scale = lw.s_q; g.k_scale = lw.s_k; g.v_scale = lw.s_v;
+        g.tail = plan.tail_qk;
+        PROF(KC_GEMM_QKV, launch_gemm_img(EPI_IMG_QKV, g, max_rows, s));
+        if (stop_after(1)) return done();
+      } else {
         GemmImgArgs g = base();
         g.A = w.himg; g.W = static_cast<const unsigned char*>(lw.wqk_i.p); g.bias = lw.bqk;
         g.qbuf = w.qbuf; g.kbuf = w.kbuf; g.N = 2 * d; g.K = d;
         g.acc_scale = 1.0f / (lw.s_h * lw.wqk_i.scale); g.q_scale = lw.s_q; g.k_scale = lw.s_k;
-        g.tail = tail_for(g.N);
+        g.tail = plan.tail_qk;
         PROF(KC_GEMM_QKV, launch_gemm_img(EPI_IMG_QK, g, max_rows, s));
-        DBG_STOP();
-      }
-      {
-        GemmImgArgs g = base();
+        if (stop_after(1)) return done();
+        g = base();
         g.A = w.himg; g.W = static_cast<const unsigned char*>(lw.wv_i.p); g.bias = lw.bv;
         g.vbuf = w.vbuf; g.N = d; g.K = d;
         g.acc_scale = 1.0f / (lw.s_h * lw.wv_i.scale); g.v_scale = lw.s_v;
-        g.tail = tail_for(g.N);
+        g.tail = plan.tail_d;
         PROF(KC_GEMM_V, launch_gemm_img(EPI_IMG_VT, g, max_rows, s));
-        DBG_STOP();
+        if (stop_after(1)) return done();
       }
-    }
-    if (!fused_attn) {
       AttnImgArgs a;
       memset(&a, 0, sizeof a);
       a.qbuf = w.qbuf; a.kbuf = w.kbuf; a.vbuf = w.vbuf;
@@ -885,56 +962,29 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode) {
       a.r_scale = lw.demb_s.p ? lw.s_k / lw.demb_s.scale : 1.f;
       a.r_scale_k = lw.demb_s.p ? lw.s_q / lw.demb_s.scale : 1.f;
       a.rkq = c.pos_type == FD_POS_RELATIVE_KEY_QUERY;
-      a.stamps = m->stamps ? m->stamps + 5 * 8 * 64 * 6 : nullptr;
+      a.stamps = stamps_at(kStampAttn);
       bool ok = true;
-      if (mode.kmask) {  // an arbitrary key mask: the general kernel (the tuned one builds its schedule on prefix masks)
+      if (plan.attn_gen) {  // indexed by head; the images stay per sub-head
         a.H = c.n_heads;
         a.kmask = mode.kmask;
-        a.L = L;
+        a.L = mode.kmask ? L : 0;
         PROF(KC_ATTN, ok = launch_attention_gen(a, head_dim(c) / 32, s));
-      } else if (head_dim(c) == 32) {
+      } else {
         PROF(KC_ATTN, ok = launch_attention_img(a, L, s));
-      } else {  // head size 64 / 96 / 128: the general kernel, indexed by head; the images stay per sub-head
-        a.H = c.n_heads;
-        PROF(KC_ATTN, ok = launch_attention_gen(a, head_dim(c) / 32, s));
       }
       if (!ok) return fail(FD_E_UNSUPPORTED, "attention: L=%d, head size %d", L, head_dim(c));
-      DBG_STOP();
+      if (stop_after(1)) return done();
     }
-    // BertIntermediate + BertOutput as ONE kernel (ffn16.hip): the 2 d wide intermediate never reaches HBM.  fuse_ffn 2 (and auto):
-    // BertSelfOutput (attention.output.dense + residual + LayerNorm) in front of it in the same launch, its output on chip too.  Passes of 128 rows, one
-    // workgroup per CU: auto = the passes fill whole rounds of the CUs (512 passes on 256 CUs: two; 315 would leave the second round
-    // a quarter full where the tile GEMMs deal 6 + 1 column tiles per pass)
-    static const int fuse_ffn_env = [] { const char* e = getenv("FDMI_FUSE_FFN"); return e ? atoi(e) : -1; }();
-    const int fuse_ffn = m->fuse_ffn >= 0 ? m->fuse_ffn : fuse_ffn_env;
-    bool ffn_auto = false;
-    {
-      // (packed rows: by the caller's row count when it gave one -- the bound B * ceil8(L) overstates ragged batches)
-      const int rows_known = m->varlen && m->rows_hint > 0 && m->rows_hint <= max_rows ? m->rows_hint : max_rows;
-      const int ncu = gemm_img_grid(1 << 30, 384), passes = (rows_known + 127) / 128;
-      const int rounds = (passes + ncu - 1) / ncu;
-      ffn_auto = (double)passes >= 0.94 * (double)rounds * ncu;
-    }
-    const bool fused_ffn = fuse_ffn != 0 && (fuse_ffn > 0 || ffn_auto) && lw.wff_i.p && ffn16_supported(d, ff) &&
-                           (size_t)w.cap * d * 4 < (1ull << 32) - 65536;
-    const bool fused_tail = fused_ffn && fuse_ffn != 1 && lw.wtail_i.p && d <= 384;
+    const bool fused_tail = plan.ffn == StepPlan::FFN_TAIL;
     if (!fused_tail) {
       GemmImgArgs g = base();
       g.A = w.cimg; g.W = static_cast<const unsigned char*>(lw.wo_i.p); g.bias = lw.bo; g.gamma = lw.ln1g; g.beta = lw.ln1b;
-      g.resid = w.himg; g.out = w.aimg; g.N = d; g.K = d;
+      g.resid = w.himg; g.out = w.aimg; g.K = d;
       g.acc_scale = 1.0f / (lw.s_v * lw.wo_i.scale); g.resid_inv = 1.0f / lw.s_h; g.out_scale = lw.s_a;
-      if (d <= 384) {
-        g.tail = tail_for(g.N);
-        PROF(KC_GEMM_OUT, launch_gemm_img(EPI_IMG_LN, g, max_rows, s));
-      } else {  // a LayerNorm row does not fit one 384-column tile: fp32 rows, then the LayerNorm kernel
-        g.out_f32 = w.tmp;
-        g.tail = tail_for(g.N);
-        PROF(KC_GEMM_OUT, launch_gemm_img(EPI_IMG_BIAS, g, max_rows, s));
-        PROF(KC_LN1, launch_ln_f32_img(w.tmp, lw.ln1g, lw.ln1b, c.ln_eps, w.dims, w.aimg, d, lw.s_a, max_rows, s));
-      }
-      DBG_STOP();
+      if (int rc = gemm_ln(g, KC_GEMM_OUT, KC_LN1)) return rc;
+      if (stop_after(1)) return done();
     }
-    if (fused_ffn) {
+    if (plan.ffn != StepPlan::FFN_GEMMS) {
       FfnArgs a;
       memset(&a, 0, sizeof a);
       a.aimg = w.aimg; a.a_bytes = (unsigned)((size_t)w.cap * d * 4);
@@ -948,80 +998,48 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode) {
       a.panels = max_rows / 128; a.dims = w.dims;
       a.up_scale = 1.0f / (lw.s_a * lw.wff_i.scale); a.g_scale = lw.s_g; a.down_scale = 1.0f / (lw.s_g * lw.wff_scale_dn);
       a.resid_inv = 1.0f / lw.s_a; a.out_scale = s_next; a.eps = c.ln_eps;
-      a.stamps = m->stamps ? m->stamps + 5 * 8 * 64 * 6 + 4 * 64 * 8 + 4 * 64 * 16 + 16384 : nullptr;
+      a.stamps = stamps_at(kStampFfn);
       bool launched = false;
-      if (fused_tail) PROF(KC_TAIL, launched = launch_ffn16(a, d, s));
-      else PROF(KC_FFN, launched = launch_ffn16(a, d, s));
+      PROF(fused_tail ? KC_TAIL : KC_FFN, launched = launch_ffn16(a, d, s));
       if (!launched) return fail(FD_E_HIP, "the fused feed-forward kernel could not be launched");
-      if (fused_tail) DBG_STOP();
-      DBG_STOP();
-      DBG_STOP();  // (two / three launches of the other path: debug_stop counts stay comparable)
+      if (stop_after(fused_tail ? 3 : 2)) return done();
       continue;
     }
     {
       GemmImgArgs g = base();
       g.A = w.aimg; g.W = static_cast<const unsigned char*>(lw.wi_i.p); g.bias = lw.bi; g.out = w.gimg; g.N = ff; g.K = d;
       g.acc_scale = 1.0f / (lw.s_a * lw.wi_i.scale); g.out_scale = lw.s_g;
-      g.tail = tail_for(g.N);
+      g.tail = plan.tail_ff;
       PROF(KC_GEMM_UP, launch_gemm_img(EPI_IMG_GELU, g, max_rows, s));
-      DBG_STOP();
+      if (stop_after(1)) return done();
     }
     {
       GemmImgArgs g = base();
       g.A = w.gimg; g.W = static_cast<const unsigned char*>(lw.wd_i.p); g.bias = lw.bd; g.gamma = lw.ln2g; g.beta = lw.ln2b;
-      g.resid = w.aimg; g.out = w.himg; g.N = d; g.K = ff;
+      g.resid = w.aimg; g.out = w.himg; g.K = ff;
       g.acc_scale = 1.0f / (lw.s_g * lw.wd_i.scale); g.resid_inv = 1.0f / lw.s_a; g.out_scale = s_next;
-      if (d <= 384) {
-        g.tail = tail_for(g.N);
-        PROF(KC_GEMM_DOWN, launch_gemm_img(EPI_IMG_LN, g, max_rows, s));
-      } else {
-        g.out_f32 = w.tmp;
-        g.tail = tail_for(g.N);
-        PROF(KC_GEMM_DOWN, launch_gemm_img(EPI_IMG_BIAS, g, max_rows, s));
-        PROF(KC_LN2, launch_ln_f32_img(w.tmp, lw.ln2g, lw.ln2b, c.ln_eps, w.dims, w.himg, d, s_next, max_rows, s));
-      }
-      DBG_STOP();
+      if (int rc = gemm_ln(g, KC_GEMM_DOWN, KC_LN2)) return rc;
+      if (stop_after(1)) return done();
     }
   }
-  UpdateArgs u;
-  memset(&u, 0, sizeof u);
+  UpdateArgs u = fill_update(m, w, mode);
   HeadImgArgs hi;
   memset(&hi, 0, sizeof hi);
   if (c.decoder == FD_DEC_MLP) {
     GemmImgArgs g = base();
     g.A = w.himg; g.W = static_cast<const unsigned char*>(m->hd_w1_i.p); g.bias = m->hd_b1; g.out = w.gimg; g.N = d; g.K = d;
     g.acc_scale = 1.0f / (m->s_hfinal * m->hd_w1_i.scale); g.out_scale = m->s_hg;
-    g.tail = tail_for(g.N);
+    g.tail = plan.tail_d;
     PROF(KC_GEMM_HEAD, launch_gemm_img(EPI_IMG_GELU, g, max_rows, s));
-      DBG_STOP();
+    if (stop_after(1)) return done();
     hi.g = w.gimg; hi.g_inv = 1.0f / m->s_hg;
-    u.gamma = m->hd_g; u.beta = m->hd_b; u.do_ln = 1;
   } else {
     hi.g = w.himg; hi.g_inv = 1.0f / m->s_hfinal;
-    u.do_ln = 0;
   }
   hi.rowinfo = w.rowinfo; hi.nrow = w.nrow; hi.dims = w.dims; hi.tslot = w.t_dev; hi.flag = w.flag;
   hi.advance = mode.advance ? 1 : 0;
-  u.w2 = m->hd_w2; u.b2 = m->hd_b2; u.x = w.x; u.coef = m->coef; u.t_dev = w.t_dev; u.T = m->T;
-  u.M = B * L; u.L = L; u.F = F; u.d = d;
-  u.ln_eps = 1e-12f;  // AnglesPredictor(eps=1e-12)  (modelling.py:187,199)
-  u.angle_mask = mode.no_wrap ? 0u : m->angle_mask;
-  u.eps_out = w.eps;
-  if (!mode.forward_only) {
-    u.x_out = w.x;
-    if (mode.use_dyn) {
-      u.dyn = w.dyn;
-    } else {
-      u.noise = mode.noise;
-      u.noise_stride = 0;
-      u.t_start = mode.t_start;
-    }
-  }
-  if (mode.use_dyn) u.noise_stride = (long long)B * L * F;
   PROF(KC_HEAD_UPDATE, launch_head_update_img(u, hi, max_rows, s));
-  HIP_TRY(hipGetLastError());
-  return FD_OK;
-#undef DBG_STOP
+  return done();
 }
 
 // token-row table of the batch (row-image path); `packed`: only the first lens[b] positions are rows
@@ -1047,9 +1065,7 @@ int check_shape(fd_model* m, int B, int L, int t) {
   if (!m->finalized) return fail(FD_E_STATE, "fd_finalize has not been called");
   if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
   if (t < 0 || t >= m->T) return fail(FD_E_INVALID, "timestep %d outside [0, %d)", t, m->T);
-  if (m->cfg.pos_type != FD_POS_ABSOLUTE && L > m->cfg.max_pos)
-    return fail(FD_E_INVALID, "L=%d exceeds max_position_embeddings=%d", L, m->cfg.max_pos);
-  if (m->cfg.pos_type == FD_POS_ABSOLUTE && L > m->cfg.max_pos)
+  if (L > m->cfg.max_pos)  // (the position table and the distance table alike)
     return fail(FD_E_INVALID, "L=%d exceeds max_position_embeddings=%d", L, m->cfg.max_pos);
   if (L > 128 && !m->img)
     return fail(FD_E_UNSUPPORTED, "L=%d: the exact-fp32 attention kernel handles L <= 128; use FD_PREC_F16X3", L);
@@ -1130,11 +1146,9 @@ static int device_roundtrip(int device_id, std::initializer_list<std::pair<const
   return device_roundtrip(device_id, inputs, {{out, out_bytes}}, launch);
 }
 
-// the workspace's captured graph still holds the launch sequence the model's options ask for
-static bool graph_current(const fd_model* m, const Workspace& w) {
-  return w.graph && w.graph_fuse_ln == m->fuse_ln && w.graph_varlen == m->varlen && w.graph_fuse_attn == m->fuse_attn && w.graph_fuse_ffn == m->fuse_ffn &&
-         w.graph_rows_hint == m->rows_hint;
-}
+// the workspace's captured graph still holds the launch sequence the model's options ask for (an option change that leads to
+// the same sequence -- another rows_hint on the same side of the automatic choice -- keeps the graph)
+static bool graph_current(const fd_model* m, const Workspace& w) { return w.graph && w.graph_plan == plan_step(m, w, false); }
 
 int ensure_graph(fd_model* m) {
   Workspace& w = m->ws;
@@ -1166,11 +1180,7 @@ int ensure_graph(fd_model* m) {
   e = hipGraphInstantiate(&w.graph, graph, nullptr, nullptr, 0);
   (void)hipGraphDestroy(graph);
   if (e != hipSuccess) return fail(FD_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-  w.graph_fuse_ln = m->fuse_ln;
-  w.graph_varlen = m->varlen;
-  w.graph_fuse_attn = m->fuse_attn;
-  w.graph_fuse_ffn = m->fuse_ffn;
-  w.graph_rows_hint = m->rows_hint;
+  w.graph_plan = plan_step(m, w, false);
   return FD_OK;
 }
 

@@ -28,6 +28,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "launch_common.h"
 
 #include <type_traits>
 
@@ -802,7 +803,6 @@ static void launch_ng(const AttnImgArgs& p, hipStream_t s) {
   constexpr int smem = G::E_BYTES + NG * (REL ? G::G_REL : G::G_ABS);
   static const bool safe = [] { const char* e = getenv("FDMI_ATTN_SAFE"); return e && atoi(e) != 0; }();
   static bool attr_set[64] = {false};
-  static int n_cu[64] = {0};
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64) dev = 0;
@@ -813,12 +813,10 @@ static void launch_ng(const AttnImgArgs& p, hipStream_t s) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_img_kernel<T, REL, ELDS, NG, false, true, RKQ>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hipDeviceProp_t prop;
-    n_cu[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     attr_set[dev] = true;
   }
   const int nitems = p.B * p.H * p.NKT;
-  int grid = n_cu[dev] * (NG == 1 ? 2 : 1);  // 8 waves per CU either way
+  int grid = cu_count() * (NG == 1 ? 2 : 1);  // 8 waves per CU either way
   if (grid > (nitems + NG - 1) / NG) grid = (nitems + NG - 1) / NG;
   if (p.stamps) hipLaunchKernelGGL((attn_img_kernel<T, REL, ELDS, NG, false, true, RKQ>), dim3(grid), dim3(256 * NG), smem, s, p);
   else if (safe) hipLaunchKernelGGL((attn_img_kernel<T, REL, ELDS, NG, true, false, RKQ>), dim3(grid), dim3(256 * NG), smem, s, p);

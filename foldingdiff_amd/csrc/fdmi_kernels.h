@@ -219,7 +219,7 @@ bool seq_attn16_supported(int d_model, int n_heads, int L, int maxpos);
 bool launch_seq_attn16(const SeqAttnArgs& p, hipStream_t s);
 
 // ffn16.hip (round 6): BertIntermediate + GELU + BertOutput (dense + residual + LayerNorm) of 128 token rows per pass in ONE kernel;
-// the intermediate never reaches HBM.  wimg = ONE stream of 24 KiB stages in consumption order (api.hip: upload_ffn16_weights).
+// the intermediate never reaches HBM.  wimg = ONE stream of 16 KiB stages in consumption order (api.hip: upload_ffn16_weights).
 struct FfnArgs {
   const unsigned char* aimg;   // input image [rows128][d/32] (BertSelfOutput's LayerNorm output): operand AND residual
   unsigned a_bytes;            // its size (rows beyond it read as zeros)

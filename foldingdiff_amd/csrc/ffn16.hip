@@ -33,6 +33,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "launch_common.h"
 
 namespace fdmi {
 namespace ffn {
@@ -560,31 +561,13 @@ __global__ __launch_bounds__(64 * NW) void ffn16_kernel(FfnArgs p) {
 #undef FD_SB
 }
 
-static int n_cu_of(int dev) {
-  static int cached[64] = {0};
-  if (dev < 0 || dev >= 64) return 256;
-  if (cached[dev] == 0) {
-    hipDeviceProp_t prop;
-    cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return cached[dev];
-}
-
 template <int NKT, bool TAIL>
 static bool launch(const FfnArgs& p, hipStream_t s) {
   constexpr int SMEM = off_p(NKT) + (TAIL ? 8 : 5) * 32 * NKT * 4;
-  static int attr_state[64] = {0};  // 0 unknown, 1 set, -1 refused
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (attr_state[dev] == 0) {
-    bool ok = true;
-    for (const void* f : {reinterpret_cast<const void*>(&ffn16_kernel<NKT, TAIL, false>), reinterpret_cast<const void*>(&ffn16_kernel<NKT, TAIL, true>)})
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) == hipSuccess;
-    attr_state[dev] = ok ? 1 : -1;
-  }
-  if (attr_state[dev] < 0) return false;
-  int grid = n_cu_of(dev);
+  static LdsOptIn lds;
+  if (!lds({reinterpret_cast<const void*>(&ffn16_kernel<NKT, TAIL, false>), reinterpret_cast<const void*>(&ffn16_kernel<NKT, TAIL, true>)}, SMEM))
+    return false;
+  int grid = cu_count();
   if (grid > p.panels) grid = p.panels;
   if (grid <= 0) return true;
   if (p.stamps) hipLaunchKernelGGL((ffn16_kernel<NKT, TAIL, true>), dim3(grid), dim3(64 * NW), SMEM, s, p);

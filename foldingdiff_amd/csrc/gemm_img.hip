@@ -41,6 +41,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "launch_common.h"
 
 namespace fdmi {
 namespace gi {
@@ -820,17 +821,6 @@ __global__ __launch_bounds__(NTHR) void gemm_img_kernel(GemmImgArgs p) {
 #undef FD_STAMP
 }
 
-static int n_cu_of_current_device() {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cached[dev] == 0) {
-    hipDeviceProp_t prop;
-    cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return cached[dev];
-}
-
 template <int EPI, bool SWAP>
 static void launch(const GemmImgArgs& p, int max_rows, hipStream_t s) {
   static bool attr_set[64] = {false};
@@ -843,10 +833,7 @@ static void launch(const GemmImgArgs& p, int max_rows, hipStream_t s) {
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     attr_set[dev] = true;
   }
-  const int ntiles_max = ((max_rows + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  int grid = n_cu_of_current_device() / 8 * 8;
-  if (grid > ntiles_max) grid = (ntiles_max + 7) / 8 * 8;
-  if (grid < 8) grid = 8;
+  const int grid = gemm_img_grid(max_rows, p.N);
   static const int force_tail = [] { const char* e = getenv("FDMI_GEMM_TAIL"); return e ? atoi(e) : -1; }();  // A/B: 0 / 1 override the host's choice
   const bool tail = force_tail >= 0 ? force_tail != 0 : p.tail != 0;
   if (p.stamps) hipLaunchKernelGGL((gemm_img_kernel<EPI, SWAP, true, 1>), dim3(grid), dim3(NTHR), SMEM, s, p);
@@ -860,7 +847,7 @@ static void launch(const GemmImgArgs& p, int max_rows, hipStream_t s) {
 // launch's tiles fill whole rounds: GemmImgArgs::tail)
 int gemm_img_grid(int max_rows, int N) {
   const int ntiles_max = ((max_rows + gi::BM - 1) / gi::BM) * ((N + gi::BN - 1) / gi::BN);
-  int grid = gi::n_cu_of_current_device() / 8 * 8;
+  int grid = cu_count() / 8 * 8;  // (whole XCDs)
   if (grid > ntiles_max) grid = (ntiles_max + 7) / 8 * 8;
   return grid < 8 ? 8 : grid;
 }

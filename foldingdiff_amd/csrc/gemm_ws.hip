@@ -38,6 +38,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "launch_common.h"
 
 #ifndef FDMI_WS_DBG
 #define FDMI_WS_DBG 0  // ablations (timing only, results wrong): 1 no epilogue, 2 no MFMA phase, 4 no copies, 8 no stores
@@ -331,15 +332,6 @@ static int current_device() {
   int dev = 0;
   return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) ? dev : 0;
 }
-static int n_cu() {  // per device (a process may hold models on several GPUs: fd_create takes any device_id)
-  static int cached[64] = {0};
-  const int dev = current_device();
-  if (!cached[dev]) {
-    hipDeviceProp_t prop;
-    cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return cached[dev];
-}
 
 template <int EPI>
 static void launch(const GemmImgArgs& p, hipStream_t s) {
@@ -361,7 +353,7 @@ static void launch(const GemmImgArgs& p, hipStream_t s) {
       if (hipMalloc(&d, n * 8) == hipSuccess && hipMemset(d, 0, n * 8) == hipSuccess) {
         GemmImgArgs q = p;
         q.stamps = d;
-        hipLaunchKernelGGL((gemm_ws_kernel<EPI>), dim3(n_cu() / 8 * 8), dim3(512), SMEM, s, q);
+        hipLaunchKernelGGL((gemm_ws_kernel<EPI>), dim3(cu_count() / 8 * 8), dim3(512), SMEM, s, q);
         std::vector<unsigned long long> h(n);
         (void)hipDeviceSynchronize();
         (void)hipMemcpy(h.data(), d, n * 8, hipMemcpyDeviceToHost);
@@ -381,7 +373,7 @@ static void launch(const GemmImgArgs& p, hipStream_t s) {
       }
     }
   }
-  hipLaunchKernelGGL((gemm_ws_kernel<EPI>), dim3(n_cu() / 8 * 8), dim3(512), SMEM, s, p);
+  hipLaunchKernelGGL((gemm_ws_kernel<EPI>), dim3(cu_count() / 8 * 8), dim3(512), SMEM, s, p);
 }
 
 }  // namespace ws
@@ -389,7 +381,7 @@ static void launch(const GemmImgArgs& p, hipStream_t s) {
 // true if this shape runs on the weight-stationary kernel (K = 384, N a multiple of 32, column-local epilogue, image output)
 bool gemm_ws_supported(int epilogue, const GemmImgArgs& p) {
   if (p.K != 32 * ws::NKT || p.N % 32 != 0) return false;
-  if ((p.N + ws::SLICE - 1) / ws::SLICE > ws::n_cu() / 8) return false;  // an XCD's workgroups must hold at least one stream of slices
+  if ((p.N + ws::SLICE - 1) / ws::SLICE > cu_count() / 8) return false;  // an XCD's workgroups must hold at least one stream of slices
   if (epilogue == EPI_IMG_QKV) return p.N == 96 * p.H && p.LTOT % 32 == 0;  // q | k | v of head size 32 in one launch
   return (epilogue == EPI_IMG_GELU || epilogue == EPI_IMG_BIAS) && p.out_f32 == nullptr && p.resid == nullptr;
 }

@@ -35,6 +35,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "launch_common.h"
 
 #ifndef FDMI_SA_SCHED
 #define FDMI_SA_SCHED 0  // 0: the source order of the slots is the schedule (sched_barrier between them); 1: the slots' order only holds for
@@ -911,31 +912,12 @@ __global__ __launch_bounds__(256) void seq_attn_kernel(SeqAttnArgs p) {
 #undef FD_SB
 }
 
-static int n_cu_of(int dev) {
-  static int cached[64] = {0};
-  if (dev < 0 || dev >= 64) return 256;
-  if (cached[dev] == 0) {
-    hipDeviceProp_t prop;
-    cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return cached[dev];
-}
-
 template <int NKT>
 static bool launch(const SeqAttnArgs& p, hipStream_t s) {
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {   // the whole LDS of a CU: a runtime that refuses the opt-in must surface here, not as a silent no-op launch
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&seq_attn_kernel<NKT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&seq_attn_kernel<NKT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    attr_set[dev] = true;
-  }
-  int grid = n_cu_of(dev);
+  static LdsOptIn lds;  // (the whole LDS of a CU)
+  if (!lds({reinterpret_cast<const void*>(&seq_attn_kernel<NKT, false>), reinterpret_cast<const void*>(&seq_attn_kernel<NKT, true>)}, SMEM))
+    return false;
+  int grid = cu_count();
   if (grid > p.B) grid = p.B;
   if (p.stamps) hipLaunchKernelGGL((seq_attn_kernel<NKT, true>), dim3(grid), dim3(256), SMEM, s, p);
   else hipLaunchKernelGGL((seq_attn_kernel<NKT, false>), dim3(grid), dim3(256), SMEM, s, p);

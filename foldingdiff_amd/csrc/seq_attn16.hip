@@ -43,6 +43,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "launch_common.h"
 
 namespace fdmi {
 namespace s16 {
@@ -743,30 +744,12 @@ __global__ __launch_bounds__(64 * NW) void seq_attn16_kernel(SeqAttnArgs p) {
 #undef FD_SB
 }
 
-static int n_cu_of(int dev) {
-  static int cached[64] = {0};
-  if (dev < 0 || dev >= 64) return 256;
-  if (cached[dev] == 0) {
-    hipDeviceProp_t prop;
-    cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return cached[dev];
-}
-
 template <int NKT>
 static bool launch(const SeqAttnArgs& p, hipStream_t s) {
-  static int attr_state[64] = {0};  // 0 unknown, 1 set, -1 refused
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (attr_state[dev] == 0) {
-    bool ok = true;
-    for (const void* f : {reinterpret_cast<const void*>(&seq_attn16_kernel<NKT, false>), reinterpret_cast<const void*>(&seq_attn16_kernel<NKT, true>)})
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) == hipSuccess;
-    attr_state[dev] = ok ? 1 : -1;
-  }
-  if (attr_state[dev] < 0) return false;
-  int grid = n_cu_of(dev);
+  static LdsOptIn lds;
+  if (!lds({reinterpret_cast<const void*>(&seq_attn16_kernel<NKT, false>), reinterpret_cast<const void*>(&seq_attn16_kernel<NKT, true>)}, SMEM))
+    return false;
+  int grid = cu_count();
   if (grid > p.B) grid = p.B;
   if (p.stamps) hipLaunchKernelGGL((seq_attn16_kernel<NKT, true>), dim3(grid), dim3(64 * NW), SMEM, s, p);
   else hipLaunchKernelGGL((seq_attn16_kernel<NKT, false>), dim3(grid), dim3(64 * NW), SMEM, s, p);
