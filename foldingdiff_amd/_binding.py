@@ -69,6 +69,7 @@ _SIGNATURES = {
     "fd_superpose_rmsd": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "fd_tm_score": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "fd_annotate_sse": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "fd_tm_align": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fd_shift_trim_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fd_test_wrap": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, _P]),
     "fd_test_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),

@@ -2021,6 +2021,72 @@ int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, con
                           });
 }
 
+int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens, int n_pairs, int max_iter,
+                double* tm_out, double* transform_out, int32_t* n_ali_out, const int64_t* map_offsets, int32_t* map_out) {
+  if (!ca || !offsets || !lens || !pair_a || !pair_b || !tm_out) return fail(FD_E_INVALID, "null argument");
+  if ((map_offsets == nullptr) != (map_out == nullptr))
+    return fail(FD_E_INVALID, "null argument: map_offsets and map_out go together");
+  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
+  if (n_pairs < 1) return fail(FD_E_INVALID, "n_pairs=%d must be >= 1", n_pairs);
+  if (max_iter < 1) return fail(FD_E_INVALID, "max_iter=%d must be >= 1", max_iter);
+  int max_len = 0;
+  for (int c = 0; c < n_chains; ++c) {
+    if (lens[c] < 1 || lens[c] > FDMI_ALIGN_MAX_LEN)
+      return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", c, lens[c], FDMI_ALIGN_MAX_LEN);
+    max_len = std::max(max_len, (int)lens[c]);
+  }
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 3, &n_res)) return rc;
+  long long n_map = 0;
+  std::vector<int32_t> norm((size_t)n_pairs);
+  for (int p = 0; p < n_pairs; ++p) {
+    if (pair_a[p] < 0 || pair_a[p] >= n_chains || pair_b[p] < 0 || pair_b[p] >= n_chains)
+      return fail(FD_E_INVALID, "pair %d = (%d, %d): chain index outside [0, %d)", p, pair_a[p], pair_b[p], n_chains);
+    const int n1 = lens[pair_a[p]], n2 = lens[pair_b[p]];
+    norm[p] = norm_lens ? norm_lens[p] : n2;
+    if (norm[p] < std::min(n1, n2))
+      return fail(FD_E_INVALID, "norm_lens[%d]=%d is below min(%d, %d)", p, norm[p], n1, n2);
+    if (map_offsets && map_offsets[p] != n_map)
+      return fail(FD_E_INVALID, "map_offsets[%d]=%lld, expected %lld (packed)", p, (long long)map_offsets[p], n_map);
+    n_map += n1;
+  }
+  // finite coordinates within 1e6 A (every squared distance stays far from overflow), and the centroids the kernel
+  // subtracts: every chain is aligned in its own centred frame
+  std::vector<double> cent((size_t)n_chains * 3, 0.0);
+  for (int c = 0; c < n_chains; ++c) {
+    for (int i = offsets[c]; i < offsets[c] + lens[c]; ++i)
+      for (int d = 0; d < 3; ++d) {
+        const double u = ca[(size_t)i * 3 + d];
+        if (!(std::fabs(u) <= 1e6))
+          return fail(FD_E_INVALID, "coordinate %d of residue %d (chain %d) is not finite or beyond 1e6: %g", d, i, c, u);
+        cent[(size_t)c * 3 + d] += u;
+      }
+    for (int d = 0; d < 3; ++d) cent[(size_t)c * 3 + d] /= lens[c];
+  }
+  const size_t na = (size_t)n_res, nc = (size_t)n_chains, np = (size_t)n_pairs;
+  const size_t map_bytes = map_out ? (size_t)n_map * 4 : 4;
+  static const int64_t no_offsets = 0;
+  return device_roundtrip(
+      device_id,
+      {{ca, na * 3 * 8}, {cent.data(), nc * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}, {pair_a, np * 4}, {pair_b, np * 4},
+       {norm.data(), np * 4}, {map_offsets ? map_offsets : &no_offsets, map_offsets ? np * 8 : 8}},
+      {{nullptr, na}, {nullptr, nc * 2 * 4}, {tm_out, np * 8}, {transform_out, np * 12 * 8}, {n_ali_out, np * 4},
+       {map_out, map_bytes}},
+      [&](const std::vector<void*>& d) {
+        // the labels of every chain first (start 2 reads them), then the pairs; both on the null stream, in order
+        launch_psea(static_cast<const double*>(d[0]), static_cast<const int*>(d[2]), static_cast<const int*>(d[3]), n_chains,
+                    max_len, static_cast<signed char*>(d[8]), static_cast<int*>(d[9]), nullptr);
+        return launch_tm_align(static_cast<const double*>(d[0]), static_cast<const double*>(d[1]),
+                               static_cast<const int*>(d[2]), static_cast<const int*>(d[3]),
+                               static_cast<const signed char*>(d[8]), static_cast<const int*>(d[4]),
+                               static_cast<const int*>(d[5]), static_cast<const int*>(d[6]),
+                               map_out ? static_cast<const long long*>(d[7]) : nullptr, n_pairs, max_iter, max_len,
+                               static_cast<double*>(d[10]), static_cast<double*>(d[11]), static_cast<int*>(d[12]),
+                               map_out ? static_cast<int*>(d[13]) : nullptr, nullptr);
+      });
+}
+
 int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L, const void* lens_dev, const void* item_off_dev,
                       const float* offset, void* out_dev, void* hip_stream) {
   if (!m || !traj_dev || !lens_dev || !item_off_dev || !out_dev) return fail(FD_E_INVALID, "null argument");

@@ -115,6 +115,14 @@ hipError_t launch_tm_score(const double* a, const double* b, const double* cent,
 // of LDS per residue).
 void launch_psea(const double* ca, const int* offsets, const int* lens, int n_chains, int max_len, signed char* sse_out,
                  int* counts_out, hipStream_t s);
+// TM-align-style alignment search (tm_align.hip), one workgroup per pair on a persistent grid: pair p = chains pair_a[p],
+// pair_b[p] of the packed traces `ca` (cent = [n_chains][3] centroids, sse = launch_psea's labels of the same chains,
+// max_len = the longest chain, <= 512).  tm_out [n_pairs], transform_out [n_pairs][12], n_ali_out [n_pairs]; map_out
+// (with map_offsets [n_pairs]) or both null.
+hipError_t launch_tm_align(const double* ca, const double* cent, const int* offsets, const int* lens, const signed char* sse,
+                           const int* pair_a, const int* pair_b, const int* norm_lens, const long long* map_offsets,
+                           int n_pairs, int max_iter, int max_len, double* tm_out, double* transform_out, int* n_ali_out,
+                           int* map_out, hipStream_t s);
 
 // *t_dev -= 1  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, hipStream_t s);

@@ -17,6 +17,11 @@ The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
   the labels from biotite's ``annotate_sse``: ``annotate_sse`` here restates that algorithm (P-SEA) on the device
   (``fd_annotate_sse``, every chain of a call in one launch), ``ss_cooccurrence`` is the plot function.
 
+* ``tmalign.run_tmalign`` / ``max_tm_across_refs`` (foldingdiff/tmalign.py:22-83) and ``get_pairwise_tmscores``
+  (bin/hclust_structures.py:38-69), which run one TM-align subprocess per pair of chains whose residues do not
+  correspond: ``tm_align``, ``pairwise_tm``, ``max_tm_across_refs`` and ``pairwise_tmscores`` search the residue
+  alignment and the superposition on the device (``fd_tm_align``, one workgroup per pair).
+
 PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PDBFile`` for them):
 
 1. a file with more than one MODEL record is rejected (``None``), as the reference does;
@@ -618,3 +623,206 @@ def ss_cooccurrence(pdb_files: Sequence[str], json_file: str = "", outpdf: str =
                           outpdf=outpdf, title=title, **kwargs)
     counts = np.array([c for _, c in kept], dtype=np.int64).reshape(-1, 2)
     return counts[:, 0], counts[:, 1]
+
+
+# ---------------------------------------------------------------------------------------------------- alignment
+ALIGN_MAX_LEN = 512   # FDMI_ALIGN_MAX_LEN
+_ALIGN_MAX_SEEDS = 256
+
+
+def _tm_seed_count(n: int, stride: int) -> int:
+    lmin = min(n, 4)
+    lengths, l = [], n
+    while l > lmin:
+        lengths.append(l)
+        l //= 2
+    lengths.append(lmin)
+    return sum((n - l) // stride + 1 + ((n - l) % stride != 0) for l in lengths)
+
+
+def tm_align_stride(n_ali: int) -> int:
+    """The stride at which ``fd_tm_align`` searches an alignment of ``n_ali`` pairs: the smallest s >= 1 that leaves
+    at most 256 seeds (one lane each)."""
+    s = 1
+    while _tm_seed_count(int(n_ali), s) > _ALIGN_MAX_SEEDS:
+        s += 1
+    return s
+
+
+def _align_traces(chains: Sequence[np.ndarray], what: str = "chain") -> List[np.ndarray]:
+    out = [np.asarray(x, dtype=np.float64) for x in chains]
+    for i, x in enumerate(out):
+        if x.ndim != 2 or x.shape[1] != 3 or not 1 <= len(x) <= ALIGN_MAX_LEN:
+            raise ValueError(f"{what} {i}: {x.shape}; expected an [n, 3] CA trace with 1 <= n <= {ALIGN_MAX_LEN}")
+    return out
+
+
+def _align_indexed(chains: List[np.ndarray], pair_a: np.ndarray, pair_b: np.ndarray, norm_lens, max_iter: int, device: int,
+                   want_map: bool):
+    """One ``fd_tm_align`` call over already-checked float64 traces: (tm [P], T [P, 12], n_ali [P], maps or None)."""
+    lens = np.array([len(x) for x in chains], dtype=np.int32)
+    P = len(pair_a)
+    pa, pb = np.ascontiguousarray(pair_a, dtype=np.int32), np.ascontiguousarray(pair_b, dtype=np.int32)
+    if P and (min(pa.min(), pb.min()) < 0 or max(pa.max(), pb.max()) >= len(chains)):
+        raise ValueError(f"pair indices must lie in [0, {len(chains)})")
+    if int(max_iter) < 1:
+        raise ValueError(f"max_iter={max_iter} must be >= 1")
+    if norm_lens is None:
+        nl = lens[pb].astype(np.int32) if P else np.zeros((0,), np.int32)
+    else:
+        nl = np.asarray(norm_lens, dtype=np.int64).reshape(-1)
+        if nl.shape != (P,) or (nl < np.minimum(lens[pa], lens[pb])).any() or (nl > np.iinfo(np.int32).max).any():
+            raise ValueError(f"norm_lens {nl.tolist()} must hold one length >= min(n1, n2) per pair")
+        nl = nl.astype(np.int32)
+    tm = np.empty((P,), dtype=np.float64)
+    T = np.empty((P, 12), dtype=np.float64)
+    n_ali = np.empty((P,), dtype=np.int32)
+    if P == 0:
+        return tm, T, n_ali, ([] if want_map else None)
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+    X = np.ascontiguousarray(np.concatenate(chains))
+    map_off = flat = None
+    if want_map:
+        map_off = np.concatenate([[0], np.cumsum(lens[pa], dtype=np.int64)[:-1]]).astype(np.int64)
+        flat = np.empty((int(lens[pa].sum()),), dtype=np.int32)
+    ptr = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)   # noqa: E731
+    _binding.check(_binding.load().fd_tm_align(
+        device, ptr(X), ptr(offsets), ptr(lens), len(chains), ptr(pa), ptr(pb), ptr(nl), P, int(max_iter), ptr(tm), ptr(T),
+        ptr(n_ali), ptr(map_off), ptr(flat)))
+    maps = [flat[o: o + lens[i]].copy() for o, i in zip(map_off, pa)] if want_map else None
+    return tm, T, n_ali, maps
+
+
+def _polish(chains, pa, pb, nl, maps, device):
+    """``tm_score`` at stride 1 over the aligned pairs of each map, normalised as the alignment was."""
+    xa = [chains[i][m >= 0] for i, m in zip(pa, maps)]
+    ya = [chains[j][m[m >= 0]] for j, m in zip(pb, maps)]
+    return tm_score(xa, ya, norm_lens=nl, stride=1, device=device, return_transform=True)
+
+
+def tm_align(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], norm_lens: Optional[Sequence[int]] = None,
+             max_iter: int = 10, return_transform: bool = False, return_map: bool = False, polish: bool = False,
+             device: int = 0):
+    """TM-score of each pair of CA traces (a[i] [n1, 3], b[i] [n2, 3], 1 <= n <= 512) whose residues need not
+    correspond, in one ``fd_tm_align`` call: float64 [len(a_list)], normalised by ``norm_lens[i]`` (>= min(n1, n2);
+    default n2, the "Chain_2" number ``tmalign.run_tmalign`` returns).  With ``return_transform`` also R [n, 3, 3] and
+    t [n, 3] with b ~ a @ R.T + t; with ``return_map`` also a list of int32 [n1] maps, ``map[i]`` = the residue of b
+    aligned with residue i of a, or -1.
+
+    The residue alignment and the superposition are searched together in the manner of TM-align (Zhang & Skolnick
+    2005): two starts (the best gapless threading; a dynamic programme over P-SEA labels), each refined by up to
+    ``max_iter`` rounds of dynamic programming on the superposition's score matrix with gap-open penalties -0.6 and 0,
+    every alignment scored by ``tm_score``'s search at the coarse stride ``tm_align_stride(n_ali)`` (DESIGN.md
+    "TM-align-style alignment" states the rules).  It is not pinned to the TMalign binary; with fewer starts than
+    TM-align's five it is a lower bound on the optimum TM-align looks for.
+
+    ``polish``: the aligned pairs are scored again by ``tm_score`` at stride 1.  Stride 1's seeds contain the coarse
+    stride's, so the polished score (and its transform) is never lower."""
+    if len(a_list) != len(b_list):
+        raise ValueError(f"{len(a_list)} traces against {len(b_list)}")
+    a, b = _align_traces(a_list, "a"), _align_traces(b_list, "b")
+    n = len(a)
+    pa, pb = np.arange(n, dtype=np.int32), np.arange(n, 2 * n, dtype=np.int32)
+    tm, T, _, maps = _align_indexed(a + b, pa, pb, norm_lens, max_iter, device, return_map or polish)
+    R, t = T[:, :9].reshape(n, 3, 3).copy(), T[:, 9:].copy()
+    if polish and n:
+        nl = [len(y) for y in b] if norm_lens is None else list(norm_lens)
+        tm, R, t = _polish(a + b, pa, pb, nl, maps, device)
+    out = (tm,) + ((R, t) if return_transform else ()) + ((maps,) if return_map else ())
+    return out if len(out) > 1 else tm
+
+
+def pairwise_tm(chains: Sequence[np.ndarray], pairs=None, norm_lens: Optional[Sequence[int]] = None, max_iter: int = 10,
+                polish: bool = False, chunk: int = 1 << 16, device: int = 0) -> np.ndarray:
+    """``tm_align`` scores of ``pairs`` (an [P, 2] list of (i, j) indices into ``chains``: chain i aligned to chain j,
+    normalised by chain j's length unless ``norm_lens`` says otherwise; default every i < j in row order): float64 [P].
+    The pair list is cut into chunks of ``chunk`` pairs and every call uploads only the chains its chunk names, so the
+    host and device buffers stay bounded however long the list is."""
+    ca = _align_traces(chains)
+    if pairs is None:
+        iu = np.triu_indices(len(ca), k=1)
+        pairs = np.stack(iu, axis=1)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pairs) and (pairs.min() < 0 or pairs.max() >= len(ca)):
+        raise ValueError(f"pair indices must lie in [0, {len(ca)})")
+    if int(chunk) < 1:
+        raise ValueError(f"chunk={chunk} must be >= 1")
+    nl = None
+    if norm_lens is not None:
+        nl = np.asarray(norm_lens, dtype=np.int64).reshape(-1)
+        if nl.shape != (len(pairs),):
+            raise ValueError(f"norm_lens must hold one length per pair ({len(pairs)}), got {nl.shape}")
+    out = np.empty((len(pairs),), dtype=np.float64)
+    for lo in range(0, len(pairs), int(chunk)):
+        sub = pairs[lo: lo + int(chunk)]
+        used, inv = np.unique(sub, return_inverse=True)
+        inv = inv.reshape(sub.shape)
+        local = [ca[i] for i in used]
+        sub_nl = None if nl is None else nl[lo: lo + len(sub)]
+        tm, _, _, maps = _align_indexed(local, inv[:, 0], inv[:, 1], sub_nl, max_iter, device, polish)
+        if polish:
+            pnl = [len(local[j]) for j in inv[:, 1]] if sub_nl is None else list(sub_nl)
+            tm = _polish(local, inv[:, 0], inv[:, 1], pnl, maps, device)[0]
+        out[lo: lo + len(sub)] = tm
+    return out
+
+
+def max_tm_across_refs(query_ca: Sequence[np.ndarray], refs_ca: Sequence[np.ndarray], max_iter: int = 10,
+                       polish: bool = False, chunk: int = 1 << 16, device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """(max, argmax) over the references of the ``tm_align`` score of every query against every reference, normalised
+    by the reference's length: ``tmalign.max_tm_across_refs`` (foldingdiff/tmalign.py:57-83) for many queries at once.
+    float64 [n_queries] and int64 [n_queries] (the first reference on a tie)."""
+    q, r = _align_traces(query_ca, "query"), _align_traces(refs_ca, "reference")
+    if not r:
+        raise ValueError("no references")
+    nq, nr = len(q), len(r)
+    qi, ri = np.meshgrid(np.arange(nq), np.arange(nr), indexing="ij")
+    pairs = np.stack([qi.ravel(), nq + ri.ravel()], axis=1)
+    tm = pairwise_tm(q + r, pairs, max_iter=max_iter, polish=polish, chunk=chunk, device=device).reshape(nq, nr)
+    best = tm.argmax(axis=1) if nq else np.zeros((0,), np.int64)
+    return tm[np.arange(nq), best], best.astype(np.int64)
+
+
+def _alignable_files(fnames: Sequence[str]) -> Tuple[List[str], List[np.ndarray]]:
+    """The files ``tm_align`` can take and their CA traces: files ``read_backbone`` rejects and chains of more than
+    512 residues are logged and left out (the reference's ``run_tmalign`` gives NaN for a file TM-align fails on)."""
+    kept, traces = [], []
+    for f in fnames:
+        ca = _single_chain_ca(f)
+        if ca is None:
+            logging.warning(f"{f}: not readable as one model - left out")
+        elif len(ca) > ALIGN_MAX_LEN:
+            logging.warning(f"{f}: {len(ca)} residues, more than {ALIGN_MAX_LEN} - left out")
+        else:
+            kept.append(f)
+            traces.append(np.asarray(ca, dtype=np.float64))
+    return kept, traces
+
+
+def pairwise_tmscores(fnames: Sequence[str], max_iter: int = 10, device: int = 0) -> pd.DataFrame:
+    """The symmetric table of ``get_pairwise_tmscores`` (bin/hclust_structures.py:38-69): index and columns are the
+    files' base names without extension, the diagonal is 1.0, and for k before v in ``fnames`` the score of k aligned
+    to v (normalised by v's length) goes on both sides."""
+    kept, traces = _alignable_files(list(fnames))
+    logging.info(f"Computing pairwise distances between {len(kept)} pdb files")
+    bnames = [os.path.splitext(os.path.basename(f))[0] for f in kept]
+    vals = np.ones((len(kept), len(kept)), dtype=np.float64)
+    if len(kept) > 1:
+        iu = np.triu_indices(len(kept), k=1)
+        tm = pairwise_tm(traces, np.stack(iu, axis=1), max_iter=max_iter, device=device)
+        vals[iu] = tm
+        vals[(iu[1], iu[0])] = tm
+    return pd.DataFrame(vals, index=bnames, columns=bnames)
+
+
+def training_tm_scores(pdb_files: Sequence[str], train_files: Sequence[str], max_iter: int = 10,
+                       device: int = 0) -> Tuple[dict, dict]:
+    """``compute_training_tm_scores`` (bin/tmscore_training.py:22-42) without the files it writes: ({sample name: the
+    largest score against the training chains}, {sample name: that training file})."""
+    samples, q = _alignable_files(list(pdb_files))
+    refs, r = _alignable_files(list(train_files))
+    if not refs:
+        raise ValueError("no usable training structure")
+    best, which = max_tm_across_refs(q, r, max_iter=max_iter, device=device) if q else ([], [])
+    names = [os.path.splitext(os.path.basename(f))[0] for f in samples]
+    return ({k: float(v) for k, v in zip(names, best)}, {k: refs[int(j)] for k, j in zip(names, which)})

@@ -38,7 +38,9 @@ extern "C" {
  *    the two-kernel path; option "fuse_ffn" (round 6) */
 /* 5: fd_internal_coords, fd_superpose_rmsd (coordinates -> internal coordinates, superposed RMSD) */
 /* 6: fd_tm_score (TM-score of residue-paired CA traces) */
-/* 7: fd_annotate_sse (P-SEA secondary structure of CA traces) */
+/* 7: fd_annotate_sse (P-SEA secondary structure of CA traces)
+ *    fd_tm_align (alignment search of CA traces) came later and is additive: no existing entry changed, so the version
+ *    stays 7; a library without it fails the binding's symbol lookup by name */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -310,6 +312,36 @@ int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* 
  * Synchronous; the result does not depend on the other chains of the call. */
 int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
                     int8_t* sse_out /* [sum lens]: 0 c, 1 a, 2 b */, int32_t* counts_out /* [n_chains][2] or NULL */);
+
+/* Longest chain fd_tm_align takes: both traces, the search's state and the 2-bit trace-back matrix of the dynamic
+ * programme (n1 x n2 / 4 bytes) sit in one workgroup's LDS. */
+#define FDMI_ALIGN_MAX_LEN 512
+
+/* TM-score of CA traces whose residues do NOT correspond: the residue alignment and the superposition are searched
+ * together, as TM-align does -- what tmalign.run_tmalign computes for tmalign.max_tm_across_refs
+ * (bin/tmscore_training.py) and get_pairwise_tmscores (bin/hclust_structures.py).  It restates the published method
+ * (Zhang & Skolnick 2005) with two of its five starts (gapless threading; secondary structure from fd_annotate_sse's
+ * labels), each refined by dynamic programming with gap-open penalties -0.6 and 0 (DESIGN.md "TM-align-style
+ * alignment" has the exact rules), in fp64, and is not pinned to the TMalign binary: the score is a lower bound on the
+ * optimum TM-align looks for.
+ *   ca, offsets, lens  host float64 [n_res][3] CA traces of n_chains chains packed back to back like
+ *              fd_annotate_sse's; 1 <= lens[c] <= FDMI_ALIGN_MAX_LEN; finite, |coordinate| <= 1e6.  Uploaded once.
+ *   pair_a, pair_b     int32 [n_pairs] chain indices: pair p aligns chain pair_a[p] (x) to chain pair_b[p] (y)
+ *   norm_lens  int32 [n_pairs] normalisation lengths Ln >= min(n1, n2), or NULL for Ln = lens[pair_b[p]] (TM-align's
+ *              "normalized by length of Chain_2")
+ *   max_iter   >= 1: dynamic-programming refinements per start and gap penalty (TM-align's default is 10)
+ *   tm_out     float64 [n_pairs]
+ *   transform_out  NULL, or float64 [n_pairs][12]: R row-major, then t, with y ~ R x + t at that score
+ *   n_ali_out  NULL, or int32 [n_pairs]: aligned residue pairs
+ *   map_offsets, map_out  both NULL, or int64 [n_pairs] and int32 [sum of lens[pair_a[p]]]: map_out[map_offsets[p] + i]
+ *              = the residue of y aligned with residue i of x, or -1; map_offsets packed (map_offsets[0] = 0,
+ *              map_offsets[p + 1] = map_offsets[p] + lens[pair_a[p]])
+ * Synchronous; the result of a pair does not depend on the other pairs of the call. */
+int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens /* null: lens[pair_b] */,
+                int n_pairs, int max_iter, double* tm_out, double* transform_out /* null or [n_pairs][12] */,
+                int32_t* n_ali_out /* null ok */, const int64_t* map_offsets, int32_t* map_out /* both null, or
+                map_out[map_offsets[p] + i] = j or -1 for i < lens[pair_a[p]] */);
 
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
