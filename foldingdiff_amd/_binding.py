@@ -120,6 +120,11 @@ def exported_symbols():
     return list(_SIGNATURES.keys())
 
 
+def ptr(a):
+    """The address of a numpy array as a ``void*`` argument, ``None`` (a null pointer) for ``None``."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
 def check(rc: int):
     if rc != FD_OK:
         msg = load().fd_last_error()

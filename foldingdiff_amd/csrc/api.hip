@@ -1,5 +1,8 @@
-// C-ABI host side of libfdmi.so: model state, weight packing, workspaces, the
-// hipGraph-captured reverse-diffusion loop and the measurement hooks.
+// C-ABI host side of libfdmi.so, the part that holds a model: model state, weight packing, workspaces, the launch plan of
+// a timestep, the hipGraph-captured reverse-diffusion loop, the profile / debug / option entries and RCCL.  The entry
+// points that take a device_id instead of an fd_model live beside it: api_structures.hip (fd_nerf, fd_internal_coords,
+// fd_superpose_rmsd, fd_tm_score, fd_annotate_sse, fd_tm_align) and api_hooks.hip (the fd_test_* hooks); what the three
+// share -- the error string, HIP_TRY, the owner of call-scoped device buffers -- is host_common.h.
 // Boundary: include/fdmi.h (each entry point cites the reference function it replaces).
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -12,20 +15,20 @@
 #include <map>
 #include <string>
 #include <tuple>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/fdmi.h"
 #include "fdmi_kernels.h"
+#include "host_common.h"
 #include "launch_common.h"
 
 using namespace fdmi;
 
 namespace {
+thread_local std::string g_err;  // one per thread for the whole library: fail() writes it, fd_last_error() reads it
+}
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
+int fdmi::fail(int code, const char* fmt, ...) {
   char buf[1024];
   va_list ap;
   va_start(ap, fmt);
@@ -35,12 +38,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return fail(FD_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                      __FILE__, __LINE__);                                          \
-  } while (0)
+namespace {
 
 struct HostTensor {
   std::vector<float> data;
@@ -237,12 +235,14 @@ void pack_split_weight(const float* W, int N, int K, std::vector<uint16_t>* out,
     }
 }
 
+}  // namespace
+
 // Row-image GEMM weights, ordered [384-row tile][k-tile][48 KiB = the workgroup's LDS stage, byte for byte]: the loader copies a
 // k-tile with lane-linear LDS-DMA from CONSECUTIVE cache lines.  The stage is 48 pieces of 8 rows, each piece unit-major:
 // [piece j][position p][row % 8][16 B] with position p holding 16-byte unit p ^ (j & 1) of the row's block (the layout the
 // compute waves' fragment reads are bank-conflict free on; gemm_img.hip uses the same for the activation pieces).
 // Rows padded to whole tiles with zeros.
-void pack_weight_tiles(const float* W, int N, int K, std::vector<uint16_t>* out, float* scale) {
+void fdmi::pack_weight_tiles(const float* W, int N, int K, std::vector<uint16_t>* out, float* scale) {  // (host_common.h)
   std::vector<uint16_t> rm;
   pack_split_weight(W, N, K, &rm, scale, 384);
   const int npad = (N + 383) / 384 * 384, nk = K / 32;
@@ -255,6 +255,7 @@ void pack_weight_tiles(const float* W, int N, int K, std::vector<uint16_t>* out,
       for (int u = 0; u < 8; ++u) memcpy(stage + (j * 1024 + (((u ^ (j & 1)) * 8 + r) << 4)) / 2, blk + u * 8, 16);
     }
 }
+namespace {
 
 int upload_split(fd_model* m, SplitW* dst, const float* W, int N, int K, int row_pad = 128) {
   std::vector<uint16_t> img;
@@ -401,12 +402,14 @@ void free_weights(fd_model* m) {
 struct Bound {
   float linf, l2;
 };
-float scale_for(float bound) {
+}  // namespace
+float fdmi::scale_for(float bound) {  // (host_common.h)
   if (!(bound > 0.f) || !std::isfinite(bound)) return 1.f;
   float e = std::floor(std::log2(30000.0f / bound));
   e = e < -40.f ? -40.f : (e > 40.f ? 40.f : e);
   return std::exp2(e);
 }
+namespace {
 Bound ln_bound(const HostTensor* g, const HostTensor* b, float extra_each = 0.f) {
   const size_t d = g->data.size();
   float gm = 0.f, bm = 0.f;
@@ -419,8 +422,9 @@ Bound ln_bound(const HostTensor* g, const HostTensor* b, float extra_each = 0.f)
   const float sd = std::sqrt((float)d);
   return Bound{gm * sd + bm + extra_each, gm * sd + (float)std::sqrt(b2) + extra_each * sd};
 }
+}  // namespace
 // bound of a dense layer's outputs (rows [r0, r1) of W [N][K]) for inputs with ||x||_2 <= in_l2
-float dense_bound(const float* W, const float* bias, int r0, int r1, int K, float in_l2) {
+float fdmi::dense_bound(const float* W, const float* bias, int r0, int r1, int K, float in_l2) {  // (host_common.h)
   float worst = 0.f;
   for (int j = r0; j < r1; ++j) {
     double n2 = 0.0;
@@ -429,6 +433,7 @@ float dense_bound(const float* W, const float* bias, int r0, int r1, int K, floa
   }
   return worst;
 }
+namespace {
 
 // expected shape of a state_dict entry; returns false if the name is not a parameter we consume
 bool expected_shape(const fd_config& c, const std::string& name, std::vector<int64_t>* shp, bool* ignored) {
@@ -1072,80 +1077,6 @@ int check_shape(fd_model* m, int B, int L, int t) {
   return FD_OK;
 }
 
-int check_lens(const int32_t* lens, int B, int L) {
-  for (int i = 0; i < B; ++i)
-    if (lens[i] < 1 || lens[i] > L) return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", i, lens[i], L);
-  return FD_OK;
-}
-
-// chains / pairs packed back to back: offsets[c] = lens[0] + ... + lens[c-1]; *total = the sum of all lengths
-static int check_packed(const int32_t* offsets, const int32_t* lens, int n, long long limit, long long* total) {
-  long long sum = 0;
-  for (int c = 0; c < n; ++c) sum += lens[c] > 0 ? lens[c] : 0;
-  if (sum > limit) return fail(FD_E_UNSUPPORTED, "%lld entries in total, at most %lld", sum, limit);
-  long long at = 0;
-  for (int c = 0; c < n; ++c) {
-    if (lens[c] < 1) return fail(FD_E_INVALID, "lens[%d]=%d must be >= 1", c, lens[c]);
-    if (offsets[c] < 0 || (long long)offsets[c] + lens[c] > sum)
-      return fail(FD_E_INVALID, "offsets[%d]=%d (length %d) outside the buffer of %lld entries", c, offsets[c], lens[c], sum);
-    if (offsets[c] != at)
-      return fail(FD_E_INVALID, "offsets[%d]=%d, expected %lld (entries are packed back to back in order)", c, offsets[c], at);
-    at += lens[c];
-  }
-  *total = sum;
-  return FD_OK;
-}
-
-// one synchronous device round trip: inputs up, one launch, the outputs down; an output with a null host pointer is a
-// device workspace that stays there.  The launch gets the device buffers in order, inputs first, and may return a
-// hipError_t (fd_internal_coords, fd_superpose_rmsd, fd_tm_score, fd_annotate_sse)
-template <typename Launch>
-static int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs,
-                            std::initializer_list<std::pair<void*, size_t>> outputs, Launch launch) {
-  HIP_TRY(hipSetDevice(device_id));
-  std::vector<void*> bufs;
-  auto cleanup = [&]() {
-    for (void* p : bufs) (void)hipFree(p);
-  };
-  auto hip = [&](hipError_t e, const char* what) -> int {
-    if (e == hipSuccess) return FD_OK;
-    cleanup();
-    return fail(FD_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  for (auto& in : inputs) {
-    void* d = nullptr;
-    if (int rc = hip(hipMalloc(&d, in.second), "hipMalloc")) return rc;
-    bufs.push_back(d);
-    if (int rc = hip(hipMemcpy(d, in.first, in.second, hipMemcpyHostToDevice), "hipMemcpy H2D")) return rc;
-  }
-  for (auto& out : outputs) {
-    void* d = nullptr;
-    if (int rc = hip(hipMalloc(&d, out.second), "hipMalloc")) return rc;
-    bufs.push_back(d);
-  }
-  if constexpr (std::is_void_v<decltype(launch(bufs))>) {
-    launch(bufs);
-  } else {
-    if (int rc = hip(launch(bufs), "launch")) return rc;
-  }
-  if (int rc = hip(hipGetLastError(), "launch")) return rc;
-  if (int rc = hip(hipDeviceSynchronize(), "hipDeviceSynchronize")) return rc;
-  size_t k = inputs.size();
-  for (auto& out : outputs) {
-    if (out.first)
-      if (int rc = hip(hipMemcpy(out.first, bufs[k], out.second, hipMemcpyDeviceToHost), "hipMemcpy D2H")) return rc;
-    ++k;
-  }
-  cleanup();
-  return FD_OK;
-}
-
-template <typename Launch>
-static int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs, void* out,
-                            size_t out_bytes, Launch launch) {
-  return device_roundtrip(device_id, inputs, {{out, out_bytes}}, launch);
-}
-
 // the workspace's captured graph still holds the launch sequence the model's options ask for (an option change that leads to
 // the same sequence -- another rows_hint on the same side of the automatic choice -- keeps the graph)
 static bool graph_current(const fd_model* m, const Workspace& w) { return w.graph && w.graph_plan == plan_step(m, w, false); }
@@ -1194,102 +1125,6 @@ int check_flag(fd_model* m) {
   if (!v) return FD_OK;
   HIP_TRY(hipMemset(w.flag, 0, 4));
   return fail(FD_E_NONFINITE, "the model produced a non-finite value (inf/NaN in the predicted noise)");
-}
-
-// Test hook plumbing of the row-image GEMM: fp32 host operands -> images (scales chosen from the data exactly as
-// fd_finalize chooses them from weight bounds) -> production kernel -> fp32.
-struct ImgHook {
-  std::vector<void*> bufs;
-  ~ImgHook() {
-    for (void* p : bufs) (void)hipFree(p);
-  }
-  hipError_t up(const void* host, size_t bytes, void** dev) {
-    hipError_t e = hipMalloc(dev, bytes);
-    if (e != hipSuccess) return e;
-    bufs.push_back(*dev);
-    return host ? hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice) : hipMemset(*dev, 0, bytes);
-  }
-};
-
-float max_abs(const float* p, size_t n) {
-  float mx = 0.f;
-  for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(p[i]));
-  return mx;
-}
-
-// epilogue: EPI_IMG_BIAS | EPI_IMG_GELU | EPI_IMG_LN
-int img_gemm_hook(int epilogue, const float* A, const float* W, const float* bias, const float* resid, const float* gamma,
-                  const float* beta, float eps, float* C, int M, int N, int K) {
-  if (N % 32 || K % 32) return fail(FD_E_UNSUPPORTED, "row-image GEMM: N=%d and K=%d must be multiples of 32", N, K);
-  if (epilogue == EPI_IMG_LN && N > 384) return fail(FD_E_UNSUPPORTED, "LN-fused GEMM: N=%d > 384", N);
-  ImgHook hk;
-#define I_TRY(expr)                                                                               \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(FD_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));    \
-  } while (0)
-  const long long rows = ((long long)M + 127) / 128 * 128;
-  float *dA, *db, *dg = nullptr, *dbt = nullptr, *dR = nullptr, *dC;
-  void *dAi, *dWi, *dRi = nullptr, *dOi, *dtrash;
-  int* ddims;
-  I_TRY(hk.up(A, (size_t)M * K * 4, (void**)&dA));
-  I_TRY(hk.up(bias, (size_t)N * 4, (void**)&db));
-  I_TRY(hk.up(nullptr, (size_t)rows * K * 4, &dAi));
-  I_TRY(hk.up(nullptr, (size_t)rows * N * 4, &dOi));
-  I_TRY(hk.up(nullptr, (size_t)rows * N * 4, (void**)&dC));
-  I_TRY(hk.up(nullptr, 1024, &dtrash));
-  const int hd[2] = {M, (int)rows};
-  I_TRY(hk.up(hd, sizeof hd, (void**)&ddims));
-  std::vector<uint16_t> img;
-  float wscale = 1.f;
-  pack_weight_tiles(W, N, K, &img, &wscale);
-  I_TRY(hk.up(img.data(), img.size() * 2, &dWi));
-  const float a_scale = scale_for(max_abs(A, (size_t)M * K));
-  launch_f32_to_img(dA, dAi, rows, K, M, a_scale, nullptr);
-  // output bound as fd_finalize derives it: ||row of A||_2 ||row of W||_2 + |bias| (+ residual); LayerNorm: gamma/beta
-  float in_l2 = 0.f;
-  for (int r = 0; r < M; ++r) {
-    double n2 = 0.0;
-    for (int k = 0; k < K; ++k) n2 += (double)A[(size_t)r * K + k] * A[(size_t)r * K + k];
-    in_l2 = std::fmax(in_l2, (float)std::sqrt(n2));
-  }
-  GemmImgArgs g;
-  memset(&g, 0, sizeof g);
-  g.A = static_cast<const unsigned char*>(dAi);
-  g.W = static_cast<const unsigned char*>(dWi);
-  g.bias = db;
-  g.out = static_cast<unsigned char*>(dOi);
-  g.trash = static_cast<unsigned char*>(dtrash);
-  g.dims = ddims;
-  g.N = N;
-  g.K = K;
-  g.acc_scale = 1.0f / (a_scale * wscale);
-  g.eps = eps;
-  float out_scale;
-  if (epilogue == EPI_IMG_LN) {
-    I_TRY(hk.up(gamma, (size_t)N * 4, (void**)&dg));
-    I_TRY(hk.up(beta, (size_t)N * 4, (void**)&dbt));
-    I_TRY(hk.up(resid, (size_t)M * N * 4, (void**)&dR));
-    I_TRY(hk.up(nullptr, (size_t)rows * N * 4, &dRi));
-    const float r_scale = scale_for(max_abs(resid, (size_t)M * N));
-    launch_f32_to_img(dR, dRi, rows, N, M, r_scale, nullptr);
-    g.resid = static_cast<const unsigned char*>(dRi);
-    g.resid_inv = 1.0f / r_scale;
-    g.gamma = dg;
-    g.beta = dbt;
-    out_scale = scale_for(max_abs(gamma, N) * std::sqrt((float)N) + max_abs(beta, N));
-  } else {
-    out_scale = scale_for(dense_bound(W, bias, 0, N, K, in_l2));
-  }
-  g.out_scale = out_scale;
-  g.tail = 1;  // (the hook's ragged row counts exercise the tail slices)
-  launch_gemm_img(epilogue, g, (int)rows, nullptr);
-  launch_img_to_f32(dOi, dC, rows, N, out_scale, nullptr);
-  I_TRY(hipGetLastError());
-  I_TRY(hipDeviceSynchronize());
-  I_TRY(hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-#undef I_TRY
-  return FD_OK;
 }
 
 }  // namespace
@@ -1835,39 +1670,19 @@ int fd_sample_ex(fd_model* m, const float* x_init, const int32_t* lens, int B, i
   const size_t nsteps = (size_t)t_start + 1;
   // rows of `out`: 1 (final only), every state, or every full_history-th state plus the final one
   const size_t out_rows = full_history ? (nsteps + full_history - 1) / full_history : 1;
-  float *d_x = nullptr, *d_noise = nullptr, *d_out = nullptr;
-  int* d_lens = nullptr;
-  int rc = FD_OK;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_x, (void*)d_noise, (void*)d_out, (void*)d_lens})
-      if (p) (void)hipFree(p);
-  };
-#define TRY_CLEAN(expr)                                                                    \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      cleanup();                                                                           \
-      return fail(FD_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                \
-    }                                                                                      \
-  } while (0)
-  TRY_CLEAN(hipMalloc((void**)&d_x, n * 4));
-  TRY_CLEAN(hipMalloc((void**)&d_lens, (size_t)B * 4));
-  TRY_CLEAN(hipMalloc((void**)&d_out, out_rows * n * 4));
-  TRY_CLEAN(hipMemcpy(d_x, x_init, n * 4, hipMemcpyHostToDevice));
-  TRY_CLEAN(hipMemcpy(d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-  if (noise) {
-    TRY_CLEAN(hipMalloc((void**)&d_noise, nsteps * n * 4));
-    TRY_CLEAN(hipMemcpy(d_noise, noise, nsteps * n * 4, hipMemcpyHostToDevice));
-  }
-  rc = fd_sample_dev(m, d_x, d_lens, B, L, t_start, d_noise, seed, seq_offset, d_out, full_history, nullptr);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
-  TRY_CLEAN(hipStreamSynchronize(m->stream));
-  TRY_CLEAN(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
-#undef TRY_CLEAN
-  cleanup();
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  const float* d_noise = nullptr;
+  int* d_lens;
+  HIP_TRY(bufs.alloc(n * 4, &d_x));
+  HIP_TRY(bufs.alloc((size_t)B * 4, &d_lens));
+  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
+  HIP_TRY(hipMemcpy(d_x, x_init, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice));
+  if (noise) HIP_TRY(bufs.upload(noise, nsteps * n * 4, &d_noise));
+  if (int rc = fd_sample_dev(m, d_x, d_lens, B, L, t_start, d_noise, seed, seq_offset, d_out, full_history, nullptr)) return rc;
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
   return check_flag(m);
 }
 
@@ -1879,212 +1694,6 @@ int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, 
   launch_philox_fill(static_cast<float*>(out_dev), seed, t, seq_offset, B, L, m->cfg.n_features, s);
   HIP_TRY(hipGetLastError());
   return FD_OK;
-}
-
-int fd_nerf(int device_id, const float* feats, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
-            int center, double* coords_out) {
-  if (!feats || !lens || !feat_idx || !coords_out || B < 1 || L < 1 || F < 3) return fail(FD_E_INVALID, "bad argument");
-  for (int i = 0; i < 9; ++i)
-    if (feat_idx[i] >= F || (i < 3 && feat_idx[i] < 0)) return fail(FD_E_INVALID, "feat_idx[%d]=%d (F=%d)", i, feat_idx[i], F);
-  if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(device_id));
-  float* d_f = nullptr;
-  int* d_l = nullptr;
-  double* d_o = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_f, (void*)d_l, (void*)d_o})
-      if (p) (void)hipFree(p);
-  };
-#define N_TRY(expr)                                                          \
-  do {                                                                       \
-    hipError_t e_ = (expr);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      cleanup();                                                             \
-      return fail(FD_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));  \
-    }                                                                        \
-  } while (0)
-  const size_t nf = (size_t)B * L * F, no = (size_t)B * 3 * L * 3;
-  N_TRY(hipMalloc((void**)&d_f, nf * 4));
-  N_TRY(hipMalloc((void**)&d_l, (size_t)B * 4));
-  N_TRY(hipMalloc((void**)&d_o, no * 8));
-  N_TRY(hipMemcpy(d_f, feats, nf * 4, hipMemcpyHostToDevice));
-  N_TRY(hipMemcpy(d_l, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-  NerfFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5], feat_idx[6], feat_idx[7], feat_idx[8]};
-  launch_nerf(d_f, d_l, B, L, F, fx, center, d_o, nullptr);
-  N_TRY(hipGetLastError());
-  N_TRY(hipDeviceSynchronize());
-  N_TRY(hipMemcpy(coords_out, d_o, no * 8, hipMemcpyDeviceToHost));
-#undef N_TRY
-  cleanup();
-  return FD_OK;
-}
-
-int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens, int n_chains,
-                       float* feats_out) {
-  if (!xyz || !chain_offsets || !chain_lens || !feats_out || n_chains < 1) return fail(FD_E_INVALID, "bad argument");
-  long long n_res = 0;
-  if (int rc = check_packed(chain_offsets, chain_lens, n_chains, 0x7fffffffLL / 9, &n_res)) return rc;
-  const size_t nr = (size_t)n_res, nc = (size_t)n_chains;
-  return device_roundtrip(device_id, {{xyz, nr * 9 * 4}, {chain_offsets, nc * 4}, {chain_lens, nc * 4}}, feats_out, nr * 9 * 4,
-                          [&](const std::vector<void*>& d) {
-                            launch_internal_coords(static_cast<const float*>(d[0]), static_cast<const int*>(d[1]),
-                                                   static_cast<const int*>(d[2]), n_chains, (int)n_res, static_cast<float*>(d[3]),
-                                                   nullptr);
-                          });
-}
-
-int fd_superpose_rmsd(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens, int n_pairs,
-                      double* rmsd_out) {
-  if (!a || !b || !offsets || !lens || !rmsd_out || n_pairs < 1) return fail(FD_E_INVALID, "bad argument");
-  long long n_atoms = 0;
-  if (int rc = check_packed(offsets, lens, n_pairs, 0x7fffffffLL / 3, &n_atoms)) return rc;
-  const size_t na = (size_t)n_atoms, np = (size_t)n_pairs;
-  return device_roundtrip(device_id, {{a, na * 3 * 8}, {b, na * 3 * 8}, {offsets, np * 4}, {lens, np * 4}}, rmsd_out, np * 8,
-                          [&](const std::vector<void*>& d) {
-                            launch_superpose_rmsd(static_cast<const double*>(d[0]), static_cast<const double*>(d[1]),
-                                                  static_cast<const int*>(d[2]), static_cast<const int*>(d[3]), n_pairs,
-                                                  static_cast<double*>(d[4]), nullptr);
-                          });
-}
-
-int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens,
-                const int32_t* norm_lens, int n_pairs, int stride, double* tm_out, double* transform_out) {
-  if (!a || !b || !offsets || !lens || !tm_out) return fail(FD_E_INVALID, "null argument");
-  if (n_pairs < 1) return fail(FD_E_INVALID, "n_pairs=%d must be >= 1", n_pairs);
-  if (stride < 1) return fail(FD_E_INVALID, "stride=%d must be >= 1", stride);
-  int max_len = 0;
-  for (int p = 0; p < n_pairs; ++p) {
-    if (lens[p] < 1 || lens[p] > FDMI_TM_MAX_LEN)
-      return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", p, lens[p], FDMI_TM_MAX_LEN);
-    if (norm_lens && norm_lens[p] < lens[p])
-      return fail(FD_E_INVALID, "norm_lens[%d]=%d is below lens[%d]=%d", p, norm_lens[p], p, lens[p]);
-    max_len = std::max(max_len, (int)lens[p]);
-  }
-  long long n_res = 0;
-  if (int rc = check_packed(offsets, lens, n_pairs, 0x7fffffffLL / 3, &n_res)) return rc;
-  // finite coordinates within 1e6 A (every squared distance stays far from overflow), and the centroids the kernel
-  // subtracts: the traces are scored in their own centred frames
-  std::vector<double> cent((size_t)n_pairs * 6, 0.0);
-  for (int p = 0; p < n_pairs; ++p) {
-    for (int i = offsets[p]; i < offsets[p] + lens[p]; ++i)
-      for (int d = 0; d < 3; ++d) {
-        const double u = a[(size_t)i * 3 + d], v = b[(size_t)i * 3 + d];
-        if (!(std::fabs(u) <= 1e6) || !(std::fabs(v) <= 1e6))
-          return fail(FD_E_INVALID, "coordinate %d of residue %d (pair %d) is not finite or beyond 1e6: a %g, b %g", d, i,
-                      p, u, v);
-        cent[(size_t)p * 6 + d] += u;
-        cent[(size_t)p * 6 + 3 + d] += v;
-      }
-    for (int d = 0; d < 6; ++d) cent[(size_t)p * 6 + d] /= lens[p];
-  }
-  std::vector<int32_t> chunk_off((size_t)n_pairs + 1);
-  const int n_chunks = tm_chunk_offsets(lens, n_pairs, stride, chunk_off.data());
-  if (n_chunks < 0) return fail(FD_E_UNSUPPORTED, "more than 2^31 - 1 seed workgroups");
-  const size_t na = (size_t)n_res, np = (size_t)n_pairs;
-  std::vector<double> transform(np * 12);
-  return device_roundtrip(
-      device_id,
-      {{a, na * 3 * 8}, {b, na * 3 * 8}, {cent.data(), np * 6 * 8}, {offsets, np * 4}, {lens, np * 4},
-       {norm_lens ? norm_lens : lens, np * 4}, {chunk_off.data(), (np + 1) * 4}},
-      {{nullptr, tm_workspace_bytes(n_chunks)}, {tm_out, np * 8}, {transform_out, np * 12 * 8}},
-      [&](const std::vector<void*>& d) {
-        return launch_tm_score(static_cast<const double*>(d[0]), static_cast<const double*>(d[1]),
-                               static_cast<const double*>(d[2]), static_cast<const int*>(d[3]), static_cast<const int*>(d[4]),
-                               static_cast<const int*>(d[5]), static_cast<const int*>(d[6]), n_pairs, n_chunks, stride,
-                               max_len, static_cast<double*>(d[7]), static_cast<double*>(d[8]), static_cast<double*>(d[9]),
-                               nullptr);
-      });
-}
-
-int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
-                    int8_t* sse_out, int32_t* counts_out) {
-  if (!ca || !offsets || !lens || !sse_out) return fail(FD_E_INVALID, "null argument");
-  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
-  int max_len = 0;
-  for (int c = 0; c < n_chains; ++c) {
-    if (lens[c] < 1 || lens[c] > FDMI_SSE_MAX_LEN)
-      return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", c, lens[c], FDMI_SSE_MAX_LEN);
-    max_len = std::max(max_len, (int)lens[c]);
-  }
-  long long n_res = 0;
-  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 3, &n_res)) return rc;
-  // finite coordinates within 1e6 A: every squared distance stays far from overflow
-  for (long long k = 0; k < n_res * 3; ++k)
-    if (!(std::fabs(ca[k]) <= 1e6))
-      return fail(FD_E_INVALID, "coordinate %d of residue %lld is not finite or beyond 1e6: %g", (int)(k % 3), k / 3, ca[k]);
-  const size_t na = (size_t)n_res, nc = (size_t)n_chains;
-  return device_roundtrip(device_id, {{ca, na * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}},
-                          {{sse_out, na}, {counts_out, nc * 2 * 4}}, [&](const std::vector<void*>& d) {
-                            launch_psea(static_cast<const double*>(d[0]), static_cast<const int*>(d[1]),
-                                        static_cast<const int*>(d[2]), n_chains, max_len, static_cast<signed char*>(d[3]),
-                                        static_cast<int*>(d[4]), nullptr);
-                          });
-}
-
-int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
-                const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens, int n_pairs, int max_iter,
-                double* tm_out, double* transform_out, int32_t* n_ali_out, const int64_t* map_offsets, int32_t* map_out) {
-  if (!ca || !offsets || !lens || !pair_a || !pair_b || !tm_out) return fail(FD_E_INVALID, "null argument");
-  if ((map_offsets == nullptr) != (map_out == nullptr))
-    return fail(FD_E_INVALID, "null argument: map_offsets and map_out go together");
-  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
-  if (n_pairs < 1) return fail(FD_E_INVALID, "n_pairs=%d must be >= 1", n_pairs);
-  if (max_iter < 1) return fail(FD_E_INVALID, "max_iter=%d must be >= 1", max_iter);
-  int max_len = 0;
-  for (int c = 0; c < n_chains; ++c) {
-    if (lens[c] < 1 || lens[c] > FDMI_ALIGN_MAX_LEN)
-      return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", c, lens[c], FDMI_ALIGN_MAX_LEN);
-    max_len = std::max(max_len, (int)lens[c]);
-  }
-  long long n_res = 0;
-  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 3, &n_res)) return rc;
-  long long n_map = 0;
-  std::vector<int32_t> norm((size_t)n_pairs);
-  for (int p = 0; p < n_pairs; ++p) {
-    if (pair_a[p] < 0 || pair_a[p] >= n_chains || pair_b[p] < 0 || pair_b[p] >= n_chains)
-      return fail(FD_E_INVALID, "pair %d = (%d, %d): chain index outside [0, %d)", p, pair_a[p], pair_b[p], n_chains);
-    const int n1 = lens[pair_a[p]], n2 = lens[pair_b[p]];
-    norm[p] = norm_lens ? norm_lens[p] : n2;
-    if (norm[p] < std::min(n1, n2))
-      return fail(FD_E_INVALID, "norm_lens[%d]=%d is below min(%d, %d)", p, norm[p], n1, n2);
-    if (map_offsets && map_offsets[p] != n_map)
-      return fail(FD_E_INVALID, "map_offsets[%d]=%lld, expected %lld (packed)", p, (long long)map_offsets[p], n_map);
-    n_map += n1;
-  }
-  // finite coordinates within 1e6 A (every squared distance stays far from overflow), and the centroids the kernel
-  // subtracts: every chain is aligned in its own centred frame
-  std::vector<double> cent((size_t)n_chains * 3, 0.0);
-  for (int c = 0; c < n_chains; ++c) {
-    for (int i = offsets[c]; i < offsets[c] + lens[c]; ++i)
-      for (int d = 0; d < 3; ++d) {
-        const double u = ca[(size_t)i * 3 + d];
-        if (!(std::fabs(u) <= 1e6))
-          return fail(FD_E_INVALID, "coordinate %d of residue %d (chain %d) is not finite or beyond 1e6: %g", d, i, c, u);
-        cent[(size_t)c * 3 + d] += u;
-      }
-    for (int d = 0; d < 3; ++d) cent[(size_t)c * 3 + d] /= lens[c];
-  }
-  const size_t na = (size_t)n_res, nc = (size_t)n_chains, np = (size_t)n_pairs;
-  const size_t map_bytes = map_out ? (size_t)n_map * 4 : 4;
-  static const int64_t no_offsets = 0;
-  return device_roundtrip(
-      device_id,
-      {{ca, na * 3 * 8}, {cent.data(), nc * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}, {pair_a, np * 4}, {pair_b, np * 4},
-       {norm.data(), np * 4}, {map_offsets ? map_offsets : &no_offsets, map_offsets ? np * 8 : 8}},
-      {{nullptr, na}, {nullptr, nc * 2 * 4}, {tm_out, np * 8}, {transform_out, np * 12 * 8}, {n_ali_out, np * 4},
-       {map_out, map_bytes}},
-      [&](const std::vector<void*>& d) {
-        // the labels of every chain first (start 2 reads them), then the pairs; both on the null stream, in order
-        launch_psea(static_cast<const double*>(d[0]), static_cast<const int*>(d[2]), static_cast<const int*>(d[3]), n_chains,
-                    max_len, static_cast<signed char*>(d[8]), static_cast<int*>(d[9]), nullptr);
-        return launch_tm_align(static_cast<const double*>(d[0]), static_cast<const double*>(d[1]),
-                               static_cast<const int*>(d[2]), static_cast<const int*>(d[3]),
-                               static_cast<const signed char*>(d[8]), static_cast<const int*>(d[4]),
-                               static_cast<const int*>(d[5]), static_cast<const int*>(d[6]),
-                               map_out ? static_cast<const long long*>(d[7]) : nullptr, n_pairs, max_iter, max_len,
-                               static_cast<double*>(d[10]), static_cast<double*>(d[11]), static_cast<int*>(d[12]),
-                               map_out ? static_cast<int*>(d[13]) : nullptr, nullptr);
-      });
 }
 
 int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L, const void* lens_dev, const void* item_off_dev,
@@ -2105,207 +1714,6 @@ int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L,
     for (int f = 0; f < a.F; ++f) a.offset[f] = offset[f];
   launch_shift_trim(a, hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream);
   HIP_TRY(hipGetLastError());
-  return FD_OK;
-}
-
-int fd_test_wrap(int device_id, int which, const float* in, int64_t n, float* out) {
-  if (!in || !out || n < 1) return fail(FD_E_INVALID, "bad argument");
-  HIP_TRY(hipSetDevice(device_id));
-  float *din = nullptr, *dout = nullptr;
-  auto cleanup = [&]() {
-    if (din) (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-  };
-#define W_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(FD_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-  W_TRY(hipMalloc((void**)&din, (size_t)n * 4));
-  W_TRY(hipMalloc((void**)&dout, (size_t)n * 4));
-  W_TRY(hipMemcpy(din, in, (size_t)n * 4, hipMemcpyHostToDevice));
-  if (which == 0) launch_wrap_test_f32(din, dout, n, nullptr);
-  else launch_wrap_test_img(din, dout, n, nullptr);
-  W_TRY(hipGetLastError());
-  W_TRY(hipDeviceSynchronize());
-  W_TRY(hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
-#undef W_TRY
-  cleanup();
-  return FD_OK;
-}
-
-int fd_test_gemm(int device_id, int precision, int epilogue, const float* A, const float* W, const float* bias,
-                 const float* resid, float* C, int M, int N, int K) {
-  if (!A || !W || !bias || !C || M < 1 || N < 1 || K < 16 || K % 32) return fail(FD_E_INVALID, "bad argument");
-  if (epilogue < EPI_BIAS || epilogue > EPI_BIAS_RESID || (epilogue == EPI_BIAS_RESID && !resid))
-    return fail(FD_E_INVALID, "bad epilogue");
-  HIP_TRY(hipSetDevice(device_id));
-  if (precision == FD_PREC_F16X3) {
-    if (epilogue == EPI_BIAS_RESID)
-      return fail(FD_E_UNSUPPORTED, "the row-image path has no unfused residual epilogue (LayerNorm is always fused): use fd_test_gemm_ln");
-    return img_gemm_hook(epilogue == EPI_BIAS_GELU ? EPI_IMG_GELU : EPI_IMG_BIAS, A, W, bias, nullptr, nullptr, nullptr, 0.f, C, M, N, K);
-  }
-  float *dA = nullptr, *dW = nullptr, *db = nullptr, *dr = nullptr, *dC = nullptr;
-  void* dWp = nullptr;
-  int rc = FD_OK;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)dA, (void*)dW, (void*)db, (void*)dr, (void*)dC, dWp})
-      if (p) (void)hipFree(p);
-  };
-#define T_TRY(expr)                                                          \
-  do {                                                                       \
-    hipError_t e_ = (expr);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      cleanup();                                                             \
-      return fail(FD_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));  \
-    }                                                                        \
-  } while (0)
-  T_TRY(hipMalloc((void**)&dA, (size_t)M * K * 4));
-  T_TRY(hipMalloc((void**)&dW, (size_t)N * K * 4));
-  T_TRY(hipMalloc((void**)&db, (size_t)N * 4));
-  T_TRY(hipMalloc((void**)&dC, (size_t)M * N * 4));
-  T_TRY(hipMemcpy(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice));
-  T_TRY(hipMemcpy(dW, W, (size_t)N * K * 4, hipMemcpyHostToDevice));
-  T_TRY(hipMemcpy(db, bias, (size_t)N * 4, hipMemcpyHostToDevice));
-  if (resid) {
-    T_TRY(hipMalloc((void**)&dr, (size_t)M * N * 4));
-    T_TRY(hipMemcpy(dr, resid, (size_t)M * N * 4, hipMemcpyHostToDevice));
-  }
-  if (precision == FD_PREC_F32) {
-    launch_gemm_f32(epilogue, dA, dW, db, dr, dC, M, N, K, nullptr);
-  } else {
-    cleanup();
-    return fail(FD_E_INVALID, "precision %d", precision);
-  }
-  T_TRY(hipGetLastError());
-  T_TRY(hipDeviceSynchronize());
-  T_TRY(hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-#undef T_TRY
-  cleanup();
-  return rc;
-}
-
-int fd_test_gemm_ln(int device_id, int precision, int use_fused, const float* A, const float* W, const float* bias,
-                    const float* resid, const float* gamma, const float* beta, float eps, float* C, int M, int N,
-                    int K) {
-  if (!A || !W || !bias || !resid || !gamma || !beta || !C || M < 1 || N < 1 || K < 32 || K % 32)
-    return fail(FD_E_INVALID, "bad argument");
-  if (precision != FD_PREC_F32 && precision != FD_PREC_F16X3) return fail(FD_E_INVALID, "precision %d", precision);
-  HIP_TRY(hipSetDevice(device_id));
-  if (precision == FD_PREC_F16X3) {
-    if (!use_fused) return fail(FD_E_UNSUPPORTED, "the row-image path always fuses the LayerNorm into the GEMM");
-    return img_gemm_hook(EPI_IMG_LN, A, W, bias, resid, gamma, beta, eps, C, M, N, K);
-  }
-  std::vector<void*> bufs;
-  auto cleanup = [&]() {
-    for (void* p : bufs) (void)hipFree(p);
-  };
-#define T_TRY(expr)                                                          \
-  do {                                                                       \
-    hipError_t e_ = (expr);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      cleanup();                                                             \
-      return fail(FD_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));  \
-    }                                                                        \
-  } while (0)
-  auto up = [&](const void* host, size_t bytes, void** dev) -> hipError_t {
-    hipError_t e = hipMalloc(dev, bytes);
-    if (e != hipSuccess) return e;
-    bufs.push_back(*dev);
-    return host ? hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice) : hipSuccess;
-  };
-  float *dA, *dW, *db, *dr, *dg, *dbt, *dT, *dC;
-  T_TRY(up(A, (size_t)M * K * 4, (void**)&dA));
-  T_TRY(up(W, (size_t)N * K * 4, (void**)&dW));
-  T_TRY(up(bias, (size_t)N * 4, (void**)&db));
-  T_TRY(up(resid, (size_t)M * N * 4, (void**)&dr));
-  T_TRY(up(gamma, (size_t)N * 4, (void**)&dg));
-  T_TRY(up(beta, (size_t)N * 4, (void**)&dbt));
-  T_TRY(up(nullptr, (size_t)M * N * 4, (void**)&dT));
-  T_TRY(up(nullptr, (size_t)M * N * 4, (void**)&dC));
-  if (use_fused) {
-    const bool ok = launch_gemm_f32_ln(dA, dW, db, dr, dg, dbt, eps, dC, M, N, K, nullptr);
-    if (!ok) {
-      cleanup();
-      return fail(FD_E_UNSUPPORTED, "no LN-fused GEMM for N=%d K=%d in this precision", N, K);
-    }
-  } else {
-    launch_gemm_f32(EPI_BIAS_RESID, dA, dW, db, dr, dT, M, N, K, nullptr);
-    launch_layernorm(dT, dg, dbt, eps, dC, M, N, nullptr);
-  }
-  T_TRY(hipGetLastError());
-  T_TRY(hipDeviceSynchronize());
-  T_TRY(hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-#undef T_TRY
-  cleanup();
-  return FD_OK;
-}
-
-int fd_test_gemm_time(int device_id, int precision, int M, int N, int K, int reps, double* ms_per_launch) {
-  if (!ms_per_launch || M < 1 || N < 1 || K < 32 || K % 32 || reps < 1) return fail(FD_E_INVALID, "bad argument");
-  if (precision == FD_PREC_F16X3 && N % 32) return fail(FD_E_UNSUPPORTED, "row-image GEMM: N=%d must be a multiple of 32", N);
-  HIP_TRY(hipSetDevice(device_id));
-  std::vector<float> hA((size_t)M * K), hW((size_t)N * K), hb(N, 0.1f);
-  unsigned st = 12345u;
-  auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xFFFF) / 32768.0f - 1.0f; };
-  for (auto& v : hA) v = rnd();
-  for (auto& v : hW) v = 0.02f * rnd();
-  ImgHook hk;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-#define T_TRY(expr)                                                          \
-  do {                                                                       \
-    hipError_t e_ = (expr);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      if (e0) (void)hipEventDestroy(e0);                                     \
-      if (e1) (void)hipEventDestroy(e1);                                     \
-      return fail(FD_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));  \
-    }                                                                        \
-  } while (0)
-  const long long rows = ((long long)M + 127) / 128 * 128;
-  float *dA, *dW, *db, *dC;
-  T_TRY(hk.up(hA.data(), hA.size() * 4, (void**)&dA));
-  T_TRY(hk.up(hW.data(), hW.size() * 4, (void**)&dW));
-  T_TRY(hk.up(hb.data(), (size_t)N * 4, (void**)&db));
-  T_TRY(hk.up(nullptr, (size_t)rows * N * 4, (void**)&dC));
-  GemmImgArgs g;
-  memset(&g, 0, sizeof g);
-  if (precision == FD_PREC_F16X3) {
-    void *dAi, *dWi, *dtrash;
-    int* ddims;
-    std::vector<uint16_t> img;
-    float wscale = 1.f;
-    pack_weight_tiles(hW.data(), N, K, &img, &wscale);
-    T_TRY(hk.up(nullptr, (size_t)rows * K * 4, &dAi));
-    T_TRY(hk.up(img.data(), img.size() * 2, &dWi));
-    T_TRY(hk.up(nullptr, 1024, &dtrash));
-    const int hd[2] = {M, (int)rows};
-    T_TRY(hk.up(hd, sizeof hd, (void**)&ddims));
-    launch_f32_to_img(dA, dAi, rows, K, M, 8192.0f, nullptr);
-    g.A = static_cast<const unsigned char*>(dAi);
-    g.W = static_cast<const unsigned char*>(dWi);
-    g.bias = db;
-    g.out = reinterpret_cast<unsigned char*>(dC);
-    g.trash = static_cast<unsigned char*>(dtrash);
-    g.dims = ddims;
-    g.N = N;
-    g.K = K;
-    g.acc_scale = 1.0f / (8192.0f * wscale);
-    g.out_scale = 1024.0f;
-  }
-  T_TRY(hipEventCreate(&e0));
-  T_TRY(hipEventCreate(&e1));
-  auto run = [&]() {
-    if (precision == FD_PREC_F16X3) launch_gemm_img(EPI_IMG_BIAS, g, (int)rows, nullptr);
-    else launch_gemm_f32(EPI_BIAS, dA, dW, db, nullptr, dC, M, N, K, nullptr);
-  };
-  for (int i = 0; i < 3; ++i) run();
-  T_TRY(hipDeviceSynchronize());
-  T_TRY(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < reps; ++i) run();
-  T_TRY(hipEventRecord(e1, nullptr));
-  T_TRY(hipEventSynchronize(e1));
-  float ms = 0.f;
-  T_TRY(hipEventElapsedTime(&ms, e0, e1));
-#undef T_TRY
-  *ms_per_launch = ms / reps;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   return FD_OK;
 }
 
@@ -2359,18 +1767,19 @@ int fd_debug_read(fd_model* m, const char* name, float* out, int64_t n_floats) {
   const float s_next = li + 1 < c.n_layers ? m->layers[li + 1].s_h : m->s_hfinal;
   const long long BH = (long long)w.B * sub_heads(c);
   long long need = 0;
+  DeviceBufs bufs;
   float* tmp = nullptr;
   auto img = [&](const unsigned char* src, int K, float scale) -> int {
     need = (long long)w.cap * K;
     if (n_floats < need) return fail(FD_E_INVALID, "fd_debug_read(%s): need %lld floats", name, need);
-    HIP_TRY(hipMalloc((void**)&tmp, need * 4));
+    HIP_TRY(bufs.alloc(need * 4, &tmp));
     launch_img_to_f32(src, tmp, w.cap, K, scale, m->stream);
     return FD_OK;
   };
   auto qkv = [&](const unsigned char* src, int rowbytes, int is_vt, float scale) -> int {
     need = BH * w.LTOT * 32;
     if (n_floats < need) return fail(FD_E_INVALID, "fd_debug_read(%s): need %lld floats", name, need);
-    HIP_TRY(hipMalloc((void**)&tmp, need * 4));
+    HIP_TRY(bufs.alloc(need * 4, &tmp));
     launch_qkv_unpack(src, tmp, BH, w.LTOT, w.LPK, rowbytes, is_vt, scale, m->stream);
     return FD_OK;
   };
@@ -2399,10 +1808,8 @@ int fd_debug_read(fd_model* m, const char* name, float* out, int64_t n_floats) {
     return FD_OK;
   } else return fail(FD_E_INVALID, "fd_debug_read: unknown buffer '%s'", name);
   if (rc) return rc;
-  hipError_t e = hipStreamSynchronize(m->stream);
-  if (e == hipSuccess) e = hipMemcpy(out, tmp, need * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(FD_E_HIP, "fd_debug_read: %s", hipGetErrorString(e));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  HIP_TRY(hipMemcpy(out, tmp, need * 4, hipMemcpyDeviceToHost));
   return FD_OK;
 }
 

@@ -1,0 +1,145 @@
+// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip).
+// None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// round trip (host_common.h).  Boundary: include/fdmi.h.
+#include <algorithm>
+#include <vector>
+
+#include "fdmi_kernels.h"
+#include "host_common.h"
+
+using namespace fdmi;
+
+extern "C" {
+
+int fd_nerf(int device_id, const float* feats, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+            int center, double* coords_out) {
+  if (!feats || !lens || !feat_idx || !coords_out || B < 1 || L < 1 || F < 3) return fail(FD_E_INVALID, "bad argument");
+  for (int i = 0; i < 9; ++i)
+    if (feat_idx[i] >= F || (i < 3 && feat_idx[i] < 0)) return fail(FD_E_INVALID, "feat_idx[%d]=%d (F=%d)", i, feat_idx[i], F);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  const NerfFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5], feat_idx[6], feat_idx[7], feat_idx[8]};
+  return device_roundtrip(device_id, {{feats, (size_t)B * L * F * 4}, {lens, (size_t)B * 4}},
+                          {{coords_out, (size_t)B * 3 * L * 3 * 8}},
+                          [&](const RoundtripBufs& d) { launch_nerf(d.in(0), d.in(1), B, L, F, fx, center, d.out(0), nullptr); });
+}
+
+int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens, int n_chains,
+                       float* feats_out) {
+  if (!xyz || !chain_offsets || !chain_lens || !feats_out || n_chains < 1) return fail(FD_E_INVALID, "bad argument");
+  long long n_res = 0;
+  if (int rc = check_packed(chain_offsets, chain_lens, n_chains, 0x7fffffffLL / 9, &n_res)) return rc;
+  const size_t nr = (size_t)n_res, nc = (size_t)n_chains;
+  return device_roundtrip(device_id, {{xyz, nr * 9 * 4}, {chain_offsets, nc * 4}, {chain_lens, nc * 4}},
+                          {{feats_out, nr * 9 * 4}}, [&](const RoundtripBufs& d) {
+                            launch_internal_coords(d.in(0), d.in(1), d.in(2), n_chains, (int)n_res, d.out(0), nullptr);
+                          });
+}
+
+int fd_superpose_rmsd(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens, int n_pairs,
+                      double* rmsd_out) {
+  if (!a || !b || !offsets || !lens || !rmsd_out || n_pairs < 1) return fail(FD_E_INVALID, "bad argument");
+  long long n_atoms = 0;
+  if (int rc = check_packed(offsets, lens, n_pairs, 0x7fffffffLL / 3, &n_atoms)) return rc;
+  const size_t na = (size_t)n_atoms, np = (size_t)n_pairs;
+  return device_roundtrip(device_id, {{a, na * 3 * 8}, {b, na * 3 * 8}, {offsets, np * 4}, {lens, np * 4}},
+                          {{rmsd_out, np * 8}}, [&](const RoundtripBufs& d) {
+                            launch_superpose_rmsd(d.in(0), d.in(1), d.in(2), d.in(3), n_pairs, d.out(0), nullptr);
+                          });
+}
+
+int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* offsets, const int32_t* lens,
+                const int32_t* norm_lens, int n_pairs, int stride, double* tm_out, double* transform_out) {
+  if (!a || !b || !offsets || !lens || !tm_out) return fail(FD_E_INVALID, "null argument");
+  if (n_pairs < 1) return fail(FD_E_INVALID, "n_pairs=%d must be >= 1", n_pairs);
+  if (stride < 1) return fail(FD_E_INVALID, "stride=%d must be >= 1", stride);
+  int max_len = 0;
+  if (int rc = check_lens(lens, n_pairs, FDMI_TM_MAX_LEN, &max_len)) return rc;
+  for (int p = 0; norm_lens && p < n_pairs; ++p)
+    if (norm_lens[p] < lens[p])
+      return fail(FD_E_INVALID, "norm_lens[%d]=%d is below lens[%d]=%d", p, norm_lens[p], p, lens[p]);
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_pairs, 0x7fffffffLL / 3, &n_res)) return rc;
+  // pair p's centroids: a's at cent[6 p], b's at cent[6 p + 3]
+  std::vector<double> cent((size_t)n_pairs * 6);
+  if (int rc = check_coords(a, offsets, lens, n_pairs, cent.data(), 6)) return rc;
+  if (int rc = check_coords(b, offsets, lens, n_pairs, cent.data() + 3, 6)) return rc;
+  std::vector<int32_t> chunk_off((size_t)n_pairs + 1);
+  const int n_chunks = tm_chunk_offsets(lens, n_pairs, stride, chunk_off.data());
+  if (n_chunks < 0) return fail(FD_E_UNSUPPORTED, "more than 2^31 - 1 seed workgroups");
+  const size_t na = (size_t)n_res, np = (size_t)n_pairs;
+  return device_roundtrip(
+      device_id,
+      {{a, na * 3 * 8}, {b, na * 3 * 8}, {cent.data(), np * 6 * 8}, {offsets, np * 4}, {lens, np * 4},
+       {norm_lens ? norm_lens : lens, np * 4}, {chunk_off.data(), (np + 1) * 4}},
+      {{nullptr, tm_workspace_bytes(n_chunks)}, {tm_out, np * 8}, {transform_out, np * 12 * 8}},
+      [&](const RoundtripBufs& d) {
+        return launch_tm_score(d.in(0), d.in(1), d.in(2), d.in(3), d.in(4), d.in(5), d.in(6), n_pairs, n_chunks, stride,
+                               max_len, d.out(0), d.out(1), d.out(2), nullptr);
+      });
+}
+
+int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                    int8_t* sse_out, int32_t* counts_out) {
+  if (!ca || !offsets || !lens || !sse_out) return fail(FD_E_INVALID, "null argument");
+  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
+  int max_len = 0;
+  if (int rc = check_lens(lens, n_chains, FDMI_SSE_MAX_LEN, &max_len)) return rc;
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 3, &n_res)) return rc;
+  if (int rc = check_coords(ca, offsets, lens, n_chains)) return rc;
+  const size_t na = (size_t)n_res, nc = (size_t)n_chains;
+  return device_roundtrip(device_id, {{ca, na * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}},
+                          {{sse_out, na}, {counts_out, nc * 2 * 4}}, [&](const RoundtripBufs& d) {
+                            launch_psea(d.in(0), d.in(1), d.in(2), n_chains, max_len, d.out(0), d.out(1), nullptr);
+                          });
+}
+
+int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens, int n_pairs, int max_iter,
+                double* tm_out, double* transform_out, int32_t* n_ali_out, const int64_t* map_offsets, int32_t* map_out) {
+  if (!ca || !offsets || !lens || !pair_a || !pair_b || !tm_out) return fail(FD_E_INVALID, "null argument");
+  if ((map_offsets == nullptr) != (map_out == nullptr))
+    return fail(FD_E_INVALID, "null argument: map_offsets and map_out go together");
+  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
+  if (n_pairs < 1) return fail(FD_E_INVALID, "n_pairs=%d must be >= 1", n_pairs);
+  if (max_iter < 1) return fail(FD_E_INVALID, "max_iter=%d must be >= 1", max_iter);
+  int max_len = 0;
+  if (int rc = check_lens(lens, n_chains, FDMI_ALIGN_MAX_LEN, &max_len)) return rc;
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 3, &n_res)) return rc;
+  long long n_map = 0;
+  std::vector<int32_t> norm((size_t)n_pairs);
+  for (int p = 0; p < n_pairs; ++p) {
+    if (pair_a[p] < 0 || pair_a[p] >= n_chains || pair_b[p] < 0 || pair_b[p] >= n_chains)
+      return fail(FD_E_INVALID, "pair %d = (%d, %d): chain index outside [0, %d)", p, pair_a[p], pair_b[p], n_chains);
+    const int n1 = lens[pair_a[p]], n2 = lens[pair_b[p]];
+    norm[p] = norm_lens ? norm_lens[p] : n2;
+    if (norm[p] < std::min(n1, n2))
+      return fail(FD_E_INVALID, "norm_lens[%d]=%d is below min(%d, %d)", p, norm[p], n1, n2);
+    if (map_offsets && map_offsets[p] != n_map)
+      return fail(FD_E_INVALID, "map_offsets[%d]=%lld, expected %lld (packed)", p, (long long)map_offsets[p], n_map);
+    n_map += n1;
+  }
+  std::vector<double> cent((size_t)n_chains * 3);
+  if (int rc = check_coords(ca, offsets, lens, n_chains, cent.data())) return rc;
+  const size_t na = (size_t)n_res, nc = (size_t)n_chains, np = (size_t)n_pairs;
+  const size_t map_bytes = map_out ? (size_t)n_map * 4 : 4;
+  static const int64_t no_offsets = 0;
+  return device_roundtrip(
+      device_id,
+      {{ca, na * 3 * 8}, {cent.data(), nc * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}, {pair_a, np * 4}, {pair_b, np * 4},
+       {norm.data(), np * 4}, {map_offsets ? map_offsets : &no_offsets, map_offsets ? np * 8 : 8}},
+      {{nullptr, na}, {nullptr, nc * 2 * 4}, {tm_out, np * 8}, {transform_out, np * 12 * 8}, {n_ali_out, np * 4},
+       {map_out, map_bytes}},
+      [&](const RoundtripBufs& d) {
+        // the labels of every chain first (start 2 reads them), then the pairs; both on the null stream, in order
+        launch_psea(d.in(0), d.in(2), d.in(3), n_chains, max_len, d.out(0), d.out(1), nullptr);
+        const long long* map_off = d.in(7);
+        int* map = d.out(5);
+        return launch_tm_align(d.in(0), d.in(1), d.in(2), d.in(3), d.out(0), d.in(4), d.in(5), d.in(6),
+                               map_out ? map_off : nullptr, n_pairs, max_iter, max_len, d.out(2), d.out(3), d.out(4),
+                               map_out ? map : nullptr, nullptr);
+      });
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// Internal launch interface between the C-ABI host code (api.hip) and the
-// gfx950 kernels.  Not installed; include/fdmi.h is the public boundary.
+// Internal launch interface between the C-ABI host code (api.hip: the model; api_structures.hip: fd_nerf and the
+// structure entries; api_hooks.hip: the fd_test_* hooks) and the gfx950 kernels.  Not installed; include/fdmi.h is the
+// public boundary.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -206,7 +207,7 @@ bool launch_attention_gen(const AttnImgArgs& p, int nb, hipStream_t s);
 struct SeqAttnArgs {
   const unsigned char* himg;   // hidden-state image [rows128][d/32] (grouped, img_common.h)
   unsigned himg_bytes;         // its size (< 4 GiB: 32-bit lane offsets; rows beyond it read as zeros)
-  const unsigned char* wimg;   // weight image [head][k-tile][unit 0-7][96 rows: q_h | k_h | v_h][16 B] at the scale of wqkv_i (api.hip: pack_seq_attn_weights)
+  const unsigned char* wimg;   // weight image [head][k-tile][unit 0-7][96 rows: q_h | k_h | v_h][16 B] at the scale of wqkv_i (api.hip: upload_seq_attn_weights)
   const float* bias;           // [3 d]: q | k | v
   const u32x4_t* demb;         // distance table image [2 maxpos - 1][128 B]
   const int* lens;             // [B] unmasked keys per sequence

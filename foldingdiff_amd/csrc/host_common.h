@@ -1,0 +1,166 @@
+// Host-only helpers shared by the three C-ABI sources (api.hip: the model; api_structures.hip: the structure entries;
+// api_hooks.hip: the test hooks): the error string, the owner of device buffers that live for one call, the synchronous
+// round trip built on it, and the argument checks of the packed-chain entries.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "../../include/fdmi.h"
+
+namespace fdmi {
+
+// sets the calling thread's error string (fd_last_error) and returns `code`; defined once, in api.hip
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define HIP_TRY(expr)                                                                               \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) return ::fdmi::fail(FD_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                                              __FILE__, __LINE__);                                  \
+  } while (0)
+
+// api.hip's weight packing and scale rules, as the test hooks use them
+void pack_weight_tiles(const float* W, int N, int K, std::vector<uint16_t>* out, float* scale);
+float scale_for(float bound);
+float dense_bound(const float* W, const float* bias, int r0, int r1, int K, float in_l2);
+
+// Device buffers that live for one call: freed when the owner goes out of scope, on every path.
+class DeviceBufs {
+ public:
+  DeviceBufs() = default;
+  DeviceBufs(const DeviceBufs&) = delete;
+  DeviceBufs& operator=(const DeviceBufs&) = delete;
+  ~DeviceBufs() {
+    for (void* p : bufs_) (void)hipFree(p);
+  }
+  template <typename T>
+  hipError_t alloc(size_t bytes, T** dev) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) bufs_.push_back(p);
+    *dev = static_cast<T*>(p);
+    return e;
+  }
+  template <typename T>
+  hipError_t upload(const void* host, size_t bytes, T** dev) {
+    const hipError_t e = alloc(bytes, dev);
+    return e != hipSuccess ? e : hipMemcpy(const_cast<std::remove_const_t<T>*>(*dev), host, bytes, hipMemcpyHostToDevice);
+  }
+  template <typename T>
+  hipError_t zeros(size_t bytes, T** dev) {
+    const hipError_t e = alloc(bytes, dev);
+    return e != hipSuccess ? e : hipMemset(*dev, 0, bytes);
+  }
+
+ private:
+  std::vector<void*> bufs_;
+};
+
+// the device buffers of a round trip as its launch sees them: in(i) / out(i) convert to the pointer type the launch
+// wrapper's parameter asks for (an input to pointers to const only)
+struct RoundtripBufs {
+  struct In {
+    const void* p;
+    template <typename T>
+    operator const T*() const { return static_cast<const T*>(p); }
+  };
+  struct Out {
+    void* p;
+    template <typename T>
+    operator T*() const { return static_cast<T*>(p); }
+  };
+  std::vector<void*> ins, outs;
+  In in(size_t i) const { return In{ins[i]}; }
+  Out out(size_t i) const { return Out{outs[i]}; }
+};
+
+// one synchronous device round trip: inputs up, the launch, the outputs down; an output with a null host pointer is a
+// device workspace (or an optional output nobody asked for) that stays there and is not zero-filled.  The launch gets
+// the device buffers and may return a hipError_t.
+template <typename Launch>
+int device_roundtrip(int device_id, std::initializer_list<std::pair<const void*, size_t>> inputs,
+                     std::initializer_list<std::pair<void*, size_t>> outputs, Launch launch) {
+  HIP_TRY(hipSetDevice(device_id));
+  DeviceBufs bufs;
+  RoundtripBufs d;
+  for (auto& in : inputs) {
+    void* p;
+    HIP_TRY(bufs.upload(in.first, in.second, &p));
+    d.ins.push_back(p);
+  }
+  for (auto& out : outputs) {
+    void* p;
+    HIP_TRY(bufs.alloc(out.second, &p));
+    d.outs.push_back(p);
+  }
+  if constexpr (std::is_void_v<decltype(launch(d))>) {
+    launch(d);
+  } else {
+    HIP_TRY(launch(d));
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  size_t k = 0;
+  for (auto& out : outputs) {
+    if (out.first) HIP_TRY(hipMemcpy(out.first, d.outs[k], out.second, hipMemcpyDeviceToHost));
+    ++k;
+  }
+  return FD_OK;
+}
+
+// lens[i] in [1, cap] (the padded length of a batch, or the most residues a kernel takes); *max_len = the longest
+inline int check_lens(const int32_t* lens, int n, int cap, int* max_len = nullptr) {
+  int longest = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lens[i] < 1 || lens[i] > cap) return fail(FD_E_INVALID, "lens[%d]=%d outside [1, %d]", i, lens[i], cap);
+    if (lens[i] > longest) longest = lens[i];
+  }
+  if (max_len) *max_len = longest;
+  return FD_OK;
+}
+
+// chains / pairs packed back to back: offsets[c] = lens[0] + ... + lens[c-1]; *total = the sum of all lengths
+inline int check_packed(const int32_t* offsets, const int32_t* lens, int n, long long limit, long long* total) {
+  long long sum = 0;
+  for (int c = 0; c < n; ++c) sum += lens[c] > 0 ? lens[c] : 0;
+  if (sum > limit) return fail(FD_E_UNSUPPORTED, "%lld entries in total, at most %lld", sum, limit);
+  long long at = 0;
+  for (int c = 0; c < n; ++c) {
+    if (lens[c] < 1) return fail(FD_E_INVALID, "lens[%d]=%d must be >= 1", c, lens[c]);
+    if (offsets[c] < 0 || (long long)offsets[c] + lens[c] > sum)
+      return fail(FD_E_INVALID, "offsets[%d]=%d (length %d) outside the buffer of %lld entries", c, offsets[c], lens[c], sum);
+    if (offsets[c] != at)
+      return fail(FD_E_INVALID, "offsets[%d]=%d, expected %lld (entries are packed back to back in order)", c, offsets[c], at);
+    at += lens[c];
+  }
+  *total = sum;
+  return FD_OK;
+}
+
+// packed coordinates [sum lens][3] (check_packed has passed): every one finite and within 1e6 A, so that every squared
+// distance stays far from overflow.  With `cent`: chain c's centroid goes to cent[c * cent_stride .. + 2] (the TM kernels
+// work on each trace in its own centred frame).
+inline int check_coords(const double* xyz, const int32_t* offsets, const int32_t* lens, int n, double* cent = nullptr,
+                        int cent_stride = 3) {
+  for (int c = 0; c < n; ++c) {
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (int i = offsets[c]; i < offsets[c] + lens[c]; ++i)
+      for (int d = 0; d < 3; ++d) {
+        const double u = xyz[(size_t)i * 3 + d];
+        if (!(std::fabs(u) <= 1e6))
+          return fail(FD_E_INVALID, "coordinate %d of residue %d (chain %d) is not finite or beyond 1e6: %g", d, i, c, u);
+        sum[d] += u;
+      }
+    if (cent)
+      for (int d = 0; d < 3; ++d) cent[(size_t)c * cent_stride + d] = sum[d] / lens[c];
+  }
+  return FD_OK;
+}
+
+}  // namespace fdmi

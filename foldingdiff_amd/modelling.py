@@ -332,7 +332,7 @@ class BertForDiffusionBase:
             for name, t in self._state.items():
                 arr = np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32, copy=False))
                 shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-                _binding.check(lib.fd_set_weight(h, name.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim))
+                _binding.check(lib.fd_set_weight(h, name.encode(), _binding.ptr(arr), shape, arr.ndim))
         except Exception:
             lib.fd_destroy(h)
             raise
@@ -364,8 +364,7 @@ class BertForDiffusionBase:
         table = np.ascontiguousarray(self.time_table(T).numpy().astype(np.float32))
         is_angle = np.ascontiguousarray(np.asarray(is_angle, dtype=np.uint8))
         _binding.check(_binding.load().fd_finalize(
-            h, T, coef.ctypes.data_as(C.c_void_p), table.ctypes.data_as(C.c_void_p),
-            is_angle.ctypes.data_as(C.c_void_p), _binding.FD_PREC[self.precision]))
+            h, T, _binding.ptr(coef), _binding.ptr(table), _binding.ptr(is_angle), _binding.FD_PREC[self.precision]))
         self._betas_key = key
         self._tables_T = T
         return h
@@ -443,14 +442,12 @@ class BertForDiffusionBase:
             es = np.empty_like(xs)
             if kmask is None:
                 ls = np.ascontiguousarray(lens[rows])
-                _binding.check(lib.fd_forward(h, xs.ctypes.data_as(C.c_void_p), int(tv), ls.ctypes.data_as(C.c_void_p),
-                                              len(rows), L, es.ctypes.data_as(C.c_void_p)))
+                _binding.check(lib.fd_forward(h, _binding.ptr(xs), int(tv), _binding.ptr(ls), len(rows), L, _binding.ptr(es)))
             else:
                 ms = np.ascontiguousarray(kmask[rows])
                 ps = np.ascontiguousarray(pids[rows]) if pids is not None else None
-                _binding.check(lib.fd_forward_ex(h, xs.ctypes.data_as(C.c_void_p), int(tv), ms.ctypes.data_as(C.c_void_p),
-                                                 ps.ctypes.data_as(C.c_void_p) if ps is not None else None,
-                                                 len(rows), L, es.ctypes.data_as(C.c_void_p)))
+                _binding.check(lib.fd_forward_ex(h, _binding.ptr(xs), int(tv), _binding.ptr(ms), _binding.ptr(ps), len(rows), L,
+                                                 _binding.ptr(es)))
             out[rows] = es
         return torch.from_numpy(out).to(inputs.device)
 

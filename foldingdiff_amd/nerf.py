@@ -7,7 +7,6 @@ foldingdiff/angles_and_coords.py:112-184): N, CA, C positions built from phi / p
 bond angles and (if the feature set has them) bond lengths; constants otherwise.  Writing PDB
 files (biotite) stays outside this path.
 """
-import ctypes as C
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -55,9 +54,8 @@ def build_backbones(
         feats[i, : len(c)] = c
         lens[i] = len(c)
     out = np.empty((B, 3 * L, 3), dtype=np.float64)
-    _binding.check(_binding.load().fd_nerf(
-        device, feats.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, L, F,
-        idx.ctypes.data_as(C.c_void_p), 1 if center_coords else 0, out.ctypes.data_as(C.c_void_p)))
+    ptr = _binding.ptr
+    _binding.check(_binding.load().fd_nerf(device, ptr(feats), ptr(lens), B, L, F, ptr(idx), 1 if center_coords else 0, ptr(out)))
     return [out[i, : 3 * lens[i]].copy() for i in range(B)]
 
 

@@ -65,8 +65,7 @@ def p_sample(model, x: torch.Tensor, t: torch.Tensor, seq_lens: Sequence[int], t
     z = _as_f32(torch.randn_like(x)) if ti > 0 else None
     out = np.empty_like(xs)
     _binding.check(_binding.load().fd_p_sample_step(
-        h, xs.ctypes.data_as(C.c_void_p), ti, lens.ctypes.data_as(C.c_void_p), B, L,
-        z.ctypes.data_as(C.c_void_p) if z is not None else None, 0, out.ctypes.data_as(C.c_void_p)))
+        h, _binding.ptr(xs), ti, _binding.ptr(lens), B, L, _binding.ptr(z), 0, _binding.ptr(out)))
     return torch.from_numpy(out).to(x.device)
 
 
@@ -91,9 +90,8 @@ def _run_fd_sample(h, x0: np.ndarray, lens: np.ndarray, t_start: int, zs: Option
     the multi-process path replace exactly this function with a CPU stand-in."""
     B, L, _ = x0.shape
     _binding.check(_binding.load().fd_sample_ex(
-        h, x0.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, L, t_start,
-        zs.ctypes.data_as(C.c_void_p) if zs is not None else None, C.c_uint64(seed), C.c_int64(seq_offset),
-        out.ctypes.data_as(C.c_void_p), full_history))
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, t_start, _binding.ptr(zs), C.c_uint64(seed), C.c_int64(seq_offset),
+        _binding.ptr(out), full_history))
 
 
 class _StepNoise:
@@ -526,7 +524,7 @@ def _shift_trim_flat(model, traj: torch.Tensor, lengths: Sequence[int], offset: 
         torch.cuda.current_stream(dev).synchronize()
         lib = _binding.load()
         _binding.check(lib.fd_shift_trim_dev(h, C.c_void_p(traj.data_ptr()), rows, B, L, C.c_void_p(lens_d.data_ptr()),
-                                             C.c_void_p(item_off.data_ptr()), o32.ctypes.data_as(C.c_void_p) if o32 is not None else None,
+                                             C.c_void_p(item_off.data_ptr()), _binding.ptr(o32),
                                              C.c_void_p(out_d.data_ptr()), None))
         _binding.check(lib.fd_synchronize(h))
         return out_d

@@ -34,7 +34,6 @@ PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PD
 7. a residue without one of N / CA / C rejects the file (``None``, with a debug log line).  This project's choice:
    it stands in for biotite's ``BadStructureError``, whose exact trigger is not pinned here.
 """
-import ctypes as C
 import glob
 import gzip
 import json
@@ -47,6 +46,7 @@ import pandas as pd
 import torch
 
 from . import _binding, datasets, nerf, utils
+from ._binding import ptr
 
 EXHAUSTIVE_ANGLES = ["phi", "psi", "omega", "tau", "CA:C:1N", "C:1N:1CA"]
 EXHAUSTIVE_DISTS = ["0C:1N", "N:CA", "CA:C"]
@@ -116,21 +116,44 @@ def extract_backbone_coords(fname: str, atoms: Sequence[str] = ("CA",)) -> Optio
     return bb[0].reshape(-1, 3, 3)[:, keep].reshape(-1, 3)
 
 
+# ---------------------------------------------------------------------------------------------------- call plumbing
+def _pack(arrays: Sequence[np.ndarray], dtype=np.float64) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """[n_i, 3] arrays laid back to back for one device call: (one contiguous [sum n_i, 3] array, int32 offsets, int32 lens)."""
+    lens = np.array([len(x) for x in arrays], dtype=np.int32)
+    offsets = (np.cumsum(lens) - lens).astype(np.int32)
+    flat = np.concatenate(arrays) if len(arrays) else np.zeros((0, 3))
+    return np.ascontiguousarray(flat, dtype=dtype), offsets, lens
+
+
+def _ca_traces(chains: Sequence[np.ndarray], cap: int, what: str = "chain") -> List[np.ndarray]:
+    """The chains as float64 arrays, each checked to be an [n, 3] trace of 1 <= n <= ``cap`` residues."""
+    out = [np.asarray(x, dtype=np.float64) for x in chains]
+    for i, x in enumerate(out):
+        if x.ndim != 2 or x.shape[1] != 3 or not 1 <= len(x) <= cap:
+            raise ValueError(f"{what} {i}: {x.shape}; expected an [n, 3] CA trace with 1 <= n <= {cap}")
+    return out
+
+
+def _norm_lens(norm_lens, floor: np.ndarray, what: str) -> np.ndarray:
+    """``norm_lens`` as int32, checked to hold one length per pair and none below ``floor`` (``what`` names it)."""
+    nl = np.asarray(norm_lens, dtype=np.int64).reshape(-1)
+    if nl.shape != floor.shape or (nl < floor).any() or (nl > np.iinfo(np.int32).max).any():
+        raise ValueError(f"norm_lens {nl.tolist()} must hold one length >= {what} per pair (floors {floor.tolist()})")
+    return nl.astype(np.int32)
+
+
 # ---------------------------------------------------------------------------------------------------- featurising
 def internal_coords(chains: Sequence[np.ndarray], device: int = 0) -> List[np.ndarray]:
     """The nine canonical features (float32 [n_i, 9], columns ``CANONICAL``) of every backbone in ``chains``
     (each [3 n_i, 3]: N, CA, C per residue), all in one ``fd_internal_coords`` launch."""
     if not chains:
         return []
-    lens = np.array([len(c) // 3 for c in chains], dtype=np.int32)
     for c in chains:
         assert c.ndim == 2 and c.shape[1] == 3 and len(c) % 3 == 0 and len(c) > 0, f"expected [3n, 3], got {c.shape}"
-    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
-    xyz = np.ascontiguousarray(np.concatenate(chains), dtype=np.float32)
+    xyz, offsets, lens = _pack(chains, np.float32)
+    offsets, lens = offsets // 3, lens // 3   # in residues
     out = np.empty((int(lens.sum()), 9), dtype=np.float32)
-    _binding.check(_binding.load().fd_internal_coords(
-        device, xyz.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
-        len(chains), out.ctypes.data_as(C.c_void_p)))
+    _binding.check(_binding.load().fd_internal_coords(device, ptr(xyz), ptr(offsets), ptr(lens), len(chains), ptr(out)))
     return [out[o: o + n] for o, n in zip(offsets, lens)]
 
 
@@ -349,13 +372,9 @@ def superposed_rmsd(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], 
     b = [np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in b_list]
     for i, (x, y) in enumerate(zip(a, b)):
         assert x.shape == y.shape and len(x) > 0, f"pair {i}: {x.shape} vs {y.shape}"
-    lens = np.array([len(x) for x in a], dtype=np.int32)
-    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
-    A, B = np.ascontiguousarray(np.concatenate(a)), np.ascontiguousarray(np.concatenate(b))
+    (A, offsets, lens), B = _pack(a), _pack(b)[0]
     out = np.empty((len(a),), dtype=np.float64)
-    _binding.check(_binding.load().fd_superpose_rmsd(
-        device, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
-        lens.ctypes.data_as(C.c_void_p), len(a), out.ctypes.data_as(C.c_void_p)))
+    _binding.check(_binding.load().fd_superpose_rmsd(device, ptr(A), ptr(B), ptr(offsets), ptr(lens), len(a), ptr(out)))
     return out
 
 
@@ -404,6 +423,9 @@ class RmsdScorer:
 rmsd_scorer = RmsdScorer()
 
 
+TM_MAX_LEN = 2048     # FDMI_TM_MAX_LEN and FDMI_SSE_MAX_LEN
+
+
 def tm_d0(Ln: int) -> float:
     """The TM-score's distance scale for normalisation length ``Ln``: 1.24 cbrt(Ln - 15) - 1.8 for Ln > 21, else 0.5."""
     return 1.24 * float(np.cbrt(Ln - 15)) - 1.8 if Ln > 21 else 0.5
@@ -422,19 +444,12 @@ def tm_score(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], norm_le
     higher."""
     if len(a_list) != len(b_list):
         raise ValueError(f"{len(a_list)} traces against {len(b_list)}")
-    a = [np.asarray(x, dtype=np.float64) for x in a_list]
-    b = [np.asarray(x, dtype=np.float64) for x in b_list]
+    a, b = _ca_traces(a_list, TM_MAX_LEN, "a"), _ca_traces(b_list, TM_MAX_LEN, "b")
     for i, (x, y) in enumerate(zip(a, b)):
-        if x.ndim != 2 or x.shape[1] != 3 or x.shape != y.shape or not 1 <= len(x) <= 2048:
-            raise ValueError(f"pair {i}: {x.shape} vs {y.shape}; expected two [n, 3] traces with 1 <= n <= 2048")
-    lens = np.array([len(x) for x in a], dtype=np.int32)
-    if norm_lens is None:
-        nl = lens.copy()
-    else:
-        nl = np.asarray(norm_lens, dtype=np.int64).reshape(-1)
-        if nl.shape != lens.shape or (nl < lens).any() or (nl > np.iinfo(np.int32).max).any():
-            raise ValueError(f"norm_lens {nl.tolist()} must hold one length >= n_i per pair (lengths {lens.tolist()})")
-        nl = nl.astype(np.int32)
+        if x.shape != y.shape:
+            raise ValueError(f"pair {i}: {x.shape} vs {y.shape}; expected two traces of one length")
+    (A, offsets, lens), B = _pack(a), _pack(b)[0]
+    nl = lens if norm_lens is None else _norm_lens(norm_lens, lens, "n_i")
     if int(stride) < 1:
         raise ValueError(f"stride={stride} must be >= 1")
     n = len(a)
@@ -442,12 +457,8 @@ def tm_score(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], norm_le
     T = np.empty((n, 12), dtype=np.float64)
     if n == 0:
         return (out, T[:, :9].reshape(0, 3, 3), T[:, 9:]) if return_transform else out
-    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
-    A, B = np.ascontiguousarray(np.concatenate(a)), np.ascontiguousarray(np.concatenate(b))
-    _binding.check(_binding.load().fd_tm_score(
-        device, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
-        lens.ctypes.data_as(C.c_void_p), nl.ctypes.data_as(C.c_void_p), n, int(stride), out.ctypes.data_as(C.c_void_p),
-        T.ctypes.data_as(C.c_void_p)))
+    _binding.check(_binding.load().fd_tm_score(device, ptr(A), ptr(B), ptr(offsets), ptr(lens), ptr(nl), n, int(stride),
+                                               ptr(out), ptr(T)))
     if return_transform:
         return out, T[:, :9].reshape(n, 3, 3).copy(), T[:, 9:].copy()
     return out
@@ -506,21 +517,14 @@ _SSE_LABELS = np.array(["c", "a", "b"])
 
 def _annotate(ca_list: Sequence[np.ndarray], device: int) -> Tuple[List[np.ndarray], np.ndarray]:
     """(int8 labels per chain, int32 [len, 2] counts) of one ``fd_annotate_sse`` call."""
-    ca = [np.asarray(x, dtype=np.float64) for x in ca_list]
-    for i, x in enumerate(ca):
-        if x.ndim != 2 or x.shape[1] != 3 or not 1 <= len(x) <= 2048:
-            raise ValueError(f"chain {i}: {x.shape}; expected an [n, 3] CA trace with 1 <= n <= 2048")
+    ca = _ca_traces(ca_list, TM_MAX_LEN)
     n = len(ca)
     counts = np.zeros((n, 2), dtype=np.int32)
     if n == 0:
         return [], counts
-    lens = np.array([len(x) for x in ca], dtype=np.int32)
-    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
-    X = np.ascontiguousarray(np.concatenate(ca))
+    X, offsets, lens = _pack(ca)
     sse = np.empty((len(X),), dtype=np.int8)
-    _binding.check(_binding.load().fd_annotate_sse(
-        device, X.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), n,
-        sse.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+    _binding.check(_binding.load().fd_annotate_sse(device, ptr(X), ptr(offsets), ptr(lens), n, ptr(sse), ptr(counts)))
     return [sse[o: o + m] for o, m in zip(offsets, lens)], counts
 
 
@@ -650,42 +654,29 @@ def tm_align_stride(n_ali: int) -> int:
 
 
 def _align_traces(chains: Sequence[np.ndarray], what: str = "chain") -> List[np.ndarray]:
-    out = [np.asarray(x, dtype=np.float64) for x in chains]
-    for i, x in enumerate(out):
-        if x.ndim != 2 or x.shape[1] != 3 or not 1 <= len(x) <= ALIGN_MAX_LEN:
-            raise ValueError(f"{what} {i}: {x.shape}; expected an [n, 3] CA trace with 1 <= n <= {ALIGN_MAX_LEN}")
-    return out
+    return _ca_traces(chains, ALIGN_MAX_LEN, what)
 
 
 def _align_indexed(chains: List[np.ndarray], pair_a: np.ndarray, pair_b: np.ndarray, norm_lens, max_iter: int, device: int,
                    want_map: bool):
     """One ``fd_tm_align`` call over already-checked float64 traces: (tm [P], T [P, 12], n_ali [P], maps or None)."""
-    lens = np.array([len(x) for x in chains], dtype=np.int32)
+    X, offsets, lens = _pack(chains)
     P = len(pair_a)
     pa, pb = np.ascontiguousarray(pair_a, dtype=np.int32), np.ascontiguousarray(pair_b, dtype=np.int32)
     if P and (min(pa.min(), pb.min()) < 0 or max(pa.max(), pb.max()) >= len(chains)):
         raise ValueError(f"pair indices must lie in [0, {len(chains)})")
     if int(max_iter) < 1:
         raise ValueError(f"max_iter={max_iter} must be >= 1")
-    if norm_lens is None:
-        nl = lens[pb].astype(np.int32) if P else np.zeros((0,), np.int32)
-    else:
-        nl = np.asarray(norm_lens, dtype=np.int64).reshape(-1)
-        if nl.shape != (P,) or (nl < np.minimum(lens[pa], lens[pb])).any() or (nl > np.iinfo(np.int32).max).any():
-            raise ValueError(f"norm_lens {nl.tolist()} must hold one length >= min(n1, n2) per pair")
-        nl = nl.astype(np.int32)
+    nl = lens[pb] if norm_lens is None else _norm_lens(norm_lens, np.minimum(lens[pa], lens[pb]), "min(n1, n2)")
     tm = np.empty((P,), dtype=np.float64)
     T = np.empty((P, 12), dtype=np.float64)
     n_ali = np.empty((P,), dtype=np.int32)
     if P == 0:
         return tm, T, n_ali, ([] if want_map else None)
-    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
-    X = np.ascontiguousarray(np.concatenate(chains))
     map_off = flat = None
     if want_map:
         map_off = np.concatenate([[0], np.cumsum(lens[pa], dtype=np.int64)[:-1]]).astype(np.int64)
         flat = np.empty((int(lens[pa].sum()),), dtype=np.int32)
-    ptr = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)   # noqa: E731
     _binding.check(_binding.load().fd_tm_align(
         device, ptr(X), ptr(offsets), ptr(lens), len(chains), ptr(pa), ptr(pb), ptr(nl), P, int(max_iter), ptr(tm), ptr(T),
         ptr(n_ali), ptr(map_off), ptr(flat)))
