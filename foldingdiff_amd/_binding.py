@@ -51,6 +51,7 @@ _SIGNATURES = {
     "fd_destroy": (None, [_P]),
     "fd_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "fd_forward": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "fd_forward_t": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "fd_forward_ex": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "fd_p_sample_step": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "fd_sample": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, C.c_int]),
@@ -70,6 +71,8 @@ _SIGNATURES = {
     "fd_tm_score": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "fd_annotate_sse": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P]),
     "fd_tm_align": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "fd_loss_terms": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, _P, _P]),
+    "fd_denoise_loss": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P]),
     "fd_shift_trim_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fd_test_wrap": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, _P]),
     "fd_test_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),

@@ -103,6 +103,9 @@ struct Workspace {
         *g = nullptr, *z = nullptr;
   int* lens = nullptr;
   int* t_dev = nullptr;  // [0] step index; the row-image kernels also use [1] (see rowwise_img.hip)
+  int* t_seq = nullptr;  // [B] one timestep per sequence (fd_forward_t, fd_denoise_loss)
+  float* loss_in = nullptr;     // fd_denoise_loss's one upload: x0 | noise ([B][L][F] each) | keep | spread | t | lens ([B] each); allocated on first use
+  double* loss_sums = nullptr;  // [B][F], with it
   UpdateDyn* dyn = nullptr;
   // row-image path (fdmi_kernels.h): images, per-(sequence, head) q / k / v^T, the token-row table
   bool img = false;
@@ -120,7 +123,7 @@ struct Workspace {
     if (graph) (void)hipGraphExecDestroy(graph);
     graph = nullptr;
     for (void* p : {(void*)x, (void*)eps, (void*)h, (void*)qkv, (void*)ctx, (void*)a, (void*)tmp, (void*)g, (void*)z,
-                    (void*)lens, (void*)t_dev, (void*)dyn, (void*)himg, (void*)aimg, (void*)cimg, (void*)gimg,
+                    (void*)lens, (void*)t_dev, (void*)t_seq, (void*)loss_in, (void*)loss_sums, (void*)dyn, (void*)himg, (void*)aimg, (void*)cimg, (void*)gimg,
                     (void*)qbuf, (void*)kbuf, (void*)vbuf, (void*)trash, (void*)rowinfo, (void*)seq_row0, (void*)nrow,
                     (void*)dims, (void*)flag, (void*)kmask, (void*)pos_ids})
       if (p) (void)hipFree(p);
@@ -575,6 +578,7 @@ int ensure_ws(fd_model* m, int B, int L) {
   HIP_TRY(al((void**)&w.z, M * F * 4));
   HIP_TRY(al((void**)&w.lens, (size_t)B * 4));
   HIP_TRY(alz((void**)&w.t_dev, 16));
+  HIP_TRY(alz((void**)&w.t_seq, (size_t)B * 4));
   HIP_TRY(al((void**)&w.dyn, sizeof(UpdateDyn)));
   if (m->img) {
     // Row images: sequences start at multiples of 8 rows, the row count is rounded up to whole 128-row tiles.
@@ -641,6 +645,7 @@ struct StepMode {
   bool no_wrap = false;  // p_sample alone, without the loop's wrap
   const unsigned char* kmask = nullptr;  // fd_forward_ex: [B][L] key mask of any pattern (device), else null: prefix masks from lens
   const int* pos_ids = nullptr;          // fd_forward_ex: [B][L] position ids of the absolute position embedding (device)
+  const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
 };
 
 int prof_begin(fd_model* m, int cls, hipStream_t s, bool on) {
@@ -814,7 +819,7 @@ int run_step(fd_model* m, hipStream_t s, const StepMode& mode) {
   Workspace& w = m->ws;
   const int B = w.B, L = w.L, M = B * L, d = c.d_model, ff = c.d_ff, F = c.n_features;
   PROF(KC_EMBED, launch_embed(w.x, m->w_in, m->b_in, m->pos_emb, m->emb_g, m->emb_b, c.ln_eps, m->time_table, w.t_dev,
-                              w.h, B, L, F, d, s));
+                              mode.t_seq, w.h, B, L, F, d, s));
   for (int li = 0; li < c.n_layers; ++li) {
     const LayerDev& lw = m->layers[li];
     PROF(KC_GEMM_QKV, launch_gemm_f32(EPI_BIAS, w.h, lw.wqkv, lw.bqkv, nullptr, w.qkv, M, 3 * d, d, s));
@@ -877,7 +882,7 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode, const StepPla
     e.time_table = m->time_table; e.tslot = w.t_dev; e.rowinfo = w.rowinfo; e.nrow = w.nrow; e.dims = w.dims;
     e.h = w.himg; e.L = L; e.F = F; e.d = d; e.eps = c.ln_eps; e.out_scale = m->layers[0].s_h;
     e.pos_ids = mode.pos_ids;
-    PROF(KC_EMBED, launch_embed_img(e, max_rows, s));
+    PROF(KC_EMBED, launch_embed_img(e, mode.t_seq, max_rows, s));
     if (stop_after(1)) return done();
   }
   if (env_overrides().stamps && !m->stamps) {
@@ -1484,6 +1489,90 @@ int fd_forward(fd_model* m, const float* x, int t, const int32_t* lens, int B, i
   mode.forward_only = true;
   if (int rc = run_step(m, s, mode)) return rc;
   HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return check_flag(m);
+}
+
+// every t[b] of a per-sequence timestep vector lies in [0, T)
+static int check_t_seq(const fd_model* m, const int32_t* t, int B) {
+  for (int b = 0; b < B; ++b)
+    if (t[b] < 0 || t[b] >= m->T) return fail(FD_E_INVALID, "timestep t[%d]=%d outside [0, %d)", b, t[b], m->T);
+  return FD_OK;
+}
+
+int fd_forward_t(fd_model* m, const float* x, const int32_t* t, const int32_t* lens, int B, int L, float* eps_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x || !t || !lens || !eps_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_t_seq(m, t, B)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  Workspace& w = m->ws;
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  hipStream_t s = m->stream;
+  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.t_seq, t, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  if (int rc = prepare_rows(m, s, 0)) return rc;  // the forward defines every position, masked ones included
+  StepMode mode{};
+  mode.forward_only = true;
+  mode.t_seq = w.t_seq;
+  if (int rc = run_step(m, s, mode)) return rc;
+  HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return check_flag(m);
+}
+
+int fd_denoise_loss(fd_model* m, const float* x0, const float* noise, const int32_t* t, const float* keep, const float* spread,
+                    const int32_t* lens, int B, int L, float beta_ang, float beta_lin, double* sums, float* corrupted_out,
+                    float* eps_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x0 || !noise || !t || !lens || !sums) return fail(FD_E_INVALID, "null argument");
+  if ((keep == nullptr) != (spread == nullptr)) return fail(FD_E_INVALID, "null argument: keep and spread go together");
+  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
+  if (int rc = check_t_seq(m, t, B)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  Workspace& w = m->ws;
+  const int F = m->cfg.n_features;
+  const size_t n = (size_t)B * L * F, nb = (size_t)B;
+  hipStream_t s = m->stream;
+  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
+  if (!w.loss_in) HIP_TRY(hipMalloc((void**)&w.loss_in, (2 * n + 4 * nb) * 4));
+  if (!w.loss_sums) HIP_TRY(hipMalloc((void**)&w.loss_sums, nb * F * 8));
+  // ONE upload: x0 | noise | keep | spread | t | lens, staged back to back.  The staging vector is pageable memory of this
+  // frame, so the copy is a blocking one, behind whatever an earlier asynchronous entry point left on the model's stream
+  std::vector<float> stage(2 * n + 4 * nb, 0.f);
+  memcpy(stage.data(), x0, n * 4);
+  memcpy(stage.data() + n, noise, n * 4);
+  if (keep) {
+    memcpy(stage.data() + 2 * n, keep, nb * 4);
+    memcpy(stage.data() + 2 * n + nb, spread, nb * 4);
+  }
+  memcpy(stage.data() + 2 * n + 2 * nb, t, nb * 4);
+  memcpy(stage.data() + 2 * n + 3 * nb, lens, nb * 4);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(w.loss_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
+  const float *x0_dev = w.loss_in, *noise_dev = w.loss_in + n, *keep_dev = w.loss_in + 2 * n, *spread_dev = keep_dev + nb;
+  HIP_TRY(hipMemcpyAsync(w.t_seq, w.loss_in + 2 * n + 2 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.lens, w.loss_in + 2 * n + 3 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
+  if (keep) {  // q(x_t | x_0) on the device, with the wrap flags fd_finalize was given
+    launch_q_sample(x0_dev, noise_dev, keep_dev, spread_dev, w.x, B, L, F, m->angle_mask, s);
+    HIP_TRY(hipGetLastError());
+  } else {     // x0 is x_t already
+    HIP_TRY(hipMemcpyAsync(w.x, x0_dev, n * 4, hipMemcpyDeviceToDevice, s));
+  }
+  if (int rc = prepare_rows(m, s, 0)) return rc;
+  StepMode mode{};
+  mode.forward_only = true;
+  mode.t_seq = w.t_seq;
+  if (int rc = run_step(m, s, mode)) return rc;
+  launch_loss_terms(w.eps, noise_dev, w.lens, B, L, F, m->angle_mask, beta_ang, beta_lin, w.loss_sums, nullptr, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(sums, w.loss_sums, nb * F * 8, hipMemcpyDeviceToHost, s));
+  if (corrupted_out) HIP_TRY(hipMemcpyAsync(corrupted_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
+  if (eps_out) HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return check_flag(m);
 }

@@ -1,5 +1,5 @@
-// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip).
-// None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip) and of
+// the loss arithmetic on its own (loss.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
 #include <vector>
@@ -140,6 +140,26 @@ int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const i
                                map_out ? map_off : nullptr, n_pairs, max_iter, max_len, d.out(2), d.out(3), d.out(4),
                                map_out ? map : nullptr, nullptr);
       });
+}
+
+int fd_loss_terms(int device_id, const float* pred, const float* target, const int32_t* lens, int B, int L, int F,
+                  const uint8_t* is_angle, float beta_ang, float beta_lin, double* sums, float* terms) {
+  if (!pred || !target || !lens || !is_angle || !sums) return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if (F < 1 || F > 32) return fail(FD_E_INVALID, "F=%d outside [1, 32]", F);
+  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
+  if ((long long)B * L * F > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * F = %lld elements, at most 2^31 - 1", (long long)B * L * F);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  unsigned angle_mask = 0;
+  for (int f = 0; f < F; ++f)
+    if (is_angle[f]) angle_mask |= 1u << f;
+  const size_t n = (size_t)B * L * F;
+  return device_roundtrip(device_id, {{pred, n * 4}, {target, n * 4}, {lens, (size_t)B * 4}},
+                          {{sums, (size_t)B * F * 8}, {terms, terms ? n * 4 : 4}}, [&](const RoundtripBufs& d) {
+                            float* terms_dev = d.out(1);
+                            launch_loss_terms(d.in(0), d.in(1), d.in(2), B, L, F, angle_mask, beta_ang, beta_lin, d.out(0),
+                                              terms ? terms_dev : nullptr, nullptr);
+                          });
 }
 
 }  // extern "C"

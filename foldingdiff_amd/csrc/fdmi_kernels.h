@@ -31,10 +31,11 @@ bool launch_gemm_f32_ln(const float* A, const float* W, const float* bias, const
 void launch_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int d,
                       hipStream_t s);
 
-// K1: h = LN(x W_in^T + b_in (+ pos_emb[l])) * g + b + time_table[*t_dev]
+// K1: h = LN(x W_in^T + b_in (+ pos_emb[l])) * g + b + time_table[*t_dev]; with t_seq ([B], device) non-null a row of
+// sequence b adds time_table[t_seq[b]] instead (one timestep per sequence: the sibling kernels, t_dev is not read)
 void launch_embed(const float* x, const float* w_in, const float* b_in, const float* pos_emb /*null unless absolute*/,
                   const float* gamma, const float* beta, float eps, const float* time_table, const int* t_dev,
-                  float* h, int B, int L, int F, int d, hipStream_t s);
+                  const int* t_seq, float* h, int B, int L, int F, int d, hipStream_t s);
 
 // K4: multi-head self-attention with additive key mask and (optionally) the
 // relative_key score term.  qkv: [B*L, 3d] (q | k | v), ctx: [B*L, d].
@@ -274,7 +275,8 @@ struct EmbedImgArgs {
   int L, F, d;
   float eps, out_scale;
 };
-void launch_embed_img(const EmbedImgArgs& a, int max_rows, hipStream_t s);
+// t_seq: null, or [B] (device) one timestep per sequence -- the sibling kernel, which reads neither tslot nor writes it
+void launch_embed_img(const EmbedImgArgs& a, const int* t_seq, int max_rows, hipStream_t s);
 
 struct HeadImgArgs {
   const unsigned char* g;      // image [rows128][d/32]: head activation (mlp decoder) or final hidden state (linear)
@@ -308,6 +310,18 @@ void launch_shift_trim(const ShiftTrimArgs& a, hipStream_t s);
 // test hook: out[i] = wrap_pi(in[i]) through the update kernels' own device function (which: 0 rowwise.hip, 1 rowwise_img.hip)
 void launch_wrap_test_f32(const float* in, float* out, long long n, hipStream_t s);
 void launch_wrap_test_img(const float* in, float* out, long long n, hipStream_t s);
+
+// ---- forward noising and the denoising loss (loss.hip)
+// x_t[b][l][f] = wrap?(keep[b] * x0 + spread[b] * eps), each product and the sum rounded once (datasets.py:861-871): the bits
+// of the host's float32 statement; features of angle_mask are wrapped to [-pi, pi).  Every position of the padded length
+// is noised, as NoisedAnglesDataset.__getitem__ does.
+void launch_q_sample(const float* x0, const float* eps, const float* keep, const float* spread, float* x_t, int B, int L, int F,
+                     unsigned angle_mask, hipStream_t s);
+// per-position smooth-L1 terms of pred against target (losses.py:29-55 for features of angle_mask, with beta_ang;
+// F.smooth_l1_loss with beta_lin for the others) over positions l < lens[b], one workgroup per sequence:
+// sums[b][f] (fp64, fixed summation order) and, when non-null, terms[b][l][f] (zeros at l >= lens[b]).  F <= 32.
+void launch_loss_terms(const float* pred, const float* target, const int* lens, int B, int L, int F, unsigned angle_mask,
+                       float beta_ang, float beta_lin, double* sums, float* terms, hipStream_t s);
 
 void launch_build_rows(const int* lens, int B, int L, int packed, int cap, int* seq_row0, int* nrow, int2* rowinfo,
                        int* dims, hipStream_t s);

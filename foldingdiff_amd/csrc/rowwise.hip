@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "fdmi_kernels.h"
+#include "wrap_pi.h"
 
 namespace fdmi {
 
@@ -178,14 +179,112 @@ __global__ __launch_bounds__(256) void embed16_kernel(const float* __restrict__ 
   }
 }
 
+// ---- one timestep per sequence (fd_forward_t, fd_denoise_loss): the siblings of the two kernels above.  t_seq[B] takes
+// t_dev's place and a token of sequence b = tok / L adds time_table[t_seq[b]]; everything else is the kernel above, line
+// for line.  Separate kernels, so that the single-timestep ones (every sampling step, the captured graph) stay as they are.
+template <int NJ>
+__global__ __launch_bounds__(256) void embed_tseq_kernel(const float* __restrict__ x, const float* __restrict__ w_in,
+                                                         const float* __restrict__ b_in, const float* __restrict__ pos_emb,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                         float eps, const float* __restrict__ time_table,
+                                                         const int* __restrict__ t_seq, float* __restrict__ h, int M, int L,
+                                                         int F, int d){
+  const int lane = threadIdx.x & 63;
+  const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tok >= M) return;
+  const int t = t_seq[tok / L];
+  float xin[kMaxFeat];
+#pragma unroll
+  for (int f = 0; f < kMaxFeat; ++f) xin[f] = f < F ? x[(size_t)tok * F + f] : 0.f;
+  float v[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = lane + 64 * j;
+    float a = 0.f;
+    if (c < d) {
+      a = b_in[c];
+      for (int f = 0; f < F; ++f) a += xin[f] * w_in[c * F + f];
+      if (pos_emb) a += pos_emb[(size_t)(tok % L) * d + c];  // absolute positions only (modelling.py:164-166)
+    }
+    v[j] = a;
+  }
+  row_layernorm<NJ>(v, lane, d, gamma, beta, eps);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = lane + 64 * j;
+    if (c < d) h[(size_t)tok * d + c] = v[j] + time_table[(size_t)t * d + c];  // added AFTER the LayerNorm (:472)
+  }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void embed16_tseq_kernel(const float* __restrict__ x, const float* __restrict__ w_in,
+                                                           const float* __restrict__ b_in, const float* __restrict__ pos_emb,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float eps, const float* __restrict__ time_table,
+                                                           const int* __restrict__ t_seq, float* __restrict__ h, int M, int L,
+                                                           int F){
+  constexpr int d = 64 * NV;
+  extern __shared__ __attribute__((aligned(16))) float wT[];  // [F][d]: w_in transposed
+  for (int i = threadIdx.x; i < F * d; i += 256) {
+    const int f = i / d, c = i - f * d;
+    wT[i] = w_in[c * F + f];
+  }
+  const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
+  float4 bi[NV], gm[NV], bt[NV], tt[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int c = 4 * (k + 16 * j);
+    bi[j] = *reinterpret_cast<const float4*>(b_in + c);
+    gm[j] = *reinterpret_cast<const float4*>(gamma + c);
+    bt[j] = *reinterpret_cast<const float4*>(beta + c);
+  }
+  __syncthreads();
+  for (int tg = blockIdx.x; tg * 16 < M; tg += gridDim.x) {
+    const int tok = tg * 16 + g;
+    const int tc = tok < M ? tok : M - 1;
+    float4 v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = bi[j];
+    for (int f = 0; f < F; ++f) {
+      const float xf = x[(size_t)tc * F + f];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        const float4 w = *reinterpret_cast<const float4*>(wT + f * d + 4 * (k + 16 * j));
+        v[j].x += xf * w.x; v[j].y += xf * w.y; v[j].z += xf * w.z; v[j].w += xf * w.w;
+      }
+    }
+    if (pos_emb) {  // absolute positions only (modelling.py:164-166)
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        const float4 pe = *reinterpret_cast<const float4*>(pos_emb + (size_t)(tc % L) * d + 4 * (k + 16 * j));
+        v[j].x += pe.x; v[j].y += pe.y; v[j].z += pe.z; v[j].w += pe.w;
+      }
+    }
+    row16_layernorm<NV>(v, gm, bt, d, eps);
+    const float* trow = time_table + (size_t)t_seq[tc / L] * d;  // the sequence's own row of the table
+#pragma unroll
+    for (int j = 0; j < NV; ++j) tt[j] = *reinterpret_cast<const float4*>(trow + 4 * (k + 16 * j));
+    if (tok < M) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j)  // time embedding added AFTER the LayerNorm (modelling.py:472)
+        *reinterpret_cast<float4*>(h + (size_t)tok * d + 4 * (k + 16 * j)) =
+            make_float4(v[j].x + tt[j].x, v[j].y + tt[j].y, v[j].z + tt[j].z, v[j].w + tt[j].w);
+    }
+  }
+}
+
 template <int NV>
 static void launch_embed16(const float* x, const float* w_in, const float* b_in, const float* pos_emb, const float* gamma,
-                           const float* beta, float eps, const float* time_table, const int* t_dev, float* h, int M, int L,
-                           int F, hipStream_t s) {
+                           const float* beta, float eps, const float* time_table, const int* t_dev, const int* t_seq, float* h,
+                           int M, int L, int F, hipStream_t s) {
   int grid = (M + 15) / 16;
   if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL((embed16_kernel<NV>), dim3(grid), dim3(256), (size_t)F * 64 * NV * 4, s, x, w_in, b_in, pos_emb, gamma,
-                     beta, eps, time_table, t_dev, h, M, L, F);
+  if (t_seq)
+    hipLaunchKernelGGL((embed16_tseq_kernel<NV>), dim3(grid), dim3(256), (size_t)F * 64 * NV * 4, s, x, w_in, b_in, pos_emb,
+                       gamma, beta, eps, time_table, t_seq, h, M, L, F);
+  else
+    hipLaunchKernelGGL((embed16_kernel<NV>), dim3(grid), dim3(256), (size_t)F * 64 * NV * 4, s, x, w_in, b_in, pos_emb, gamma,
+                       beta, eps, time_table, t_dev, h, M, L, F);
 }
 
 // FDMI_ROWWISE16=0 keeps the one-wave-per-token kernels (also the generic path for d % 64 != 0 or d > 512)
@@ -195,19 +294,25 @@ static bool use_row16(int d) {
 }
 
 void launch_embed(const float* x, const float* w_in, const float* b_in, const float* pos_emb, const float* gamma,
-                  const float* beta, float eps, const float* time_table, const int* t_dev, float* h, int B, int L, int F,
-                  int d, hipStream_t s) {
+                  const float* beta, float eps, const float* time_table, const int* t_dev, const int* t_seq, float* h, int B,
+                  int L, int F, int d, hipStream_t s) {
   const int M = B * L;
   if (use_row16(d)) {
-#define FD_E16(NV) case NV: launch_embed16<NV>(x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, t_dev, h, M, L, F, s); return;
+#define FD_E16(NV) case NV: launch_embed16<NV>(x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, t_dev, t_seq, h, M, L, F, s); return;
     switch (d / 64) { FD_E16(1) FD_E16(2) FD_E16(3) FD_E16(4) FD_E16(5) FD_E16(6) FD_E16(7) FD_E16(8) }
 #undef FD_E16
   }
   const dim3 grid((M + 3) / 4), block(256);
   const int nj = (d + 63) / 64;
-#define FD_EMBED(NJ)                                                                                             \
-  hipLaunchKernelGGL((embed_kernel<NJ>), grid, block, 0, s, x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, \
-                     t_dev, h, M, L, F, d)
+#define FD_EMBED(NJ)                                                                                                       \
+  do {                                                                                                                     \
+    if (t_seq)                                                                                                             \
+      hipLaunchKernelGGL((embed_tseq_kernel<NJ>), grid, block, 0, s, x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, \
+                         t_seq, h, M, L, F, d);                                                                            \
+    else                                                                                                                   \
+      hipLaunchKernelGGL((embed_kernel<NJ>), grid, block, 0, s, x, w_in, b_in, pos_emb, gamma, beta, eps, time_table,      \
+                         t_dev, h, M, L, F, d);                                                                            \
+  } while (0)
   if (nj <= 1) FD_EMBED(1);
   else if (nj <= 3) FD_EMBED(3);
   else if (nj <= 6) FD_EMBED(6);
@@ -305,18 +410,7 @@ void launch_philox_fill(float* out, unsigned long long seed, int t, long long se
 }
 
 // --------------------------------------------- head tail + p_sample update (K8/K9)
-// wrap: ((v - lo) % (hi - lo)) + lo with lo = -pi, hi = pi evaluated as torch does on a
-// float32 tensor with python-float bounds: v + f32(pi); torch.remainder(., f32(2 pi));
-// + f32(-pi).  Explicit __f*_rn keeps the compiler from contracting into FMAs, so for
-// identical inputs the result is bit-identical to the reference's CPU arithmetic.
-__device__ __forceinline__ float wrap_pi(float v) {
-  const float PI_F = 3.14159274101257324f, TWO_PI_F = 6.28318548202514648f;
-  const float sft = __fadd_rn(v, PI_F);
-  float m = fmodf(sft, TWO_PI_F);
-  if (m != 0.f && m < 0.f) m = __fadd_rn(m, TWO_PI_F);
-  return __fadd_rn(m, -PI_F);
-}
-
+// (the wrap to [-pi, pi) of the update: wrap_pi.h)
 __global__ void wrap_test_f32_kernel(const float* in, float* out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = wrap_pi(in[i]);

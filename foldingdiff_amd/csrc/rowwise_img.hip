@@ -13,6 +13,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "wrap_pi.h"
 
 namespace fdmi {
 
@@ -232,6 +233,87 @@ __global__ __launch_bounds__(256) void embed_img_kernel(EmbedImgArgs a) {
   }
 }
 
+// One timestep per sequence (fd_forward_t, fd_denoise_loss): the sibling of the kernel above.  The LDS block cannot hold ONE time
+// row any more, so a lane reads its 8-column slices of row t_seq[b] of the table from global memory per token (at most 1000 x 384
+// floats: the table stays in L2); tslot is neither read nor written (a forward-only step: no other kernel of it reads the timestep).
+// Everything else is the kernel above, line for line.  A separate kernel, so that the single-timestep one stays as it is.
+template <int NV, int LPT>
+__global__ __launch_bounds__(256) void embed_img_tseq_kernel(EmbedImgArgs a, const int* __restrict__ t_seq) {
+  extern __shared__ __attribute__((aligned(16))) float wT[];  // [F][d] + [3][d]
+  const int d = a.d, F = a.F, nu = d >> 3;
+  float* par = wT + F * d;
+  for (int i = threadIdx.x; i < F * d; i += 256) {
+    const int f = i / d, c = i - f * d;
+    wT[i] = a.w_in[c * F + f];
+  }
+  for (int i = threadIdx.x; i < d; i += 256) {
+    par[i] = a.b_in[i];
+    par[d + i] = a.gamma[i];
+    par[2 * d + i] = a.beta[i];
+  }
+  const int k = threadIdx.x & (LPT - 1), g = threadIdx.x / LPT;
+  bool ok[NV];
+  int col[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    ok[j] = k + LPT * j < nu;
+    col[j] = ok[j] ? 8 * (k + LPT * j) : 0;
+  }
+  __syncthreads();
+  const int rows = a.dims[1];  // every row of the padded range is written (pad rows: zeros)
+  const int nb = d >> 5;
+  for (int tg = blockIdx.x; tg * (256 / LPT) < rows; tg += gridDim.x) {
+    const int row = tg * (256 / LPT) + g;
+    if (row >= rows) continue;  // (no barriers below)
+    const int2 ri = a.rowinfo[row];
+    const bool real = ri.x >= 0 && ri.y < a.nrow[ri.x >= 0 ? ri.x : 0];
+    const size_t xo = real ? ((size_t)ri.x * a.L + ri.y) * F : 0;
+    Unit8 v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) load8(par + col[j], v[j].v);
+    for (int f = 0; f < F; ++f) {
+      const float xf = a.x[xo + f];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        float w[8];
+        load8(wT + f * d + col[j], w);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[j].v[e] += xf * w[e];
+      }
+    }
+    if (a.pos_emb) {  // absolute positions only (modelling.py:164-166)
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        float pe[8];
+        const int pid = !real ? 0 : (a.pos_ids ? a.pos_ids[(size_t)ri.x * a.L + ri.y] : ri.y);
+        load8(a.pos_emb + (size_t)pid * d + col[j], pe);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[j].v[e] += pe[e];
+      }
+    }
+    float mean, rstd;
+    row16_layernorm<NV, LPT>(v, ok, d, a.eps, mean, rstd);
+    const float* trow = a.time_table + (size_t)(real ? t_seq[ri.x] : 0) * d;  // the sequence's own row of the table
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (!ok[j]) continue;
+      float gm[8], bt[8], tt[8], o[8];
+      load8(par + d + col[j], gm);
+      load8(par + 2 * d + col[j], bt);
+      load8(trow + col[j], tt);
+      // time embedding added AFTER the LayerNorm (modelling.py:472); pad rows are zero rows
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = real ? (v[j].v[e] * rstd * gm[e] + bt[e]) + tt[e] : 0.f;
+      u32x4 hi, lo;
+      split8(o, a.out_scale, hi, lo);
+      const int u = k + LPT * j;
+      unsigned char* blk = a.h + img_unit_offset(row, nb, u >> 2, u & 3);
+      *reinterpret_cast<u32x4*>(blk) = hi;
+      *reinterpret_cast<u32x4*>(blk + 4 * 512) = lo;
+    }
+  }
+}
+
 // LayerNorm of fp32 rows -> image (models with d_model > 384: the LayerNorm row does not fit one 384-column GEMM tile, so the
 // projection writes dense + bias + residual as fp32 rows and this kernel normalises them; BertSelfOutput / BertOutput)
 template <int NV, int LPT>
@@ -303,15 +385,6 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, int t, l
   float sn, cs;
   sincosf(6.283185307179586f * u2, &sn, &cs);
   return (f & 1) ? rad * sn : rad * cs;
-}
-
-// wrap to [-pi, pi) exactly as torch evaluates modulo_with_wrapped_range on fp32 (utils.py:100-106)
-__device__ __forceinline__ float wrap_pi(float v) {
-  const float PI_F = 3.14159274101257324f, TWO_PI_F = 6.28318548202514648f;
-  const float sft = __fadd_rn(v, PI_F);
-  float m = fmodf(sft, TWO_PI_F);
-  if (m != 0.f && m < 0.f) m = __fadd_rn(m, TWO_PI_F);
-  return __fadd_rn(m, -PI_F);
 }
 
 // ---------------------------------------------------------------- head tail + p_sample update (K8/K9)
@@ -524,8 +597,12 @@ static int row_lpt(int d, int F) {  // F > 0: the head kernel (one lane per outp
   return F > 0 ? 16 : 8;
 }
 
-void launch_embed_img(const EmbedImgArgs& a, int max_rows, hipStream_t s) {
+void launch_embed_img(const EmbedImgArgs& a, const int* t_seq, int max_rows, hipStream_t s) {
   const int lpt = row_lpt(a.d, 0), nv = (a.d / 8 + lpt - 1) / lpt, grid = row_grid(max_rows, lpt, lpt == 8 ? 512 : 1024);
+  if (t_seq) {
+    const size_t smem = (size_t)(a.F + 3) * a.d * 4;
+    FD_ROW_SWITCH(embed_img_tseq_kernel, a, t_seq);
+  }
   const size_t smem = (size_t)(a.F + 4) * a.d * 4;
   FD_ROW_SWITCH(embed_img_kernel, a);
 }

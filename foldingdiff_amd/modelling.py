@@ -453,6 +453,78 @@ class BertForDiffusionBase:
 
     __call__ = forward
 
+    # ------------------------------------------------- one timestep per sequence, and the denoising loss
+    def _batch_arrays(self, inputs: torch.Tensor, timestep: torch.Tensor, attention_mask: torch.Tensor):
+        """(x float32 [B, L, F], t int32 [B], lens int32 [B]) of a batch with a prefix mask; the tables cover max(t)."""
+        assert attention_mask is not None
+        assert inputs.dim() == 3 and inputs.shape[2] == self.n_inputs
+        B = int(inputs.shape[0])
+        lens = self.lengths_from_mask(attention_mask)
+        if lens is None:
+            raise ValueError("one timestep per sequence is built for prefix masks (ones followed by zeros, at least one "
+                             "position per sequence) only; forward() takes any mask, one launch per distinct timestep")
+        t = timestep.detach().cpu().reshape(-1).long()
+        if t.numel() != B:
+            raise ValueError(f"{t.numel()} timesteps for a batch of {B}")
+        need_T = int(t.max()) + 1
+        if self._tables_T is None or self._tables_T < need_T:
+            self.prepare(beta_schedules.cosine_beta_schedule(max(need_T, 1000)))
+        x = np.ascontiguousarray(inputs.detach().cpu().numpy().astype(np.float32))
+        return x, np.ascontiguousarray(t.numpy().astype(np.int32)), lens
+
+    def forward_mixed_t(self, inputs: torch.Tensor, timestep: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+        """``forward`` for a batch whose sequences sit at different timesteps (a training / validation batch,
+        modelling.py:553-566) as ONE device forward (``fd_forward_t``): sequence b adds ``time_embed(timestep[b])``.
+        ``forward`` makes one launch sequence per distinct timestep instead.  With all timesteps equal the two return the
+        same bits.  Prefix masks and default position ids only; anything else raises ``ValueError`` -- use ``forward``."""
+        x, t, lens = self._batch_arrays(inputs, timestep, attention_mask)
+        out = np.empty_like(x)
+        _binding.check(_binding.load().fd_forward_t(self._ensure_handle(), _binding.ptr(x), _binding.ptr(t), _binding.ptr(lens),
+                                                    x.shape[0], x.shape[1], _binding.ptr(out)))
+        return torch.from_numpy(out).to(inputs.device)
+
+    def denoise_loss_sums(self, x: torch.Tensor, noise: torch.Tensor, timestep: torch.Tensor, attention_mask: torch.Tensor,
+                          keep: Optional[torch.Tensor] = None, spread: Optional[torch.Tensor] = None,
+                          return_corrupted: bool = False, return_eps: bool = False):
+        """``fd_denoise_loss``: float64 [B, F] sums over each sequence's unmasked positions of the smooth-L1 terms
+        (``losses``: beta pi / 10 for angular features, 1 for the others) of the predicted noise against ``noise``.
+        ``keep`` / ``spread`` ([B]: sqrt_alphas_cumprod_t, sqrt_one_minus_alphas_cumprod_t) given: ``x`` is the clean x_0
+        and the device noises it (every position, angular features wrapped, the bits of ``NoisedAnglesDataset``); both
+        None: ``x`` is the corrupted x_t already.  Returns ``sums``, or ``(sums, extras)`` with the requested
+        ``"corrupted"`` / ``"eps"`` [B, L, F] arrays."""
+        from . import losses
+        if (keep is None) != (spread is None):
+            raise ValueError("keep and spread go together")
+        xa, t, lens = self._batch_arrays(x, timestep, attention_mask)
+        B, L, F = xa.shape
+        na = np.ascontiguousarray(noise.detach().cpu().numpy().astype(np.float32))
+        if na.shape != xa.shape:
+            raise ValueError(f"noise {na.shape} != x {xa.shape}")
+        vec = lambda v: None if v is None else np.ascontiguousarray(torch.as_tensor(v).detach().cpu().reshape(-1).numpy().astype(np.float32))  # noqa: E731
+        ka, sa = vec(keep), vec(spread)
+        if ka is not None and (ka.shape != (B,) or sa.shape != (B,)):
+            raise ValueError(f"keep / spread must hold one value per sequence ({B})")
+        sums = np.empty((B, F), np.float64)
+        corrupted = np.empty_like(xa) if return_corrupted else None
+        eps = np.empty_like(xa) if return_eps else None
+        _binding.check(_binding.load().fd_denoise_loss(
+            self._ensure_handle(), _binding.ptr(xa), _binding.ptr(na), _binding.ptr(t), _binding.ptr(ka), _binding.ptr(sa),
+            _binding.ptr(lens), B, L, float(losses.ANGULAR_BETA), float(losses.NONANGULAR_BETA), _binding.ptr(sums),
+            _binding.ptr(corrupted), _binding.ptr(eps)))
+        if return_corrupted or return_eps:
+            return sums, {k: v for k, v in (("corrupted", corrupted), ("eps", eps)) if v is not None}
+        return sums
+
+    def loss_terms(self, batch) -> torch.Tensor:
+        """``BertForDiffusion._get_loss_terms(batch)`` (modelling.py:553-604) with loss "smooth_l1", no circle penalty and
+        no pairwise-distance loss: a [F] tensor, per feature the mean over all unmasked positions of the batch of the
+        smooth-L1 term of the predicted against the known noise.  ``batch`` has the reference's keys ``corrupted``, ``t``,
+        ``known_noise`` and ``attn_mask`` (a prefix mask).  One device call: forward with one timestep per sequence, terms
+        and per-sequence fp64 sums; the mean is taken here in float64 (the reference's is a float32 ``torch.mean``)."""
+        sums = self.denoise_loss_sums(batch["corrupted"], batch["known_noise"], batch["t"], batch["attn_mask"])
+        count = int((batch["attn_mask"].detach().cpu() != 0).sum())
+        return torch.from_numpy(sums.sum(axis=0) / count)
+
 
 # The reference's sampling entry points take the Lightning subclass or the base
 # class interchangeably; only the base (inference) surface exists here.

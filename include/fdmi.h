@@ -41,6 +41,8 @@ extern "C" {
 /* 7: fd_annotate_sse (P-SEA secondary structure of CA traces)
  *    fd_tm_align (alignment search of CA traces) came later and is additive: no existing entry changed, so the version
  *    stays 7; a library without it fails the binding's symbol lookup by name */
+/*    fd_forward_t (one timestep per sequence), fd_loss_terms and fd_denoise_loss (the denoising loss of a fixed checkpoint)
+ *    are additive in the same way: no existing entry or struct changed, the version stays 7 */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -164,6 +166,12 @@ int fd_fused_attn_supported(fd_model* m, int L);
  * are addressed with 32-bit offsets, so B * n_heads * ceil(L / 32) * 4096 bytes must stay below 4 GiB (B < 21,845 sequences of
  * L = 128 at 12 heads) -- FD_E_UNSUPPORTED beyond; sampling.sample chunks by batch_size long before that. */
 int fd_forward(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float* eps_out);
+
+/* fd_forward with one timestep per sequence, t = int32[B] (host), every t[b] in [0, T): what the reference's forward takes from
+ * a training or validation batch (modelling.py:384-484 with batch["t"], :553-566).  A row of sequence b adds time_embed(t[b])
+ * behind the embedding LayerNorm (modelling.py:472), the only place the timestep enters; every later launch is the one
+ * fd_forward makes for the same (B, L).  With all t[b] equal the result has fd_forward's bits.  Both precisions. */
+int fd_forward_t(fd_model* m, const float* x, const int32_t* t, const int32_t* lens, int B, int L, float* eps_out);
 
 /* The same forward with what the reference's forward also honours (modelling.py:434-452, :464-467) and the sampler never produces:
  *   key_mask      uint8[B][L], 1 = attend, 0 = masked key, ANY pattern (NULL: every key is attended to); masked keys get the
@@ -342,6 +350,38 @@ int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const i
                 int n_pairs, int max_iter, double* tm_out, double* transform_out /* null or [n_pairs][12] */,
                 int32_t* n_ali_out /* null ok */, const int64_t* map_offsets, int32_t* map_out /* both null, or
                 map_out[map_offsets[p] + i] = j or -1 for i < lens[pair_a[p]] */);
+
+/* ---- the denoising loss of a fixed checkpoint (forward only): BertForDiffusion._get_loss_terms / validation_step
+ * (foldingdiff/modelling.py:553-604, :720-751) with loss = "smooth_l1", circle_reg = 0 and no pairwise-distance loss ----
+ *
+ * Per-position terms of pred against target (host float32 [B][L][F]) and their per-sequence sums.  Feature f with
+ * is_angle[f] != 0: losses.radian_smooth_l1_loss (losses.py:29-55), d = wrap(target - pred) to [-pi, pi), term =
+ * |d| < beta_ang ? 0.5 d^2 / beta_ang : |d| - 0.5 beta_ang (the reference uses beta_ang = pi / 10); other features:
+ * F.smooth_l1_loss, the same with the unwrapped d and beta_lin (the reference uses 1).  float32 in the reference's operation
+ * order.  1 <= F <= 32, 1 <= lens[b] <= L, both betas > 0.
+ *   sums    float64 [B][F]: the sum of the terms over positions l < lens[b], accumulated in fp64 in a fixed order -- the same
+ *           bits from run to run and wherever the sequence sits in the batch.  _get_loss_terms' value for feature f is
+ *           sum_b sums[b][f] / sum_b lens[b].
+ *   terms   NULL, or float32 [B][L][F]: the terms themselves, 0 at positions l >= lens[b]
+ * Model-free and synchronous, like fd_nerf. */
+int fd_loss_terms(int device_id, const float* pred, const float* target, const int32_t* lens, int B, int L, int F,
+                  const uint8_t* is_angle, float beta_ang, float beta_lin, double* sums /* [B][F] */,
+                  float* terms /* [B][L][F] or NULL */);
+
+/* Noising, forward and loss of one batch in one call on the model's stream: one upload, one [B][F] download.
+ *   x0, noise   host float32 [B][L][F]: the clean features and the N(0,1) draw eps (NoisedAnglesDataset.sample_noise); noise
+ *               is also the target of the loss (batch["known_noise"])
+ *   t           int32 [B], each in [0, T);  lens int32 [B]
+ *   keep, spread  float32 [B]: sqrt_alphas_cumprod[t[b]] and sqrt_one_minus_alphas_cumprod[t[b]].  The device computes
+ *               x_t = keep[b] * x0 + spread[b] * noise, wrapped to [-pi, pi) where fd_finalize's is_angle says so, at EVERY
+ *               position of the padded length -- the bits of NoisedAnglesDataset.__getitem__ (datasets.py:861-871).
+ *               BOTH NULL: x0 is x_t already (batch["corrupted"]) and nothing is noised; noise is still the target.
+ *   sums        float64 [B][F] as fd_loss_terms', of pred = model(x_t, t, mask(lens)) against noise; angularity is what
+ *               fd_finalize was given
+ *   corrupted_out, eps_out  NULL, or float32 [B][L][F]: x_t and the predicted noise */
+int fd_denoise_loss(fd_model* m, const float* x0, const float* noise, const int32_t* t, const float* keep, const float* spread,
+                    const int32_t* lens, int B, int L, float beta_ang, float beta_lin, double* sums /* [B][F] */,
+                    float* corrupted_out /* or NULL */, float* eps_out /* or NULL */);
 
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
