@@ -1845,6 +1845,21 @@ int fd_synchronize(fd_model* m) {
 
 int fd_debug_read(fd_model* m, const char* name, float* out, int64_t n_floats) {
   if (!m || !name || !out) return fail(FD_E_INVALID, "null argument");
+  if (std::string(name) == "scales") {  // what fd_finalize chose: needs the model, not a workspace
+    if (!m->finalized || !m->img || m->layers.empty()) return fail(FD_E_STATE, "fd_debug_read(scales): no model finalized with FD_PREC_F16X3");
+    if (m->debug_layer < 0 || m->debug_layer >= m->cfg.n_layers)
+      return fail(FD_E_INVALID, "fd_debug_read(scales): debug_layer %d of %d layers", m->debug_layer, m->cfg.n_layers);
+    const LayerDev& lw = m->layers[m->debug_layer];
+    const float s_next = m->debug_layer + 1 < m->cfg.n_layers ? m->layers[m->debug_layer + 1].s_h : m->s_hfinal;
+    auto of = [](const SplitW& w) { return w.p ? w.scale : 0.f; };
+    const float v[] = {lw.s_h, lw.s_q, lw.s_k, lw.s_v, lw.s_a, lw.s_g, s_next, m->s_hfinal, m->s_hg,
+                       of(lw.wqkv_i), of(lw.wqk_i), of(lw.wv_i), of(lw.wsa16_i), of(lw.wsa_i), of(lw.wo_i), of(lw.wtail_i),
+                       of(lw.wi_i), of(lw.wd_i), of(lw.wff_i), lw.wff_i.p ? lw.wff_scale_dn : 0.f, of(lw.demb_s)};
+    const long long n = sizeof v / sizeof v[0];
+    if (n_floats < n) return fail(FD_E_INVALID, "fd_debug_read(scales): need %lld floats", n);
+    memcpy(out, v, sizeof v);
+    return FD_OK;
+  }
   Workspace& w = m->ws;
   if (!w.img) return fail(FD_E_STATE, "fd_debug_read: the current workspace is not on the row-image path");
   HIP_TRY(hipSetDevice(m->device));

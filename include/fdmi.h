@@ -438,7 +438,16 @@ int fd_check_finite(fd_model* m);
 
 /* Debug / test aid (FD_PREC_F16X3 only): copy an intermediate of the last step back as float32.  `name`: "h", "a",
  * "ctx", "g", "g_head", "h_out" ([rows rounded up to 128][width]) or "q", "k", "v" ([B][H][padded L][32]); scales are
- * those of layer option "debug_layer"; option "debug_stop" = n ends a step after n kernel launches. */
+ * those of layer option "debug_layer"; option "debug_stop" = n ends a step after n kernel launches.
+ * "rowinfo": (sequence, position) of every token row as floats, (-1, -1) for a row that is none ([rows rounded up to 128][2]).
+ * "scales": the power-of-two scales fd_finalize chose for layer "debug_layer" (which must name a layer), 21 floats; needs a
+ * model finalized with FD_PREC_F16X3 and no workspace:
+ *    0..5   s_h, s_q, s_k, s_v, s_a, s_g                  activation images of the layer: input, q, k, v (and context),
+ *                                                        attention.output LayerNorm, GELU
+ *    6      scale of the layer's output image            (the next layer's s_h; s_hfinal after the last layer)
+ *    7, 8   s_hfinal, s_hg                               last hidden state, the head's GELU (the same for every layer)
+ *    9..20  wqkv_i, wqk_i, wv_i, wsa16_i, wsa_i, wo_i, wtail_i, wi_i, wd_i, wff_i, wff_scale_dn, demb_s
+ *                                                        the layer's weight images; 0 where an image was not uploaded */
 int fd_debug_read(fd_model* m, const char* name, float* out, int64_t n_floats);
 
 const char* fd_last_error(void);

@@ -30,6 +30,21 @@ def test_abi_version_and_error_string(lib):
     assert rc == -1
 
 
+def test_debug_read_rejects_a_null_model(lib):
+    """fd_debug_read without a model: -1, "null" in fd_last_error(), the output left alone.  This is all that can be asked without
+    a device (no model can be created), and it does not reach the "scales" branch: its own bad-argument cases -- an unfinalized
+    model, a short buffer, a debug_layer that names no layer, a model finalized in FD_PREC_F32 -- need a model and are in
+    tests/test_gpu_parity.py::test_debug_read_scales_arguments."""
+    import ctypes as C
+
+    import numpy as np
+
+    out = np.full(21, -7, np.float32)
+    rc = lib.fd_debug_read(None, b"scales", out.ctypes.data_as(C.c_void_p), out.size)
+    assert rc == -1 and b"null" in lib.fd_last_error(), (rc, lib.fd_last_error())
+    assert (out == -7).all()
+
+
 def test_model_free_entries_reject_bad_arguments_before_touching_a_device(lib):
     """The ten entries that take a device_id check every argument before their first HIP call: each bad call returns
     -1 with its word in fd_last_error() and leaves the outputs alone, on a machine without a GPU too.  No valid call
