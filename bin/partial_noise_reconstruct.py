@@ -17,6 +17,12 @@ reference's key and one for the file's own backbone:
      "tmscores": {file: TM-score of NeRF(reconstruction) to NeRF(original angles)},
      "tmscores_coord": {file: TM-score of NeRF(reconstruction) to the file's CA atoms, normalised by its length}
 
+With --lddt they are also scored by lDDT (structures.lddt_scorer: N, CA and C atoms, the reconstruction as the model;
+higher is better, 1 = every local distance kept):
+
+     "lddt": {file: lDDT of NeRF(reconstruction) against NeRF(original angles)},
+     "lddt_coord": {file: lDDT of NeRF(reconstruction) against the file's own backbone}
+
 The model must be a local directory (no hub download): training_args.json, config.json, models/ and
 training_mean_offset.npy.  Files the parser rejects (several models, a residue without N / CA / C, angles out of
 range) or that are shorter than the model's min_seq_len are left out of the output.
@@ -76,6 +82,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("-d", "--device", type=int, default=0, help="GPU to use (default: 0)")
     parser.add_argument("--tmscore", action="store_true",
                         help='also write TM-scores ("tmscores", "tmscores_coord") of the same reconstructions')
+    parser.add_argument("--lddt", action="store_true", help='also write lDDT scores ("lddt", "lddt_coord") of the same reconstructions')
     return parser
 
 
@@ -92,28 +99,35 @@ def get_reconstruction_error(pdb_files: Collection[str], timesteps: int, model: 
     return ({f: float(s) for f, s in zip(files, scores)}, {f: float(s) for f, s in zip(files, coord_scores)})
 
 
-def get_reconstruction_scores(pdb_files: Collection[str], timesteps: int, model: str,
-                              device: int = 0) -> Dict[str, Dict[str, float]]:
-    """One reconstruction per file, scored by both scorers: {"rmsd", "rmsd_coord", "tmscores", "tmscores_coord"},
-    each {file: score} over the files that entered the dataset."""
+def get_reconstruction_scores(pdb_files: Collection[str], timesteps: int, model: str, device: int = 0,
+                              tmscore: bool = True, lddt: bool = False) -> Dict[str, Dict[str, float]]:
+    """One reconstruction per file, scored by the RMSD scorer and the chosen others: {"rmsd", "rmsd_coord" [, "tmscores",
+    "tmscores_coord"] [, "lddt", "lddt_coord"]}, each {file: score} over the files that entered the dataset."""
     assert os.path.isdir(model), f"Model path {model} is not a local directory"
     dset = load_dataset(pdb_files, Path(model))
     net = modelling.BertForDiffusionBase.from_dir(model).to(torch.device(f"cuda:{device}"))
     recon, truth, files = sampling.reconstruct(net, dset, noise_timesteps=timesteps)
     out = {}
-    for key, scorer in (("rmsd", structures.RmsdScorer(device=device)), ("tmscores", structures.TmScorer(device=device))):
+    scorers = [("rmsd", structures.RmsdScorer(device=device))]
+    if tmscore:
+        scorers.append(("tmscores", structures.TmScorer(device=device)))
+    if lddt:
+        scorers.append(("lddt", structures.LddtScorer(device=device)))
+    for key, scorer in scorers:
         scores, coord_scores = scorer.score_batch(recon, truth, files)
         out[key] = {f: float(s) for f, s in zip(files, scores)}
         out[f"{key}_coord"] = {f: float(s) for f, s in zip(files, coord_scores)}
-    logging.info(f"Reconstruction TM-score from t={timesteps}: {min(out['tmscores'].values()):.3f}-"
-                 f"{max(out['tmscores'].values()):.3f}")
+    for key in ("tmscores", "lddt"):
+        if key in out:
+            logging.info(f"Reconstruction {key} from t={timesteps}: {min(out[key].values()):.3f}-{max(out[key].values()):.3f}")
     return out
 
 
 def main():
     args = build_parser().parse_args()
-    if args.tmscore:
-        scores = get_reconstruction_scores(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device)
+    if args.tmscore or args.lddt:
+        scores = get_reconstruction_scores(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device,
+                                           tmscore=args.tmscore, lddt=args.lddt)
         with open(args.output_json, "w") as sink:
             json.dump({"timesteps": args.timesteps, "model": args.model, **scores}, sink, indent=4)
         return

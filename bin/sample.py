@@ -11,6 +11,10 @@ reference's ``bin/sample.py`` (same flags, same files):
     with --psea: plots/ss_cooccurrence_sampled.json  {generated_{i}.pdb: [n_alpha, n_beta]} of the final backbones and
                  plots/ss_cooccurrence_sampled.pdf   their 2-D histogram, when matplotlib is installed (:456-469)
 
+    with --clashes: clash_counts.json               {generated_{i}.pdb: van der Waals clash count} of the final backbones
+                    (structures.count_clashes on the coordinates as written: what bin/vdw_clashes.py gives on the files;
+                    without --clashes the output tree is unchanged)
+
 The secondary structures are annotated on the device (structures.count_secondary_structures: P-SEA, in place of
 biotite's annotate_sse) from the coordinates of the backbones just written, without reading the files back.  The step
 is opt-in: the reference runs it unless --nopsea is given, here it runs only with --psea, and without --psea the
@@ -75,6 +79,8 @@ def build_parser() -> argparse.ArgumentParser:
     psea.add_argument("--psea", action="store_true",
                       help="count the helices and strands of the sampled backbones (P-SEA on the device) into plots/ss_cooccurrence_sampled.json [.pdf]")
     psea.add_argument("--nopsea", action="store_true", help="accepted for compatibility: the P-SEA step runs only with --psea")
+    parser.add_argument("--clashes", action="store_true",
+                        help="count the van der Waals clashes of the sampled backbones (on the device) into clash_counts.json")
     parser.add_argument("--seed", type=int, default=SEED, help="Random seed")
     parser.add_argument("--device", type=str, default="cuda:0", help="Device to use")
     return parser
@@ -161,6 +167,13 @@ def main(argv=None) -> None:
             counts = structures.count_secondary_structures([coords_as_written(xyz[1::3]) for _, xyz in kept], device=device_index)
             structures.write_ss_cooccurrence([name for name, _ in kept], counts, json_file=str(plotdir / "ss_cooccurrence_sampled.json"),
                                              outpdf=str(plotdir / "ss_cooccurrence_sampled.pdf"), title="Secondary structure co-occurrence, sampled")
+        if args.clashes:
+            # what bin/vdw_clashes.py counts on the files just written: their three-decimal coordinates as float32
+            kept = [(os.path.basename(f), xyz) for f, xyz in zip(pdb_files, final_coords) if f]
+            device_index = torch.device(args.device).index or 0
+            counts = structures.count_clashes([coords_as_written(xyz).astype("float32") for _, xyz in kept], device=device_index)
+            with open(outdir / "clash_counts.json", "w") as sink:
+                json.dump({name: int(c) for (name, _), c in zip(kept, counts)}, sink, indent=4)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

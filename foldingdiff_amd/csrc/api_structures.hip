@@ -1,4 +1,4 @@
-// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip) and of
+// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, clash_lddt.hip) and of
 // the loss arithmetic on its own (loss.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
@@ -159,6 +159,55 @@ int fd_loss_terms(int device_id, const float* pred, const float* target, const i
                             float* terms_dev = d.out(1);
                             launch_loss_terms(d.in(0), d.in(1), d.in(2), B, L, F, angle_mask, beta_ang, beta_lin, d.out(0),
                                               terms ? terms_dev : nullptr, nullptr);
+                          });
+}
+
+int fd_backbone_clashes(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens,
+                        int n_chains, double alpha, int32_t* counts_out, uint8_t* flags_out) {
+  if (!xyz || !chain_offsets || !chain_lens || !counts_out) return fail(FD_E_INVALID, "null argument");
+  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
+  if (!(alpha > 0.0) || !std::isfinite(alpha)) return fail(FD_E_INVALID, "alpha=%g must be > 0 and finite", alpha);
+  long long n_res = 0;
+  if (int rc = check_packed(chain_offsets, chain_lens, n_chains, 0x7fffffffLL / 9, &n_res)) return rc;
+  if (int rc = check_atom_cap(chain_lens, n_chains, 3)) return rc;
+  if (int rc = check_coords_f32(xyz, chain_offsets, chain_lens, n_chains, 3)) return rc;
+  const size_t nr = (size_t)n_res, nc = (size_t)n_chains;
+  return device_roundtrip(device_id, {{xyz, nr * 9 * 4}, {chain_offsets, nc * 4}, {chain_lens, nc * 4}},
+                          {{counts_out, nc * 4}, {flags_out, flags_out ? nr * 3 : 4}}, [&](const RoundtripBufs& d) {
+                            unsigned char* flags_dev = d.out(1);
+                            launch_backbone_clashes(d.in(0), d.in(1), d.in(2), n_chains, alpha, d.out(0),
+                                                    flags_out ? flags_dev : nullptr, nullptr);
+                          });
+}
+
+int fd_lddt(int device_id, const float* model, const float* ref, const int32_t* offsets, const int32_t* lens, int n_pairs,
+            int atoms_per_res, double radius, const double* thresholds, int n_thresholds, int64_t* counts_out,
+            int32_t* res_counts_out) {
+  if (!model || !ref || !offsets || !lens || !thresholds || !counts_out) return fail(FD_E_INVALID, "null argument");
+  if (n_pairs < 1) return fail(FD_E_INVALID, "n_pairs=%d must be >= 1", n_pairs);
+  if (atoms_per_res < 1 || atoms_per_res > 8) return fail(FD_E_INVALID, "atoms_per_res=%d outside [1, 8]", atoms_per_res);
+  if (!(radius > 0.0) || !std::isfinite(radius)) return fail(FD_E_INVALID, "radius=%g must be > 0 and finite", radius);
+  if (n_thresholds < 1 || n_thresholds > kLddtMaxThresholds)
+    return fail(FD_E_INVALID, "n_thresholds=%d outside [1, %d]", n_thresholds, kLddtMaxThresholds);
+  LddtThresholds thr{};   // unused places stay 0: no pair passes them
+  for (int k = 0; k < n_thresholds; ++k) {
+    if (!(thresholds[k] > 0.0) || !std::isfinite(thresholds[k]))
+      return fail(FD_E_INVALID, "thresholds[%d]=%g must be > 0 and finite", k, thresholds[k]);
+    thr.t[k] = thresholds[k];
+  }
+  const int A = atoms_per_res;
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_pairs, 0x7fffffffLL / (3 * A), &n_res)) return rc;
+  if (int rc = check_atom_cap(lens, n_pairs, A)) return rc;
+  if (int rc = check_coords_f32(model, offsets, lens, n_pairs, A)) return rc;
+  if (int rc = check_coords_f32(ref, offsets, lens, n_pairs, A)) return rc;
+  const size_t nr = (size_t)n_res, np = (size_t)n_pairs;
+  return device_roundtrip(device_id, {{model, nr * A * 3 * 4}, {ref, nr * A * 3 * 4}, {offsets, np * 4}, {lens, np * 4}},
+                          {{counts_out, np * 2 * 8}, {res_counts_out, res_counts_out ? nr * 2 * 4 : 4}},
+                          [&](const RoundtripBufs& d) {
+                            int* res_dev = d.out(1);
+                            launch_lddt(d.in(0), d.in(1), d.in(2), d.in(3), n_pairs, A, radius, thr, d.out(0),
+                                        res_counts_out ? res_dev : nullptr, nullptr);
                           });
 }
 

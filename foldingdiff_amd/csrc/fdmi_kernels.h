@@ -126,6 +126,20 @@ hipError_t launch_tm_align(const double* ca, const double* cent, const int* offs
                            int n_pairs, int max_iter, int max_len, double* tm_out, double* transform_out, int* n_ali_out,
                            int* map_out, hipStream_t s);
 
+// Integer pair counts over all atom pairs of a structure (clash_lddt.hip), one workgroup per structure, float32
+// coordinates packed like launch_internal_coords'.  Clashes: xyz [n_res][3][3] -> counts_out [n_chains] (atoms that clash),
+// flags_out [3 n_res] or null.  lDDT: model, ref [n_res][A][3], 1 <= A <= 8 -> counts_out [n_pairs][2] (conserved pairs
+// summed over the thresholds, included pairs), res_counts_out [n_res][2] or null; the unused places of `thr` hold 0,
+// which no pair passes.  At most 65536 atoms per structure (the per-atom counters are 32-bit).
+constexpr int kLddtMaxThresholds = 8;
+struct LddtThresholds {
+  double t[kLddtMaxThresholds];
+};
+void launch_backbone_clashes(const float* xyz, const int* offsets, const int* lens, int n_chains, double alpha,
+                             int* counts_out, unsigned char* flags_out, hipStream_t s);
+void launch_lddt(const float* model, const float* ref, const int* offsets, const int* lens, int n_pairs, int atoms_per_res,
+                 double radius, const LddtThresholds& thr, long long* counts_out, int* res_counts_out, hipStream_t s);
+
 // *t_dev -= 1  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, hipStream_t s);
 

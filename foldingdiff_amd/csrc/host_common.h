@@ -163,4 +163,25 @@ inline int check_coords(const double* xyz, const int32_t* offsets, const int32_t
   return FD_OK;
 }
 
+// the same for packed float32 coordinates with `per` atoms to an entry ([sum lens][per][3]); names the atom and its chain
+inline int check_coords_f32(const float* xyz, const int32_t* offsets, const int32_t* lens, int n, int per) {
+  for (int c = 0; c < n; ++c)
+    for (long long i = (long long)offsets[c] * per; i < ((long long)offsets[c] + lens[c]) * per; ++i)
+      for (int d = 0; d < 3; ++d) {
+        const float u = xyz[(size_t)i * 3 + d];
+        if (!(std::fabs(u) <= 1e6f))
+          return fail(FD_E_INVALID, "coordinate %d of atom %lld (chain %d) is not finite or beyond 1e6: %g", d, i, c, (double)u);
+      }
+  return FD_OK;
+}
+
+// at most FDMI_PAIRCOUNT_MAX_ATOMS atoms in every structure of a packed call with `per` atoms to an entry
+inline int check_atom_cap(const int32_t* lens, int n, int per) {
+  for (int c = 0; c < n; ++c)
+    if ((long long)lens[c] * per > FDMI_PAIRCOUNT_MAX_ATOMS)
+      return fail(FD_E_UNSUPPORTED, "lens[%d]=%d: %lld atoms, at most %d in one structure", c, lens[c], (long long)lens[c] * per,
+                  FDMI_PAIRCOUNT_MAX_ATOMS);
+  return FD_OK;
+}
+
 }  // namespace fdmi

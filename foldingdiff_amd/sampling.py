@@ -620,7 +620,7 @@ def get_reconstruction_error(model, dset, noise_timesteps: int = 250, bs: int = 
     score_coord)`` -- the role of the reference's ``_score_angles`` (foldingdiff/sampling.py:266-284).
     ``structures.tm_scorer`` gives the reference's TM-scores (CA traces, device search); a scorer with a
     ``score_batch(recon, truth, files) -> (scores, coord_scores)`` method (``structures.tm_scorer``,
-    ``structures.rmsd_scorer``) scores all items in one call.  Returns (scores, coord_scores) as the reference does."""
+    ``structures.rmsd_scorer``, ``structures.lddt_scorer``) scores all items in one call.  Returns (scores, coord_scores) as the reference does."""
     if scorer is None:
         raise NotImplementedError("pass scorer=...: structures.tm_scorer for the reference's TM-scores, "
                                   "structures.rmsd_scorer for RMSDs; use reconstruct() for the angle sets")

@@ -22,6 +22,11 @@ The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
   correspond: ``tm_align``, ``pairwise_tm``, ``max_tm_across_refs`` and ``pairwise_tmscores`` search the residue
   alignment and the superposition on the device (``fd_tm_align``, one workgroup per pair).
 
+* ``count_clashes`` / ``count_clashes_parallel`` (foldingdiff/vdw_clashes.py:34-78), a Python double loop over atom pairs
+  in one process per file, and ``lddt`` / ``lddt_sampled_folded`` (foldingdiff/lddt.py:32-100), one OpenStructure
+  container per pair: ``count_clashes``, ``count_clashes_parallel``, ``lddt`` and ``lddt_scorer`` count the atom pairs on
+  the device (``fd_backbone_clashes``, ``fd_lddt``: one workgroup per structure, integer results).
+
 PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PDBFile`` for them):
 
 1. a file with more than one MODEL record is rejected (``None``), as the reference does;
@@ -817,3 +822,191 @@ def training_tm_scores(pdb_files: Sequence[str], train_files: Sequence[str], max
     best, which = max_tm_across_refs(q, r, max_iter=max_iter, device=device) if q else ([], [])
     names = [os.path.splitext(os.path.basename(f))[0] for f in samples]
     return ({k: float(v) for k, v in zip(names, best)}, {k: refs[int(j)] for k, j in zip(names, which)})
+
+
+# ---------------------------------------------------------------------------------------------------- clashes and lDDT
+PAIRCOUNT_MAX_ATOMS = 65536   # FDMI_PAIRCOUNT_MAX_ATOMS
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+
+
+def _atom_arrays(arrays: Sequence[np.ndarray], per: int, what: str) -> List[np.ndarray]:
+    """The structures as float32 arrays, each checked to be [per * n, 3] with n >= 1 and at most 65536 atoms."""
+    out = [np.asarray(x, dtype=np.float32) for x in arrays]
+    for i, x in enumerate(out):
+        if x.ndim != 2 or x.shape[1] != 3 or len(x) == 0 or len(x) % per or len(x) > PAIRCOUNT_MAX_ATOMS:
+            raise ValueError(f"{what} {i}: {x.shape}; expected [{per} n, 3] coordinates with n >= 1 and at most "
+                             f"{PAIRCOUNT_MAX_ATOMS} atoms")
+    return out
+
+
+def count_clashes(chains: Sequence[np.ndarray], alpha: float = 0.63, device: int = 0, return_flags: bool = False):
+    """Van der Waals clashes of every backbone in ``chains`` (each [3 n_i, 3]: N, CA, C per residue), all in one
+    ``fd_backbone_clashes`` launch: an int64 array of the number of atoms that clash with at least one other atom --
+    ``count_clashes`` (foldingdiff/vdw_clashes.py:34-68) -- and with ``return_flags`` also a list of boolean [3 n_i] arrays,
+    True for an atom that clashes.
+
+    Atoms a and b (indices in file order) clash iff |a - b| >= 2 and d(a, b) <= alpha * (r_a + r_b), r = 1.55 for N and
+    1.7 for CA and C (DESIGN.md "Clash counts and lDDT").  Unlike the reference, two neighbouring atoms at distance
+    exactly 0 do not clash."""
+    alpha = float(alpha)
+    if not (alpha > 0 and np.isfinite(alpha)):
+        raise ValueError(f"alpha={alpha} must be > 0 and finite")
+    xs = _atom_arrays(chains, 3, "chain")
+    n = len(xs)
+    counts = np.zeros((n,), dtype=np.int32)
+    if n == 0:
+        return (counts.astype(np.int64), []) if return_flags else counts.astype(np.int64)
+    xyz, offsets, lens = _pack(xs, np.float32)
+    flags = np.empty((len(xyz),), dtype=np.uint8) if return_flags else None
+    _binding.check(_binding.load().fd_backbone_clashes(device, ptr(xyz), ptr(offsets // 3), ptr(lens // 3), n, alpha,
+                                                       ptr(counts), ptr(flags)))
+    if return_flags:
+        return counts.astype(np.int64), [flags[o: o + m].astype(bool) for o, m in zip(offsets, lens)]
+    return counts.astype(np.int64)
+
+
+def count_clashes_parallel(filenames: Sequence[str], nthreads: Optional[int] = None, device: int = 0) -> dict:
+    """``count_clashes_parallel`` (foldingdiff/vdw_clashes.py:71-78): {file name: clash count} with the reference's
+    default ``alpha``, the files parsed on the host by ``read_backbone`` and counted in one launch.  ``nthreads`` is
+    accepted for the reference's signature and ignored.  A file ``read_backbone`` rejects raises ``ValueError``."""
+    filenames = list(filenames)
+    chains = []
+    for f in filenames:
+        bb = read_backbone(f)
+        if bb is None:
+            raise ValueError(f"{f}: not readable as one model with N, CA and C in every residue")
+        chains.append(bb[0])
+    return {f: int(c) for f, c in zip(filenames, count_clashes(chains, device=device))}
+
+
+def lddt(models: Sequence[np.ndarray], refs: Sequence[np.ndarray], atoms_per_res: int = 3, radius: float = 15.0,
+         thresholds: Sequence[float] = LDDT_THRESHOLDS, per_residue: bool = False, device: int = 0,
+         return_counts: bool = False):
+    """lDDT (Mariani et al. 2013) of ``models[i]`` against ``refs[i]``, every pair in one ``fd_lddt`` launch: float64
+    [len(models)], NaN where no atom pair of the reference is within ``radius`` (a single residue).  Both of a pair are
+    [atoms_per_res * n_i, 3] with the same residues and the same atoms per residue in the same order (1 for CA traces, 3
+    for N, CA, C backbones; at most 8).
+
+    A pair of atoms of different residues is included iff its distance in the reference is below ``radius``, and
+    conserved at a threshold iff its distance in the model differs by less than it; the score is the mean over the
+    thresholds of conserved / included (DESIGN.md "Clash counts and lDDT").  These are the defaults of OpenStructure's
+    ``compare-structures --lddt``, which the reference runs in a container per pair (foldingdiff/lddt.py:32-56), without
+    its stereochemistry checks; the score is not pinned to that binary.
+
+    ``per_residue``: also a list of float64 [n_i] arrays, the same ratio over the included pairs with an atom in the
+    residue (NaN where there is none).  ``return_counts``: the integers instead of the ratios -- int64 [len, 2]
+    (conserved summed over the thresholds, included) and, with ``per_residue``, a list of int64 [n_i, 2]."""
+    A = int(atoms_per_res)
+    if not 1 <= A <= 8:
+        raise ValueError(f"atoms_per_res={atoms_per_res} outside [1, 8]")
+    radius = float(radius)
+    if not (radius > 0 and np.isfinite(radius)):
+        raise ValueError(f"radius={radius} must be > 0 and finite")
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    if not 1 <= len(thr) <= 8 or not (np.isfinite(thr) & (thr > 0)).all():
+        raise ValueError(f"thresholds={list(thresholds)}: expected 1 to 8 positive finite values")
+    if len(models) != len(refs):
+        raise ValueError(f"{len(models)} models against {len(refs)} references")
+    ms, rs = _atom_arrays(models, A, "model"), _atom_arrays(refs, A, "reference")
+    for i, (x, y) in enumerate(zip(ms, rs)):
+        if x.shape != y.shape:
+            raise ValueError(f"pair {i}: model {x.shape} vs reference {y.shape}; expected the same residues in both")
+    n = len(ms)
+    counts = np.zeros((n, 2), dtype=np.int64)
+    res_counts = []
+    if n:
+        (M, offsets, lens), R = _pack(ms, np.float32), _pack(rs, np.float32)[0]
+        res = np.empty((len(M) // A, 2), dtype=np.int32) if per_residue else None
+        _binding.check(_binding.load().fd_lddt(device, ptr(M), ptr(R), ptr(offsets // A), ptr(lens // A), n, A, radius,
+                                               ptr(thr), len(thr), ptr(counts), ptr(res)))
+        if per_residue:
+            res_counts = [res[o: o + m].astype(np.int64) for o, m in zip(offsets // A, lens // A)]
+    if return_counts:
+        return (counts, res_counts) if per_residue else counts
+
+    def ratio(c):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(c[..., 1] > 0, c[..., 0] / (len(thr) * c[..., 1].astype(np.float64)), np.nan)
+
+    return (ratio(counts), [ratio(c) for c in res_counts]) if per_residue else ratio(counts)
+
+
+class LddtScorer:
+    """A ``scorer=`` for ``sampling.get_reconstruction_error``, shaped like ``TmScorer``: per item (lDDT of
+    NeRF(reconstruction) against NeRF(truth), lDDT of NeRF(reconstruction) against the backbone of the item's PDB
+    file), over the N, CA and C atoms with the reconstruction as the model.  The file's backbone is compared over the
+    residues the item holds (the first ``len`` of them: left-aligned items); an unreadable file, or one shorter than
+    the item, scores NaN.  Like the other scorers, the backbones are built from the angles exactly as ``reconstruct``
+    returns them.  ``score_batch`` scores all items of a call with one NeRF launch and one lDDT launch."""
+
+    def __init__(self, device: int = 0, radius: float = 15.0, thresholds: Sequence[float] = LDDT_THRESHOLDS):
+        self.device, self.radius, self.thresholds = device, radius, tuple(thresholds)
+
+    def __call__(self, reconst_angles, truth_angles, truth_pdb_file: str) -> Tuple[float, float]:
+        s, c = self.score_batch([reconst_angles], [truth_angles], [truth_pdb_file])
+        return float(s[0]), float(c[0])
+
+    def score_batch(self, recon: Sequence, truth: Sequence, files: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+        n = len(recon)
+        assert len(truth) == n == len(files)
+        if n == 0:
+            return np.zeros((0,)), np.zeros((0,))
+        recon = [np.asarray(r, dtype=np.float32) for r in recon]
+        truth = [np.asarray(t, dtype=np.float32) for t in truth]
+        F = recon[0].shape[1]
+        names = [v for k, v in datasets.FEATURE_SET_NAMES_TO_FEATURE_NAMES.items() if k in DATASETS and len(v) == F]
+        assert names, f"no canonical feature set has {F} features"
+        xyz = nerf.build_backbones(recon + truth, names[0], device=self.device)
+        a, b, which = [], [], []
+        for i, f in enumerate(files):
+            a.append(xyz[i]); b.append(xyz[n + i]); which.append(("angles", i))
+            bb = read_backbone(f) if os.path.isfile(f) else None
+            if bb is not None and len(bb[0]) >= len(xyz[i]):
+                a.append(xyz[i]); b.append(bb[0][: len(xyz[i])]); which.append(("coords", i))
+        r = lddt(a, b, atoms_per_res=3, radius=self.radius, thresholds=self.thresholds, device=self.device)
+        scores, coord_scores = np.full(n, np.nan), np.full(n, np.nan)
+        for (kind, i), v in zip(which, r):
+            (scores if kind == "angles" else coord_scores)[i] = v
+        return scores, coord_scores
+
+
+lddt_scorer = LddtScorer()
+
+
+def lddt_sampled_folded(sampled_dir: str, folded_dir: str, out_path: str = "lddt.json", device: int = 0) -> dict:
+    """``lddt_sampled_folded`` (foldingdiff/lddt.py:59-100): {sampled stem: {folded stem: lDDT}} for every
+    ``<sampled_dir>/<stem>.pdb`` and each of its ``<folded_dir>/<stem>_*.pdb``, the folded structure as the model and
+    the sampled one as the reference, over N, CA and C; written to ``out_path`` when that is not empty.  All pairs are
+    scored in one launch.  A pair that cannot be scored (a file ``read_backbone`` rejects, different residue counts, or
+    no atom pair within the radius) gets -1.0, the reference's failure value."""
+    sampled = sorted(glob.glob(os.path.join(sampled_dir, "*.pdb")))
+    logging.info(f"Found {len(sampled)} sampled structures in {sampled_dir}")
+    pairs = []   # (sampled file, folded file)
+    for s in sampled:
+        stem = os.path.splitext(os.path.basename(s))[0]
+        pairs.extend((s, f) for f in sorted(glob.glob(os.path.join(folded_dir, f"{glob.escape(stem)}_*.pdb"))))
+    backbones = {}
+    for f in {f for pair in pairs for f in pair}:
+        try:
+            bb = read_backbone(f)
+        except (OSError, ValueError) as e:
+            logging.error(f"Cannot read {f}: {e}")
+            bb = None
+        backbones[f] = None if bb is None else bb[0]
+    ok = [k for k, (s, f) in enumerate(pairs)
+          if backbones[s] is not None and backbones[f] is not None and backbones[s].shape == backbones[f].shape]
+    values = [-1.0] * len(pairs)
+    scores = lddt([backbones[pairs[k][1]] for k in ok], [backbones[pairs[k][0]] for k in ok], atoms_per_res=3, device=device)
+    for k, v in zip(ok, scores):
+        if np.isfinite(v):
+            values[k] = float(v)
+    out: dict = {}
+    for (s, f), v in zip(pairs, values):
+        if v < 0:
+            logging.error(f"Failed to compute lDDT for {f} and {s}")
+        out.setdefault(os.path.splitext(os.path.basename(s))[0], {})[os.path.splitext(os.path.basename(f))[0]] = v
+    if out_path:
+        logging.info(f"Writing lDDT scores to {out_path}")
+        with open(out_path, "w") as sink:
+            json.dump(out, sink, indent=4)
+    return out

@@ -43,6 +43,7 @@ extern "C" {
  *    stays 7; a library without it fails the binding's symbol lookup by name */
 /*    fd_forward_t (one timestep per sequence), fd_loss_terms and fd_denoise_loss (the denoising loss of a fixed checkpoint)
  *    are additive in the same way: no existing entry or struct changed, the version stays 7 */
+/*    fd_backbone_clashes and fd_lddt (integer pair counts over the atoms of a structure) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -350,6 +351,43 @@ int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const i
                 int n_pairs, int max_iter, double* tm_out, double* transform_out /* null or [n_pairs][12] */,
                 int32_t* n_ali_out /* null ok */, const int64_t* map_offsets, int32_t* map_out /* both null, or
                 map_out[map_offsets[p] + i] = j or -1 for i < lens[pair_a[p]] */);
+
+/* Most atoms of one structure fd_backbone_clashes and fd_lddt take (the per-atom pair counters are 32-bit). */
+#define FDMI_PAIRCOUNT_MAX_ATOMS 65536
+
+/* Van der Waals clashes of backbones: count_clashes / count_clashes_parallel (foldingdiff/vdw_clashes.py:34-78), every
+ * chain of a call in one launch, one workgroup per chain.  Atoms of a chain in file order: 3i = N (radius 1.55), 3i + 1 =
+ * CA and 3i + 2 = C (radius 1.7).  Atoms a and b clash iff |a - b| >= 2 and d(a, b) <= alpha * (r_a + r_b), the distance
+ * and the product in fp64 from the float32 coordinates.  Unlike the reference, a neighbouring pair (|a - b| = 1) at
+ * distance exactly 0 does not clash (DESIGN.md "Clash counts and lDDT").
+ *   xyz           host float32 [n_res][3][3]: N, CA, C of each residue; chains packed back to back like
+ *                 fd_internal_coords'; 3 * chain_lens[c] <= FDMI_PAIRCOUNT_MAX_ATOMS; finite, |coordinate| <= 1e6
+ *   alpha         > 0 and finite (the reference's default is 0.63)
+ *   counts_out    int32 [n_chains]: the atoms of the chain that clash with at least one other atom
+ *   flags_out     NULL, or uint8 [3 n_res]: 1 = this atom clashes
+ * Synchronous; the result does not depend on the other chains of the call. */
+int fd_backbone_clashes(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens,
+                        int n_chains, double alpha, int32_t* counts_out /* [n_chains] */,
+                        uint8_t* flags_out /* NULL or [3 n_res]: 1 = this atom clashes */);
+
+/* lDDT of models against references of the same residues: lddt / lddt_sampled_folded (foldingdiff/lddt.py:32-100), which
+ * start one OpenStructure container per pair.  It restates Mariani et al. 2013 with the defaults of OpenStructure's
+ * compare-structures --lddt (DESIGN.md "Clash counts and lDDT" has the exact rules) and is not pinned to that binary; no
+ * stereochemistry checks are made.  Residue i of the model corresponds to residue i of the reference, atoms_per_res atoms
+ * per residue in the same order in both.  An unordered pair of atoms of different residues is included iff d_ref <
+ * radius, and conserved at threshold tau iff |d_model - d_ref| < tau (fp64 from the float32 coordinates).
+ *   model, ref    host float32 [n_res][atoms_per_res][3]; pair p = residues offsets[p] .. offsets[p] + lens[p] - 1 of
+ *                 both, packed back to back; 1 <= atoms_per_res <= 8; atoms_per_res * lens[p] <=
+ *                 FDMI_PAIRCOUNT_MAX_ATOMS; finite, |coordinate| <= 1e6
+ *   radius        > 0 and finite (default 15);  thresholds  float64 [n_thresholds], 1 <= n_thresholds <= 8, each > 0 and
+ *                 finite (defaults 0.5, 1, 2, 4)
+ *   counts_out    int64 [n_pairs][2]: conserved (summed over the thresholds), total (included pairs); the score is
+ *                 conserved / (n_thresholds * total), undefined for total = 0
+ *   res_counts_out  NULL, or int32 [n_res][2]: the same two numbers over the included pairs with an atom in the residue
+ * Synchronous; the result does not depend on the other pairs of the call. */
+int fd_lddt(int device_id, const float* model, const float* ref, const int32_t* offsets, const int32_t* lens, int n_pairs,
+            int atoms_per_res, double radius, const double* thresholds, int n_thresholds,
+            int64_t* counts_out /* [n_pairs][2]: conserved, total */, int32_t* res_counts_out /* NULL or [n_res][2] */);
 
 /* ---- the denoising loss of a fixed checkpoint (forward only): BertForDiffusion._get_loss_terms / validation_step
  * (foldingdiff/modelling.py:553-604, :720-751) with loss = "smooth_l1", circle_reg = 0 and no pairwise-distance loss ----
