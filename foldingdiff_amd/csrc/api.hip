@@ -646,6 +646,7 @@ struct StepMode {
   const unsigned char* kmask = nullptr;  // fd_forward_ex: [B][L] key mask of any pattern (device), else null: prefix masks from lens
   const int* pos_ids = nullptr;          // fd_forward_ex: [B][L] position ids of the absolute position embedding (device)
   const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
+  bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
 };
 
 int prof_begin(fd_model* m, int cls, hipStream_t s, bool on) {
@@ -717,7 +718,9 @@ const EnvOverrides& env_overrides() {
 
 // Which kernels make up a timestep on workspace `w` (the model's device is current).  key_mask: fd_forward_ex's arbitrary key mask.
 // The weight images every layer has are asked of layer 0 (fd_finalize uploads the same set for every layer).
-StepPlan plan_step(const fd_model* m, const Workspace& w, bool key_mask) {
+// dyn_rows: the row count of the launches is decided on the device (fd_ar_sample's growing prefix), as with option "varlen"; it
+// changes the GEMM tails only.
+StepPlan plan_step(const fd_model* m, const Workspace& w, bool key_mask, bool dyn_rows = false) {
   StepPlan p;
   p.img = w.img;
   if (!p.img) {
@@ -763,7 +766,7 @@ StepPlan plan_step(const fd_model* m, const Workspace& w, bool key_mask) {
   // do the tiles of an N-column GEMM over this workspace fill whole rounds of the launch's workgroups?  Padded rows: the row count
   // is the workspace's capacity, known here; packed rows (sampling.sample): data dependent -> the slice-capable instantiation
   auto tail_for = [&](int N) {
-    if (m->varlen) return 1;
+    if (m->varlen || dyn_rows) return 1;
     const int ntiles = (max_rows / 128) * ((N + 383) / 384);
     return ntiles % gemm_img_grid(max_rows, N) != 0 ? 1 : 0;
   };
@@ -882,7 +885,7 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode, const StepPla
     e.time_table = m->time_table; e.tslot = w.t_dev; e.rowinfo = w.rowinfo; e.nrow = w.nrow; e.dims = w.dims;
     e.h = w.himg; e.L = L; e.F = F; e.d = d; e.eps = c.ln_eps; e.out_scale = m->layers[0].s_h;
     e.pos_ids = mode.pos_ids;
-    PROF(KC_EMBED, launch_embed_img(e, mode.t_seq, max_rows, s));
+    PROF(KC_EMBED, launch_embed_img(e, mode.t_seq, max_rows, s, mode.ar));
     if (stop_after(1)) return done();
   }
   if (env_overrides().stamps && !m->stamps) {
@@ -1519,6 +1522,91 @@ int fd_forward_t(fd_model* m, const float* x, const int32_t* t, const int32_t* l
   mode.t_seq = w.t_seq;
   if (int rc = run_step(m, s, mode)) return rc;
   HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return check_flag(m);
+}
+
+// the arguments fd_ar_forward and fd_ar_sample share, all checked before the first HIP call
+static int check_ar(fd_model* m, const void* x, const int32_t* seq_lengths, const void* out, int B, int L, const char* who) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x || !seq_lengths || !out) return fail(FD_E_INVALID, "null argument");
+  if (!m->img)
+    return fail(FD_E_UNSUPPORTED, "%s: the autoregressive baseline runs on the row-image kernels only; finalize the model with "
+                "FD_PREC_F16X3 (the exact-fp32 mode has no autoregressive embedding)", who);
+  for (int b = 0; b < B; ++b)  // the length indexes the table fd_finalize was given in place of a timestep
+    if (seq_lengths[b] < 0 || seq_lengths[b] >= m->T)
+      return fail(FD_E_INVALID, "seq_lengths[%d]=%d outside [0, %d)", b, seq_lengths[b], m->T);
+  return FD_OK;
+}
+
+int fd_ar_forward(fd_model* m, const float* x, const int32_t* seq_lengths, const int32_t* key_lens, int B, int L, float* out) {
+  if (int rc = check_ar(m, x, seq_lengths, out, B, L, "fd_ar_forward")) return rc;
+  if (!key_lens) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_lens(key_lens, B, L)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  Workspace& w = m->ws;
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  hipStream_t s = m->stream;
+  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.lens, key_lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.t_seq, seq_lengths, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  if (int rc = prepare_rows(m, s, 0)) return rc;  // the forward defines every position, masked ones included
+  StepMode mode{};
+  mode.forward_only = true;
+  mode.t_seq = w.t_seq;
+  mode.ar = true;
+  if (int rc = run_step(m, s, mode)) return rc;
+  HIP_TRY(hipMemcpyAsync(out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return check_flag(m);
+}
+
+int fd_ar_sample(fd_model* m, const float* seed, const int32_t* seq_lengths, int B, int L, int num_seed, float* out) {
+  if (int rc = check_ar(m, seed, seq_lengths, out, B, L, "fd_ar_sample")) return rc;
+  if (num_seed < 1)  // (no seed: the first step's keys would all be masked)
+    return fail(FD_E_INVALID, "num_seed=%d must be at least 1", num_seed);
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    if (seq_lengths[b] > L) return fail(FD_E_INVALID, "seq_lengths[%d]=%d exceeds L=%d", b, seq_lengths[b], L);
+    longest = seq_lengths[b] > longest ? seq_lengths[b] : longest;
+  }
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  Workspace& w = m->ws;
+  const int F = m->cfg.n_features;
+  const size_t n = (size_t)B * L * F, nb = (size_t)B;
+  hipStream_t s = m->stream;
+  // ONE upload, seed | seq_lengths, through fd_denoise_loss's staging buffer (allocated at that entry's size, so that either may
+  // come first).  The staging vector is pageable memory of this frame: a blocking copy, behind whatever is left on the stream
+  if (!w.loss_in) HIP_TRY(hipMalloc((void**)&w.loss_in, (2 * n + 4 * nb) * 4));
+  std::vector<float> stage(n + nb, 0.f);
+  memcpy(stage.data(), seed, n * 4);
+  memcpy(stage.data() + n, seq_lengths, nb * 4);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(w.loss_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpyAsync(w.x, w.loss_in, n * 4, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.t_seq, w.loss_in + n, nb * 4, hipMemcpyDeviceToDevice, s));
+  // Step i is a forward over the rows 0 .. i of every sequence with the keys 0 .. i-1 unmasked (rows > i are masked keys and
+  // queries nobody reads: they can influence nothing); its head writes eps[b][0 .. i], and row i of it becomes x[b][i].  The
+  // row count grows on the device, so the GEMMs run their slice-capable instantiation; everything else is plan_step's choice
+  const StepPlan plan = plan_step(m, w, false, true);
+  StepMode mode{};
+  mode.forward_only = true;
+  mode.t_seq = w.t_seq;
+  mode.ar = true;
+  auto tail = [&](int copy_pos, int rows_next) -> int {
+    launch_ar_step(w.x, w.eps, B, L, F, copy_pos, rows_next, w.cap, w.lens, w.nrow, w.seq_row0, w.rowinfo, w.dims, s);
+    HIP_TRY(hipGetLastError());
+    return FD_OK;
+  };
+  if (num_seed < longest)
+    if (int rc = tail(-1, num_seed + 1)) return rc;
+  for (int i = num_seed; i < longest; ++i) {
+    if (int rc = run_step_img(m, s, mode, plan)) return rc;
+    if (int rc = tail(i, i + 1 < longest ? i + 2 : 0)) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(out, w.x, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return check_flag(m);
 }

@@ -290,7 +290,14 @@ struct EmbedImgArgs {
   float eps, out_scale;
 };
 // t_seq: null, or [B] (device) one timestep per sequence -- the sibling kernel, which reads neither tslot nor writes it
-void launch_embed_img(const EmbedImgArgs& a, const int* t_seq, int max_rows, hipStream_t s);
+// ar (needs t_seq): the autoregressive baseline's order -- the row time_table[t_seq[b]] goes in BEFORE the position embedding and
+// the LayerNorm and nothing behind it (BertForAutoregressiveBase.forward); pos_ids is not read
+void launch_embed_img(const EmbedImgArgs& a, const int* t_seq, int max_rows, hipStream_t s, bool ar = false);
+// fd_ar_sample, one launch per step: x[b][copy_pos] = eps[b][copy_pos] for every sequence (copy_pos < 0: no copy), then the row
+// table of a step in which every sequence has rows_next token rows and rows_next - 1 unmasked keys (rows_next <= 0: no table).
+// cap = the workspace's row capacity, B * ceil8(rows_next) <= cap
+void launch_ar_step(float* x, const float* eps, int B, int L, int F, int copy_pos, int rows_next, int cap, int* lens, int* nrow,
+                    int* seq_row0, int2* rowinfo, int* dims, hipStream_t s);
 
 struct HeadImgArgs {
   const unsigned char* g;      // image [rows128][d/32]: head activation (mlp decoder) or final hidden state (linear)

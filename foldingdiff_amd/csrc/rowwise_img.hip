@@ -314,6 +314,124 @@ __global__ __launch_bounds__(256) void embed_img_tseq_kernel(EmbedImgArgs a, con
   }
 }
 
+// The autoregressive baseline's embedding (fd_ar_forward, fd_ar_sample; BertForAutoregressiveBase.forward, modelling.py:823-851):
+// the row time_table[t_seq[b]] -- there the embedding of the sequence's target LENGTH, constant over the rollout -- is added to the
+// Linear's output BEFORE the position embedding and the LayerNorm, and nothing is added behind the LayerNorm.  Rows, lanes, padding-row
+// zeros and out_scale (layers[0].s_h) are those of the kernel above.  s_h was derived for |LayerNorm output + time row|; a LayerNorm
+// output without the time row (every component of which is at most 1 in magnitude) lies inside that bound, so the image cannot
+// overflow and only gives away headroom it never used.  A separate kernel, so that the two diffusion ones stay as they are.
+template <int NV, int LPT>
+__global__ __launch_bounds__(256) void embed_img_ar_kernel(EmbedImgArgs a, const int* __restrict__ t_seq) {
+  extern __shared__ __attribute__((aligned(16))) float wT[];  // [F][d] + [3][d]
+  const int d = a.d, F = a.F, nu = d >> 3;
+  float* par = wT + F * d;
+  for (int i = threadIdx.x; i < F * d; i += 256) {
+    const int f = i / d, c = i - f * d;
+    wT[i] = a.w_in[c * F + f];
+  }
+  for (int i = threadIdx.x; i < d; i += 256) {
+    par[i] = a.b_in[i];
+    par[d + i] = a.gamma[i];
+    par[2 * d + i] = a.beta[i];
+  }
+  const int k = threadIdx.x & (LPT - 1), g = threadIdx.x / LPT;
+  bool ok[NV];
+  int col[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    ok[j] = k + LPT * j < nu;
+    col[j] = ok[j] ? 8 * (k + LPT * j) : 0;
+  }
+  __syncthreads();
+  const int rows = a.dims[1];  // every row of the padded range is written (pad rows: zeros)
+  const int nb = d >> 5;
+  for (int tg = blockIdx.x; tg * (256 / LPT) < rows; tg += gridDim.x) {
+    const int row = tg * (256 / LPT) + g;
+    if (row >= rows) continue;  // (no barriers below)
+    const int2 ri = a.rowinfo[row];
+    const bool real = ri.x >= 0 && ri.y < a.nrow[ri.x >= 0 ? ri.x : 0];
+    const size_t xo = real ? ((size_t)ri.x * a.L + ri.y) * F : 0;
+    Unit8 v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) load8(par + col[j], v[j].v);
+    for (int f = 0; f < F; ++f) {
+      const float xf = a.x[xo + f];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        float w[8];
+        load8(wT + f * d + col[j], w);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[j].v[e] += xf * w[e];
+      }
+    }
+    const float* trow = a.time_table + (size_t)(real ? t_seq[ri.x] : 0) * d;  // the row of the sequence's own length
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {  // inputs_upscaled += len_embed (modelling.py:827-828), in front of the embeddings module
+      float tt[8];
+      load8(trow + col[j], tt);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[j].v[e] += tt[e];
+    }
+    if (a.pos_emb) {  // absolute positions only (modelling.py:164-166); position = row index
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        float pe[8];
+        load8(a.pos_emb + (size_t)(real ? ri.y : 0) * d + col[j], pe);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[j].v[e] += pe[e];
+      }
+    }
+    float mean, rstd;
+    row16_layernorm<NV, LPT>(v, ok, d, a.eps, mean, rstd);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (!ok[j]) continue;
+      float gm[8], bt[8], o[8];
+      load8(par + d + col[j], gm);
+      load8(par + 2 * d + col[j], bt);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = real ? v[j].v[e] * rstd * gm[e] + bt[e] : 0.f;  // pad rows are zero rows
+      u32x4 hi, lo;
+      split8(o, a.out_scale, hi, lo);
+      const int u = k + LPT * j;
+      unsigned char* blk = a.h + img_unit_offset(row, nb, u >> 2, u & 3);
+      *reinterpret_cast<u32x4*>(blk) = hi;
+      *reinterpret_cast<u32x4*>(blk + 4 * 512) = lo;
+    }
+  }
+}
+
+// The tail of an autoregressive step and the tables of the next one, in one launch (fd_ar_sample): with copy_pos >= 0 position
+// copy_pos of every sequence takes the head's output, x[b][copy_pos] = eps[b][copy_pos] (retval[:, i] = forward(...)[:, i],
+// modelling.py:887-892); with rows_next > 0 every sequence then has rows_next token rows -- positions 0 .. rows_next - 1, packed
+// at multiples of 8 rows as build_rows packs them -- of which the first rows_next - 1 are unmasked keys: the last row is a query
+// and, like a masked position of a padded batch, a key behind the additive -10000.  Both counts come in by value and are the same
+// for every sequence, so each thread writes its entries from its own index and the host is not asked anything.
+__global__ __launch_bounds__(256) void ar_step_kernel(float* __restrict__ x, const float* __restrict__ eps, int B, int L, int F,
+                                                      int copy_pos, int rows_next, int cap, int* __restrict__ lens,
+                                                      int* __restrict__ nrow, int* __restrict__ seq_row0,
+                                                      int2* __restrict__ rowinfo, int* __restrict__ dims) {
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+  if (copy_pos >= 0)
+    for (int i = tid; i < B * F; i += nth) {
+      const size_t o = ((size_t)(i / F) * L + copy_pos) * F + i % F;
+      x[o] = eps[o];
+    }
+  if (rows_next <= 0) return;
+  const int R = (rows_next + 7) & ~7, total = B * R;
+  for (int b = tid; b < B; b += nth) {
+    lens[b] = rows_next - 1;
+    nrow[b] = rows_next;
+    seq_row0[b] = b * R;
+  }
+  if (tid == 0) {
+    seq_row0[B] = total;
+    dims[0] = total;
+    dims[1] = (total + 127) & ~127;
+  }
+  for (int r = tid; r < cap; r += nth) rowinfo[r] = r < total ? make_int2(r / R, r % R) : make_int2(-1, -1);
+}
+
 // LayerNorm of fp32 rows -> image (models with d_model > 384: the LayerNorm row does not fit one 384-column GEMM tile, so the
 // projection writes dense + bias + residual as fp32 rows and this kernel normalises them; BertSelfOutput / BertOutput)
 template <int NV, int LPT>
@@ -597,14 +715,25 @@ static int row_lpt(int d, int F) {  // F > 0: the head kernel (one lane per outp
   return F > 0 ? 16 : 8;
 }
 
-void launch_embed_img(const EmbedImgArgs& a, const int* t_seq, int max_rows, hipStream_t s) {
+void launch_embed_img(const EmbedImgArgs& a, const int* t_seq, int max_rows, hipStream_t s, bool ar) {
   const int lpt = row_lpt(a.d, 0), nv = (a.d / 8 + lpt - 1) / lpt, grid = row_grid(max_rows, lpt, lpt == 8 ? 512 : 1024);
+  if (ar) {
+    const size_t smem = (size_t)(a.F + 3) * a.d * 4;
+    FD_ROW_SWITCH(embed_img_ar_kernel, a, t_seq);
+  }
   if (t_seq) {
     const size_t smem = (size_t)(a.F + 3) * a.d * 4;
     FD_ROW_SWITCH(embed_img_tseq_kernel, a, t_seq);
   }
   const size_t smem = (size_t)(a.F + 4) * a.d * 4;
   FD_ROW_SWITCH(embed_img_kernel, a);
+}
+
+void launch_ar_step(float* x, const float* eps, int B, int L, int F, int copy_pos, int rows_next, int cap, int* lens, int* nrow,
+                    int* seq_row0, int2* rowinfo, int* dims, hipStream_t s) {
+  const int grid = (cap + 255) / 256 < 64 ? (cap + 255) / 256 : 64;
+  hipLaunchKernelGGL(ar_step_kernel, dim3(grid < 1 ? 1 : grid), dim3(256), 0, s, x, eps, B, L, F, copy_pos, rows_next, cap, lens,
+                     nrow, seq_row0, rowinfo, dims);
 }
 
 void launch_head_update_img(const UpdateArgs& a, const HeadImgArgs& ia, int max_rows, hipStream_t s) {

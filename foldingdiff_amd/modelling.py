@@ -526,6 +526,76 @@ class BertForDiffusionBase:
         return torch.from_numpy(sums.sum(axis=0) / count)
 
 
+class BertForAutoregressiveBase(BertForDiffusionBase):
+    """The autoregressive baseline (foldingdiff/modelling.py:807-893): the same network, checkpoint layout and ``from_dir``,
+    with the time embedding reused as an embedding of each sequence's target length -- added to the input projection
+    *before* the position embedding and the embeddings LayerNorm -- and a sampler that predicts one residue per step from
+    the residues before it.  Runs on the row-image kernels (precision "f16x3") only."""
+
+    def prepare(self, is_angle=None):
+        """Upload the length table: ``time_embed(n)`` for n = 0 .. max_position_embeddings, built like the diffusion
+        model's time table.  There is no schedule; the coefficient rows ``fd_finalize`` wants are those of a cosine
+        schedule of the same size, and nothing on this path reads them."""
+        T = int(self.config.max_position_embeddings) + 1
+        return super().prepare(beta_schedules.cosine_beta_schedule(T), is_angle=is_angle)
+
+    def _lengths(self, seq_lengths, B: int) -> np.ndarray:
+        n = torch.as_tensor(seq_lengths).detach().cpu().reshape(-1).long()
+        if n.numel() != B:
+            raise ValueError(f"{n.numel()} sequence lengths for a batch of {B}")
+        T = int(self.config.max_position_embeddings) + 1
+        if int(n.min()) < 0 or int(n.max()) >= T:
+            raise ValueError(f"seq_lengths must lie in [0, {T}): the length table has max_position_embeddings + 1 rows")
+        return np.ascontiguousarray(n.numpy().astype(np.int32))
+
+    def forward(self, inputs: torch.Tensor, attention_mask: torch.Tensor, seq_lengths: torch.Tensor,
+                position_ids: Optional[torch.Tensor] = None, **_unused) -> torch.Tensor:
+        """``forward(inputs, attention_mask, seq_lengths)`` of the reference (modelling.py:812-862): [B, L, F] -> [B, L, F],
+        every position computed.  Prefix masks (ones followed by zeros, at least one position per sequence) only."""
+        assert attention_mask is not None
+        assert inputs.dim() == 3 and inputs.shape[2] == self.n_inputs
+        if position_ids is not None:
+            raise NotImplementedError("explicit position_ids are not implemented for the autoregressive forward")
+        B, L = int(inputs.shape[0]), int(inputs.shape[1])
+        key_lens = self.lengths_from_mask(attention_mask)
+        if key_lens is None:
+            raise NotImplementedError("the autoregressive forward takes prefix masks only (ones followed by zeros, at least "
+                                      "one position per sequence): what sample() builds")
+        lens = self._lengths(seq_lengths, B)
+        h = self.prepare()
+        x = np.ascontiguousarray(inputs.detach().cpu().numpy().astype(np.float32))
+        out = np.empty_like(x)
+        _binding.check(_binding.load().fd_ar_forward(h, _binding.ptr(x), _binding.ptr(lens), _binding.ptr(key_lens), B, L,
+                                                     _binding.ptr(out)))
+        return torch.from_numpy(out).to(inputs.device)
+
+    __call__ = forward
+
+    def sample(self, seed_angles: torch.Tensor, seq_lengths: torch.Tensor, num_seed: int = 2,
+               pbar: bool = True) -> List[torch.Tensor]:
+        """``sample`` of the reference (modelling.py:864-893): the first ``num_seed`` positions of ``seed_angles``
+        [B, L, F] are kept, position i = num_seed .. max(seq_lengths) - 1 becomes row i of the forward over the positions
+        before it (row i itself enters with what ``seed_angles`` holds there), and sequence b is returned trimmed to
+        ``seq_lengths[b]``.  The whole loop is one device call (``fd_ar_sample``), so there is nothing for ``pbar`` to show;
+        it is accepted for the signature."""
+        assert torch.all(seed_angles[:, :num_seed, :] <= torch.pi)
+        assert torch.all(seed_angles[:, :num_seed, :] >= -torch.pi)
+        assert seed_angles.ndim == 3 and seed_angles.shape[2] == self.n_inputs
+        B, L = int(seed_angles.shape[0]), int(seed_angles.shape[1])
+        if num_seed < 1:
+            raise ValueError("num_seed must be at least 1: without a seed the first position would see masked keys only")
+        lens = self._lengths(seq_lengths, B)
+        if int(lens.max()) > L:
+            raise ValueError(f"max(seq_lengths)={int(lens.max())} exceeds the {L} positions of seed_angles")
+        h = self.prepare()
+        x = np.ascontiguousarray(seed_angles.detach().cpu().numpy().astype(np.float32))
+        out = np.empty_like(x)
+        _binding.check(_binding.load().fd_ar_sample(h, _binding.ptr(x), _binding.ptr(lens), B, L, int(num_seed), _binding.ptr(out)))
+        ret = torch.from_numpy(out).to(seed_angles.device)
+        return [ret[i, :n, :] for i, n in enumerate(lens.tolist())]
+
+
 # The reference's sampling entry points take the Lightning subclass or the base
 # class interchangeably; only the base (inference) surface exists here.
 BertForDiffusion = BertForDiffusionBase
+BertForAutoregressive = BertForAutoregressiveBase

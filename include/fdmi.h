@@ -44,6 +44,7 @@ extern "C" {
 /*    fd_forward_t (one timestep per sequence), fd_loss_terms and fd_denoise_loss (the denoising loss of a fixed checkpoint)
  *    are additive in the same way: no existing entry or struct changed, the version stays 7 */
 /*    fd_backbone_clashes and fd_lddt (integer pair counts over the atoms of a structure) are additive too */
+/*    fd_ar_forward and fd_ar_sample (the autoregressive baseline) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -173,6 +174,24 @@ int fd_forward(fd_model* m, const float* x, int t, const int32_t* lens, int B, i
  * behind the embedding LayerNorm (modelling.py:472), the only place the timestep enters; every later launch is the one
  * fd_forward makes for the same (B, L).  With all t[b] equal the result has fd_forward's bits.  Both precisions. */
 int fd_forward_t(fd_model* m, const float* x, const int32_t* t, const int32_t* lens, int B, int L, float* eps_out);
+
+/* ---- the autoregressive baseline: BertForAutoregressiveBase.forward / .sample (modelling.py:807-893).  The same network and the
+ * same weights; the time embedding is reused as an embedding of the sequence's target LENGTH: the row seq_lengths[b] of the table
+ * fd_finalize was given (0 <= seq_lengths[b] < T; the coefficient rows are not read) is added to the input Linear's output BEFORE
+ * the position embedding and the embeddings LayerNorm, and nothing is added behind it.  FD_PREC_F16X3 only (FD_E_UNSUPPORTED on an
+ * FD_PREC_F32 model).  Host buffers; every argument is checked before the first device call.
+ *
+ * fd_ar_forward: out[B][L][F] = forward(x, prefix mask of key_lens, seq_lengths), 1 <= key_lens[b] <= L unmasked keys per
+ * sequence; the other keys get the additive -10000 and every one of the L positions is computed as a query, like fd_forward_t. */
+int fd_ar_forward(fd_model* m, const float* x, const int32_t* seq_lengths, const int32_t* key_lens, int B, int L, float* out);
+
+/* fd_ar_sample: the rollout.  ret = seed[B][L][F]; for i = num_seed .. max(seq_lengths) - 1: the keys 0 .. i-1 of every sequence
+ * are unmasked and ret[:, i] = forward(ret, that mask, seq_lengths)[:, i].  out[B][L][F] = the final ret: positions < num_seed
+ * come back bit for bit, positions >= max(seq_lengths) keep the seed, and the caller trims sequence b to seq_lengths[b].  Row i
+ * enters step i with whatever the seed holds there; nothing is wrapped.  Needs 1 <= num_seed (without a seed the first row would
+ * see masked keys only: FD_E_INVALID) and max(seq_lengths) <= L.  Step i runs over the rows 0 .. i only -- later rows are masked
+ * keys and unread queries -- so the loop costs half the reference's; one upload, one download, no host synchronisation between. */
+int fd_ar_sample(fd_model* m, const float* seed, const int32_t* seq_lengths, int B, int L, int num_seed, float* out);
 
 /* The same forward with what the reference's forward also honours (modelling.py:434-452, :464-467) and the sampler never produces:
  *   key_mask      uint8[B][L], 1 = attend, 0 = masked key, ANY pattern (NULL: every key is attended to); masked keys get the
