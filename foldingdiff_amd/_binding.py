@@ -77,6 +77,10 @@ _SIGNATURES = {
     "fd_lddt": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P]),
     "fd_loss_terms": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, _P, _P]),
     "fd_denoise_loss": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P]),
+    "fd_loss_terms_ex": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P]),
+    "fd_pairwise_dist": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "fd_denoise_loss_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P,
+                                     _P, _P, _P, _P]),
     "fd_shift_trim_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fd_test_wrap": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, _P]),
     "fd_test_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),

@@ -106,6 +106,8 @@ struct Workspace {
   int* t_seq = nullptr;  // [B] one timestep per sequence (fd_forward_t, fd_denoise_loss)
   float* loss_in = nullptr;     // fd_denoise_loss's one upload: x0 | noise ([B][L][F] each) | keep | spread | t | lens ([B] each); allocated on first use
   double* loss_sums = nullptr;  // [B][F], with it
+  float* loss_ex_in = nullptr;  // fd_denoise_loss_ex's one upload: x0 | noise | corrupted ([B][L][F] each) | keep | spread | coef | t | lens ([B] each)
+  double* loss_ex_out = nullptr;  // its one download, in 8-byte words: sums | turns ([B][F] each) | pair_sums | pairs ([B] each)
   UpdateDyn* dyn = nullptr;
   // row-image path (fdmi_kernels.h): images, per-(sequence, head) q / k / v^T, the token-row table
   bool img = false;
@@ -123,7 +125,7 @@ struct Workspace {
     if (graph) (void)hipGraphExecDestroy(graph);
     graph = nullptr;
     for (void* p : {(void*)x, (void*)eps, (void*)h, (void*)qkv, (void*)ctx, (void*)a, (void*)tmp, (void*)g, (void*)z,
-                    (void*)lens, (void*)t_dev, (void*)t_seq, (void*)loss_in, (void*)loss_sums, (void*)dyn, (void*)himg, (void*)aimg, (void*)cimg, (void*)gimg,
+                    (void*)lens, (void*)t_dev, (void*)t_seq, (void*)loss_in, (void*)loss_sums, (void*)loss_ex_in, (void*)loss_ex_out, (void*)dyn, (void*)himg, (void*)aimg, (void*)cimg, (void*)gimg,
                     (void*)qbuf, (void*)kbuf, (void*)vbuf, (void*)trash, (void*)rowinfo, (void*)seq_row0, (void*)nrow,
                     (void*)dims, (void*)flag, (void*)kmask, (void*)pos_ids})
       if (p) (void)hipFree(p);
@@ -1663,6 +1665,92 @@ int fd_denoise_loss(fd_model* m, const float* x0, const float* noise, const int3
   if (eps_out) HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return check_flag(m);
+}
+
+int fd_denoise_loss_ex(fd_model* m, const float* x0, const float* corrupted, const float* noise, const int32_t* t,
+                       const float* keep, const float* spread, const int32_t* lens, int B, int L, int kind, float beta_ang,
+                       float beta_lin, const float* coef, const int32_t* feat_idx, double* sums, int64_t* turns,
+                       double* pair_sums, int64_t* pairs, float* corrupted_out, float* eps_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x0 || !noise || !t || !lens || !sums) return fail(FD_E_INVALID, "null argument");
+  if ((keep == nullptr) != (spread == nullptr)) return fail(FD_E_INVALID, "null argument: keep and spread go together");
+  if (!corrupted && !keep) return fail(FD_E_INVALID, "null argument: without corrupted the device noises x0 and needs keep and spread");
+  if (kind != 0 && kind != 1) return fail(FD_E_INVALID, "kind=%d: 0 (smooth_l1) or 1 (l1)", kind);
+  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
+  const int F = m->cfg.n_features;
+  if (pair_sums) {
+    if (!keep) return fail(FD_E_INVALID, "null argument: the pairwise term needs keep and spread");
+    if (!pairs || !feat_idx) return fail(FD_E_INVALID, "null argument: the pairwise term needs pairs and feat_idx");
+    if (int rc = check_pairwise(keep, coef, feat_idx, B, L, F)) return rc;
+  }
+  if (int rc = check_t_seq(m, t, B)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  Workspace& w = m->ws;
+  const size_t n = (size_t)B * L * F, nb = (size_t)B, nf = nb * F;
+  hipStream_t s = m->stream;
+  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
+  if (!w.loss_ex_in) HIP_TRY(hipMalloc((void**)&w.loss_ex_in, (3 * n + 5 * nb) * 4));
+  if (!w.loss_ex_out) HIP_TRY(hipMalloc((void**)&w.loss_ex_out, (2 * nf + 2 * nb) * 8));
+  // ONE upload, staged back to back as fd_denoise_loss does (a blocking copy from pageable memory of this frame)
+  std::vector<float> stage(3 * n + 5 * nb, 0.f);
+  memcpy(stage.data(), x0, n * 4);
+  memcpy(stage.data() + n, noise, n * 4);
+  if (corrupted) memcpy(stage.data() + 2 * n, corrupted, n * 4);
+  float* vec = stage.data() + 3 * n;
+  if (keep) {
+    memcpy(vec, keep, nb * 4);
+    memcpy(vec + nb, spread, nb * 4);
+  }
+  if (coef) memcpy(vec + 2 * nb, coef, nb * 4);
+  memcpy(vec + 3 * nb, t, nb * 4);
+  memcpy(vec + 4 * nb, lens, nb * 4);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(w.loss_ex_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
+  const float *x0_dev = w.loss_ex_in, *noise_dev = x0_dev + n, *corrupted_dev = x0_dev + 2 * n, *keep_dev = x0_dev + 3 * n,
+              *spread_dev = keep_dev + nb, *coef_dev = keep_dev + 2 * nb;
+  HIP_TRY(hipMemcpyAsync(w.t_seq, keep_dev + 3 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.lens, keep_dev + 4 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
+  if (!corrupted) {  // q(x_t | x_0) on the device, with the wrap flags fd_finalize was given
+    launch_q_sample(x0_dev, noise_dev, keep_dev, spread_dev, w.x, B, L, F, m->angle_mask, s);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemcpyAsync(w.x, corrupted_dev, n * 4, hipMemcpyDeviceToDevice, s));
+  }
+  if (int rc = prepare_rows(m, s, 0)) return rc;
+  StepMode mode{};
+  mode.forward_only = true;
+  mode.t_seq = w.t_seq;
+  if (int rc = run_step(m, s, mode)) return rc;
+  double* sums_dev = w.loss_ex_out;
+  long long* turns_dev = (long long*)(w.loss_ex_out + nf);
+  double* pair_sums_dev = w.loss_ex_out + 2 * nf;
+  long long* pairs_dev = (long long*)(w.loss_ex_out + 2 * nf + nb);
+  launch_loss_terms_ex(w.eps, noise_dev, w.lens, B, L, F, m->angle_mask, kind, beta_ang, beta_lin, sums_dev, nullptr,
+                       turns ? turns_dev : nullptr, s);
+  HIP_TRY(hipGetLastError());
+  if (pair_sums) {  // the forward's x_t and prediction stay where they are: w.x, w.eps
+    const PairwiseFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5]};
+    launch_pairwise_dist(x0_dev, w.x, w.eps, keep_dev, spread_dev, coef ? coef_dev : nullptr, w.lens, B, L, F, fx, pair_sums_dev,
+                         pairs_dev, nullptr, s);
+    HIP_TRY(hipGetLastError());
+  }
+  // ONE download of what was asked for: sums [| turns] [| pair_sums | pairs] are contiguous up to the last one wanted
+  const size_t words = pair_sums ? 2 * nf + 2 * nb : turns ? 2 * nf : nf;
+  std::vector<double> back(words);
+  HIP_TRY(hipMemcpyAsync(back.data(), w.loss_ex_out, words * 8, hipMemcpyDeviceToHost, s));
+  if (corrupted_out) HIP_TRY(hipMemcpyAsync(corrupted_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
+  if (eps_out) HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (int rc = check_flag(m)) return rc;
+  memcpy(sums, back.data(), nf * 8);
+  if (turns) memcpy(turns, back.data() + nf, nf * 8);
+  if (pair_sums) {
+    memcpy(pair_sums, back.data() + 2 * nf, nb * 8);
+    memcpy(pairs, back.data() + 2 * nf + nb, nb * 8);
+  }
+  return FD_OK;
 }
 
 int fd_forward_ex(fd_model* m, const float* x, int t, const uint8_t* key_mask, const int32_t* position_ids, int B, int L,

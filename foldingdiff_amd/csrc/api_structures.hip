@@ -1,5 +1,5 @@
 // C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, clash_lddt.hip) and of
-// the loss arithmetic on its own (loss.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// the loss arithmetic on its own (loss.hip, loss_variants.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
 #include <vector>
@@ -159,6 +159,54 @@ int fd_loss_terms(int device_id, const float* pred, const float* target, const i
                             float* terms_dev = d.out(1);
                             launch_loss_terms(d.in(0), d.in(1), d.in(2), B, L, F, angle_mask, beta_ang, beta_lin, d.out(0),
                                               terms ? terms_dev : nullptr, nullptr);
+                          });
+}
+
+int fd_loss_terms_ex(int device_id, const float* pred, const float* target, const int32_t* lens, int B, int L, int F,
+                     const uint8_t* is_angle, int kind, float beta_ang, float beta_lin, double* sums, float* terms,
+                     int64_t* turns) {
+  if (!pred || !target || !lens || !is_angle || !sums) return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if (F < 1 || F > 32) return fail(FD_E_INVALID, "F=%d outside [1, 32]", F);
+  if (kind != 0 && kind != 1) return fail(FD_E_INVALID, "kind=%d: 0 (smooth_l1) or 1 (l1)", kind);
+  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
+  if ((long long)B * L * F > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * F = %lld elements, at most 2^31 - 1", (long long)B * L * F);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  unsigned angle_mask = 0;
+  for (int f = 0; f < F; ++f)
+    if (is_angle[f]) angle_mask |= 1u << f;
+  const size_t n = (size_t)B * L * F;
+  return device_roundtrip(device_id, {{pred, n * 4}, {target, n * 4}, {lens, (size_t)B * 4}},
+                          {{sums, (size_t)B * F * 8}, {terms, terms ? n * 4 : 4}, {turns, turns ? (size_t)B * F * 8 : 8}},
+                          [&](const RoundtripBufs& d) {
+                            float* terms_dev = d.out(1);
+                            long long* turns_dev = d.out(2);
+                            launch_loss_terms_ex(d.in(0), d.in(1), d.in(2), B, L, F, angle_mask, kind, beta_ang, beta_lin, d.out(0),
+                                                 terms ? terms_dev : nullptr, turns ? turns_dev : nullptr, nullptr);
+                          });
+}
+
+int fd_pairwise_dist(int device_id, const float* angles, const float* corrupted, const float* pred, const float* keep,
+                     const float* spread, const float* coef, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                     double* sums, int64_t* pairs, double* ca_out) {
+  if (!angles || !corrupted || !pred || !keep || !spread || !lens || !feat_idx || !sums || !pairs)
+    return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if (F < 6 || F > 32) return fail(FD_E_INVALID, "F=%d outside [6, 32]", F);
+  if (int rc = check_pairwise(keep, coef, feat_idx, B, L, F)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  const PairwiseFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5]};
+  const size_t n = (size_t)B * L * F, nb = (size_t)B;
+  static const float no_coef = 1.f;
+  return device_roundtrip(device_id,
+                          {{angles, n * 4}, {corrupted, n * 4}, {pred, n * 4}, {keep, nb * 4}, {spread, nb * 4},
+                           {coef ? coef : &no_coef, coef ? nb * 4 : 4}, {lens, nb * 4}},
+                          {{sums, nb * 8}, {pairs, nb * 8}, {ca_out, ca_out ? nb * 2 * L * 3 * 8 : 8}},
+                          [&](const RoundtripBufs& d) {
+                            const float* coef_dev = d.in(5);
+                            double* ca_dev = d.out(2);
+                            launch_pairwise_dist(d.in(0), d.in(1), d.in(2), d.in(3), d.in(4), coef ? coef_dev : nullptr, d.in(6),
+                                                 B, L, F, fx, d.out(0), d.out(1), ca_out ? ca_dev : nullptr, nullptr);
                           });
 }
 

@@ -344,6 +344,25 @@ void launch_q_sample(const float* x0, const float* eps, const float* keep, const
 void launch_loss_terms(const float* pred, const float* target, const int* lens, int B, int L, int F, unsigned angle_mask,
                        float beta_ang, float beta_lin, double* sums, float* terms, hipStream_t s);
 
+// ---- the rest of _get_loss_terms (loss_variants.hip)
+// launch_loss_terms with a loss kind (0: the smooth-L1 pair, 1: "l1" -- losses.radian_l1_loss, losses.py:12-26, for the
+// features of angle_mask and F.l1_loss for the others; the betas are then unused) and, when non-null, turns[b][f] = the
+// sum over l < lens[b] of trunc(|pred| / pi) for the features of angle_mask, 0 for the others (losses.py:57-61).
+// kind 0 gives launch_loss_terms' bits.
+void launch_loss_terms_ex(const float* pred, const float* target, const int* lens, int B, int L, int F, unsigned angle_mask,
+                          int kind, float beta_ang, float beta_lin, double* sums, float* terms, long long* turns,
+                          hipStream_t s);
+// The pairwise-distance term (modelling.py:616-677), one workgroup per sequence, L <= kPairwiseMaxLen: sums[b] = the fp64
+// sum over the lens[b] (lens[b] - 1) / 2 CA pairs of coef[b] * (d_denoised - d_clean)^2 (float32 terms; coef null: 1),
+// pairs[b] = their number, ca_out (or null) [B][2][L][3] the CA traces of the clean and of the denoised angles.
+constexpr int kPairwiseMaxLen = 128;
+struct PairwiseFeatures {
+  int phi, psi, omega, tau, ang_ca_c_n, ang_c_n_ca;   // columns of "phi", "psi", "omega", "tau", "CA:C:1N", "C:1N:1CA"
+};
+void launch_pairwise_dist(const float* angles, const float* corrupted, const float* pred, const float* keep, const float* spread,
+                          const float* coef, const int* lens, int B, int L, int F, const PairwiseFeatures& fx, double* sums,
+                          long long* pairs, double* ca_out, hipStream_t s);
+
 void launch_build_rows(const int* lens, int B, int L, int packed, int cap, int* seq_row0, int* nrow, int2* rowinfo,
                        int* dims, hipStream_t s);
 // fp32 [src_rows][K] -> image [rows][K/32] (rows >= src_rows are zero rows), value * scale = hi + lo; and back

@@ -184,4 +184,20 @@ inline int check_atom_cap(const int32_t* lens, int n, int per) {
   return FD_OK;
 }
 
+// the pairwise-distance term's own arguments (fd_pairwise_dist, fd_denoise_loss_ex): the padded length the kernel takes,
+// six distinct feature columns, a denoising divisor that is not 0, positive weights
+inline int check_pairwise(const float* keep, const float* coef, const int32_t* feat_idx, int B, int L, int F) {
+  if (L > FDMI_PAIRWISE_MAX_LEN) return fail(FD_E_UNSUPPORTED, "L=%d: the pairwise-distance term takes L <= %d", L, FDMI_PAIRWISE_MAX_LEN);
+  for (int i = 0; i < 6; ++i) {
+    if (feat_idx[i] < 0 || feat_idx[i] >= F) return fail(FD_E_INVALID, "feat_idx[%d]=%d outside [0, %d)", i, feat_idx[i], F);
+    for (int j = 0; j < i; ++j)
+      if (feat_idx[j] == feat_idx[i]) return fail(FD_E_INVALID, "feat_idx[%d]=%d repeats feat_idx[%d]", i, feat_idx[i], j);
+  }
+  for (int b = 0; b < B; ++b) {
+    if (!(keep[b] != 0.f) || !std::isfinite(keep[b])) return fail(FD_E_INVALID, "keep[%d]=%g must be finite and not 0", b, (double)keep[b]);
+    if (coef && !(coef[b] > 0.f)) return fail(FD_E_INVALID, "coef[%d]=%g must be > 0", b, (double)coef[b]);
+  }
+  return FD_OK;
+}
+
 }  // namespace fdmi

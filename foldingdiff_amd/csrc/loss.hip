@@ -7,6 +7,7 @@
 // reference's CPU statements.  The sums are fp64 in a fixed order, so they do not depend on the run or on where a
 // sequence sits in the batch; the means over the batch are the host's business (they need the count of all positions).
 #include "fdmi_kernels.h"
+#include "smooth_l1_term.h"
 #include "wrap_pi.h"
 
 namespace fdmi {
@@ -32,16 +33,6 @@ void launch_q_sample(const float* x0, const float* eps, const float* keep, const
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(q_sample_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x0, eps, keep, spread, x_t, n, L * F, F,
                      angle_mask);
-}
-
-// d = target - pred (wrapped for an angle);  |d| < beta ? 0.5 * d^2 / beta : |d| - 0.5 * beta.  torch evaluates
-// 0.5 * (d ** 2) / beta as ((0.5 * (d * d)) / f32(beta)) and abs_d - 0.5 * beta with the python product rounded to float32;
-// F.smooth_l1_loss's 0.5 * z * z / beta differs only in where the exact halving happens.
-__device__ __forceinline__ float smooth_l1_term(float pred, float target, bool angular, float beta, float half_beta) {
-  float d = __fsub_rn(target, pred);
-  if (angular) d = wrap_pi(d);
-  const float ad = fabsf(d);
-  return ad < beta ? __fdiv_rn(__fmul_rn(0.5f, __fmul_rn(d, d)), beta) : __fsub_rn(ad, half_beta);
 }
 
 // One workgroup per sequence.  Thread tid owns feature tid % F and the positions tid / F, tid / F + P, ... (P = 256 / F

@@ -26,13 +26,13 @@ import os
 import re
 import shutil
 from pathlib import Path
-from typing import Dict, List, Literal, Optional, Sequence
+from typing import Dict, List, Literal, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from . import _binding, beta_schedules
-from .datasets import FEATURE_SET_NAMES_TO_ANGULARITY
+from .datasets import FEATURE_SET_NAMES_TO_ANGULARITY, FEATURE_SET_NAMES_TO_FEATURE_NAMES
 
 DEFAULT_PRECISION = "f16x3"  # fp16 hi/lo split on the fp16 matrix cores: fp32-class accuracy (measured <= the exact-fp32 kernels' error), > 2x faster
 TIME_ENCODING = Literal["gaussian_fourier", "sinusoidal"]
@@ -165,6 +165,11 @@ class BertForDiffusionBase:
             raise NotImplementedError(f"hidden_act={config.hidden_act!r}: only exact-erf 'gelu' is implemented")
         self.time_encoding = time_encoding
         self.decoder = decoder
+        # what loss_terms reports (BertForDiffusion's loss / circle_reg / use_pairwise_dist_loss, modelling.py:492-543);
+        # from_dir reads them from training_args.json, and all three may be set afterwards
+        self.loss_key = "smooth_l1"
+        self.circle_lambda = 0.0
+        self.use_pairwise_dist_loss = 0.0
         # arithmetic of the GEMM kernels: "f32" (exact fp32 MFMA) or "f16x3" (fp16 hi/lo split
         # on the fp16 MFMA, fp32-class error); env FOLDINGDIFF_AMD_PRECISION overrides the default
         self.precision = os.environ.get("FOLDINGDIFF_AMD_PRECISION", DEFAULT_PRECISION)
@@ -214,6 +219,13 @@ class BertForDiffusionBase:
         tkey = "time_encoding" if "time_encoding" in train_args else "seq_len_encoding"
         model = cls(config=config, ft_is_angular=ft_is_angular, time_encoding=train_args[tkey],
                     decoder=train_args["decoder"], **kwargs)
+        # the loss the run was trained with (bin/train.py's loss, circle_reg, use_pdist_loss): what loss_terms reports
+        model.set_loss(train_args.get("loss", "smooth_l1"), train_args.get("circle_reg", 0.0),
+                       train_args.get("use_pdist_loss", 0.0))
+        from . import losses
+        if losses.pairwise_is_on(model.use_pairwise_dist_loss) and "ft_names" not in kwargs:
+            # the pairwise term finds its six angles by name (bin/train.py hands the dataset's names to the model)
+            model.ft_names = list(FEATURE_SET_NAMES_TO_FEATURE_NAMES[train_args["angles_definitions"]])
         ckpt_name = None
         subfolder = f"best_by_{best_by}"
         if load_weights:
@@ -387,6 +399,19 @@ class BertForDiffusionBase:
         opts[name] = int(value)
         return prev
 
+    def set_loss(self, loss: str = "smooth_l1", circle_reg: float = 0.0, use_pdist_loss=0.0):
+        """The three loss settings of ``BertForDiffusion.__init__`` as ``loss_key``, ``circle_lambda`` and
+        ``use_pairwise_dist_loss`` (a scalar, or ``(min_coef, max_coef, max_timesteps)``; a JSON list becomes the tuple),
+        with the reference's autocorrection of the legacy key "radian_l1_smooth"."""
+        from . import losses
+        loss = losses.LOSS_AUTOCORRECT.get(loss, loss)
+        if loss not in losses.LOSS_KINDS:
+            raise ValueError(f"loss={loss!r}; expected one of {sorted(losses.LOSS_KINDS)}")
+        self.loss_key = loss
+        self.circle_lambda = float(circle_reg)
+        self.use_pairwise_dist_loss = tuple(use_pdist_loss) if isinstance(use_pdist_loss, (list, tuple)) else float(use_pdist_loss)
+        return self
+
     # ------------------------------------------------------------------ forward
     @staticmethod
     def lengths_from_mask(attention_mask: torch.Tensor) -> Optional[np.ndarray]:
@@ -515,15 +540,102 @@ class BertForDiffusionBase:
             return sums, {k: v for k, v in (("corrupted", corrupted), ("eps", eps)) if v is not None}
         return sums
 
+    def denoise_loss_ex(self, x0: torch.Tensor, noise: torch.Tensor, timestep: torch.Tensor, attention_mask: torch.Tensor,
+                        corrupted: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                        spread: Optional[torch.Tensor] = None, kind: Union[int, str] = 0, return_turns: bool = False,
+                        pairwise: bool = False, coef=None, return_corrupted: bool = False, return_eps: bool = False) -> Dict[str, np.ndarray]:
+        """``fd_denoise_loss_ex``: ``denoise_loss_sums`` with the loss kind (0 / "smooth_l1", 1 / "l1"), the turn counts
+        of the circle penalty and the pairwise-distance sums of the forward's own prediction -- one upload, one small
+        download, the prediction never leaves the device.  ``x0`` is the clean batch; ``corrupted`` None: the device
+        noises it with ``keep`` / ``spread``.  ``pairwise=True`` needs ``keep`` / ``spread`` and a feature set with the
+        six angles; ``coef``: None, a scalar, or one weight per sequence.  Returns a dict: ``"sums"`` float64 [B, F],
+        and where asked for ``"turns"`` int64 [B, F], ``"pair_sums"`` float64 [B] with ``"pairs"`` int64 [B],
+        ``"corrupted"`` / ``"eps"`` float32 [B, L, F]."""
+        from . import losses
+        kind = losses.LOSS_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if (keep is None) != (spread is None):
+            raise ValueError("keep and spread go together")
+        if corrupted is None and keep is None:
+            raise ValueError("without corrupted the device noises x0 and needs keep and spread")
+        if pairwise and keep is None:
+            raise ValueError("the pairwise-distance term needs keep and spread (sqrt_alphas_cumprod_t, sqrt_one_minus_alphas_cumprod_t)")
+        idx = losses.pairwise_columns(self.ft_names) if pairwise else None
+        xa, t, lens = self._batch_arrays(x0, timestep, attention_mask)
+        B, L, F = xa.shape
+        f32 = lambda v: np.ascontiguousarray(torch.as_tensor(v).detach().cpu().numpy().astype(np.float32))  # noqa: E731
+        na = f32(noise)
+        ca = None if corrupted is None else f32(corrupted)
+        if na.shape != xa.shape or (ca is not None and ca.shape != xa.shape):
+            raise ValueError(f"noise {na.shape} / corrupted {None if ca is None else ca.shape} != x0 {xa.shape}")
+        vec = lambda v: None if v is None else np.ascontiguousarray(f32(v).reshape(-1))  # noqa: E731
+        ka, sa, wa = vec(keep), vec(spread), vec(coef)
+        if ka is not None and (ka.shape != (B,) or sa.shape != (B,)):
+            raise ValueError(f"keep / spread must hold one value per sequence ({B})")
+        if wa is not None:
+            wa = np.ascontiguousarray(np.broadcast_to(wa, (B,))) if wa.size == 1 else wa
+            if wa.shape != (B,):
+                raise ValueError(f"coef must be a scalar or hold one value per sequence ({B})")
+        out = {"sums": np.empty((B, F), np.float64)}
+        if return_turns:
+            out["turns"] = np.empty((B, F), np.int64)
+        if pairwise:
+            out["pair_sums"], out["pairs"] = np.empty(B, np.float64), np.empty(B, np.int64)
+        if return_corrupted:
+            out["corrupted"] = np.empty_like(xa)
+        if return_eps:
+            out["eps"] = np.empty_like(xa)
+        P = _binding.ptr
+        _binding.check(_binding.load().fd_denoise_loss_ex(
+            self._ensure_handle(), P(xa), P(ca), P(na), P(t), P(ka), P(sa), P(lens), B, L, kind, float(losses.ANGULAR_BETA),
+            float(losses.NONANGULAR_BETA), P(wa if pairwise else None), P(idx), P(out["sums"]), P(out.get("turns")),
+            P(out.get("pair_sums")), P(out.get("pairs")), P(out.get("corrupted")), P(out.get("eps"))))
+        return out
+
     def loss_terms(self, batch) -> torch.Tensor:
-        """``BertForDiffusion._get_loss_terms(batch)`` (modelling.py:553-604) with loss "smooth_l1", no circle penalty and
-        no pairwise-distance loss: a [F] tensor, per feature the mean over all unmasked positions of the batch of the
-        smooth-L1 term of the predicted against the known noise.  ``batch`` has the reference's keys ``corrupted``, ``t``,
-        ``known_noise`` and ``attn_mask`` (a prefix mask).  One device call: forward with one timestep per sequence, terms
-        and per-sequence fp64 sums; the mean is taken here in float64 (the reference's is a float32 ``torch.mean``)."""
-        sums = self.denoise_loss_sums(batch["corrupted"], batch["known_noise"], batch["t"], batch["attn_mask"])
+        """``BertForDiffusion._get_loss_terms(batch)`` (modelling.py:553-679) under the model's ``loss_key``,
+        ``circle_lambda`` and ``use_pairwise_dist_loss``: a float64 [F] tensor, per feature the mean over all unmasked
+        positions of the batch of the term of the predicted against the known noise (smooth L1 or l1; angular features
+        wrapped), plus ``circle_lambda`` times the mean turn count of the predicted noise for angular features under
+        "smooth_l1"; with the pairwise-distance term on, [F + 1]: the last entry is the mean over all CA pairs of the
+        batch of the weighted squared distance difference between the chains of the clean and of the denoised angles
+        (NaN when no sequence has two residues).  ``batch`` has the reference's keys ``corrupted``, ``t``,
+        ``known_noise`` and ``attn_mask`` (a prefix mask), and with the pairwise term also ``angles``, ``lengths``,
+        ``sqrt_alphas_cumprod_t`` and ``sqrt_one_minus_alphas_cumprod_t``.  One device call: forward with one timestep
+        per sequence, terms and per-sequence fp64 sums; the means are taken here in float64 (the reference's are float32
+        ``torch.mean``s)."""
+        from . import losses
+        pairwise = losses.pairwise_is_on(self.use_pairwise_dist_loss)
+        circle = self.loss_key == "smooth_l1" and self.circle_lambda > 0
+        need = ["corrupted", "t", "known_noise", "attn_mask"]
+        if pairwise:
+            need += ["angles", "lengths", "sqrt_alphas_cumprod_t", "sqrt_one_minus_alphas_cumprod_t"]
+        missing = [k for k in need if k not in batch]
+        if missing:
+            raise KeyError(f"loss_terms: the batch lacks {missing}" + (" (needed by the pairwise-distance loss)" if pairwise else ""))
         count = int((batch["attn_mask"].detach().cpu() != 0).sum())
-        return torch.from_numpy(sums.sum(axis=0) / count)
+        if self.loss_key == "smooth_l1" and not circle and not pairwise:
+            sums = self.denoise_loss_sums(batch["corrupted"], batch["known_noise"], batch["t"], batch["attn_mask"])
+            return torch.from_numpy(sums.sum(axis=0) / count)
+        if pairwise:
+            lens = self.lengths_from_mask(batch["attn_mask"])
+            given = torch.as_tensor(batch["lengths"]).detach().cpu().reshape(-1).numpy()
+            if lens is None or not np.array_equal(lens, given):
+                raise ValueError("batch['lengths'] and the prefix mask batch['attn_mask'] disagree")
+            coef = losses.pairwise_coef(self.use_pairwise_dist_loss, batch["t"].detach().cpu())
+            out = self.denoise_loss_ex(batch["angles"], batch["known_noise"], batch["t"], batch["attn_mask"],
+                                       corrupted=batch["corrupted"], keep=batch["sqrt_alphas_cumprod_t"],
+                                       spread=batch["sqrt_one_minus_alphas_cumprod_t"], kind=self.loss_key, return_turns=circle,
+                                       pairwise=True, coef=coef)
+        else:
+            out = self.denoise_loss_ex(batch["corrupted"], batch["known_noise"], batch["t"], batch["attn_mask"],
+                                       corrupted=batch["corrupted"], kind=self.loss_key, return_turns=circle)
+        terms = out["sums"].sum(axis=0) / count
+        if circle:
+            terms = terms + self.circle_lambda * (out["turns"].sum(axis=0).astype(np.float64) / count)
+        if pairwise:
+            n_pairs = int(out["pairs"].sum())
+            terms = np.append(terms, out["pair_sums"].sum() / n_pairs if n_pairs else np.nan)
+        return torch.from_numpy(terms)
 
 
 class BertForAutoregressiveBase(BertForDiffusionBase):

@@ -45,6 +45,8 @@ extern "C" {
  *    are additive in the same way: no existing entry or struct changed, the version stays 7 */
 /*    fd_backbone_clashes and fd_lddt (integer pair counts over the atoms of a structure) are additive too */
 /*    fd_ar_forward and fd_ar_sample (the autoregressive baseline) are additive too */
+/*    fd_loss_terms_ex, fd_pairwise_dist and fd_denoise_loss_ex (the "l1" loss, the circle penalty and the pairwise-distance
+ *    term of the denoising loss) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -409,7 +411,8 @@ int fd_lddt(int device_id, const float* model, const float* ref, const int32_t* 
             int64_t* counts_out /* [n_pairs][2]: conserved, total */, int32_t* res_counts_out /* NULL or [n_res][2] */);
 
 /* ---- the denoising loss of a fixed checkpoint (forward only): BertForDiffusion._get_loss_terms / validation_step
- * (foldingdiff/modelling.py:553-604, :720-751) with loss = "smooth_l1", circle_reg = 0 and no pairwise-distance loss ----
+ * (foldingdiff/modelling.py:553-604, :720-751) with loss = "smooth_l1", circle_reg = 0 and no pairwise-distance loss; the other
+ * settings follow below (fd_loss_terms_ex, fd_pairwise_dist, fd_denoise_loss_ex) ----
  *
  * Per-position terms of pred against target (host float32 [B][L][F]) and their per-sequence sums.  Feature f with
  * is_angle[f] != 0: losses.radian_smooth_l1_loss (losses.py:29-55), d = wrap(target - pred) to [-pi, pi), term =
@@ -439,6 +442,57 @@ int fd_loss_terms(int device_id, const float* pred, const float* target, const i
 int fd_denoise_loss(fd_model* m, const float* x0, const float* noise, const int32_t* t, const float* keep, const float* spread,
                     const int32_t* lens, int B, int L, float beta_ang, float beta_lin, double* sums /* [B][F] */,
                     float* corrupted_out /* or NULL */, float* eps_out /* or NULL */);
+
+/* ---- the rest of _get_loss_terms (modelling.py:553-679): loss = "l1", the circle penalty, the pairwise-distance term ----
+ *
+ * fd_loss_terms with a loss kind and the turn counts of the circle penalty.
+ *   kind    0: the smooth-L1 pair, fd_loss_terms' bits.  1: "l1" -- losses.radian_l1_loss (losses.py:12-26) for angular
+ *           features: target % 2 pi, pred % 2 pi (torch's remainder: the divisor's sign), d = target - pred,
+ *           d = (d + pi) % 2 pi - pi, |d|; F.l1_loss, |target - pred|, for the others.  The betas must be > 0 and are
+ *           unused with kind 1.
+ *   turns   NULL, or int64 [B][F]: the sum over positions l < lens[b] of trunc(|pred| / pi) (a float32 division) for
+ *           angular features, 0 for the others.  radian_smooth_l1_loss's circle penalty (losses.py:57-61) adds
+ *           circle_penalty * sum_b turns[b][f] / sum_b lens[b] to feature f's value.
+ * Model-free and synchronous, like fd_loss_terms. */
+int fd_loss_terms_ex(int device_id, const float* pred, const float* target, const int32_t* lens, int B, int L, int F,
+                     const uint8_t* is_angle, int kind, float beta_ang, float beta_lin, double* sums /* [B][F] */,
+                     float* terms /* [B][L][F] or NULL */, int64_t* turns /* [B][F] or NULL */);
+
+/* The pairwise-distance term (modelling.py:616-677, losses.pairwise_dist_loss, nerf.nerf_build_batch) of one batch.
+ *   angles, corrupted, pred   host float32 [B][L][F]: the clean x_0, x_t and the predicted noise
+ *   keep, spread   float32 [B], keep[b] != 0: denoised = (corrupted - spread[b] * pred) / keep[b], float32 in that order,
+ *                  not wrapped
+ *   coef           NULL (1), or float32 [B], each > 0: the weight of sequence b's pairs
+ *   lens           int32 [B], 1 <= lens[b] <= L;  L <= FDMI_PAIRWISE_MAX_LEN
+ *   feat_idx       int32 [6]: the columns of phi, psi, omega, tau, CA:C:1N, C:1N:1CA, each in [0, F), no two equal
+ * Two chains per sequence, of the clean and of the denoised angles: float32 trigonometry, float64 frames from the float64
+ * seed atoms, bond lengths 1.34 / 1.46 / 1.54.  Over the lens[b] (lens[b] - 1) / 2 pairs of the first lens[b] CA atoms:
+ * both distances rounded to float32, term = coef[b] * (d_denoised - d_clean)^2 in float32.
+ *   sums     float64 [B]: the terms of sequence b summed in fp64 in a fixed order (0 for lens[b] = 1)
+ *   pairs    int64 [B]: lens[b] (lens[b] - 1) / 2.  The reference's value is sum_b sums[b] / sum_b pairs[b].
+ *   ca_out   NULL, or float64 [B][2][L][3]: the CA traces of the clean ([b][0]) and of the denoised angles, 0 past lens[b]
+ * Model-free and synchronous; the result does not depend on the other sequences of the call. */
+#define FDMI_PAIRWISE_MAX_LEN 128
+int fd_pairwise_dist(int device_id, const float* angles, const float* corrupted, const float* pred, const float* keep,
+                     const float* spread, const float* coef, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                     double* sums /* [B] */, int64_t* pairs /* [B] */, double* ca_out /* [B][2][L][3] or NULL */);
+
+/* fd_denoise_loss with the three settings: one upload, the forward with one timestep per sequence, the terms, the turn
+ * counts and the pairwise sums where asked for, one small download.
+ *   x0          host float32 [B][L][F], the clean features (batch["angles"]), always
+ *   corrupted   NULL: the device noises x0 with keep / spread as fd_denoise_loss does;  or float32 [B][L][F], x_t as given
+ *   noise, t, lens, beta_ang, beta_lin, sums, corrupted_out, eps_out   as fd_denoise_loss'
+ *   keep, spread   float32 [B], both or neither; required with corrupted = NULL and with the pairwise term (keep[b] != 0)
+ *   kind, turns    as fd_loss_terms_ex'
+ *   pair_sums   NULL (the pairwise term is off), or float64 [B] as fd_pairwise_dist's sums, of the forward's own
+ *               prediction; then pairs (int64 [B]) and feat_idx (int32 [6]) are required, coef is optional and L <=
+ *               FDMI_PAIRWISE_MAX_LEN
+ * With kind 0, turns = NULL and pair_sums = NULL, sums has fd_denoise_loss's bits. */
+int fd_denoise_loss_ex(fd_model* m, const float* x0, const float* corrupted, const float* noise, const int32_t* t,
+                       const float* keep, const float* spread, const int32_t* lens, int B, int L, int kind, float beta_ang,
+                       float beta_lin, const float* coef, const int32_t* feat_idx, double* sums /* [B][F] */,
+                       int64_t* turns /* [B][F] or NULL */, double* pair_sums /* [B] or NULL */, int64_t* pairs /* [B] or NULL */,
+                       float* corrupted_out /* or NULL */, float* eps_out /* or NULL */);
 
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
