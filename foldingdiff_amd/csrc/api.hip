@@ -118,6 +118,7 @@ struct Workspace {
   int *seq_row0 = nullptr, *nrow = nullptr, *dims = nullptr, *flag = nullptr;
   unsigned char* kmask = nullptr;  // [B][L] explicit key mask of fd_forward_ex (allocated on first use)
   int* pos_ids = nullptr;          // [B][L] explicit position ids of fd_forward_ex (allocated on first use)
+  int grids[3] = {0, 0, 0};  // x-grid of the latest launch of seq_attn16 | seq_attn | ffn16 on this workspace (fd_debug_read "grids")
   hipGraphExec_t graph = nullptr;
   StepPlan graph_plan;  // the launch sequence `graph` was captured with
   uint64_t last_use = 0;
@@ -170,6 +171,7 @@ struct fd_model {
   unsigned long long* stamps = nullptr;  // debug cycle stamps (FDMI_STAMPS=1): gemm [5][8][64][6], attention [4][64][8], fused attention [4][64][16]
   int debug_stop = 0;  // row-image path: stop a step after this many launches (debug dumps; 0 = off)
   int debug_layer = 0; // layer whose scales fd_debug_read uses
+  int debug_grid = 0;  // > 0: at most this many workgroups for the persistent fused kernels (tests of their item-to-item code; 0 = off)
   int split_qkv = 0; // row-image path: 1 = q | k and v^T as two launches even when one would do (A/B, tests)
   int varlen = 0;    // row-image path: only the first lens[b] positions of a sequence are token rows
   int fuse_attn = -1;  // row-image path: q | k | v projection + attention as ONE kernel per sequence: -1 auto (seq_attn16.hip for padded rows
@@ -937,7 +939,7 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode, const StepPla
       a.r_scale = lw.s_k / lw.demb_s.scale;
       a.stamps = stamps_at(kStampSeqAttn);
       bool launched = false;
-      PROF(KC_SEQ_ATTN, launched = fused16 ? launch_seq_attn16(a, s) : launch_seq_attn(a, s));
+      PROF(KC_SEQ_ATTN, launched = fused16 ? launch_seq_attn16(a, s, m->debug_grid, &w.grids[0]) : launch_seq_attn(a, s, m->debug_grid, &w.grids[1]));
       if (!launched)
         return fused16 ? fail(FD_E_HIP, "the fused projection + attention kernel could not be launched (%d bytes of LDS per workgroup)", 160256)
                        : fail(FD_E_HIP, "the 32-row fused projection + attention kernel could not be launched (%d bytes of LDS per workgroup)", 160 * 1024);
@@ -1015,7 +1017,7 @@ int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode, const StepPla
       a.resid_inv = 1.0f / lw.s_a; a.out_scale = s_next; a.eps = c.ln_eps;
       a.stamps = stamps_at(kStampFfn);
       bool launched = false;
-      PROF(fused_tail ? KC_TAIL : KC_FFN, launched = launch_ffn16(a, d, s));
+      PROF(fused_tail ? KC_TAIL : KC_FFN, launched = launch_ffn16(a, d, s, m->debug_grid, &w.grids[2]));
       if (!launched) return fail(FD_E_HIP, "the fused feed-forward kernel could not be launched");
       if (stop_after(fused_tail ? 3 : 2)) return done();
       continue;
@@ -1463,6 +1465,11 @@ int fd_set_option(fd_model* m, const char* name, int value) {
     m->debug_stop = value;
   }
   else if (n == "debug_layer") m->debug_layer = value;
+  else if (n == "debug_grid") {
+    const int v = value > 0 ? value : 0;
+    if (m->debug_grid != v) drop_workspaces(m);  // captured graphs hold the other grid
+    m->debug_grid = v;
+  }
   else return fail(FD_E_INVALID, "unknown option '%s'", name);
   return FD_OK;
 }
@@ -2078,6 +2085,10 @@ int fd_debug_read(fd_model* m, const char* name, float* out, int64_t n_floats) {
     if (n_floats < 2 * need) return fail(FD_E_INVALID, "fd_debug_read(stamps): need %lld floats (uint64 view)", 2 * need);
     if (!m->stamps) return fail(FD_E_STATE, "no stamps were recorded (FDMI_STAMPS=1)");
     HIP_TRY(hipMemcpy(out, m->stamps, need * 8, hipMemcpyDeviceToHost));
+    return FD_OK;
+  } else if (nm == "grids") {
+    if (n_floats < 3) return fail(FD_E_INVALID, "fd_debug_read(grids): need 3 floats");
+    for (int i = 0; i < 3; ++i) out[i] = (float)w.grids[i];
     return FD_OK;
   } else if (nm == "rowinfo") {
     need = 2LL * w.cap;

@@ -21,9 +21,10 @@ float max_abs(const float* p, size_t n) {
 // Test hook plumbing of the row-image GEMM: fp32 host operands -> images (scales chosen from the data exactly as
 // fd_finalize chooses them from weight bounds) -> production kernel -> fp32.  The images are zero-filled before the
 // conversion kernels write them: their padding rows must hold zeros.
-// epilogue: EPI_IMG_BIAS | EPI_IMG_GELU | EPI_IMG_LN
+// epilogue: EPI_IMG_BIAS | EPI_IMG_GELU | EPI_IMG_LN; tail: GemmImgArgs::tail (1 = the instantiation that cuts an incomplete last
+// round into row slices -- the hook's ragged row counts exercise them; 0 = whole tiles only: valid for every shape, same bits)
 int img_gemm_hook(int epilogue, const float* A, const float* W, const float* bias, const float* resid, const float* gamma,
-                  const float* beta, float eps, float* C, int M, int N, int K) {
+                  const float* beta, float eps, float* C, int M, int N, int K, int tail = 1) {
   if (N % 32 || K % 32) return fail(FD_E_UNSUPPORTED, "row-image GEMM: N=%d and K=%d must be multiples of 32", N, K);
   if (epilogue == EPI_IMG_LN && N > 384) return fail(FD_E_UNSUPPORTED, "LN-fused GEMM: N=%d > 384", N);
   DeviceBufs bufs;
@@ -85,7 +86,7 @@ int img_gemm_hook(int epilogue, const float* A, const float* W, const float* bia
     out_scale = scale_for(dense_bound(W, bias, 0, N, K, in_l2));
   }
   g.out_scale = out_scale;
-  g.tail = 1;  // (the hook's ragged row counts exercise the tail slices)
+  g.tail = tail;
   launch_gemm_img(epilogue, g, (int)rows, nullptr);
   launch_img_to_f32(dOi, dC, rows, N, out_scale, nullptr);
   HIP_TRY(hipGetLastError());
@@ -128,13 +129,15 @@ int fd_test_wrap(int device_id, int which, const float* in, int64_t n, float* ou
 int fd_test_gemm(int device_id, int precision, int epilogue, const float* A, const float* W, const float* bias,
                  const float* resid, float* C, int M, int N, int K) {
   if (!A || !W || !bias || !C || M < 1 || N < 1 || K < 16 || K % 32) return fail(FD_E_INVALID, "bad argument");
+  const int tail = epilogue & FD_TEST_GEMM_WHOLE_TILES ? 0 : 1;
+  epilogue &= ~FD_TEST_GEMM_WHOLE_TILES;
   if (epilogue < EPI_BIAS || epilogue > EPI_BIAS_RESID || (epilogue == EPI_BIAS_RESID && !resid))
     return fail(FD_E_INVALID, "bad epilogue");
   HIP_TRY(hipSetDevice(device_id));
   if (precision == FD_PREC_F16X3) {
     if (epilogue == EPI_BIAS_RESID)
       return fail(FD_E_UNSUPPORTED, "the row-image path has no unfused residual epilogue (LayerNorm is always fused): use fd_test_gemm_ln");
-    return img_gemm_hook(epilogue == EPI_BIAS_GELU ? EPI_IMG_GELU : EPI_IMG_BIAS, A, W, bias, nullptr, nullptr, nullptr, 0.f, C, M, N, K);
+    return img_gemm_hook(epilogue == EPI_BIAS_GELU ? EPI_IMG_GELU : EPI_IMG_BIAS, A, W, bias, nullptr, nullptr, nullptr, 0.f, C, M, N, K, tail);
   }
   DeviceBufs bufs;
   float *dA, *dW, *db, *dC;

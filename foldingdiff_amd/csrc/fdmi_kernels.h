@@ -236,11 +236,12 @@ struct SeqAttnArgs {
   unsigned long long* stamps;  // null, or [4 waves][64 slots][16] cycle stamps of workgroup 0 (debug)
 };
 bool seq_attn_supported(int d_model, int n_heads, int L, int maxpos);
-bool launch_seq_attn(const SeqAttnArgs& p, hipStream_t s);   // false: the LDS opt-in or the launch was refused
+// grid_cap > 0: at most that many workgroups (launch_common.h persistent_grid; option "debug_grid"); *grid_used: the x-grid launched
+bool launch_seq_attn(const SeqAttnArgs& p, hipStream_t s, int grid_cap = 0, int* grid_used = nullptr);   // false: the LDS opt-in or the launch was refused
 // seq_attn16.hip (round 6): the same operation with 16-row waves, two per SIMD (v_mfma_f32_16x16x32_f16); wimg = [head][k32 step][tile]
 // [unit][row][16 B] (api.hip: upload_seq_attn16_weights); any L <= 128, padded or packed rows.  false: the launch failed.
 bool seq_attn16_supported(int d_model, int n_heads, int L, int maxpos);
-bool launch_seq_attn16(const SeqAttnArgs& p, hipStream_t s);
+bool launch_seq_attn16(const SeqAttnArgs& p, hipStream_t s, int grid_cap = 0, int* grid_used = nullptr);
 
 // ffn16.hip (round 6): BertIntermediate + GELU + BertOutput (dense + residual + LayerNorm) of 128 token rows per pass in ONE kernel;
 // the intermediate never reaches HBM.  wimg = ONE stream of 16 KiB stages in consumption order (api.hip: upload_ffn16_weights).
@@ -276,7 +277,7 @@ struct FfnArgs {
   unsigned long long* stamps;  // null, or [8 waves][16 passes][16] cycle stamps of workgroup 0 (debug)
 };
 bool ffn16_supported(int d_model, int d_ff);
-bool launch_ffn16(const FfnArgs& p, int d_model, hipStream_t s);   // false: the launch failed
+bool launch_ffn16(const FfnArgs& p, int d_model, hipStream_t s, int grid_cap = 0, int* grid_used = nullptr);   // false: the launch failed (grid_cap, grid_used: as launch_seq_attn)
 
 struct EmbedImgArgs {
   const float* x;              // [B][L][F]

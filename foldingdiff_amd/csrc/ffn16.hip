@@ -562,14 +562,14 @@ __global__ __launch_bounds__(64 * NW) void ffn16_kernel(FfnArgs p) {
 }
 
 template <int NKT, bool TAIL>
-static bool launch(const FfnArgs& p, hipStream_t s) {
+static bool launch(const FfnArgs& p, hipStream_t s, int grid_cap, int* grid_used) {
   constexpr int SMEM = off_p(NKT) + (TAIL ? 8 : 5) * 32 * NKT * 4;
   static LdsOptIn lds;
   if (!lds({reinterpret_cast<const void*>(&ffn16_kernel<NKT, TAIL, false>), reinterpret_cast<const void*>(&ffn16_kernel<NKT, TAIL, true>)}, SMEM))
     return false;
-  int grid = cu_count();
-  if (grid > p.panels) grid = p.panels;
+  const int grid = persistent_grid(p.panels, grid_cap);
   if (grid <= 0) return true;
+  if (grid_used) *grid_used = grid;
   if (p.stamps) hipLaunchKernelGGL((ffn16_kernel<NKT, TAIL, true>), dim3(grid), dim3(64 * NW), SMEM, s, p);
   else hipLaunchKernelGGL((ffn16_kernel<NKT, TAIL, false>), dim3(grid), dim3(64 * NW), SMEM, s, p);
   return hipGetLastError() == hipSuccess;
@@ -580,9 +580,9 @@ static bool launch(const FfnArgs& p, hipStream_t s) {
 // d_model 384 / 192 (every released configuration / the reference's test fixture) with the intermediate size 2 d_model they all have
 bool ffn16_supported(int d_model, int d_ff) { return (d_model == 384 || d_model == 192) && d_ff == 2 * d_model; }
 
-bool launch_ffn16(const FfnArgs& p, int d_model, hipStream_t s) {
-  if (p.cimg) return d_model == 384 ? ffn::launch<12, true>(p, s) : ffn::launch<6, true>(p, s);
-  return d_model == 384 ? ffn::launch<12, false>(p, s) : ffn::launch<6, false>(p, s);
+bool launch_ffn16(const FfnArgs& p, int d_model, hipStream_t s, int grid_cap, int* grid_used) {
+  if (p.cimg) return d_model == 384 ? ffn::launch<12, true>(p, s, grid_cap, grid_used) : ffn::launch<6, true>(p, s, grid_cap, grid_used);
+  return d_model == 384 ? ffn::launch<12, false>(p, s, grid_cap, grid_used) : ffn::launch<6, false>(p, s, grid_cap, grid_used);
 }
 
 }  // namespace fdmi

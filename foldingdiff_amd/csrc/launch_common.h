@@ -21,6 +21,15 @@ inline int cu_count() {
   return cached[dev];
 }
 
+// x-grid of a persistent launch whose workgroups walk `items` (blockIdx.x, + gridDim.x, ...): one workgroup per CU and none without
+// an item.  cap > 0 (option "debug_grid", tests only) lowers the workgroup count, so that a few items already give every workgroup
+// several; it never raises it.
+inline int persistent_grid(int items, int cap) {
+  int grid = cu_count();
+  if (cap > 0 && cap < grid) grid = cap;
+  return items < grid ? items : grid;
+}
+
 // Opt-in of a kernel's instantiations to `bytes` of dynamic LDS, once per device (the attribute is per device).  One static
 // instance per launch wrapper.  Tri-state: a runtime that refuses the opt-in must surface as a refused launch on every
 // call, not as a silent no-op launch, and is not asked again.

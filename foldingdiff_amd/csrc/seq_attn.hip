@@ -913,12 +913,12 @@ __global__ __launch_bounds__(256) void seq_attn_kernel(SeqAttnArgs p) {
 }
 
 template <int NKT>
-static bool launch(const SeqAttnArgs& p, hipStream_t s) {
+static bool launch(const SeqAttnArgs& p, hipStream_t s, int grid_cap, int* grid_used) {
   static LdsOptIn lds;  // (the whole LDS of a CU)
   if (!lds({reinterpret_cast<const void*>(&seq_attn_kernel<NKT, false>), reinterpret_cast<const void*>(&seq_attn_kernel<NKT, true>)}, SMEM))
     return false;
-  int grid = cu_count();
-  if (grid > p.B) grid = p.B;
+  const int grid = persistent_grid(p.B, grid_cap);
+  if (grid_used) *grid_used = grid;
   if (p.stamps) hipLaunchKernelGGL((seq_attn_kernel<NKT, true>), dim3(grid), dim3(256), SMEM, s, p);
   else hipLaunchKernelGGL((seq_attn_kernel<NKT, false>), dim3(grid), dim3(256), SMEM, s, p);
   return hipGetLastError() == hipSuccess;
@@ -932,8 +932,8 @@ bool seq_attn_supported(int d_model, int n_heads, int L, int maxpos) {
   return (d_model == 384 || d_model == 192) && n_heads * 32 == d_model && L > 96 && L <= 128 && maxpos <= 128 && maxpos >= L;
 }
 
-bool launch_seq_attn(const SeqAttnArgs& p, hipStream_t s) {
-  return p.H == 12 ? sa::launch<12>(p, s) : sa::launch<6>(p, s);
+bool launch_seq_attn(const SeqAttnArgs& p, hipStream_t s, int grid_cap, int* grid_used) {
+  return p.H == 12 ? sa::launch<12>(p, s, grid_cap, grid_used) : sa::launch<6>(p, s, grid_cap, grid_used);
 }
 
 }  // namespace fdmi

@@ -745,12 +745,12 @@ __global__ __launch_bounds__(64 * NW) void seq_attn16_kernel(SeqAttnArgs p) {
 }
 
 template <int NKT>
-static bool launch(const SeqAttnArgs& p, hipStream_t s) {
+static bool launch(const SeqAttnArgs& p, hipStream_t s, int grid_cap, int* grid_used) {
   static LdsOptIn lds;
   if (!lds({reinterpret_cast<const void*>(&seq_attn16_kernel<NKT, false>), reinterpret_cast<const void*>(&seq_attn16_kernel<NKT, true>)}, SMEM))
     return false;
-  int grid = cu_count();
-  if (grid > p.B) grid = p.B;
+  const int grid = persistent_grid(p.B, grid_cap);
+  if (grid_used) *grid_used = grid;
   if (p.stamps) hipLaunchKernelGGL((seq_attn16_kernel<NKT, true>), dim3(grid), dim3(64 * NW), SMEM, s, p);
   else hipLaunchKernelGGL((seq_attn16_kernel<NKT, false>), dim3(grid), dim3(64 * NW), SMEM, s, p);
   return hipGetLastError() == hipSuccess;
@@ -764,8 +764,8 @@ bool seq_attn16_supported(int d_model, int n_heads, int L, int maxpos) {
   return (d_model == 384 || d_model == 192) && n_heads * 32 == d_model && L >= 1 && L <= 128 && maxpos <= 128 && maxpos >= L;
 }
 
-bool launch_seq_attn16(const SeqAttnArgs& p, hipStream_t s) {
-  return p.H == 12 ? s16::launch<12>(p, s) : s16::launch<6>(p, s);
+bool launch_seq_attn16(const SeqAttnArgs& p, hipStream_t s, int grid_cap, int* grid_used) {
+  return p.H == 12 ? s16::launch<12>(p, s, grid_cap, grid_used) : s16::launch<6>(p, s, grid_cap, grid_used);
 }
 
 }  // namespace fdmi

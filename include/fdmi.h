@@ -153,7 +153,11 @@ void fd_destroy(fd_model* m);
  *   "split_qkv"  FD_PREC_F16X3: 1 = project q | k and v^T in two launches even when n_heads % 6 == 0 would allow one
  *                (A/B measurements, tests); 0 (default).
  *   "debug_stop" n > 0: a step returns after its first n launches (FD_PREC_F16X3; stage-by-stage comparison with
- *                fd_debug_read, scripts/debug_img.py); "debug_layer": which encoder layer fd_debug_read sees. */
+ *                fd_debug_read, scripts/debug_img.py); "debug_layer": which encoder layer fd_debug_read sees.
+ *   "debug_grid" n > 0: the persistent fused kernels (fused projection + attention, both forms; fused feed-forward / layer tail) run
+ *                on at most n workgroups, so that a batch of a few sequences already gives every workgroup several items (tests of
+ *                their item-to-item code; the automatic kernel choices do not look at it); <= 0 (default): one per compute unit.
+ *                A change drops the workspaces and their captured graphs.  Same bits at every value. */
 int fd_set_option(fd_model* m, const char* name, int value);
 
 /* 1 if option "fuse_attn" = 1 (or 2, when that is the current value) runs the fused projection + attention kernel for batches of
@@ -497,7 +501,11 @@ int fd_denoise_loss_ex(fd_model* m, const float* x0, const float* corrupted, con
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
  * kernels of the given precision (epilogue: 0 bias, 1 bias+GELU, 2 bias+residual).  Host buffers,
- * K % 32 == 0.  Used by tests/ to measure kernel error against fp64 in isolation. */
+ * K % 32 == 0.  Used by tests/ to measure kernel error against fp64 in isolation.
+ * FD_PREC_F16X3: epilogue | FD_TEST_GEMM_WHOLE_TILES launches the tile kernel's whole-tiles instantiation (the one a step
+ * takes when its tiles fill whole rounds of the workgroups) instead of the row-slice capable one; valid for every shape, same
+ * bits.  Ignored by FD_PREC_F32. */
+#define FD_TEST_GEMM_WHOLE_TILES 0x100
 int fd_test_gemm(int device_id, int precision, int epilogue, const float* A, const float* W, const float* bias,
                  const float* resid, float* C, int M, int N, int K);
 
@@ -550,6 +558,8 @@ int fd_check_finite(fd_model* m);
 /* Debug / test aid (FD_PREC_F16X3 only): copy an intermediate of the last step back as float32.  `name`: "h", "a",
  * "ctx", "g", "g_head", "h_out" ([rows rounded up to 128][width]) or "q", "k", "v" ([B][H][padded L][32]); scales are
  * those of layer option "debug_layer"; option "debug_stop" = n ends a step after n kernel launches.
+ * "grids": 3 floats, the x-grid of the most recent launch of the 16-row fused attention, the 32-row fused attention and the fused
+ * feed-forward / layer tail on the current workspace (0: none since the workspace was made); see option "debug_grid".
  * "rowinfo": (sequence, position) of every token row as floats, (-1, -1) for a row that is none ([rows rounded up to 128][2]).
  * "scales": the power-of-two scales fd_finalize chose for layer "debug_layer" (which must name a layer), 21 floats; needs a
  * model finalized with FD_PREC_F16X3 and no workspace:

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Repeat one small configuration of scripts/ffn16_check.py many times (races show as occasional wrong rows).  Env: D (192 / 384), N."""
+"""Repeat one small configuration of scripts/ffn16_check.py many times (races show as occasional wrong rows).  Env: D (192 / 384), N.
+The bounded form of this, with a different input per run and half of the runs on one workgroup, is part of `pytest -m gpu`:
+tests/test_persistent_passes_gpu.py::test_a_sequence_of_different_inputs_through_one_handle."""
 import os
 import sys
 
