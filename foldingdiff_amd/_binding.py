@@ -81,6 +81,11 @@ _SIGNATURES = {
     "fd_pairwise_dist": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "fd_denoise_loss_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P,
                                      _P, _P, _P, _P]),
+    "fd_hist_columns": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "fd_noise_minmax": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_uint64, C.c_uint64,
+                                  C.c_int64, _P, _P, _P]),
+    "fd_noise_hist": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_uint64, C.c_uint64,
+                                C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "fd_shift_trim_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fd_test_wrap": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, _P]),
     "fd_test_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),

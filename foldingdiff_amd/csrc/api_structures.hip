@@ -1,7 +1,8 @@
-// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, clash_lddt.hip) and of
-// the loss arithmetic on its own (loss.hip, loss_variants.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, clash_lddt.hip), of
+// the loss arithmetic on its own (loss.hip, loss_variants.hip) and of the angle histograms (angle_stats.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "fdmi_kernels.h"
@@ -257,6 +258,135 @@ int fd_lddt(int device_id, const float* model, const float* ref, const int32_t* 
                             launch_lddt(d.in(0), d.in(1), d.in(2), d.in(3), n_pairs, A, radius, thr, d.out(0),
                                         res_counts_out ? res_dev : nullptr, nullptr);
                           });
+}
+
+// rows of non-decreasing edges without a NaN: edges[rows][nbins + 1]
+static int check_edges(const double* edges, long long rows, int nbins) {
+  for (long long r = 0; r < rows; ++r) {
+    const double* e = edges + r * (nbins + 1);
+    for (int i = 0; i <= nbins; ++i)
+      if (std::isnan(e[i]) || (i > 0 && e[i] < e[i - 1]))
+        return fail(FD_E_INVALID, "edges: row %lld is decreasing or NaN at %d (%g)", r, i, e[i]);
+  }
+  return FD_OK;
+}
+
+static int check_hist_shape(int64_t N, int F, int nbins) {
+  if (N < 1 || N > 0x7fffffffLL) return fail(FD_E_INVALID, "N=%lld outside [1, 2^31 - 1]", (long long)N);
+  if (F < 1 || F > 32) return fail(FD_E_INVALID, "F=%d outside [1, 32]", F);
+  if (nbins < 1 || nbins > FDMI_HIST_MAX_BINS) return fail(FD_E_INVALID, "nbins=%d outside [1, %d]", nbins, FDMI_HIST_MAX_BINS);
+  return FD_OK;
+}
+
+int fd_hist_columns(int device_id, const float* values, int64_t N, int F, const double* edges, int nbins,
+                    const uint8_t* rows_valid, int64_t* counts, int64_t* outside) {
+  if (!values || !edges || !counts || !outside) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_hist_shape(N, F, nbins)) return rc;
+  if (int rc = check_edges(edges, F, nbins)) return rc;
+  const size_t n = (size_t)N, nf = (size_t)F, count_bytes = nf * nbins * 8;
+  static const uint8_t no_rows = 1;
+  return device_roundtrip(device_id, {{values, n * nf * 4}, {edges, nf * (nbins + 1) * 8}, {rows_valid ? rows_valid : &no_rows, rows_valid ? n : 1}},
+                          {{counts, count_bytes}, {outside, nf * 8}}, [&](const RoundtripBufs& d) -> hipError_t {
+                            unsigned long long *counts_dev = d.out(0), *outside_dev = d.out(1);
+                            const unsigned char* valid_dev = d.in(2);
+                            if (hipError_t e = hipMemsetAsync(counts_dev, 0, count_bytes, nullptr)) return e;
+                            if (hipError_t e = hipMemsetAsync(outside_dev, 0, nf * 8, nullptr)) return e;
+                            launch_hist_columns(d.in(0), N, F, d.in(1), nbins, rows_valid ? valid_dev : nullptr, counts_dev,
+                                                outside_dev, nullptr);
+                            return hipSuccess;
+                          });
+}
+
+// the arguments fd_noise_minmax and fd_noise_hist share
+static int check_noise(const float* x0, int64_t N, int F, const uint8_t* is_angle, const float* scale, const float* keep,
+                       const float* spread, int T, const int32_t* timesteps, int nT, const float* eps_in, const float* cmp_in,
+                       unsigned* angle_mask) {
+  if (!x0 || !is_angle || !scale || !keep || !spread || !timesteps) return fail(FD_E_INVALID, "null argument");
+  if ((eps_in == nullptr) != (cmp_in == nullptr)) return fail(FD_E_INVALID, "null argument: eps_in and cmp_in go together");
+  if (int rc = check_hist_shape(N, F, 1)) return rc;
+  if (T < 1) return fail(FD_E_INVALID, "T=%d must be >= 1", T);
+  if (nT < 1 || nT > 65535) return fail(FD_E_INVALID, "nT=%d outside [1, 65535]", nT);
+  for (int i = 0; i < nT; ++i)
+    if (timesteps[i] < 0 || timesteps[i] >= T) return fail(FD_E_INVALID, "timesteps[%d]=%d outside [0, %d)", i, timesteps[i], T);
+  for (int t = 0; t < T; ++t)
+    if (!std::isfinite(keep[t]) || !std::isfinite(spread[t]))
+      return fail(FD_E_INVALID, "keep[%d]=%g spread[%d]=%g must be finite", t, (double)keep[t], t, (double)spread[t]);
+  *angle_mask = 0;
+  for (int f = 0; f < F; ++f) {
+    if (!std::isfinite(scale[f])) return fail(FD_E_INVALID, "scale[%d]=%g must be finite", f, (double)scale[f]);
+    if (is_angle[f]) *angle_mask |= 1u << f;
+  }
+  return FD_OK;
+}
+
+int fd_noise_minmax(int device_id, const float* x0, int64_t N, int F, const uint8_t* is_angle, const float* scale,
+                    const float* keep, const float* spread, int T, const int32_t* timesteps, int nT, uint64_t seed_eps,
+                    uint64_t seed_cmp, int64_t row_offset, const float* eps_in, const float* cmp_in, float* minmax_out) {
+  unsigned angle_mask = 0;
+  if (int rc = check_noise(x0, N, F, is_angle, scale, keep, spread, T, timesteps, nT, eps_in, cmp_in, &angle_mask)) return rc;
+  if (!minmax_out) return fail(FD_E_INVALID, "null argument");
+  const size_t n = (size_t)N * F, draws = (size_t)nT * n * 4, keys = (size_t)nT * 2 * F;
+  static const float no_draws = 0.f;
+  std::vector<uint32_t> mins(keys), maxs(keys);
+  const int rc = device_roundtrip(
+      device_id,
+      {{x0, n * 4}, {scale, (size_t)F * 4}, {keep, (size_t)T * 4}, {spread, (size_t)T * 4}, {timesteps, (size_t)nT * 4},
+       {eps_in ? eps_in : &no_draws, eps_in ? draws : 4}, {cmp_in ? cmp_in : &no_draws, cmp_in ? draws : 4}},
+      {{mins.data(), keys * 4}, {maxs.data(), keys * 4}}, [&](const RoundtripBufs& d) -> hipError_t {
+        unsigned *mins_dev = d.out(0), *maxs_dev = d.out(1);
+        const float *eps_dev = d.in(5), *cmp_dev = d.in(6);
+        if (hipError_t e = hipMemsetAsync(mins_dev, 0xff, keys * 4, nullptr)) return e;
+        if (hipError_t e = hipMemsetAsync(maxs_dev, 0, keys * 4, nullptr)) return e;
+        const NoiseArgs a{d.in(0), d.in(1), d.in(2), d.in(3), d.in(4), eps_in ? eps_dev : nullptr, cmp_in ? cmp_dev : nullptr,
+                          (long long)N, (long long)row_offset, F, 4, angle_mask, seed_eps, seed_cmp};
+        launch_noise_minmax(a, nT, mins_dev, maxs_dev, nullptr);
+        return hipSuccess;
+      });
+  if (rc != FD_OK) return rc;
+  // the kernel's order-preserving keys back to floats
+  auto value = [](uint32_t key) {
+    const uint32_t bits = (key & 0x80000000u) ? key ^ 0x80000000u : ~key;
+    float v;
+    memcpy(&v, &bits, 4);
+    return v;
+  };
+  for (size_t k = 0; k < keys; ++k) {
+    minmax_out[2 * k] = value(mins[k]);
+    minmax_out[2 * k + 1] = value(maxs[k]);
+  }
+  return FD_OK;
+}
+
+int fd_noise_hist(int device_id, const float* x0, int64_t N, int F, const uint8_t* is_angle, const float* scale,
+                  const float* keep, const float* spread, int T, const int32_t* timesteps, int nT, uint64_t seed_eps,
+                  uint64_t seed_cmp, int64_t row_offset, const float* eps_in, const float* cmp_in, const double* edges,
+                  int nbins, int64_t* counts, int64_t* outside, float* x_t_out, float* cmp_out, float* eps_out) {
+  unsigned angle_mask = 0;
+  if (int rc = check_noise(x0, N, F, is_angle, scale, keep, spread, T, timesteps, nT, eps_in, cmp_in, &angle_mask)) return rc;
+  if (!edges || !counts || !outside) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_hist_shape(N, F, nbins)) return rc;
+  if (int rc = check_edges(edges, (long long)nT * F, nbins)) return rc;
+  const size_t n = (size_t)N * F, draws = (size_t)nT * n * 4, slabs = (size_t)nT * 2 * F, count_bytes = slabs * nbins * 8;
+  static const float no_draws = 0.f;
+  return device_roundtrip(
+      device_id,
+      {{x0, n * 4}, {scale, (size_t)F * 4}, {keep, (size_t)T * 4}, {spread, (size_t)T * 4}, {timesteps, (size_t)nT * 4},
+       {eps_in ? eps_in : &no_draws, eps_in ? draws : 4}, {cmp_in ? cmp_in : &no_draws, cmp_in ? draws : 4},
+       {edges, (size_t)nT * F * (nbins + 1) * 8}},
+      {{counts, count_bytes}, {outside, slabs * 8}, {x_t_out, x_t_out ? draws : 4}, {cmp_out, cmp_out ? draws : 4},
+       {eps_out, eps_out ? draws : 4}},
+      [&](const RoundtripBufs& d) -> hipError_t {
+        unsigned long long *counts_dev = d.out(0), *outside_dev = d.out(1);
+        float *x_t_dev = d.out(2), *cmp_out_dev = d.out(3), *eps_out_dev = d.out(4);
+        const float *eps_dev = d.in(5), *cmp_dev = d.in(6);
+        if (hipError_t e = hipMemsetAsync(counts_dev, 0, count_bytes, nullptr)) return e;
+        if (hipError_t e = hipMemsetAsync(outside_dev, 0, slabs * 8, nullptr)) return e;
+        const NoiseArgs a{d.in(0), d.in(1), d.in(2), d.in(3), d.in(4), eps_in ? eps_dev : nullptr, cmp_in ? cmp_dev : nullptr,
+                          (long long)N, (long long)row_offset, F, noise_features_per_group(nbins), angle_mask, seed_eps, seed_cmp};
+        launch_noise_hist(a, nT, d.in(7), nbins, counts_dev, outside_dev, x_t_out ? x_t_dev : nullptr,
+                          cmp_out ? cmp_out_dev : nullptr, eps_out ? eps_out_dev : nullptr, nullptr);
+        return hipSuccess;
+      });
 }
 
 }  // extern "C"

@@ -364,6 +364,35 @@ void launch_pairwise_dist(const float* angles, const float* corrupted, const flo
                           const float* coef, const int* lens, int B, int L, int F, const PairwiseFeatures& fx, double* sums,
                           long long* pairs, double* ca_out, hipStream_t s);
 
+// ---- histogram statistics of angle columns (angle_stats.hip; the rules are in its header)
+// counts[F][nbins] / outside[F] += np.histogram of column f of values[N][F] (rows with rows_valid[r] == 0 skipped when
+// rows_valid is non-null) against edges[f][0..nbins]; the totals must be zero before the launch.  F <= 32, nbins <= 4096.
+void launch_hist_columns(const float* values, long long N, int F, const double* edges, int nbins,
+                         const unsigned char* rows_valid, unsigned long long* counts, unsigned long long* outside,
+                         hipStream_t s);
+// features a workgroup of launch_noise_* holds in LDS at this nbins: 4, 2 or 1
+int noise_features_per_group(int nbins);
+struct NoiseArgs {
+  const float* x0;         // [N][F]
+  const float* scale;      // [F]: the variance scale of the draws
+  const float* keep;       // [T] sqrt_alphas_cumprod
+  const float* spread;     // [T] sqrt_one_minus_alphas_cumprod
+  const int* timesteps;    // [nT], each in [0, T)
+  const float* eps_in;     // [nT][N][F], the noising draws as given (already scaled and wrapped), or null: Philox
+  const float* cmp_in;     // the same for the comparison draws; null exactly when eps_in is
+  long long N, row_offset; // Philox sequence of row r = r + row_offset
+  int F, G;                // G = noise_features_per_group(nbins) (the min / max pass holds nothing in LDS: 4)
+  unsigned angle_mask;
+  unsigned long long seed_eps, seed_cmp;
+};
+// pass 1: mins / maxs [nT][2][F] as order-preserving keys (host: memset to 0xff / 0 before, decode after), [.][0] of x_t,
+// [.][1] of the comparison draw
+void launch_noise_minmax(const NoiseArgs& a, int nT, unsigned* mins, unsigned* maxs, hipStream_t s);
+// pass 2: counts[nT][2][F][nbins] / outside[nT][2][F] += the histograms of the same two streams against
+// edges[nT][F][nbins + 1]; x_t_out / cmp_out / eps_out: null, or [nT][N][F]
+void launch_noise_hist(const NoiseArgs& a, int nT, const double* edges, int nbins, unsigned long long* counts,
+                       unsigned long long* outside, float* x_t_out, float* cmp_out, float* eps_out, hipStream_t s);
+
 void launch_build_rows(const int* lens, int B, int L, int packed, int cap, int* seq_row0, int* nrow, int2* rowinfo,
                        int* dims, hipStream_t s);
 // fp32 [src_rows][K] -> image [rows][K/32] (rows >= src_rows are zero rows), value * scale = hi + lo; and back

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "fdmi_kernels.h"
+#include "philox_normal.h"
 #include "wrap_pi.h"
 
 namespace fdmi {
@@ -356,40 +357,7 @@ void launch_layernorm(const float* x, const float* gamma, const float* beta, flo
 #undef FD_LN
 }
 
-// ---------------------------------------------------------- Philox4x32-10
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// N(0,1) for feature f of token (global sequence `seq`, position l) at step t.
-// Counter = (seq lo, seq hi | l << 8 ... ) keeps the stream independent of how the
-// batch is sharded across GPUs (the key is the user seed).
-__device__ __forceinline__ float philox_normal(unsigned long long seed, int t, long long seq, int l, int f) {
-  unsigned o[4];
-  philox4x32_10((unsigned)seq, (unsigned)((unsigned long long)seq >> 32), (unsigned)l | ((unsigned)(f >> 2) << 24),
-                (unsigned)t, (unsigned)seed, (unsigned)(seed >> 32), o);
-  const int pair = (f >> 1) & 1;
-  const float u1 = ((float)o[2 * pair] + 0.5f) * 2.3283064365386963e-10f;      // (0, 1]
-  const float u2 = ((float)o[2 * pair + 1] + 0.5f) * 2.3283064365386963e-10f;
-  const float rad = sqrtf(-2.0f * logf(u1));
-  float sn, cs;
-  sincosf(6.283185307179586f * u2, &sn, &cs);
-  return (f & 1) ? rad * sn : rad * cs;
-}
-
+// ---------------------------------------------------------- Philox4x32-10 (philox_normal.h)
 __global__ void philox_fill_kernel(float* __restrict__ out, unsigned long long seed, int t, long long seq_offset, int B,
                                    int L, int F) {
   const long long n = (long long)B * L * F;

@@ -498,6 +498,52 @@ int fd_denoise_loss_ex(fd_model* m, const float* x0, const float* corrupted, con
                        int64_t* turns /* [B][F] or NULL */, double* pair_sums /* [B] or NULL */, int64_t* pairs /* [B] or NULL */,
                        float* corrupted_out /* or NULL */, float* eps_out /* or NULL */);
 
+/* ---- histogram statistics of angle columns: the counts behind custom_metrics.kl_from_empirical / kl_from_dset ----
+ *
+ * np.histogram of every column of a float32 table against that column's own explicit edges.
+ *   values      host float32 [N][F], 1 <= N <= 2^31 - 1, 1 <= F <= 32
+ *   edges       host float64 [F][nbins + 1], non-decreasing along a row, no NaN;  1 <= nbins <= FDMI_HIST_MAX_BINS
+ *   rows_valid  NULL (every row), or uint8 [N]: rows with 0 are skipped
+ *   counts      int64 [F][nbins]: bin i of column f holds edges[f][i] <= x < edges[f][i + 1], the last bin also
+ *               x == edges[f][nbins] (numpy's rule); x is widened to float64 first, so every comparison is exact
+ *   outside     int64 [F]: the counted rows of column f in no bin (below, above, NaN)
+ * Integer results: they do not depend on the run.  Model-free and synchronous. */
+#define FDMI_HIST_MAX_BINS 4096
+int fd_hist_columns(int device_id, const float* values, int64_t N, int F, const double* edges, int nbins,
+                    const uint8_t* rows_valid /* [N] or NULL */, int64_t* counts /* [F][nbins] */, int64_t* outside /* [F] */);
+
+/* The two passes of custom_metrics.kl_from_dset over a list of timesteps, one launch each.  For row r, feature f and
+ * timestep t = timesteps[i], two streams:
+ *   eps = scale[f] * z, wrapped to [-pi, pi) where is_angle[f] (NoisedAnglesDataset.sample_noise, datasets.py:772-799);
+ *   x_t = keep[t] * x0[r][f] + spread[t] * eps, two rounded float32 products and one rounded sum, wrapped where
+ *         is_angle[f]: fd_denoise_loss's noising statement (datasets.py:861-871);                          -- stream 0
+ *   cmp = a second, independent draw treated like eps: the reference's dset.sample_noise(values).        -- stream 1
+ * z is N(0, 1) from Philox4x32-10 as fd_philox_normal_dev draws it with sequence = r + row_offset, position 0, step = t,
+ * under seed_eps for eps and seed_cmp for cmp.  With eps_in and cmp_in (float32 [nT][N][F], both or neither) the streams take
+ * eps / cmp from there AS GIVEN (scaled and wrapped already) instead: a reference run's recorded draws.
+ *   x0          host float32 [N][F], 1 <= N <= 2^31 - 1, 1 <= F <= 32
+ *   is_angle    uint8 [F];  scale  float32 [F], finite (angular_variance / nonangular_variance per feature)
+ *   keep, spread   float32 [T], finite: sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod
+ *   timesteps   int32 [nT], each in [0, T), 1 <= nT <= 65535
+ * fd_noise_minmax:  minmax_out  float32 [nT][2][F][2]: per timestep, stream and feature the smallest and largest value.
+ * fd_noise_hist:    edges       float64 [nT][F][nbins + 1], rows as fd_hist_columns'; BOTH streams of (i, f) are counted
+ *                               against edges[i][f]
+ *                   counts      int64 [nT][2][F][nbins], outside int64 [nT][2][F], as fd_hist_columns'.  With edges that
+ *                               span fd_noise_minmax's result for the same arguments, outside is 0 and a row of counts
+ *                               sums to N: the two passes saw the same streams.
+ *                   x_t_out, cmp_out, eps_out   NULL, or float32 [nT][N][F]: stream 0, stream 1 and eps (small N)
+ * Integer results and exact min / max: they do not depend on the run.  Model-free and synchronous. */
+int fd_noise_minmax(int device_id, const float* x0, int64_t N, int F, const uint8_t* is_angle, const float* scale,
+                    const float* keep, const float* spread, int T, const int32_t* timesteps, int nT, uint64_t seed_eps,
+                    uint64_t seed_cmp, int64_t row_offset, const float* eps_in /* or NULL */, const float* cmp_in /* or NULL */,
+                    float* minmax_out /* [nT][2][F][2] */);
+int fd_noise_hist(int device_id, const float* x0, int64_t N, int F, const uint8_t* is_angle, const float* scale,
+                  const float* keep, const float* spread, int T, const int32_t* timesteps, int nT, uint64_t seed_eps,
+                  uint64_t seed_cmp, int64_t row_offset, const float* eps_in /* or NULL */, const float* cmp_in /* or NULL */,
+                  const double* edges /* [nT][F][nbins + 1] */, int nbins, int64_t* counts /* [nT][2][F][nbins] */,
+                  int64_t* outside /* [nT][2][F] */, float* x_t_out /* or NULL */, float* cmp_out /* or NULL */,
+                  float* eps_out /* or NULL */);
+
 /* ---- test hook ----
  * One token GEMM  C[M,N] = A[M,K] W[N,K]^T + bias (+GELU | +resid) through the production
  * kernels of the given precision (epilogue: 0 bias, 1 bias+GELU, 2 bias+residual).  Host buffers,
