@@ -109,6 +109,9 @@ struct Workspace {
   float* loss_ex_in = nullptr;  // fd_denoise_loss_ex's one upload: x0 | noise | corrupted ([B][L][F] each) | keep | spread | coef | t | lens ([B] each)
   double* loss_ex_out = nullptr;  // its one download, in 8-byte words: sums | turns ([B][F] each) | pair_sums | pairs ([B] each)
   UpdateDyn* dyn = nullptr;
+  // motif-conditioned sampling (fd_sample_inpaint, fd_p_sample_step_inpaint), allocated on first use:
+  // known | z_known ([B][L][F] floats each) | known_coef ([2][T+1] floats) | fixed ([B][L][F] bytes)
+  float* inpaint = nullptr;
   // row-image path (fdmi_kernels.h): images, per-(sequence, head) q / k / v^T, the token-row table
   bool img = false;
   int cap = 0, LPK = 0, LTOT = 0, NKT = 0;  // rows128 capacity = ceil128(B * ceil8(L)); key-tile geometry
@@ -126,7 +129,7 @@ struct Workspace {
     if (graph) (void)hipGraphExecDestroy(graph);
     graph = nullptr;
     for (void* p : {(void*)x, (void*)eps, (void*)h, (void*)qkv, (void*)ctx, (void*)a, (void*)tmp, (void*)g, (void*)z,
-                    (void*)lens, (void*)t_dev, (void*)t_seq, (void*)loss_in, (void*)loss_sums, (void*)loss_ex_in, (void*)loss_ex_out, (void*)dyn, (void*)himg, (void*)aimg, (void*)cimg, (void*)gimg,
+                    (void*)lens, (void*)t_dev, (void*)t_seq, (void*)loss_in, (void*)loss_sums, (void*)loss_ex_in, (void*)loss_ex_out, (void*)dyn, (void*)inpaint, (void*)himg, (void*)aimg, (void*)cimg, (void*)gimg,
                     (void*)qbuf, (void*)kbuf, (void*)vbuf, (void*)trash, (void*)rowinfo, (void*)seq_row0, (void*)nrow,
                     (void*)dims, (void*)flag, (void*)kmask, (void*)pos_ids})
       if (p) (void)hipFree(p);
@@ -649,6 +652,9 @@ struct StepMode {
   bool no_wrap = false;  // p_sample alone, without the loop's wrap
   const unsigned char* kmask = nullptr;  // fd_forward_ex: [B][L] key mask of any pattern (device), else null: prefix masks from lens
   const int* pos_ids = nullptr;          // fd_forward_ex: [B][L] position ids of the absolute position embedding (device)
+  // fd_p_sample_step_inpaint: the replacement's arrays (device; z_known = the one slab of level t), null otherwise
+  const float *known = nullptr, *known_coef = nullptr, *z_known = nullptr;
+  const unsigned char* fixed = nullptr;
   const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
   bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
 };
@@ -809,6 +815,7 @@ UpdateArgs fill_update(const fd_model* m, const Workspace& w, const StepMode& mo
     } else {
       u.noise = mode.noise;
       u.t_start = mode.t_start;
+      u.known = mode.known; u.fixed = mode.fixed; u.known_noise = mode.z_known; u.known_coef = mode.known_coef;
     }
   }
   if (mode.use_dyn) u.noise_stride = (long long)u.M * u.F;
@@ -1137,6 +1144,39 @@ int check_flag(fd_model* m) {
   if (!v) return FD_OK;
   HIP_TRY(hipMemset(w.flag, 0, 4));
   return fail(FD_E_NONFINITE, "the model produced a non-finite value (inf/NaN in the predicted noise)");
+}
+
+// ---- motif-conditioned sampling: argument checks (before the first device call) and the workspace's staging buffer
+int check_inpaint(const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* lens, int B, int L, int F) {
+  if (!fixed) return fail(FD_E_INVALID, "fixed is null");
+  if (!known) return fail(FD_E_INVALID, "known is null (fixed is given)");
+  if (!known_coef) return fail(FD_E_INVALID, "known_coef is null");
+  for (int b = 0; b < B; ++b)
+    for (int l = lens[b]; l < L; ++l)
+      for (int f = 0; f < F; ++f)
+        if (fixed[((size_t)b * L + l) * F + f])
+          return fail(FD_E_INVALID, "fixed element beyond a length: sequence %d position %d feature %d, lens[%d] = %d", b, l, f, b, lens[b]);
+  return FD_OK;
+}
+
+struct InpaintDev {
+  float *known, *z_known, *coef;
+  unsigned char* fixed;
+};
+
+// uploads known / fixed / known_coef into the current workspace's staging buffer (allocated on first use), stream-ordered on s
+int stage_inpaint(fd_model* m, hipStream_t s, const float* known, const uint8_t* fixed, const float* known_coef, InpaintDev* d) {
+  Workspace& w = m->ws;
+  const size_t n = (size_t)w.B * w.L * m->cfg.n_features, nc = 2 * ((size_t)m->T + 1);
+  if (!w.inpaint) HIP_TRY(hipMalloc((void**)&w.inpaint, (2 * n + nc) * 4 + n));
+  d->known = w.inpaint;
+  d->z_known = w.inpaint + n;
+  d->coef = w.inpaint + 2 * n;
+  d->fixed = reinterpret_cast<unsigned char*>(w.inpaint + 2 * n + nc);
+  HIP_TRY(hipMemcpyAsync(d->known, known, n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d->coef, known_coef, nc * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d->fixed, fixed, n, hipMemcpyHostToDevice, s));
+  return FD_OK;
 }
 
 }  // namespace
@@ -1832,6 +1872,39 @@ int fd_p_sample_step(fd_model* m, const float* x, int t, const int32_t* lens, in
   return check_flag(m);
 }
 
+int fd_p_sample_step_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
+                             const float* known, const uint8_t* fixed, const float* known_coef, const float* z_known,
+                             float* x_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (t > 0 && !z) return fail(FD_E_INVALID, "z is required for t > 0");
+  if (t > 0 && !z_known) return fail(FD_E_INVALID, "z_known is required for t > 0");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  Workspace& w = m->ws;
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  hipStream_t s = m->stream;
+  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  if (z) HIP_TRY(hipMemcpyAsync(w.z, z, n * 4, hipMemcpyHostToDevice, s));
+  InpaintDev ip;
+  if (int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip)) return rc;
+  if (t > 0) HIP_TRY(hipMemcpyAsync(ip.z_known, z_known, n * 4, hipMemcpyHostToDevice, s));
+  if (int rc = prepare_rows(m, s, 0)) return rc;
+  if (int rc = set_t(m, s, t)) return rc;
+  StepMode mode{};
+  mode.noise = w.z;
+  mode.t_start = t;
+  mode.no_wrap = !wrap;
+  mode.known = ip.known; mode.fixed = ip.fixed; mode.known_coef = ip.coef; mode.z_known = ip.z_known;
+  if (int rc = run_step(m, s, mode)) return rc;
+  HIP_TRY(hipMemcpyAsync(x_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return check_flag(m);
+}
+
 int fd_sample_begin_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_start,
                         uint64_t seed, int64_t seq_offset, void* out_dev, int full_history, void* hip_stream) {
   if (int rc = check_shape(m, B, L, t_start)) return rc;
@@ -1954,6 +2027,58 @@ int fd_sample_ex(fd_model* m, const float* x_init, const int32_t* lens, int B, i
   if (noise) HIP_TRY(bufs.upload(noise, nsteps * n * 4, &d_noise));
   if (int rc = fd_sample_dev(m, d_x, d_lens, B, L, t_start, d_noise, seed, seq_offset, d_out, full_history, nullptr)) return rc;
   HIP_TRY(hipStreamSynchronize(m->stream));
+  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
+  return check_flag(m);
+}
+
+int fd_sample_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
+                      const float* known, const uint8_t* fixed, const float* known_coef, const float* known_noise,
+                      uint64_t seed, int64_t seq_offset, float* out, int full_history) {
+  if (int rc = check_shape(m, B, L, t_start)) return rc;
+  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  const size_t nsteps = (size_t)t_start + 1;
+  const size_t out_rows = full_history ? (nsteps + full_history - 1) / full_history : 1;
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  const float *d_noise = nullptr, *d_known_noise = nullptr;
+  int* d_lens;
+  HIP_TRY(bufs.alloc(n * 4, &d_x));
+  HIP_TRY(bufs.alloc((size_t)B * 4, &d_lens));
+  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
+  HIP_TRY(hipMemcpy(d_x, x_init, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice));
+  if (noise) HIP_TRY(bufs.upload(noise, nsteps * n * 4, &d_noise));
+  if (known_noise) HIP_TRY(bufs.upload(known_noise, (nsteps + 1) * n * 4, &d_known_noise));  // rows = levels 0 .. t_start + 1
+  if (int rc = fd_sample_begin_dev(m, d_x, d_lens, B, L, t_start, seed, seq_offset, d_out, full_history, nullptr)) return rc;
+  hipStream_t s = m->stream;
+  InpaintDev ip;
+  int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip);
+  if (!rc) {
+    // the start point enters step t_start, so it is at level t_start + 1
+    launch_inpaint_init(m->ws.x, ip.known, ip.fixed, d_known_noise ? d_known_noise + nsteps * n : nullptr, ip.coef, m->T, t_start + 1,
+                        seed, seq_offset, B, L, m->cfg.n_features, m->angle_mask, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
+  }
+  if (!rc) {
+    // the per-run values of the update kernels travel through UpdateDyn: the captured step graph is the plain sampler's
+    m->dyn_host.known = ip.known; m->dyn_host.fixed = ip.fixed; m->dyn_host.known_coef = ip.coef; m->dyn_host.known_noise = d_known_noise;
+    rc = fd_sample_steps_dev(m, t_start + 1, d_noise, 0, nullptr);
+  }
+  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
+  // the run is over (or failed, at any point behind fd_sample_begin_dev): it is closed, and a later run on this model, plain or
+  // not, starts from cleared fields, on the host and on the device
+  m->run_open = false;
+  m->run_t = -1;
+  m->dyn_host.known = nullptr; m->dyn_host.fixed = nullptr; m->dyn_host.known_coef = nullptr; m->dyn_host.known_noise = nullptr;
+  hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, m->ws.dyn, m->dyn_host);
+  HIP_TRY(hipStreamSynchronize(s));
+  if (rc) return rc;
   HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
   return check_flag(m);
 }

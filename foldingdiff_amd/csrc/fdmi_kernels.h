@@ -59,6 +59,11 @@ struct UpdateDyn {
   long long seq_offset;
   int t_start;
   int hist_every;        // keep every k-th state (and the final one) in `hist`; <= 1: every state
+  // motif-conditioned sampling (inpaint_replace.h): all null unless fd_sample_inpaint is running
+  const float* known;          // [M, F] values of the fixed elements (model space)
+  const unsigned char* fixed;  // [M, F] != 0: the element is replaced after every step instead of updated
+  const float* known_noise;    // [t_start+2, M, F] draws of the replacement (row j: level j) or null (Philox, tagged step word)
+  const float* known_coef;     // [2, T+1] keep | spread per level
 };
 struct UpdateArgs {
   const UpdateDyn* dyn;  // device pointer; when non-null it overrides noise/hist/seed/seq_offset/t_start
@@ -83,8 +88,19 @@ struct UpdateArgs {
   int do_ln;
   float ln_eps;
   unsigned angle_mask;   // bit f set => wrap feature f
+  // motif-conditioned sampling without `dyn` (fd_p_sample_step_inpaint); null by default.  known_noise rows are
+  // noise_stride apart, like `noise`'s
+  const float* known;
+  const unsigned char* fixed;
+  const float* known_noise;
+  const float* known_coef;
 };
 void launch_head_update(const UpdateArgs& a, hipStream_t s);
+// The replacement of the start point of a motif-conditioned run (inpaint_replace.h): x[o] = the level-`level` value of
+// every element with fixed[o] != 0 (level >= 1); known_noise = the [B][L][F] slab of that level, or null (Philox).
+void launch_inpaint_init(float* x, const float* known, const unsigned char* fixed, const float* known_noise,
+                         const float* known_coef, int T, int level, unsigned long long seed, long long seq_offset, int B,
+                         int L, int F, unsigned angle_mask, hipStream_t s);
 
 // N1: NeRF internal -> Cartesian backbone coordinates, one lane per chain, fp64.
 // Feature column of each quantity in the [B][L][F] float32 array; -1 => the reference's constant.

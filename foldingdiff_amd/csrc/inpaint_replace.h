@@ -1,0 +1,30 @@
+// Motif-conditioned sampling ("replacement"): the one device definition of the value a FIXED element of a state
+// takes, shared by the three head + p_sample update kernels (rowwise.hip, rowwise_img.hip) and the kernel that replaces
+// the fixed elements of the start point, so that the statement cannot drift between them.
+//
+// Levels.  A state at level j = 0 .. T has seen j forward-noising steps: the state that enters reverse step t is at level
+// t + 1, the state that step t leaves is at level t.  coef = [2][T + 1]: keep[j] then spread[j], keep[0] = 1,
+// spread[0] = 0, keep[j] = sqrt_alphas_cumprod[j - 1], spread[j] = sqrt_one_minus_alphas_cumprod[j - 1].
+//   level j >= 1: wrap?(keep[j] * known + spread[j] * z), each product and the sum rounded once -- launch_q_sample's
+//                 statement (loss.hip); z = known_noise[j][o], or with known_noise null the Philox draw whose step word
+//                 is j with the top bit set (a stream disjoint from the update's own draws, whose step word is t < 2^31)
+//   level 0:      the bits of known[o]; no arithmetic, no draw
+#pragma once
+#include "philox_normal.h"
+#include "wrap_pi.h"
+
+namespace fdmi {
+
+__device__ __forceinline__ float inpaint_value(const float* __restrict__ known, const float* __restrict__ known_noise,
+                                               const float* __restrict__ coef, int T, long long noise_stride, int level,
+                                               size_t o, unsigned long long seed, long long seq, int l, int f, bool angular) {
+  const float kv = known[o];
+  if (level <= 0) return kv;
+  const float z = known_noise ? known_noise[(size_t)level * (size_t)noise_stride + o]
+                              : philox_normal(seed, (int)(0x80000000u | (unsigned)level), seq, l, f);
+  float v = __fadd_rn(__fmul_rn(coef[level], kv), __fmul_rn(coef[T + 1 + level], z));
+  if (angular) v = wrap_pi(v);
+  return v;
+}
+
+}  // namespace fdmi

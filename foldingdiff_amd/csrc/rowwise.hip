@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "fdmi_kernels.h"
+#include "inpaint_replace.h"
 #include "philox_normal.h"
 #include "wrap_pi.h"
 
@@ -419,19 +420,28 @@ __global__ __launch_bounds__(256) void head_update_kernel(UpdateArgs a) {
   unsigned long long seed = a.seed;
   long long seq_offset = a.seq_offset;
   int t_start = a.t_start, hist_every = 1;
+  const float *known = a.known, *known_noise = a.known_noise, *known_coef = a.known_coef;  // (inpaint_replace.h)
+  const unsigned char* fixed = a.fixed;
   if (a.dyn) {
     noise = a.dyn->noise; hist = a.dyn->hist; seed = a.dyn->seed; seq_offset = a.dyn->seq_offset; t_start = a.dyn->t_start;
     hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
+    known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
   }
   const float c1 = a.coef[t], bt = a.coef[a.T + t], c3 = a.coef[2 * a.T + t], sg = a.coef[3 * a.T + t];
   // model_mean = sqrt_recip_alphas_t * (x - betas_t * eps / sqrt_one_minus_alphas_cumprod_t)   (sampling.py:62-67)
-  float xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(bt, mine), c3)));
-  if (t > 0) {  // sampling.py:69-75
-    const float z = noise ? noise[(size_t)t * a.noise_stride + o]
-                          : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, lane);
-    xn = __fadd_rn(xn, __fmul_rn(sg, z));
+  float xn;
+  if (fixed && fixed[o]) {  // a fixed element leaves step t at level t, whatever the model predicted
+    xn = inpaint_value(known, known_noise, known_coef, a.T, a.noise_stride, t, o, seed, seq_offset + tok / a.L, tok % a.L, lane,
+                       (a.angle_mask >> lane) & 1u);
+  } else {
+    xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(bt, mine), c3)));
+    if (t > 0) {  // sampling.py:69-75
+      const float z = noise ? noise[(size_t)t * a.noise_stride + o]
+                            : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, lane);
+      xn = __fadd_rn(xn, __fmul_rn(sg, z));
+    }
+    if ((a.angle_mask >> lane) & 1u) xn = wrap_pi(xn);
   }
-  if ((a.angle_mask >> lane) & 1u) xn = wrap_pi(xn);
   a.x_out[o] = xn;
   if (hist && ((t_start - t + 1) % hist_every == 0 || t == 0))  // state j = t_start - t goes to row j / hist_every
     hist[(size_t)((t_start - t) / hist_every) * a.M * F + o] = xn;
@@ -460,9 +470,12 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
   unsigned long long seed = a.seed;
   long long seq_offset = a.seq_offset;
   int t_start = a.t_start, hist_every = 1;
+  const float *known = a.known, *known_noise = a.known_noise, *known_coef = a.known_coef;  // (inpaint_replace.h)
+  const unsigned char* fixed = a.fixed;
   if (a.dyn) {
     noise = a.dyn->noise; hist = a.dyn->hist; seed = a.dyn->seed; seq_offset = a.dyn->seq_offset; t_start = a.dyn->t_start;
     hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
+    known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
   }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
   if (a.x_out) { c1 = a.coef[t]; btc = a.coef[a.T + t]; c3 = a.coef[2 * a.T + t]; sg = a.coef[3 * a.T + t]; }
@@ -491,13 +504,19 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
       if (a.eps_out) a.eps_out[o] = mine;
       if (a.x_out) {
         // model_mean = sqrt_recip_alphas_t * (x - betas_t * eps / sqrt_one_minus_alphas_cumprod_t)   (sampling.py:62-67)
-        float xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
-        if (t > 0) {  // sampling.py:69-75
-          const float z = noise ? noise[(size_t)t * a.noise_stride + o]
-                                : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, k);
-          xn = __fadd_rn(xn, __fmul_rn(sg, z));
+        float xn;
+        if (fixed && fixed[o]) {  // a fixed element leaves step t at level t, whatever the model predicted
+          xn = inpaint_value(known, known_noise, known_coef, a.T, a.noise_stride, t, o, seed, seq_offset + tok / a.L,
+                             tok % a.L, k, (a.angle_mask >> k) & 1u);
+        } else {
+          xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
+          if (t > 0) {  // sampling.py:69-75
+            const float z = noise ? noise[(size_t)t * a.noise_stride + o]
+                                  : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, k);
+            xn = __fadd_rn(xn, __fmul_rn(sg, z));
+          }
+          if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         }
-        if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         a.x_out[o] = xn;
         if (hist && ((t_start - t + 1) % hist_every == 0 || t == 0))  // state j = t_start - t goes to row j / hist_every
     hist[(size_t)((t_start - t) / hist_every) * a.M * F + o] = xn;
@@ -528,6 +547,34 @@ void launch_head_update(const UpdateArgs& a, hipStream_t s) {
   else if (nj <= 12) FD_HU(12);
   else FD_HU(16);
 #undef FD_HU
+}
+
+// ---- the start point of a motif-conditioned run: its fixed elements at level `level` (inpaint_replace.h)
+__global__ __launch_bounds__(256) void inpaint_init_kernel(float* __restrict__ x, const float* __restrict__ known,
+                                                           const unsigned char* __restrict__ fixed,
+                                                           const float* __restrict__ known_noise,
+                                                           const float* __restrict__ known_coef, int T, int level,
+                                                           unsigned long long seed, long long seq_offset, long long n, int L,
+                                                           int F, unsigned angle_mask) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    if (!fixed[i]) continue;
+    const int f = (int)(i % F);
+    const long long tok = i / F;
+    // known_noise is the slab of this level already: stride 0
+    x[i] = inpaint_value(known, known_noise, known_coef, T, 0, level, (size_t)i, seed, seq_offset + tok / L, (int)(tok % L), f,
+                         (angle_mask >> f) & 1u);
+  }
+}
+
+void launch_inpaint_init(float* x, const float* known, const unsigned char* fixed, const float* known_noise,
+                         const float* known_coef, int T, int level, unsigned long long seed, long long seq_offset, int B,
+                         int L, int F, unsigned angle_mask, hipStream_t s) {
+  const long long n = (long long)B * L * F;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(inpaint_init_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, known, fixed, known_noise, known_coef, T,
+                     level, seed, seq_offset, n, L, F, angle_mask);
 }
 
 __global__ void step_advance_kernel(int* t_dev) { *t_dev -= 1; }

@@ -13,6 +13,7 @@
 
 #include "fdmi_kernels.h"
 #include "img_common.h"
+#include "inpaint_replace.h"
 #include "philox_normal.h"
 #include "wrap_pi.h"
 
@@ -502,9 +503,12 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
   unsigned long long seed = a.seed;
   long long seq_offset = a.seq_offset;
   int t_start = a.t_start, hist_every = 1;
+  const float *known = a.known, *known_noise = a.known_noise, *known_coef = a.known_coef;  // (inpaint_replace.h)
+  const unsigned char* fixed = a.fixed;
   if (a.dyn) {
     noise = a.dyn->noise; hist = a.dyn->hist; seed = a.dyn->seed; seq_offset = a.dyn->seq_offset; t_start = a.dyn->t_start;
     hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
+    known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
   }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
   if (a.x_out) { c1 = a.coef[t]; btc = a.coef[a.T + t]; c3 = a.coef[2 * a.T + t]; sg = a.coef[3 * a.T + t]; }
@@ -557,12 +561,18 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
       bad |= !(__builtin_fabsf(mine) <= 3.0e38f);  // inf or NaN
       if (a.x_out) {
         // model_mean = sqrt_recip_alphas_t * (x - betas_t * eps / sqrt_one_minus_alphas_cumprod_t)   (sampling.py:62-67)
-        float xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
-        if (t > 0) {  // sampling.py:69-75
-          const float z = noise ? noise[(size_t)t * a.noise_stride + o] : philox_normal(seed, t, seq_offset + ri.x, ri.y, k);
-          xn = __fadd_rn(xn, __fmul_rn(sg, z));
+        float xn;
+        if (fixed && fixed[o]) {  // a fixed element leaves step t at level t, whatever the model predicted
+          xn = inpaint_value(known, known_noise, known_coef, a.T, a.noise_stride, t, o, seed, seq_offset + ri.x, ri.y, k,
+                             (a.angle_mask >> k) & 1u);
+        } else {
+          xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
+          if (t > 0) {  // sampling.py:69-75
+            const float z = noise ? noise[(size_t)t * a.noise_stride + o] : philox_normal(seed, t, seq_offset + ri.x, ri.y, k);
+            xn = __fadd_rn(xn, __fmul_rn(sg, z));
+          }
+          if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         }
-        if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         a.x_out[o] = xn;
         if (hist && ((t_start - t + 1) % hist_every == 0 || t == 0))  // state j = t_start - t goes to row j / hist_every
           hist[(size_t)((t_start - t) / hist_every) * BLF + o] = xn;

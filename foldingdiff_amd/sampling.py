@@ -632,6 +632,172 @@ def get_reconstruction_error(model, dset, noise_timesteps: int = 250, bs: int = 
     return np.array(scores), np.array(coord_scores)
 
 
+# --------------------------------------------------------------------------------- motif-conditioned sampling
+def inpaint_levels(betas) -> np.ndarray:
+    """float32 [2, T + 1]: ``keep[j]`` then ``spread[j]`` for the noise levels j = 0 .. T of a state (``fd_sample_inpaint``'s
+    ``known_coef``).  Level 0 is the clean state (1, 0); level j >= 1 is ``sqrt_alphas_cumprod[j - 1]``,
+    ``sqrt_one_minus_alphas_cumprod[j - 1]`` -- the float32 terms ``NoisedAnglesDataset`` noises with.  The state that
+    enters reverse step t is at level t + 1, the state that step t leaves is at level t."""
+    terms = beta_schedules.compute_alphas(torch.as_tensor(betas).detach().to(dtype=torch.float32, device="cpu"))
+    T = len(terms["betas"])
+    out = np.empty((2, T + 1), dtype=np.float32)
+    out[0, 0], out[1, 0] = 1.0, 0.0
+    out[0, 1:] = terms["sqrt_alphas_cumprod"].numpy()
+    out[1, 1:] = terms["sqrt_one_minus_alphas_cumprod"].numpy()
+    return out
+
+
+def _run_fd_inpaint(h, x0: np.ndarray, lens: np.ndarray, t_start: int, known: np.ndarray, fixed: np.ndarray, coef: np.ndarray,
+                    seed: int, out: np.ndarray, full_history: int) -> None:
+    """The one call into libfdmi.so of ``inpaint`` (fd_sample_inpaint, Philox for both noise streams).  Tests of the host
+    preparation replace exactly this function with a stand-in."""
+    B, L, _ = x0.shape
+    _binding.check(_binding.load().fd_sample_inpaint(
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, t_start, None, _binding.ptr(known), _binding.ptr(fixed),
+        _binding.ptr(coef), None, C.c_uint64(seed), C.c_int64(0), _binding.ptr(out), full_history))
+
+
+def _model_space(vals: np.ndarray, offset: Optional[np.ndarray], angular: np.ndarray) -> np.ndarray:
+    """Data-space angles -> what the model sees: minus the training mean offset (when there is one), the angular columns
+    wrapped to [-pi, pi); float32.  The inverse of the shift ``_shift_trim`` applies to the samples."""
+    if offset is None:
+        return np.array(vals, dtype=np.float32)
+    off = np.asarray(offset)
+    v = (np.asarray(vals, dtype=np.float32) - off) if off.dtype == np.float32 else (np.asarray(vals, dtype=np.float64) - off)
+    v[:, angular] = utils.modulo_with_wrapped_range(v[:, angular], range_min=-np.pi, range_max=np.pi)
+    return v.astype(np.float32)
+
+
+@torch.no_grad()
+def inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.ndarray], batch_size: int = 512,
+            t_start: Optional[int] = None, final_only: bool = True, feature_key: str = "angles") -> List[np.ndarray]:
+    """Motif-conditioned sampling by replacement: generate one backbone per item while the elements marked in ``fixed[i]``
+    are held to ``known[i]``.  After every reverse step the fixed elements are overwritten with a forward-noised copy of
+    their known values at the level the state has just reached, the last step writes the known values themselves
+    ("Motif-conditioned sampling"); this happens inside the update kernel, through ``fd_sample_inpaint``.
+
+    ``known[i]``: ``[len_i, F]`` angles in data space, as ``structures.featurize`` returns them; NaN is allowed where
+    nothing is fixed.  ``fixed[i]``: bool ``[len_i]`` (whole rows) or ``[len_i, F]``.  ``dset`` is ``sample()``'s
+    ``train_dset``: its mean offset is subtracted from the known values (and added back to the result), its
+    ``sample_noise`` draws the start point, its ``pad`` bounds the lengths.  The per-step noise of both streams is
+    Philox, seeded from torch's CPU generator (``torch.manual_seed`` reproducible); the replacement's draws are plain
+    N(0, 1), the statement ``NoisedAnglesDataset.__getitem__`` makes with ``angular_variance = 1``.
+
+    Returns one ``[len_i, F]`` array per item, or ``[t_start + 1, len_i, F]`` with ``final_only=False`` (row j = the state
+    after step t = t_start - j).  Runs on a single device: sharding the items across ranks is not built."""
+    n = len(known)
+    assert len(fixed) == n, f"{n} known arrays, {len(fixed)} masks"
+    F = model.n_inputs
+    T = dset.timesteps
+    t_start = T - 1 if t_start is None else int(t_start)
+    assert 0 <= t_start < T, f"t_start={t_start} outside the {T}-step schedule"
+    inner = getattr(dset, "dset", None)
+    offset = None
+    if inner is not None and hasattr(inner, "get_masked_means"):
+        try:
+            offset = inner.get_masked_means()
+        except NotImplementedError:
+            offset = None
+    angular = np.asarray(dset.feature_is_angular[feature_key], dtype=bool)
+    pad = dset.pad
+    ks, fs, lengths = [], [], []
+    for i in range(n):
+        k = np.asarray(known[i])
+        assert k.ndim == 2 and k.shape[1] == F, f"known[{i}] is {k.shape}, expected [len, {F}]"
+        if not 1 <= len(k) <= pad:
+            raise ValueError(f"known[{i}] has {len(k)} residues, the dataset pads to {pad}")
+        fx = np.asarray(fixed[i]).astype(bool)
+        if fx.ndim == 1:
+            fx = np.repeat(fx[:, None], F, axis=1)
+        assert fx.shape == k.shape, f"fixed[{i}] is {fx.shape}, known[{i}] is {k.shape}"
+        if not np.isfinite(k[fx]).all():
+            raise ValueError(f"known[{i}] is not finite at a fixed element")
+        v = _model_space(np.where(fx, k, 0.0), offset, angular)
+        ks.append(np.where(fx, v, np.float32(0.0)).astype(np.float32))
+        fs.append(fx.astype(np.uint8))
+        lengths.append(len(k))
+    betas = dset.alpha_beta_terms["betas"]
+    h = model.prepare(betas, dset.feature_is_angular[feature_key])
+    coef = inpaint_levels(betas)
+    rows = 1 if final_only else t_start + 1
+    on_gpu = _run_fd_inpaint is _run_fd_inpaint_default and getattr(getattr(model, "device", None), "type", "") == "cuda"
+    results: List[np.ndarray] = []
+    for start in range(0, n, batch_size):
+        these = lengths[start: start + batch_size]
+        B, L = len(these), max(these)
+        x0 = _as_f32(dset.sample_noise(torch.zeros((B, pad, F), dtype=torch.float32))[:, :L, :])
+        kb = np.zeros((B, L, F), dtype=np.float32)
+        fb = np.zeros((B, L, F), dtype=np.uint8)
+        for i, l in enumerate(these):
+            kb[i, :l] = ks[start + i]
+            fb[i, :l] = fs[start + i]
+        seed = _draw_philox_seed()
+        out = np.empty((rows, B, L, F), dtype=np.float32)
+        prev_varlen = model.set_option("varlen", 1)   # positions beyond an item's length are cut away below, as in sample()
+        try:
+            if on_gpu:
+                model.set_option("rows_hint", sum((int(l) + 7) // 8 * 8 for l in these))
+            _run_fd_inpaint(h, x0, _lens_array(these, B, L), t_start, kb, fb, coef, seed, out, 0 if final_only else 1)
+        finally:
+            if on_gpu:
+                model.set_option("rows_hint", 0)
+            model.set_option("varlen", prev_varlen if prev_varlen is not None else 0)
+        results.extend(_shift_trim(model, torch.from_numpy(out), these, offset, angular))
+    return [r[0] for r in results] if final_only else results
+
+
+_run_fd_inpaint_default = _run_fd_inpaint
+
+
+def scaffold(model, dset, motif: np.ndarray, total_lengths: Sequence[int], offsets=None, pin_lead_angle: bool = True,
+             feature_key: str = "angles", **kwargs) -> Tuple[List[np.ndarray], List[int]]:
+    """Generate one backbone of each of ``total_lengths`` around ``motif`` (``[m, F]`` data-space angles, rows of what
+    ``structures.featurize`` returns): the motif's rows sit at residues ``offset .. offset + m - 1`` with all their
+    features fixed, the rest of the chain is sampled (``inpaint``; ``kwargs`` go there).  ``offsets``: ``None`` = centred
+    (``(length - m) // 2``), ``"random"`` = drawn from numpy's global generator, an int, or one int per length.
+
+    The six features of a residue are internal angles, so the fixed rows reproduce the motif's backbone up to NeRF's
+    constant bond lengths -- with one exception, which ``pin_lead_angle`` closes: NeRF reads the N-CA-C angle of residue
+    i + 1 from row i (``nerf.py``'s reference quirk), so the angle inside the motif's FIRST residue comes from the row before
+    the motif.  With ``pin_lead_angle`` (default) that one element, ``tau`` of row ``offset - 1``, is fixed to the motif's
+    first ``tau`` as well (``structures.motif_backbone`` builds the motif's own backbone with the same lead-in).
+
+    Returns ``(samples, offsets)``: ``inpaint``'s list and the offset used for each."""
+    motif = np.asarray(motif, dtype=np.float32)
+    assert motif.ndim == 2 and motif.shape[1] == model.n_inputs, f"motif is {motif.shape}, expected [m, {model.n_inputs}]"
+    m, F = motif.shape
+    total_lengths = [int(l) for l in total_lengths]
+    if any(l < m for l in total_lengths):
+        raise ValueError(f"every total length must hold the {m} residues of the motif, got {total_lengths}")
+    if offsets is None:
+        offs = [(l - m) // 2 for l in total_lengths]
+    elif isinstance(offsets, str):
+        if offsets != "random":
+            raise ValueError(f"offsets={offsets!r}: expected None, 'random', an int or one int per length")
+        offs = [int(np.random.randint(0, l - m + 1)) for l in total_lengths]
+    elif np.ndim(offsets) == 0:
+        offs = [int(offsets)] * len(total_lengths)
+    else:
+        offs = [int(o) for o in offsets]
+        assert len(offs) == len(total_lengths), f"{len(offs)} offsets for {len(total_lengths)} lengths"
+    names = list(dset.feature_names[feature_key])
+    tau = names.index("tau") if pin_lead_angle and "tau" in names else -1
+    known, fixed = [], []
+    for l, o in zip(total_lengths, offs):
+        if not 0 <= o <= l - m:
+            raise ValueError(f"offset {o} does not place {m} residues in a chain of {l}")
+        k = np.full((l, F), np.nan, dtype=np.float32)
+        f = np.zeros((l, F), dtype=bool)
+        k[o: o + m] = motif
+        f[o: o + m] = True
+        if tau >= 0 and o >= 1:
+            k[o - 1, tau] = motif[0, tau]
+            f[o - 1, tau] = True
+        known.append(k)
+        fixed.append(f)
+    return inpaint(model, dset, known, fixed, feature_key=feature_key, **kwargs), offs
+
+
 def sample_simple(model_dir: str, n: int = 10, sweep_lengths: Tuple[int, int] = (50, 128)):
     """Load model + dummy dataset from ``model_dir`` and return one DataFrame of final
     angles per sampled backbone."""

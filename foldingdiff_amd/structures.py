@@ -383,6 +383,35 @@ def superposed_rmsd(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], 
     return out
 
 
+def motif_backbone(motif: np.ndarray, feature_names: Sequence[str], at_chain_start: bool = False, device: int = 0) -> np.ndarray:
+    """The motif's own NeRF-built backbone, float64 ``[3 m, 3]`` (N, CA, C per residue), from its ``[m, F]`` angle rows
+    alone.  NeRF's first residue is a constant seed (with the seed's bond lengths), and the N-CA-C angle of residue i + 1
+    is read from row i; so the rows are built behind one lead-in row -- a copy of the first row, of which only ``tau``
+    shapes the motif -- and the seed residue is dropped.  This is the geometry ``sampling.scaffold`` (``pin_lead_angle``)
+    reproduces at any offset >= 1.  ``at_chain_start``: the motif as the start of a chain (offset 0), where its first
+    residue is the seed residue itself: the rows built as they are."""
+    motif = np.asarray(motif, dtype=np.float32)
+    if at_chain_start:
+        return nerf.build_backbones([motif], feature_names, center_coords=False, device=device)[0]
+    xyz = nerf.build_backbones([np.concatenate([motif[:1], motif])], feature_names, center_coords=False, device=device)[0]
+    return xyz[3:].copy()
+
+
+def motif_rmsd(backbones: Sequence[np.ndarray], motif_backbone: np.ndarray, offsets: Sequence[int], device: int = 0) -> np.ndarray:
+    """N / CA / C RMSD (Angstrom, after optimal superposition) of residues ``offsets[i] .. offsets[i] + m - 1`` of every
+    generated backbone (``[3 len_i, 3]``, ``nerf.build_backbones``) against the motif's backbone (``[3 m, 3]``,
+    ``motif_backbone``); float64 ``[len(backbones)]``."""
+    ref = np.asarray(motif_backbone, dtype=np.float64).reshape(-1, 3)
+    assert len(backbones) == len(offsets) and len(ref) % 3 == 0
+    m3 = len(ref)
+    parts = []
+    for i, (bb, o) in enumerate(zip(backbones, offsets)):
+        bb = np.asarray(bb, dtype=np.float64).reshape(-1, 3)
+        assert 0 <= 3 * int(o) and 3 * int(o) + m3 <= len(bb), f"backbone {i}: {len(bb) // 3} residues, motif at {o} .. {int(o) + m3 // 3 - 1}"
+        parts.append(bb[3 * int(o): 3 * int(o) + m3])
+    return superposed_rmsd(parts, [ref] * len(parts), device=device)
+
+
 class RmsdScorer:
     """A ``scorer=`` for ``sampling.get_reconstruction_error``: per item (RMSD of NeRF(reconstruction) to NeRF(truth),
     RMSD of NeRF(reconstruction) to the backbone of the item's PDB file), in Angstrom after optimal superposition --

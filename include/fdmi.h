@@ -47,6 +47,7 @@ extern "C" {
 /*    fd_ar_forward and fd_ar_sample (the autoregressive baseline) are additive too */
 /*    fd_loss_terms_ex, fd_pairwise_dist and fd_denoise_loss_ex (the "l1" loss, the circle penalty and the pairwise-distance
  *    term of the denoising loss) are additive too */
+/*    fd_sample_inpaint and fd_p_sample_step_inpaint (motif-conditioned sampling) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -260,6 +261,40 @@ int fd_sample_begin_dev(fd_model* m, const void* x_init_dev, const void* lens_de
                         uint64_t seed, int64_t seq_offset, void* out_dev, int full_history, void* hip_stream);
 int fd_sample_steps_dev(fd_model* m, int n_steps, const void* noise_dev, int noise_t0, void* hip_stream);
 int fd_sample_end_dev(fd_model* m, void* out_dev, void* hip_stream);
+
+/* ---- motif-conditioned sampling ("replacement"): chosen elements of the state are held to known values while the rest
+ * of the chain is generated around them.
+ *
+ * Levels.  A state at level j = 0 .. T has seen j forward-noising steps.  The state that ENTERS reverse step t is at level
+ * t + 1, the state that step t LEAVES is at level t.  keep[0] = 1, spread[0] = 0; keep[j] = sqrt_alphas_cumprod[j-1] and
+ * spread[j] = sqrt_one_minus_alphas_cumprod[j-1] for j >= 1, in float32 (what NoisedAnglesDataset noises with).
+ *
+ * Replacement.  An element o = (b, l, f) with fixed[o] != 0 of a state at level j is
+ *   j >= 1:  keep[j] * known[o] + spread[j] * z, each product and the sum rounded once (fd_denoise_loss's noising
+ *            statement), wrapped to [-pi, pi) where the model's feature f is an angle
+ *   j == 0:  the bits of known[o]
+ * with z = known_noise[j][o], or, known_noise NULL, the Philox draw of (seed, 0x80000000 | j, seq_offset + b, l, f): the
+ * sampler's generator with the top bit of its step word set, a stream disjoint from the update's own draws.  It is made
+ * once on x_init (level t_start + 1) and at the end of every step t (level t), inside the update kernel: no extra launch.
+ * Elements with fixed[o] == 0 go through the plain sampler's arithmetic; the history rows hold the replaced values.
+ *
+ *   known        [B][L][F] values of the fixed elements, in the model's space (mean offset subtracted); elsewhere unread
+ *   fixed        uint8 [B][L][F]; a fixed element at a position >= lens[b] is FD_E_INVALID ("fixed" in fd_last_error())
+ *   known_coef   float32 [2][T+1]: keep[0..T], then spread[0..T]
+ *   known_noise  [t_start+2][B][L][F], row j = the draws of level j (row 0 is never read), or NULL (Philox)
+ * fd_sample_inpaint is fd_sample_ex plus these four (host buffers; `noise` and `known_noise` are given or NULL independently of
+ * each other).  known, fixed or known_coef NULL: FD_E_INVALID, before any device call.  A later fd_sample* on the same model
+ * is unaffected.  Options "use_graph" and "varlen", both precisions and full_history = 0, 1, k as in fd_sample. */
+int fd_sample_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
+                      const float* known, const uint8_t* fixed, const float* known_coef, const float* known_noise,
+                      uint64_t seed, int64_t seq_offset, float* out, int full_history);
+
+/* The parity hook of the above: fd_p_sample_step, then the replacement of the fixed elements at level t with the draws
+ * z_known [B][L][F] (required for t > 0; level 0 writes known's bits).  x is taken as given: no initial replacement.
+ * With wrap == 0 neither the update nor the replacement wraps. */
+int fd_p_sample_step_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
+                             const float* known, const uint8_t* fixed, const float* known_coef, const float* z_known,
+                             float* x_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
