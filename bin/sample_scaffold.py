@@ -14,7 +14,8 @@ no such script; the flags and the output tree follow bin/sample.py:
 
 --motif_residues LO HI are 0-based residue indices into the file's parsed backbone, HI exclusive.  One backbone is
 generated per length in range(*--lengths), --num times.  Single device; the model must be a local directory, as for
-bin/sample.py.  Whether the scaffolds are designable is not measured here: nothing in this repository folds a sequence.
+bin/sample.py.  --jump_length J --n_resample R (both off by default) run a resampling schedule: the run goes
+back up J noise levels and comes down again, R descents per stretch.  Whether the scaffolds are designable is not measured here: nothing in this repository folds a sequence.
 """
 import argparse
 import json
@@ -71,6 +72,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--num", "-n", type=int, default=1, help="Number of scaffolds to generate *per length*")
     parser.add_argument("--placement", type=placement, default="center",
                         help="where the motif's first residue goes: center, random (numpy's generator, seeded by --seed) or an index")
+    parser.add_argument("--jump_length", type=int, default=None,
+                        help="resampling: noise levels to go back up at every jump (default: off, the plain descent)")
+    parser.add_argument("--n_resample", type=int, default=1, help="resampling: descents per stretch of --jump_length levels (1: off)")
     parser.add_argument("-b", "--batchsize", type=int, default=512, help="Batch size to use when sampling")
     parser.add_argument("--outdir", "-o", type=str, default=os.getcwd(), help="Path to output directory")
     parser.add_argument("--seed", type=int, default=SEED, help="Random seed")
@@ -108,7 +112,13 @@ def main(argv=None) -> None:
     torch.manual_seed(args.seed)
     np.random.seed(args.seed % (2 ** 32))
     offsets = {"center": None, "random": "random"}.get(args.placement, args.placement)
-    sampled, offsets = sampling.scaffold(model, train_dset, motif, lengths, offsets=offsets, batch_size=args.batchsize)
+    resample = {}
+    n_visits = train_dset.timesteps
+    if args.jump_length is not None and args.n_resample > 1:
+        resample = dict(jump_length=args.jump_length, n_resample=args.n_resample)
+        n_visits = len(sampling.resample_schedule(train_dset.timesteps - 1, args.jump_length, args.n_resample))
+    logging.info(f"{len(lengths)} chains, {n_visits} reverse steps (visits) per chain over {train_dset.timesteps} timesteps")
+    sampled, offsets = sampling.scaffold(model, train_dset, motif, lengths, offsets=offsets, batch_size=args.batchsize, **resample)
 
     sampled_dfs = [pd.DataFrame(s, columns=names) for s in sampled]
     angles_dir = outdir / "sampled_angles"

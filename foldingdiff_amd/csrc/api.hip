@@ -1179,6 +1179,36 @@ int stage_inpaint(fd_model* m, hipStream_t s, const float* known, const uint8_t*
   return FD_OK;
 }
 
+// ---- resampling schedules: argument checks of fd_sample_inpaint_resample / fd_inpaint_jump
+uint64_t segment_seed(uint64_t seed, int s) { return seed + (uint64_t)s * 0x9E3779B97F4A7C15ull; }
+
+int check_jump_coef(float jk, float js, int jump) {
+  if (!std::isfinite(jk) || !std::isfinite(js) || jk < 0.f || jk > 1.f || js < 0.f || js > 1.f)
+    return fail(FD_E_INVALID, "jump_coef of jump %d: jk = %g, js = %g must be finite and within [0, 1]", jump, (double)jk, (double)js);
+  return FD_OK;
+}
+
+// the rules of a legal schedule; *n_jumps = the number of jumps in it
+int check_visits(const int32_t* visits, int n_visits, int t_start, const float* jump_coef, int* n_jumps) {
+  if (!visits) return fail(FD_E_INVALID, "visits is null");
+  if (n_visits < 1) return fail(FD_E_INVALID, "n_visits = %d must be positive", n_visits);
+  if (visits[0] != t_start) return fail(FD_E_INVALID, "visits[0] = %d, the run starts with step t_start = %d", visits[0], t_start);
+  int jumps = 0;
+  for (int i = 1; i < n_visits; ++i) {
+    if (visits[i] < 0 || visits[i] > t_start) return fail(FD_E_INVALID, "visits[%d] = %d outside [0, %d]", i, visits[i], t_start);
+    if (visits[i] == visits[i - 1] - 1) continue;
+    if (visits[i] < visits[i - 1])
+      return fail(FD_E_INVALID, "visits[%d] = %d follows %d: neither the next step down nor a jump up", i, visits[i], visits[i - 1]);
+    ++jumps;
+  }
+  if (visits[n_visits - 1] != 0) return fail(FD_E_INVALID, "visits[%d] = %d, the run ends with step 0", n_visits - 1, visits[n_visits - 1]);
+  if (jumps && !jump_coef) return fail(FD_E_INVALID, "jump_coef is null and the schedule has %d jumps", jumps);
+  for (int j = 0; j < jumps; ++j)
+    if (int rc = check_jump_coef(jump_coef[2 * j], jump_coef[2 * j + 1], j)) return rc;
+  *n_jumps = jumps;
+  return FD_OK;
+}
+
 }  // namespace
 
 // ---- RCCL, bound at run time (dlopen): the library has no link-time dependency on it, and a host process that already
@@ -2081,6 +2111,95 @@ int fd_sample_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int
   if (rc) return rc;
   HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
   return check_flag(m);
+}
+
+int fd_sample_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start,
+                               const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* visits,
+                               int n_visits, const float* jump_coef, uint64_t seed, int64_t seq_offset, float* out) {
+  if (int rc = check_shape(m, B, L, t_start)) return rc;
+  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  int n_jumps = 0;
+  if (int rc = check_visits(visits, n_visits, t_start, jump_coef, &n_jumps)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  int* d_lens;
+  HIP_TRY(bufs.alloc(n * 4, &d_x));
+  HIP_TRY(bufs.alloc((size_t)B * 4, &d_lens));
+  HIP_TRY(bufs.alloc(n * 4, &d_out));
+  HIP_TRY(hipMemcpy(d_x, x_init, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice));
+  if (int rc = fd_sample_begin_dev(m, d_x, d_lens, B, L, t_start, seed, seq_offset, d_out, 0, nullptr)) return rc;
+  hipStream_t s = m->stream;
+  InpaintDev ip;
+  int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip);
+  if (!rc) {
+    launch_inpaint_init(m->ws.x, ip.known, ip.fixed, nullptr, ip.coef, m->T, t_start + 1, seed, seq_offset, B, L, m->cfg.n_features,
+                        m->angle_mask, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
+  }
+  if (!rc) {
+    m->dyn_host.known = ip.known; m->dyn_host.fixed = ip.fixed; m->dyn_host.known_coef = ip.coef; m->dyn_host.known_noise = nullptr;
+  }
+  // one segment per pass: the jump that enters it (none in front of the first), then its descent.  Launches only.
+  for (int i = 0, seg = 0; !rc && i < n_visits; ++seg) {
+    int j = i + 1;
+    while (j < n_visits && visits[j] == visits[j - 1] - 1) ++j;
+    if (seg > 0) {
+      const uint64_t seed_s = segment_seed(seed, seg);
+      launch_inpaint_jump(m->ws.x, m->ws.lens, ip.known, ip.fixed, ip.coef, m->T, visits[i] + 1, jump_coef[2 * (seg - 1)],
+                          jump_coef[2 * (seg - 1) + 1], seed_s, seq_offset, B, L, m->cfg.n_features, m->angle_mask, s);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_jump: %s", hipGetErrorString(e));
+      if (!rc) rc = set_t(m, s, visits[i]);
+      m->run_t = visits[i];
+      m->dyn_host.seed = seed_s;
+    }
+    if (!rc) rc = fd_sample_steps_dev(m, j - i, nullptr, 0, nullptr);  // (re-sends dyn: the segment's seed)
+    i = j;
+  }
+  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
+  // closed like fd_sample_inpaint's run: a later run on this model starts from cleared fields, on the host and on the device
+  m->run_open = false;
+  m->run_t = -1;
+  m->dyn_host.known = nullptr; m->dyn_host.fixed = nullptr; m->dyn_host.known_coef = nullptr; m->dyn_host.known_noise = nullptr;
+  hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, m->ws.dyn, m->dyn_host);
+  HIP_TRY(hipStreamSynchronize(s));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
+  return check_flag(m);
+}
+
+int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int L, int level_to, float jk, float js,
+                    const float* known, const uint8_t* fixed, const float* known_coef, uint64_t seed, int64_t seq_offset,
+                    float* x_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (level_to < 1 || level_to > m->T) return fail(FD_E_INVALID, "level_to = %d outside [1, %d]", level_to, m->T);
+  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  if (int rc = check_jump_coef(jk, js, 0)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  Workspace& w = m->ws;
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  hipStream_t s = m->stream;
+  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  InpaintDev ip;
+  if (int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip)) return rc;
+  launch_inpaint_jump(w.x, w.lens, ip.known, ip.fixed, ip.coef, m->T, level_to, jk, js, seed, seq_offset, B, L, m->cfg.n_features,
+                      m->angle_mask, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(x_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FD_OK;
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

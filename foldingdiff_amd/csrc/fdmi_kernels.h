@@ -101,6 +101,12 @@ void launch_head_update(const UpdateArgs& a, hipStream_t s);
 void launch_inpaint_init(float* x, const float* known, const unsigned char* fixed, const float* known_noise,
                          const float* known_coef, int T, int level, unsigned long long seed, long long seq_offset, int B,
                          int L, int F, unsigned angle_mask, hipStream_t s);
+// The jump of a resampling schedule (inpaint_jump.hip): x [B][L][F] in place from its level up to `level_to` >= 1 -- fixed
+// elements as above (Philox), free ones jk * x + js * z with the draws of the step word 0x40000000 | level_to, both wrapped
+// where angular; positions l >= lens[b] are left as they are.
+void launch_inpaint_jump(float* x, const int* lens, const float* known, const unsigned char* fixed, const float* known_coef,
+                         int T, int level_to, float jk, float js, unsigned long long seed, long long seq_offset, int B, int L,
+                         int F, unsigned angle_mask, hipStream_t s);
 
 // N1: NeRF internal -> Cartesian backbone coordinates, one lane per chain, fp64.
 // Feature column of each quantity in the [B][L][F] float32 array; -1 => the reference's constant.

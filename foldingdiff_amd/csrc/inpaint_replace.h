@@ -9,6 +9,11 @@
 //                 statement (loss.hip); z = known_noise[j][o], or with known_noise null the Philox draw whose step word
 //                 is j with the top bit set (a stream disjoint from the update's own draws, whose step word is t < 2^31)
 //   level 0:      the bits of known[o]; no arithmetic, no draw
+//
+// Resampling: a jump takes a state from level a up to level b > a.  Its fixed elements are inpaint_value at
+// level b; a FREE element is wrap?(jk * x + js * z), each product and the sum rounded once, jk = sqrt(acp(b) / acp(a)),
+// js = sqrt(1 - acp(b) / acp(a)) made by the host, z = the Philox draw whose step word is b with bit 30 set: a third
+// stream, disjoint from the other two while T < 2^30.  jump_value is that statement, shared by the jump kernel and its hook.
 #pragma once
 #include "philox_normal.h"
 #include "wrap_pi.h"
@@ -23,6 +28,14 @@ __device__ __forceinline__ float inpaint_value(const float* __restrict__ known, 
   const float z = known_noise ? known_noise[(size_t)level * (size_t)noise_stride + o]
                               : philox_normal(seed, (int)(0x80000000u | (unsigned)level), seq, l, f);
   float v = __fadd_rn(__fmul_rn(coef[level], kv), __fmul_rn(coef[T + 1 + level], z));
+  if (angular) v = wrap_pi(v);
+  return v;
+}
+
+__device__ __forceinline__ float jump_value(float x, float jk, float js, int level_to, unsigned long long seed, long long seq,
+                                            int l, int f, bool angular) {
+  const float z = philox_normal(seed, (int)(0x40000000u | (unsigned)level_to), seq, l, f);
+  float v = __fadd_rn(__fmul_rn(jk, x), __fmul_rn(js, z));
   if (angular) v = wrap_pi(v);
   return v;
 }

@@ -48,6 +48,7 @@ extern "C" {
 /*    fd_loss_terms_ex, fd_pairwise_dist and fd_denoise_loss_ex (the "l1" loss, the circle penalty and the pairwise-distance
  *    term of the denoising loss) are additive too */
 /*    fd_sample_inpaint and fd_p_sample_step_inpaint (motif-conditioned sampling) are additive too */
+/*    fd_sample_inpaint_resample and fd_inpaint_jump (resampling schedules of motif-conditioned sampling) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -295,6 +296,42 @@ int fd_sample_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int
 int fd_p_sample_step_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
                              const float* known, const uint8_t* fixed, const float* known_coef, const float* z_known,
                              float* x_out);
+
+/* ---- resampling ("jump") schedules of motif-conditioned sampling: the run goes back up the noise ladder and comes down
+ * again, so that the free elements get further chances to agree with the fixed ones (Lugmayr et al. 2022, RePaint).
+ *
+ * Visits.  visits[0 .. n_visits) is the step index t of every reverse step in the order run.  Legal: visits[0] == t_start,
+ * visits[n_visits - 1] == 0, 0 <= visits[i] <= t_start, and for i > 0 either visits[i] == visits[i-1] - 1 (descent) or
+ * visits[i] >= visits[i-1] (a JUMP: the state step visits[i-1] left at level a = visits[i-1] is forward-noised to level
+ * b = visits[i] + 1 > a before step visits[i] runs).
+ *
+ * Segments and seeds.  Segment s is the run of visits behind the s-th jump (s = 0 in front of the first).  Every draw of
+ * segment s -- the update's, the replacement's, and the jump that enters it -- has the Philox key
+ * seed_s = seed + s * 0x9E3779B97F4A7C15 (mod 2^64); seed_0 = seed, so a schedule without a jump is fd_sample_inpaint's run
+ * bit for bit, and a step index visited again draws fresh noise.
+ *
+ * The jump to level b entering segment s, for every element o = (i, l, f) with l < lens[i]:
+ *   fixed[o] != 0:  the replacement at level b with seed_s (the known value noised afresh)
+ *   otherwise:      jk * x[o] + js * z, each product and the sum rounded once, wrapped to [-pi, pi) where feature f is an
+ *                   angle; z = the Philox draw of (seed_s, 0x40000000 | b, seq_offset + i, l, f), a third stream (T < 2^30)
+ * Positions l >= lens[i] are left as they are.  jump_coef [n_jumps][2] = (jk, js) per jump in the order met:
+ * jk = sqrt(acp(b) / acp(a)), js = sqrt(1 - acp(b) / acp(a)), acp(0) = 1, acp(j) = alphas_cumprod[j-1]; each finite and
+ * within [0, 1].  NULL is allowed when the schedule has no jump.
+ *
+ * Both noise streams come from Philox; `out` [B][L][F] receives the final state only (the history of a non-monotone run is
+ * not built).  Between the upload and the download the host issues launches only; the captured step graph is the plain
+ * sampler's.  An illegal schedule (fd_last_error() names the index), a NULL visits, n_visits < 1, a NULL jump_coef with a
+ * jump, a jk / js outside [0, 1] or anything fd_sample_inpaint rejects: FD_E_INVALID before any device call, `out` untouched.
+ * Options "use_graph" and "varlen" and both precisions as in fd_sample_inpaint; a later fd_sample* is unaffected. */
+int fd_sample_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start,
+                               const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* visits,
+                               int n_visits, const float* jump_coef, uint64_t seed, int64_t seq_offset, float* out);
+
+/* The parity hook of one jump: x_out = x taken to level level_to (1 .. T) with (jk, js) and the Philox key `seed` (the
+ * caller passes the segment's seed).  x is taken as given. */
+int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int L, int level_to, float jk, float js,
+                    const float* known, const uint8_t* fixed, const float* known_coef, uint64_t seed, int64_t seq_offset,
+                    float* x_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
