@@ -1,8 +1,9 @@
 // C-ABI host side of libfdmi.so, the part that holds a model: model state, weight packing, workspaces, the launch plan of
-// a timestep, the hipGraph-captured reverse-diffusion loop, the profile / debug / option entries and RCCL.  The entry
-// points that take a device_id instead of an fd_model live beside it: api_structures.hip (fd_nerf, fd_internal_coords,
-// fd_superpose_rmsd, fd_tm_score, fd_annotate_sse, fd_tm_align) and api_hooks.hip (the fd_test_* hooks); what the three
-// share -- the error string, HIP_TRY, the owner of call-scoped device buffers -- is host_common.h.
+// a timestep, the captured step graph, the profile / debug / option entries and RCCL.  The entry points that run the model
+// (forward, loss, sampling) are api_run.hip, which sees this source through model.h.  The entry points that take a
+// device_id instead of an fd_model live beside them: api_structures.hip (fd_nerf, fd_internal_coords, fd_superpose_rmsd,
+// fd_tm_score, fd_annotate_sse, fd_tm_align) and api_hooks.hip (the fd_test_* hooks); what the four share -- the error
+// string, HIP_TRY, the owner of call-scoped device buffers -- is host_common.h.
 // Boundary: include/fdmi.h (each entry point cites the reference function it replaces).
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -21,6 +22,7 @@
 #include "fdmi_kernels.h"
 #include "host_common.h"
 #include "launch_common.h"
+#include "model.h"
 
 using namespace fdmi;
 
@@ -40,171 +42,11 @@ int fdmi::fail(int code, const char* fmt, ...) {
 
 namespace {
 
-struct HostTensor {
-  std::vector<float> data;
-  std::vector<int64_t> shape;
-};
-
-// split-precision image of one weight matrix (gemm_f16x3.hip)
-struct SplitW {
-  void* p = nullptr;
-  float scale = 1.f;
-};
-
-struct LayerDev {
-  SplitW demb_s;  // distance table as an fp16 hi|lo row image (row-image attention)
-  // row-image path: weight images padded to 384 rows, and the (static, power-of-two) scales of this layer's
-  // activation images -- derived from norm bounds of the weights at fd_finalize, so nothing can overflow fp16
-  SplitW wqk_i, wv_i, wqkv_i, wo_i, wi_i, wd_i;  // wqkv_i: q | k | v rows in one image (n_heads % 6 == 0: one launch)
-  SplitW wsa_i;  // the same q | k | v weights ordered per head for the 32-row fused projection + attention kernel (seq_attn.hip), or null
-  SplitW wff_i;    // intermediate.dense + output.dense as ONE stream of ring stages (ffn16.hip), or null; scale = the first dense's
-  float wff_scale_dn = 1.f;  // ... the second dense's
-  SplitW wtail_i;  // attention.output.dense's stages in front of that stream (ffn16.hip TAIL), or null; scale = attention.output.dense's
-  SplitW wsa16_i;  // ... for the 16-row kernel (seq_attn16.hip: rows of a head permuted into its operand tiles), or null
-  float *bqk = nullptr, *bv = nullptr;  // bias slices of bqkv
-  float s_h = 1.f, s_q = 1.f, s_k = 1.f, s_v = 1.f, s_a = 1.f, s_g = 1.f;
-  float *wqkv = nullptr, *bqkv = nullptr, *demb = nullptr;
-  float *wo = nullptr, *bo = nullptr, *ln1g = nullptr, *ln1b = nullptr;
-  float *wi = nullptr, *bi = nullptr, *wd = nullptr, *bd = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-};
-
-enum KClass {
-  KC_EMBED = 0, KC_GEMM_QKV, KC_GEMM_V, KC_ATTN, KC_GEMM_OUT, KC_LN1, KC_GEMM_UP, KC_GEMM_DOWN, KC_LN2, KC_GEMM_HEAD,
-  KC_HEAD_UPDATE, KC_ADVANCE, KC_SEQ_ATTN, KC_FFN, KC_TAIL, KC_COUNT
-};
-const char* const kClassName[KC_COUNT] = {
-    "embed_ln_time", "gemm_qkv", "gemm_v", "attention", "gemm_attn_out", "layernorm_attn", "gemm_ffn_up",
-    "gemm_ffn_down", "layernorm_ffn", "gemm_head_dense1", "head_update_wrap", "step_advance", "qkv_attention_fused", "ffn_fused", "attn_out_ffn_fused"};
-
-// The launch sequence of one timestep: every choice between kernels, made once per step (plan_step) from the model's options,
-// the environment overrides and the workspace's shape.  run_step launches from it; a captured graph is current for as long as
-// the plan it was captured with is the plan the options lead to (graph_current).
-struct StepPlan {
-  enum Attn { ATTN_QKV, ATTN_QK_VT, ATTN_FUSED16, ATTN_FUSED32 };  // q | k | v in one launch; q | k + v^T; projection + attention fused:
-                                                                   // seq_attn16.hip (16-row waves) / seq_attn.hip (32-row waves)
-  enum Ffn { FFN_GEMMS, FFN_FUSED, FFN_TAIL };  // two GEMMs; ffn16.hip; ffn16.hip with BertSelfOutput in front of it in the same launch
-  bool img = false;       // the row-image kernels (FD_PREC_F16X3), else the fp32 ones
-  bool fuse_ln = false;   // fp32 path: the LN-fused GEMMs
-  int attn = ATTN_QKV;
-  bool attn_gen = false;  // attention_gen.hip (arbitrary key masks, head sizes 64 / 96 / 128), else attention_img.hip
-  int ffn = FFN_GEMMS;
-  bool split_ln = false;  // d_model > 384: a LayerNorm row does not fit one 384-column tile -- fp32 rows, then the LayerNorm kernel
-  int tail_qk = 0, tail_d = 0, tail_ff = 0;  // GemmImgArgs::tail of the GEMMs of N = 3 d (2 d when v^T is its own launch), d and d_ff
-  bool fused_attn() const { return attn == ATTN_FUSED16 || attn == ATTN_FUSED32; }
-  bool operator==(const StepPlan& o) const {
-    return std::tie(img, fuse_ln, attn, attn_gen, ffn, split_ln, tail_qk, tail_d, tail_ff) ==
-           std::tie(o.img, o.fuse_ln, o.attn, o.attn_gen, o.ffn, o.split_ln, o.tail_qk, o.tail_d, o.tail_ff);
-  }
-};
-
-struct Workspace {
-  int B = 0, L = 0;
-  float *x = nullptr, *eps = nullptr, *h = nullptr, *qkv = nullptr, *ctx = nullptr, *a = nullptr, *tmp = nullptr,
-        *g = nullptr, *z = nullptr;
-  int* lens = nullptr;
-  int* t_dev = nullptr;  // [0] step index; the row-image kernels also use [1] (see rowwise_img.hip)
-  int* t_seq = nullptr;  // [B] one timestep per sequence (fd_forward_t, fd_denoise_loss)
-  float* loss_in = nullptr;     // fd_denoise_loss's one upload: x0 | noise ([B][L][F] each) | keep | spread | t | lens ([B] each); allocated on first use
-  double* loss_sums = nullptr;  // [B][F], with it
-  float* loss_ex_in = nullptr;  // fd_denoise_loss_ex's one upload: x0 | noise | corrupted ([B][L][F] each) | keep | spread | coef | t | lens ([B] each)
-  double* loss_ex_out = nullptr;  // its one download, in 8-byte words: sums | turns ([B][F] each) | pair_sums | pairs ([B] each)
-  UpdateDyn* dyn = nullptr;
-  // motif-conditioned sampling (fd_sample_inpaint, fd_p_sample_step_inpaint), allocated on first use:
-  // known | z_known ([B][L][F] floats each) | known_coef ([2][T+1] floats) | fixed ([B][L][F] bytes)
-  float* inpaint = nullptr;
-  // row-image path (fdmi_kernels.h): images, per-(sequence, head) q / k / v^T, the token-row table
-  bool img = false;
-  int cap = 0, LPK = 0, LTOT = 0, NKT = 0;  // rows128 capacity = ceil128(B * ceil8(L)); key-tile geometry
-  unsigned char *himg = nullptr, *aimg = nullptr, *cimg = nullptr, *gimg = nullptr, *qbuf = nullptr, *kbuf = nullptr,
-                *vbuf = nullptr, *trash = nullptr;
-  int2* rowinfo = nullptr;
-  int *seq_row0 = nullptr, *nrow = nullptr, *dims = nullptr, *flag = nullptr;
-  unsigned char* kmask = nullptr;  // [B][L] explicit key mask of fd_forward_ex (allocated on first use)
-  int* pos_ids = nullptr;          // [B][L] explicit position ids of fd_forward_ex (allocated on first use)
-  int grids[3] = {0, 0, 0};  // x-grid of the latest launch of seq_attn16 | seq_attn | ffn16 on this workspace (fd_debug_read "grids")
-  hipGraphExec_t graph = nullptr;
-  StepPlan graph_plan;  // the launch sequence `graph` was captured with
-  uint64_t last_use = 0;
-  void release() {
-    if (graph) (void)hipGraphExecDestroy(graph);
-    graph = nullptr;
-    for (void* p : {(void*)x, (void*)eps, (void*)h, (void*)qkv, (void*)ctx, (void*)a, (void*)tmp, (void*)g, (void*)z,
-                    (void*)lens, (void*)t_dev, (void*)t_seq, (void*)loss_in, (void*)loss_sums, (void*)loss_ex_in, (void*)loss_ex_out, (void*)dyn, (void*)inpaint, (void*)himg, (void*)aimg, (void*)cimg, (void*)gimg,
-                    (void*)qbuf, (void*)kbuf, (void*)vbuf, (void*)trash, (void*)rowinfo, (void*)seq_row0, (void*)nrow,
-                    (void*)dims, (void*)flag, (void*)kmask, (void*)pos_ids})
-      if (p) (void)hipFree(p);
-    *this = Workspace();
-  }
-};
-
 // debug cycle stamps (FDMI_STAMPS=1), one table per kernel family back to back (in 8-byte words): the GEMMs' [5][8][64][6] first
 constexpr long long kStampAttn = 5 * 8 * 64 * 6;                     // attention [4][64][8]
 constexpr long long kStampSeqAttn = kStampAttn + 4 * 64 * 8;          // fused attention [4][64][16] (+ 32 K floats of register dumps, seq_attn.hip FDMI_SA_DUMP)
 constexpr long long kStampFfn = kStampSeqAttn + 4 * 64 * 16 + 16384;  // ffn16.hip's [8][16][16]
 constexpr long long kStampWords = kStampFfn + 8 * 16 * 16;
-
-struct PendingEvent {
-  int cls;
-  hipEvent_t e0, e1;
-};
-
-}  // namespace
-
-struct fd_model {
-  fd_config cfg;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::map<std::string, HostTensor> host;
-  bool finalized = false;
-  int T = 0;
-  int precision = 0;
-  unsigned angle_mask = 0;
-  // device weights
-  std::vector<void*> allocs;
-  float *w_in = nullptr, *b_in = nullptr, *pos_emb = nullptr, *emb_g = nullptr, *emb_b = nullptr;
-  std::vector<LayerDev> layers;
-  float *hd_w1 = nullptr, *hd_b1 = nullptr, *hd_g = nullptr, *hd_b = nullptr, *hd_w2 = nullptr, *hd_b2 = nullptr;
-  SplitW hd_w1_i;
-  float s_hfinal = 1.f, s_hg = 1.f;  // row-image scales: last hidden state, head activation
-  bool img = false;                  // FD_PREC_F16X3 runs on the row-image kernels
-  float *coef = nullptr, *time_table = nullptr;
-  // options
-  int fuse_ln = -1;  // -1 auto: LN-fused GEMMs with fp16x3 (measured 9.37 vs 10.15 ms/step), not with fp32 (slower there)
-  int use_graph = 1;
-  unsigned long long* stamps = nullptr;  // debug cycle stamps (FDMI_STAMPS=1): gemm [5][8][64][6], attention [4][64][8], fused attention [4][64][16]
-  int debug_stop = 0;  // row-image path: stop a step after this many launches (debug dumps; 0 = off)
-  int debug_layer = 0; // layer whose scales fd_debug_read uses
-  int debug_grid = 0;  // > 0: at most this many workgroups for the persistent fused kernels (tests of their item-to-item code; 0 = off)
-  int split_qkv = 0; // row-image path: 1 = q | k and v^T as two launches even when one would do (A/B, tests)
-  int varlen = 0;    // row-image path: only the first lens[b] positions of a sequence are token rows
-  int fuse_attn = -1;  // row-image path: q | k | v projection + attention as ONE kernel per sequence: -1 auto (seq_attn16.hip for padded rows
-                     // of 97 .. 128 positions in whole rounds of the CUs), 0 never, 1 seq_attn16.hip wherever it applies (any L <= 128, packed
-                     // rows too), 2 seq_attn.hip (32-row waves) wherever it applies (97 .. 128 positions)
-  int fuse_ffn = -1;   // row-image path: BertIntermediate + BertOutput as ONE kernel (ffn16.hip): -1 auto (whole rounds of 128-row passes: 2),
-                     // 0 never, 1 wherever the kernel applies, 2 with BertSelfOutput in front of it in the same launch
-  int rows_hint = 0;   // packed rows: the caller's exact count of token rows of the next calls (sum of the lengths rounded up to 8), or 0 = unknown;
-                     // the auto choices of the fused kernels then go by it instead of the bound B * ceil8(L) (the count itself lives in device memory)
-  // workspaces (buffers + captured graph) are kept per (B, L): sample_length()-driven sampling and ragged chunks
-  // alternate between a few shapes
-  std::vector<Workspace> cache;
-  uint64_t use_clock = 0;
-  Workspace ws;      // the current one (moved in and out of `cache`)
-  void* comm = nullptr;  // ncclComm_t (fd_comm_init)
-  int comm_world = 0, comm_rank = 0;
-  UpdateDyn dyn_host{};  // per-run values of the sampling loop in progress (fd_sample_begin_dev .. fd_sample_end_dev)
-  int run_t = -1;        // next timestep of that run (-1: none left)
-  bool run_open = false; // between fd_sample_begin_dev and fd_sample_end_dev, with no other call on the model in between
-  int run_B = 0, run_L = 0;  // its shape: fd_sample_steps_dev / _end_dev refuse to run on another workspace
-  // profiling
-  int profile_every = 0;
-  double prof_ms[KC_COUNT] = {0};
-  int64_t prof_n[KC_COUNT] = {0};
-  double prof_flops[KC_COUNT] = {0}, prof_bytes[KC_COUNT] = {0};
-  std::vector<PendingEvent> pending;
-  std::vector<hipEvent_t> event_pool;
-};
-
-namespace {
 
 int dev_alloc(fd_model* m, float** out, size_t n_floats) {
   void* p = nullptr;
@@ -509,7 +351,9 @@ size_t kHeadBytes(const fd_config& c) { return (size_t)(c.d_model / c.n_heads) *
 int head_dim(const fd_config& c) { return c.d_model / c.n_heads; }
 int sub_heads(const fd_config& c) { return c.d_model / 32; }
 
-int ensure_ws(fd_model* m, int B, int L) {
+}  // namespace
+
+int fdmi::ensure_ws(fd_model* m, int B, int L) {
   Workspace& w = m->ws;
   // every entry point that takes a workspace comes through here: a sampling run begun earlier (fd_sample_begin_dev) is over --
   // its state (x, the step counter) is about to be overwritten or parked; fd_sample_begin_dev re-opens one afterwards
@@ -641,23 +485,7 @@ int ensure_ws(fd_model* m, int B, int L) {
   return FD_OK;
 }
 
-struct StepMode {
-  bool forward_only;   // write eps only (fd_forward)
-  bool use_dyn;        // read per-call values from ws.dyn (sampling loop)
-  bool advance;        // decrement *t_dev at the end
-  bool profile;        // bracket every kernel with events
-  // by-value per-call values when !use_dyn (fd_p_sample_step)
-  const float* noise = nullptr;
-  int t_start = 0;
-  bool no_wrap = false;  // p_sample alone, without the loop's wrap
-  const unsigned char* kmask = nullptr;  // fd_forward_ex: [B][L] key mask of any pattern (device), else null: prefix masks from lens
-  const int* pos_ids = nullptr;          // fd_forward_ex: [B][L] position ids of the absolute position embedding (device)
-  // fd_p_sample_step_inpaint: the replacement's arrays (device; z_known = the one slab of level t), null otherwise
-  const float *known = nullptr, *known_coef = nullptr, *z_known = nullptr;
-  const unsigned char* fixed = nullptr;
-  const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
-  bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
-};
+namespace {
 
 int prof_begin(fd_model* m, int cls, hipStream_t s, bool on) {
   if (!on) return FD_OK;
@@ -726,11 +554,13 @@ const EnvOverrides& env_overrides() {
   return env;
 }
 
+}  // namespace
+
 // Which kernels make up a timestep on workspace `w` (the model's device is current).  key_mask: fd_forward_ex's arbitrary key mask.
 // The weight images every layer has are asked of layer 0 (fd_finalize uploads the same set for every layer).
 // dyn_rows: the row count of the launches is decided on the device (fd_ar_sample's growing prefix), as with option "varlen"; it
 // changes the GEMM tails only.
-StepPlan plan_step(const fd_model* m, const Workspace& w, bool key_mask, bool dyn_rows = false) {
+StepPlan fdmi::plan_step(const fd_model* m, const Workspace& w, bool key_mask, bool dyn_rows) {
   StepPlan p;
   p.img = w.img;
   if (!p.img) {
@@ -786,6 +616,8 @@ StepPlan plan_step(const fd_model* m, const Workspace& w, bool key_mask, bool dy
   return p;
 }
 
+namespace {
+
 // the arguments of the head + p_sample update launch that both paths share (the caller adds the head's input)
 UpdateArgs fill_update(const fd_model* m, const Workspace& w, const StepMode& mode) {
   UpdateArgs u;
@@ -822,7 +654,9 @@ UpdateArgs fill_update(const fd_model* m, const Workspace& w, const StepMode& mo
   return u;
 }
 
-int run_step_img(fd_model* m, hipStream_t s, const StepMode& mode, const StepPlan& plan);
+}  // namespace
+
+namespace fdmi {
 
 // One reverse-diffusion step = BertForDiffusionBase.forward (modelling.py:384-484) + the
 // p_sample update and wrap (sampling.py:62-75, :119-130), as a fixed kernel sequence.
@@ -1078,6 +912,8 @@ int prepare_rows(fd_model* m, hipStream_t s, int packed) {
 __global__ void set_int_kernel(int* p, int v) { *p = v; }
 __global__ void set_dyn_kernel(UpdateDyn* p, UpdateDyn v) { *p = v; }
 
+void send_dyn(fd_model* m, hipStream_t s, const UpdateDyn& v) { hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, m->ws.dyn, v); }
+
 int set_t(fd_model* m, hipStream_t s, int t) {
   hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, s, m->ws.t_dev, t);
   HIP_TRY(hipGetLastError());
@@ -1098,7 +934,7 @@ int check_shape(fd_model* m, int B, int L, int t) {
 
 // the workspace's captured graph still holds the launch sequence the model's options ask for (an option change that leads to
 // the same sequence -- another rows_hint on the same side of the automatic choice -- keeps the graph)
-static bool graph_current(const fd_model* m, const Workspace& w) { return w.graph && w.graph_plan == plan_step(m, w, false); }
+bool graph_current(const fd_model* m, const Workspace& w) { return w.graph && w.graph_plan == plan_step(m, w, false); }
 
 int ensure_graph(fd_model* m) {
   Workspace& w = m->ws;
@@ -1146,70 +982,7 @@ int check_flag(fd_model* m) {
   return fail(FD_E_NONFINITE, "the model produced a non-finite value (inf/NaN in the predicted noise)");
 }
 
-// ---- motif-conditioned sampling: argument checks (before the first device call) and the workspace's staging buffer
-int check_inpaint(const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* lens, int B, int L, int F) {
-  if (!fixed) return fail(FD_E_INVALID, "fixed is null");
-  if (!known) return fail(FD_E_INVALID, "known is null (fixed is given)");
-  if (!known_coef) return fail(FD_E_INVALID, "known_coef is null");
-  for (int b = 0; b < B; ++b)
-    for (int l = lens[b]; l < L; ++l)
-      for (int f = 0; f < F; ++f)
-        if (fixed[((size_t)b * L + l) * F + f])
-          return fail(FD_E_INVALID, "fixed element beyond a length: sequence %d position %d feature %d, lens[%d] = %d", b, l, f, b, lens[b]);
-  return FD_OK;
-}
-
-struct InpaintDev {
-  float *known, *z_known, *coef;
-  unsigned char* fixed;
-};
-
-// uploads known / fixed / known_coef into the current workspace's staging buffer (allocated on first use), stream-ordered on s
-int stage_inpaint(fd_model* m, hipStream_t s, const float* known, const uint8_t* fixed, const float* known_coef, InpaintDev* d) {
-  Workspace& w = m->ws;
-  const size_t n = (size_t)w.B * w.L * m->cfg.n_features, nc = 2 * ((size_t)m->T + 1);
-  if (!w.inpaint) HIP_TRY(hipMalloc((void**)&w.inpaint, (2 * n + nc) * 4 + n));
-  d->known = w.inpaint;
-  d->z_known = w.inpaint + n;
-  d->coef = w.inpaint + 2 * n;
-  d->fixed = reinterpret_cast<unsigned char*>(w.inpaint + 2 * n + nc);
-  HIP_TRY(hipMemcpyAsync(d->known, known, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d->coef, known_coef, nc * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d->fixed, fixed, n, hipMemcpyHostToDevice, s));
-  return FD_OK;
-}
-
-// ---- resampling schedules: argument checks of fd_sample_inpaint_resample / fd_inpaint_jump
-uint64_t segment_seed(uint64_t seed, int s) { return seed + (uint64_t)s * 0x9E3779B97F4A7C15ull; }
-
-int check_jump_coef(float jk, float js, int jump) {
-  if (!std::isfinite(jk) || !std::isfinite(js) || jk < 0.f || jk > 1.f || js < 0.f || js > 1.f)
-    return fail(FD_E_INVALID, "jump_coef of jump %d: jk = %g, js = %g must be finite and within [0, 1]", jump, (double)jk, (double)js);
-  return FD_OK;
-}
-
-// the rules of a legal schedule; *n_jumps = the number of jumps in it
-int check_visits(const int32_t* visits, int n_visits, int t_start, const float* jump_coef, int* n_jumps) {
-  if (!visits) return fail(FD_E_INVALID, "visits is null");
-  if (n_visits < 1) return fail(FD_E_INVALID, "n_visits = %d must be positive", n_visits);
-  if (visits[0] != t_start) return fail(FD_E_INVALID, "visits[0] = %d, the run starts with step t_start = %d", visits[0], t_start);
-  int jumps = 0;
-  for (int i = 1; i < n_visits; ++i) {
-    if (visits[i] < 0 || visits[i] > t_start) return fail(FD_E_INVALID, "visits[%d] = %d outside [0, %d]", i, visits[i], t_start);
-    if (visits[i] == visits[i - 1] - 1) continue;
-    if (visits[i] < visits[i - 1])
-      return fail(FD_E_INVALID, "visits[%d] = %d follows %d: neither the next step down nor a jump up", i, visits[i], visits[i - 1]);
-    ++jumps;
-  }
-  if (visits[n_visits - 1] != 0) return fail(FD_E_INVALID, "visits[%d] = %d, the run ends with step 0", n_visits - 1, visits[n_visits - 1]);
-  if (jumps && !jump_coef) return fail(FD_E_INVALID, "jump_coef is null and the schedule has %d jumps", jumps);
-  for (int j = 0; j < jumps; ++j)
-    if (int rc = check_jump_coef(jump_coef[2 * j], jump_coef[2 * j + 1], j)) return rc;
-  *n_jumps = jumps;
-  return FD_OK;
-}
-
-}  // namespace
+}  // namespace fdmi
 
 // ---- RCCL, bound at run time (dlopen): the library has no link-time dependency on it, and a host process that already
 // carries an RCCL (PyTorch does) shares that instance.  Only what the single gather of SURVEY 8(e) needs.
@@ -1552,685 +1325,6 @@ int fd_fused_attn_supported(fd_model* m, int L) {
   const LayerDev& lw = m->layers[0];
   if (m->fuse_attn == 2) return lw.wsa_i.p && seq_attn_supported(c.d_model, c.n_heads, L, c.max_pos) ? 1 : 0;
   return lw.wsa16_i.p && seq_attn16_supported(c.d_model, c.n_heads, L, c.max_pos) ? 1 : 0;
-}
-
-int fd_forward(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float* eps_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !eps_out) return fail(FD_E_INVALID, "null argument");
-  if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  hipStream_t s = m->stream;
-  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  if (int rc = prepare_rows(m, s, 0)) return rc;  // the forward defines every position, masked ones included
-  if (int rc = set_t(m, s, t)) return rc;
-  StepMode mode{};
-  mode.forward_only = true;
-  if (int rc = run_step(m, s, mode)) return rc;
-  HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-// every t[b] of a per-sequence timestep vector lies in [0, T)
-static int check_t_seq(const fd_model* m, const int32_t* t, int B) {
-  for (int b = 0; b < B; ++b)
-    if (t[b] < 0 || t[b] >= m->T) return fail(FD_E_INVALID, "timestep t[%d]=%d outside [0, %d)", b, t[b], m->T);
-  return FD_OK;
-}
-
-int fd_forward_t(fd_model* m, const float* x, const int32_t* t, const int32_t* lens, int B, int L, float* eps_out) {
-  if (int rc = check_shape(m, B, L, 0)) return rc;
-  if (!x || !t || !lens || !eps_out) return fail(FD_E_INVALID, "null argument");
-  if (int rc = check_t_seq(m, t, B)) return rc;
-  if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  hipStream_t s = m->stream;
-  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.t_seq, t, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  if (int rc = prepare_rows(m, s, 0)) return rc;  // the forward defines every position, masked ones included
-  StepMode mode{};
-  mode.forward_only = true;
-  mode.t_seq = w.t_seq;
-  if (int rc = run_step(m, s, mode)) return rc;
-  HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-// the arguments fd_ar_forward and fd_ar_sample share, all checked before the first HIP call
-static int check_ar(fd_model* m, const void* x, const int32_t* seq_lengths, const void* out, int B, int L, const char* who) {
-  if (int rc = check_shape(m, B, L, 0)) return rc;
-  if (!x || !seq_lengths || !out) return fail(FD_E_INVALID, "null argument");
-  if (!m->img)
-    return fail(FD_E_UNSUPPORTED, "%s: the autoregressive baseline runs on the row-image kernels only; finalize the model with "
-                "FD_PREC_F16X3 (the exact-fp32 mode has no autoregressive embedding)", who);
-  for (int b = 0; b < B; ++b)  // the length indexes the table fd_finalize was given in place of a timestep
-    if (seq_lengths[b] < 0 || seq_lengths[b] >= m->T)
-      return fail(FD_E_INVALID, "seq_lengths[%d]=%d outside [0, %d)", b, seq_lengths[b], m->T);
-  return FD_OK;
-}
-
-int fd_ar_forward(fd_model* m, const float* x, const int32_t* seq_lengths, const int32_t* key_lens, int B, int L, float* out) {
-  if (int rc = check_ar(m, x, seq_lengths, out, B, L, "fd_ar_forward")) return rc;
-  if (!key_lens) return fail(FD_E_INVALID, "null argument");
-  if (int rc = check_lens(key_lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  hipStream_t s = m->stream;
-  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, key_lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.t_seq, seq_lengths, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  if (int rc = prepare_rows(m, s, 0)) return rc;  // the forward defines every position, masked ones included
-  StepMode mode{};
-  mode.forward_only = true;
-  mode.t_seq = w.t_seq;
-  mode.ar = true;
-  if (int rc = run_step(m, s, mode)) return rc;
-  HIP_TRY(hipMemcpyAsync(out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-int fd_ar_sample(fd_model* m, const float* seed, const int32_t* seq_lengths, int B, int L, int num_seed, float* out) {
-  if (int rc = check_ar(m, seed, seq_lengths, out, B, L, "fd_ar_sample")) return rc;
-  if (num_seed < 1)  // (no seed: the first step's keys would all be masked)
-    return fail(FD_E_INVALID, "num_seed=%d must be at least 1", num_seed);
-  int longest = 0;
-  for (int b = 0; b < B; ++b) {
-    if (seq_lengths[b] > L) return fail(FD_E_INVALID, "seq_lengths[%d]=%d exceeds L=%d", b, seq_lengths[b], L);
-    longest = seq_lengths[b] > longest ? seq_lengths[b] : longest;
-  }
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const int F = m->cfg.n_features;
-  const size_t n = (size_t)B * L * F, nb = (size_t)B;
-  hipStream_t s = m->stream;
-  // ONE upload, seed | seq_lengths, through fd_denoise_loss's staging buffer (allocated at that entry's size, so that either may
-  // come first).  The staging vector is pageable memory of this frame: a blocking copy, behind whatever is left on the stream
-  if (!w.loss_in) HIP_TRY(hipMalloc((void**)&w.loss_in, (2 * n + 4 * nb) * 4));
-  std::vector<float> stage(n + nb, 0.f);
-  memcpy(stage.data(), seed, n * 4);
-  memcpy(stage.data() + n, seq_lengths, nb * 4);
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(w.loss_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpyAsync(w.x, w.loss_in, n * 4, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.t_seq, w.loss_in + n, nb * 4, hipMemcpyDeviceToDevice, s));
-  // Step i is a forward over the rows 0 .. i of every sequence with the keys 0 .. i-1 unmasked (rows > i are masked keys and
-  // queries nobody reads: they can influence nothing); its head writes eps[b][0 .. i], and row i of it becomes x[b][i].  The
-  // row count grows on the device, so the GEMMs run their slice-capable instantiation; everything else is plan_step's choice
-  const StepPlan plan = plan_step(m, w, false, true);
-  StepMode mode{};
-  mode.forward_only = true;
-  mode.t_seq = w.t_seq;
-  mode.ar = true;
-  auto tail = [&](int copy_pos, int rows_next) -> int {
-    launch_ar_step(w.x, w.eps, B, L, F, copy_pos, rows_next, w.cap, w.lens, w.nrow, w.seq_row0, w.rowinfo, w.dims, s);
-    HIP_TRY(hipGetLastError());
-    return FD_OK;
-  };
-  if (num_seed < longest)
-    if (int rc = tail(-1, num_seed + 1)) return rc;
-  for (int i = num_seed; i < longest; ++i) {
-    if (int rc = run_step_img(m, s, mode, plan)) return rc;
-    if (int rc = tail(i, i + 1 < longest ? i + 2 : 0)) return rc;
-  }
-  HIP_TRY(hipMemcpyAsync(out, w.x, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-int fd_denoise_loss(fd_model* m, const float* x0, const float* noise, const int32_t* t, const float* keep, const float* spread,
-                    const int32_t* lens, int B, int L, float beta_ang, float beta_lin, double* sums, float* corrupted_out,
-                    float* eps_out) {
-  if (int rc = check_shape(m, B, L, 0)) return rc;
-  if (!x0 || !noise || !t || !lens || !sums) return fail(FD_E_INVALID, "null argument");
-  if ((keep == nullptr) != (spread == nullptr)) return fail(FD_E_INVALID, "null argument: keep and spread go together");
-  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
-  if (int rc = check_t_seq(m, t, B)) return rc;
-  if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const int F = m->cfg.n_features;
-  const size_t n = (size_t)B * L * F, nb = (size_t)B;
-  hipStream_t s = m->stream;
-  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
-  if (!w.loss_in) HIP_TRY(hipMalloc((void**)&w.loss_in, (2 * n + 4 * nb) * 4));
-  if (!w.loss_sums) HIP_TRY(hipMalloc((void**)&w.loss_sums, nb * F * 8));
-  // ONE upload: x0 | noise | keep | spread | t | lens, staged back to back.  The staging vector is pageable memory of this
-  // frame, so the copy is a blocking one, behind whatever an earlier asynchronous entry point left on the model's stream
-  std::vector<float> stage(2 * n + 4 * nb, 0.f);
-  memcpy(stage.data(), x0, n * 4);
-  memcpy(stage.data() + n, noise, n * 4);
-  if (keep) {
-    memcpy(stage.data() + 2 * n, keep, nb * 4);
-    memcpy(stage.data() + 2 * n + nb, spread, nb * 4);
-  }
-  memcpy(stage.data() + 2 * n + 2 * nb, t, nb * 4);
-  memcpy(stage.data() + 2 * n + 3 * nb, lens, nb * 4);
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(w.loss_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-  const float *x0_dev = w.loss_in, *noise_dev = w.loss_in + n, *keep_dev = w.loss_in + 2 * n, *spread_dev = keep_dev + nb;
-  HIP_TRY(hipMemcpyAsync(w.t_seq, w.loss_in + 2 * n + 2 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, w.loss_in + 2 * n + 3 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
-  if (keep) {  // q(x_t | x_0) on the device, with the wrap flags fd_finalize was given
-    launch_q_sample(x0_dev, noise_dev, keep_dev, spread_dev, w.x, B, L, F, m->angle_mask, s);
-    HIP_TRY(hipGetLastError());
-  } else {     // x0 is x_t already
-    HIP_TRY(hipMemcpyAsync(w.x, x0_dev, n * 4, hipMemcpyDeviceToDevice, s));
-  }
-  if (int rc = prepare_rows(m, s, 0)) return rc;
-  StepMode mode{};
-  mode.forward_only = true;
-  mode.t_seq = w.t_seq;
-  if (int rc = run_step(m, s, mode)) return rc;
-  launch_loss_terms(w.eps, noise_dev, w.lens, B, L, F, m->angle_mask, beta_ang, beta_lin, w.loss_sums, nullptr, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(sums, w.loss_sums, nb * F * 8, hipMemcpyDeviceToHost, s));
-  if (corrupted_out) HIP_TRY(hipMemcpyAsync(corrupted_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
-  if (eps_out) HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-int fd_denoise_loss_ex(fd_model* m, const float* x0, const float* corrupted, const float* noise, const int32_t* t,
-                       const float* keep, const float* spread, const int32_t* lens, int B, int L, int kind, float beta_ang,
-                       float beta_lin, const float* coef, const int32_t* feat_idx, double* sums, int64_t* turns,
-                       double* pair_sums, int64_t* pairs, float* corrupted_out, float* eps_out) {
-  if (int rc = check_shape(m, B, L, 0)) return rc;
-  if (!x0 || !noise || !t || !lens || !sums) return fail(FD_E_INVALID, "null argument");
-  if ((keep == nullptr) != (spread == nullptr)) return fail(FD_E_INVALID, "null argument: keep and spread go together");
-  if (!corrupted && !keep) return fail(FD_E_INVALID, "null argument: without corrupted the device noises x0 and needs keep and spread");
-  if (kind != 0 && kind != 1) return fail(FD_E_INVALID, "kind=%d: 0 (smooth_l1) or 1 (l1)", kind);
-  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
-  const int F = m->cfg.n_features;
-  if (pair_sums) {
-    if (!keep) return fail(FD_E_INVALID, "null argument: the pairwise term needs keep and spread");
-    if (!pairs || !feat_idx) return fail(FD_E_INVALID, "null argument: the pairwise term needs pairs and feat_idx");
-    if (int rc = check_pairwise(keep, coef, feat_idx, B, L, F)) return rc;
-  }
-  if (int rc = check_t_seq(m, t, B)) return rc;
-  if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * F, nb = (size_t)B, nf = nb * F;
-  hipStream_t s = m->stream;
-  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
-  if (!w.loss_ex_in) HIP_TRY(hipMalloc((void**)&w.loss_ex_in, (3 * n + 5 * nb) * 4));
-  if (!w.loss_ex_out) HIP_TRY(hipMalloc((void**)&w.loss_ex_out, (2 * nf + 2 * nb) * 8));
-  // ONE upload, staged back to back as fd_denoise_loss does (a blocking copy from pageable memory of this frame)
-  std::vector<float> stage(3 * n + 5 * nb, 0.f);
-  memcpy(stage.data(), x0, n * 4);
-  memcpy(stage.data() + n, noise, n * 4);
-  if (corrupted) memcpy(stage.data() + 2 * n, corrupted, n * 4);
-  float* vec = stage.data() + 3 * n;
-  if (keep) {
-    memcpy(vec, keep, nb * 4);
-    memcpy(vec + nb, spread, nb * 4);
-  }
-  if (coef) memcpy(vec + 2 * nb, coef, nb * 4);
-  memcpy(vec + 3 * nb, t, nb * 4);
-  memcpy(vec + 4 * nb, lens, nb * 4);
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(w.loss_ex_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-  const float *x0_dev = w.loss_ex_in, *noise_dev = x0_dev + n, *corrupted_dev = x0_dev + 2 * n, *keep_dev = x0_dev + 3 * n,
-              *spread_dev = keep_dev + nb, *coef_dev = keep_dev + 2 * nb;
-  HIP_TRY(hipMemcpyAsync(w.t_seq, keep_dev + 3 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, keep_dev + 4 * nb, nb * 4, hipMemcpyDeviceToDevice, s));
-  if (!corrupted) {  // q(x_t | x_0) on the device, with the wrap flags fd_finalize was given
-    launch_q_sample(x0_dev, noise_dev, keep_dev, spread_dev, w.x, B, L, F, m->angle_mask, s);
-    HIP_TRY(hipGetLastError());
-  } else {
-    HIP_TRY(hipMemcpyAsync(w.x, corrupted_dev, n * 4, hipMemcpyDeviceToDevice, s));
-  }
-  if (int rc = prepare_rows(m, s, 0)) return rc;
-  StepMode mode{};
-  mode.forward_only = true;
-  mode.t_seq = w.t_seq;
-  if (int rc = run_step(m, s, mode)) return rc;
-  double* sums_dev = w.loss_ex_out;
-  long long* turns_dev = (long long*)(w.loss_ex_out + nf);
-  double* pair_sums_dev = w.loss_ex_out + 2 * nf;
-  long long* pairs_dev = (long long*)(w.loss_ex_out + 2 * nf + nb);
-  launch_loss_terms_ex(w.eps, noise_dev, w.lens, B, L, F, m->angle_mask, kind, beta_ang, beta_lin, sums_dev, nullptr,
-                       turns ? turns_dev : nullptr, s);
-  HIP_TRY(hipGetLastError());
-  if (pair_sums) {  // the forward's x_t and prediction stay where they are: w.x, w.eps
-    const PairwiseFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5]};
-    launch_pairwise_dist(x0_dev, w.x, w.eps, keep_dev, spread_dev, coef ? coef_dev : nullptr, w.lens, B, L, F, fx, pair_sums_dev,
-                         pairs_dev, nullptr, s);
-    HIP_TRY(hipGetLastError());
-  }
-  // ONE download of what was asked for: sums [| turns] [| pair_sums | pairs] are contiguous up to the last one wanted
-  const size_t words = pair_sums ? 2 * nf + 2 * nb : turns ? 2 * nf : nf;
-  std::vector<double> back(words);
-  HIP_TRY(hipMemcpyAsync(back.data(), w.loss_ex_out, words * 8, hipMemcpyDeviceToHost, s));
-  if (corrupted_out) HIP_TRY(hipMemcpyAsync(corrupted_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
-  if (eps_out) HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (int rc = check_flag(m)) return rc;
-  memcpy(sums, back.data(), nf * 8);
-  if (turns) memcpy(turns, back.data() + nf, nf * 8);
-  if (pair_sums) {
-    memcpy(pair_sums, back.data() + 2 * nf, nb * 8);
-    memcpy(pairs, back.data() + 2 * nf + nb, nb * 8);
-  }
-  return FD_OK;
-}
-
-int fd_forward_ex(fd_model* m, const float* x, int t, const uint8_t* key_mask, const int32_t* position_ids, int B, int L,
-                  float* eps_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !eps_out) return fail(FD_E_INVALID, "null argument");
-  if (!key_mask && !position_ids) return fail(FD_E_INVALID, "fd_forward_ex without a mask and without position ids: use fd_forward");
-  if (!m->img) return fail(FD_E_UNSUPPORTED, "fd_forward_ex (arbitrary key masks / position ids) needs FD_PREC_F16X3");
-  const fd_config& c = m->cfg;
-  if (position_ids && c.pos_type == FD_POS_ABSOLUTE)
-    for (size_t i = 0; i < (size_t)B * L; ++i)
-      if (position_ids[i] < 0 || position_ids[i] >= c.max_pos)
-        return fail(FD_E_INVALID, "position_ids[%zu]=%d outside [0, %d)", i, position_ids[i], c.max_pos);
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * c.n_features;
-  hipStream_t s = m->stream;
-  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
-  if (key_mask && !w.kmask) HIP_TRY(hipMalloc((void**)&w.kmask, (size_t)B * L));
-  if (position_ids && c.pos_type == FD_POS_ABSOLUTE && !w.pos_ids) HIP_TRY(hipMalloc((void**)&w.pos_ids, (size_t)B * L * 4));
-  std::vector<int32_t> lens(B, L);  // every position is a row and a key; what is attended to is the mask's business
-  // `lens` is a pageable vector of this frame, and the early returns below would destroy it under an asynchronous copy: a blocking
-  // one -- which goes through the NULL stream and is not ordered against work still queued on the model's non-blocking stream (an
-  // earlier asynchronous entry point reading w.lens), so that stream is drained first
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(w.lens, lens.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
-  StepMode mode{};
-  mode.forward_only = true;
-  if (key_mask) {
-    HIP_TRY(hipMemcpyAsync(w.kmask, key_mask, (size_t)B * L, hipMemcpyHostToDevice, s));
-    mode.kmask = w.kmask;
-  }
-  // (relative position types: the reference's embeddings add no position embedding and HF's distance uses arange, so
-  // position_ids change nothing there -- modelling.py:157-166, BertSelfAttention)
-  if (position_ids && c.pos_type == FD_POS_ABSOLUTE) {
-    HIP_TRY(hipMemcpyAsync(w.pos_ids, position_ids, (size_t)B * L * 4, hipMemcpyHostToDevice, s));
-    mode.pos_ids = w.pos_ids;
-  }
-  if (int rc = prepare_rows(m, s, 0)) return rc;
-  if (int rc = set_t(m, s, t)) return rc;
-  if (int rc = run_step(m, s, mode)) return rc;
-  HIP_TRY(hipMemcpyAsync(eps_out, w.eps, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-int fd_p_sample_step(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
-                     float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
-  if (t > 0 && !z) return fail(FD_E_INVALID, "z is required for t > 0");
-  if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  hipStream_t s = m->stream;
-  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  if (z) HIP_TRY(hipMemcpyAsync(w.z, z, n * 4, hipMemcpyHostToDevice, s));
-  if (int rc = prepare_rows(m, s, 0)) return rc;
-  if (int rc = set_t(m, s, t)) return rc;
-  StepMode mode{};
-  mode.noise = w.z;
-  mode.t_start = t;
-  mode.no_wrap = !wrap;
-  if (int rc = run_step(m, s, mode)) return rc;
-  HIP_TRY(hipMemcpyAsync(x_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-int fd_p_sample_step_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
-                             const float* known, const uint8_t* fixed, const float* known_coef, const float* z_known,
-                             float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
-  if (t > 0 && !z) return fail(FD_E_INVALID, "z is required for t > 0");
-  if (t > 0 && !z_known) return fail(FD_E_INVALID, "z_known is required for t > 0");
-  if (int rc = check_lens(lens, B, L)) return rc;
-  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  hipStream_t s = m->stream;
-  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  if (z) HIP_TRY(hipMemcpyAsync(w.z, z, n * 4, hipMemcpyHostToDevice, s));
-  InpaintDev ip;
-  if (int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip)) return rc;
-  if (t > 0) HIP_TRY(hipMemcpyAsync(ip.z_known, z_known, n * 4, hipMemcpyHostToDevice, s));
-  if (int rc = prepare_rows(m, s, 0)) return rc;
-  if (int rc = set_t(m, s, t)) return rc;
-  StepMode mode{};
-  mode.noise = w.z;
-  mode.t_start = t;
-  mode.no_wrap = !wrap;
-  mode.known = ip.known; mode.fixed = ip.fixed; mode.known_coef = ip.coef; mode.z_known = ip.z_known;
-  if (int rc = run_step(m, s, mode)) return rc;
-  HIP_TRY(hipMemcpyAsync(x_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_flag(m);
-}
-
-int fd_sample_begin_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_start,
-                        uint64_t seed, int64_t seq_offset, void* out_dev, int full_history, void* hip_stream) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init_dev || !lens_dev || !out_dev) return fail(FD_E_INVALID, "null argument");
-  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream;
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  HIP_TRY(hipMemcpyAsync(w.x, x_init_dev, n * 4, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, lens_dev, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-  if (m->varlen && full_history)  // packed rows: positions beyond a sequence's length are never written
-    HIP_TRY(hipMemsetAsync(out_dev, 0, ((size_t)(t_start + full_history) / full_history) * n * 4, s));
-  if (int rc = prepare_rows(m, s, m->varlen)) return rc;
-  if (m->use_graph && !graph_current(m, w)) {
-    // first use of this (B, L): the warm-up step and the capture run on the model's stream and need the
-    // lengths / row table that were just queued on `s`
-    if (s != m->stream) HIP_TRY(hipStreamSynchronize(s));
-    if (int rc = ensure_graph(m)) return rc;
-    HIP_TRY(hipStreamSynchronize(m->stream));
-  }
-  UpdateDyn& dyn = m->dyn_host;
-  memset(&dyn, 0, sizeof dyn);
-  dyn.hist = full_history ? static_cast<float*>(out_dev) : nullptr;
-  dyn.seed = seed;
-  dyn.seq_offset = seq_offset;
-  dyn.t_start = t_start;
-  dyn.hist_every = full_history;
-  m->run_t = t_start;
-  m->run_open = true;
-  m->run_B = B;
-  m->run_L = L;
-  if (int rc = set_t(m, s, t_start)) return rc;
-  return FD_OK;
-}
-
-int fd_sample_steps_dev(fd_model* m, int n_steps, const void* noise_dev, int noise_t0, void* hip_stream) {
-  if (!m || !m->finalized || m->ws.B == 0) return fail(FD_E_STATE, "fd_sample_steps_dev without fd_sample_begin_dev");
-  if (!m->run_open) return fail(FD_E_STATE, "fd_sample_steps_dev: no sampling run in progress (another call on this model has taken its workspace)");
-  if (m->ws.B != m->run_B || m->ws.L != m->run_L)
-    return fail(FD_E_STATE, "fd_sample_steps_dev: the workspace now holds B=%d L=%d, the run was begun with B=%d L=%d", m->ws.B, m->ws.L, m->run_B, m->run_L);
-  if (n_steps < 0 || n_steps > m->run_t + 1) return fail(FD_E_INVALID, "n_steps = %d with %d steps left", n_steps, m->run_t + 1);
-  if (noise_dev && (noise_t0 < 0 || noise_t0 > m->run_t - n_steps + 1))  // (the row of t = 0 is read too, and multiplied by sigma_0 = 0)
-    return fail(FD_E_INVALID, "noise rows start at t = %d, the steps run down to t = %d", noise_t0, m->run_t - n_steps + 1);
-  HIP_TRY(hipSetDevice(m->device));
-  Workspace& w = m->ws;
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream;
-  // the kernel reads the draw of step t at noise + t * (B L F): rebase the chunk (row 0 = step noise_t0)
-  const size_t n = (size_t)w.B * w.L * m->cfg.n_features;
-  UpdateDyn dyn = m->dyn_host;
-  dyn.noise = noise_dev ? static_cast<const float*>(noise_dev) - (ptrdiff_t)noise_t0 * (ptrdiff_t)n : nullptr;
-  hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, w.dyn, dyn);
-  for (int i = 0; i < n_steps; ++i) {
-    const int done = m->dyn_host.t_start - m->run_t;  // steps already run
-    const bool prof = m->profile_every > 0 && (done % m->profile_every) == m->profile_every / 2;
-    if (m->use_graph && !prof) {
-      HIP_TRY(hipGraphLaunch(w.graph, s));
-    } else {
-      StepMode mode{};
-      mode.use_dyn = true;
-      mode.advance = true;
-      mode.profile = prof;
-      if (int rc = run_step(m, s, mode)) return rc;
-    }
-    --m->run_t;
-  }
-  return FD_OK;
-}
-
-int fd_sample_end_dev(fd_model* m, void* out_dev, void* hip_stream) {
-  if (!m || !m->finalized || m->ws.B == 0) return fail(FD_E_STATE, "fd_sample_end_dev without fd_sample_begin_dev");
-  if (!m->run_open) return fail(FD_E_STATE, "fd_sample_end_dev: no sampling run in progress (another call on this model has taken its workspace)");
-  if (m->run_t >= 0) return fail(FD_E_STATE, "%d reverse steps have not been run", m->run_t + 1);
-  if (m->ws.B != m->run_B || m->ws.L != m->run_L)
-    return fail(FD_E_STATE, "fd_sample_end_dev: the workspace now holds B=%d L=%d, the run was begun with B=%d L=%d", m->ws.B, m->ws.L, m->run_B, m->run_L);
-  HIP_TRY(hipSetDevice(m->device));
-  Workspace& w = m->ws;
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream;
-  const size_t n = (size_t)w.B * w.L * m->cfg.n_features;
-  if (!m->dyn_host.hist_every) HIP_TRY(hipMemcpyAsync(out_dev, w.x, n * 4, hipMemcpyDeviceToDevice, s));
-  m->run_open = false;
-  return FD_OK;
-}
-
-int fd_sample_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_start,
-                  const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev, int full_history,
-                  void* hip_stream) {
-  if (int rc = fd_sample_begin_dev(m, x_init_dev, lens_dev, B, L, t_start, seed, seq_offset, out_dev, full_history, hip_stream))
-    return rc;
-  if (int rc = fd_sample_steps_dev(m, t_start + 1, noise_dev, 0, hip_stream)) return rc;
-  return fd_sample_end_dev(m, out_dev, hip_stream);
-}
-
-int fd_sample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
-              uint64_t seed, float* out, int full_history) {
-  return fd_sample_ex(m, x_init, lens, B, L, t_start, noise, seed, 0, out, full_history);
-}
-
-int fd_sample_ex(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
-                 uint64_t seed, int64_t seq_offset, float* out, int full_history) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
-  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
-  if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  const size_t nsteps = (size_t)t_start + 1;
-  // rows of `out`: 1 (final only), every state, or every full_history-th state plus the final one
-  const size_t out_rows = full_history ? (nsteps + full_history - 1) / full_history : 1;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  const float* d_noise = nullptr;
-  int* d_lens;
-  HIP_TRY(bufs.alloc(n * 4, &d_x));
-  HIP_TRY(bufs.alloc((size_t)B * 4, &d_lens));
-  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
-  HIP_TRY(hipMemcpy(d_x, x_init, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-  if (noise) HIP_TRY(bufs.upload(noise, nsteps * n * 4, &d_noise));
-  if (int rc = fd_sample_dev(m, d_x, d_lens, B, L, t_start, d_noise, seed, seq_offset, d_out, full_history, nullptr)) return rc;
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
-  return check_flag(m);
-}
-
-int fd_sample_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
-                      const float* known, const uint8_t* fixed, const float* known_coef, const float* known_noise,
-                      uint64_t seed, int64_t seq_offset, float* out, int full_history) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
-  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
-  if (int rc = check_lens(lens, B, L)) return rc;
-  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  const size_t nsteps = (size_t)t_start + 1;
-  const size_t out_rows = full_history ? (nsteps + full_history - 1) / full_history : 1;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  const float *d_noise = nullptr, *d_known_noise = nullptr;
-  int* d_lens;
-  HIP_TRY(bufs.alloc(n * 4, &d_x));
-  HIP_TRY(bufs.alloc((size_t)B * 4, &d_lens));
-  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
-  HIP_TRY(hipMemcpy(d_x, x_init, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-  if (noise) HIP_TRY(bufs.upload(noise, nsteps * n * 4, &d_noise));
-  if (known_noise) HIP_TRY(bufs.upload(known_noise, (nsteps + 1) * n * 4, &d_known_noise));  // rows = levels 0 .. t_start + 1
-  if (int rc = fd_sample_begin_dev(m, d_x, d_lens, B, L, t_start, seed, seq_offset, d_out, full_history, nullptr)) return rc;
-  hipStream_t s = m->stream;
-  InpaintDev ip;
-  int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip);
-  if (!rc) {
-    // the start point enters step t_start, so it is at level t_start + 1
-    launch_inpaint_init(m->ws.x, ip.known, ip.fixed, d_known_noise ? d_known_noise + nsteps * n : nullptr, ip.coef, m->T, t_start + 1,
-                        seed, seq_offset, B, L, m->cfg.n_features, m->angle_mask, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
-  }
-  if (!rc) {
-    // the per-run values of the update kernels travel through UpdateDyn: the captured step graph is the plain sampler's
-    m->dyn_host.known = ip.known; m->dyn_host.fixed = ip.fixed; m->dyn_host.known_coef = ip.coef; m->dyn_host.known_noise = d_known_noise;
-    rc = fd_sample_steps_dev(m, t_start + 1, d_noise, 0, nullptr);
-  }
-  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
-  // the run is over (or failed, at any point behind fd_sample_begin_dev): it is closed, and a later run on this model, plain or
-  // not, starts from cleared fields, on the host and on the device
-  m->run_open = false;
-  m->run_t = -1;
-  m->dyn_host.known = nullptr; m->dyn_host.fixed = nullptr; m->dyn_host.known_coef = nullptr; m->dyn_host.known_noise = nullptr;
-  hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, m->ws.dyn, m->dyn_host);
-  HIP_TRY(hipStreamSynchronize(s));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
-  return check_flag(m);
-}
-
-int fd_sample_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start,
-                               const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* visits,
-                               int n_visits, const float* jump_coef, uint64_t seed, int64_t seq_offset, float* out) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
-  if (int rc = check_lens(lens, B, L)) return rc;
-  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
-  int n_jumps = 0;
-  if (int rc = check_visits(visits, n_visits, t_start, jump_coef, &n_jumps)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  int* d_lens;
-  HIP_TRY(bufs.alloc(n * 4, &d_x));
-  HIP_TRY(bufs.alloc((size_t)B * 4, &d_lens));
-  HIP_TRY(bufs.alloc(n * 4, &d_out));
-  HIP_TRY(hipMemcpy(d_x, x_init, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-  if (int rc = fd_sample_begin_dev(m, d_x, d_lens, B, L, t_start, seed, seq_offset, d_out, 0, nullptr)) return rc;
-  hipStream_t s = m->stream;
-  InpaintDev ip;
-  int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip);
-  if (!rc) {
-    launch_inpaint_init(m->ws.x, ip.known, ip.fixed, nullptr, ip.coef, m->T, t_start + 1, seed, seq_offset, B, L, m->cfg.n_features,
-                        m->angle_mask, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
-  }
-  if (!rc) {
-    m->dyn_host.known = ip.known; m->dyn_host.fixed = ip.fixed; m->dyn_host.known_coef = ip.coef; m->dyn_host.known_noise = nullptr;
-  }
-  // one segment per pass: the jump that enters it (none in front of the first), then its descent.  Launches only.
-  for (int i = 0, seg = 0; !rc && i < n_visits; ++seg) {
-    int j = i + 1;
-    while (j < n_visits && visits[j] == visits[j - 1] - 1) ++j;
-    if (seg > 0) {
-      const uint64_t seed_s = segment_seed(seed, seg);
-      launch_inpaint_jump(m->ws.x, m->ws.lens, ip.known, ip.fixed, ip.coef, m->T, visits[i] + 1, jump_coef[2 * (seg - 1)],
-                          jump_coef[2 * (seg - 1) + 1], seed_s, seq_offset, B, L, m->cfg.n_features, m->angle_mask, s);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_jump: %s", hipGetErrorString(e));
-      if (!rc) rc = set_t(m, s, visits[i]);
-      m->run_t = visits[i];
-      m->dyn_host.seed = seed_s;
-    }
-    if (!rc) rc = fd_sample_steps_dev(m, j - i, nullptr, 0, nullptr);  // (re-sends dyn: the segment's seed)
-    i = j;
-  }
-  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
-  // closed like fd_sample_inpaint's run: a later run on this model starts from cleared fields, on the host and on the device
-  m->run_open = false;
-  m->run_t = -1;
-  m->dyn_host.known = nullptr; m->dyn_host.fixed = nullptr; m->dyn_host.known_coef = nullptr; m->dyn_host.known_noise = nullptr;
-  hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, m->ws.dyn, m->dyn_host);
-  HIP_TRY(hipStreamSynchronize(s));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
-  return check_flag(m);
-}
-
-int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int L, int level_to, float jk, float js,
-                    const float* known, const uint8_t* fixed, const float* known_coef, uint64_t seed, int64_t seq_offset,
-                    float* x_out) {
-  if (int rc = check_shape(m, B, L, 0)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
-  if (level_to < 1 || level_to > m->T) return fail(FD_E_INVALID, "level_to = %d outside [1, %d]", level_to, m->T);
-  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
-  if (int rc = check_jump_coef(jk, js, 0)) return rc;
-  if (int rc = check_lens(lens, B, L)) return rc;
-  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  if (int rc = ensure_ws(m, B, L)) return rc;
-  Workspace& w = m->ws;
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  hipStream_t s = m->stream;
-  HIP_TRY(hipMemcpyAsync(w.x, x, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(w.lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  InpaintDev ip;
-  if (int rc = stage_inpaint(m, s, known, fixed, known_coef, &ip)) return rc;
-  launch_inpaint_jump(w.x, w.lens, ip.known, ip.fixed, ip.coef, m->T, level_to, jk, js, seed, seq_offset, B, L, m->cfg.n_features,
-                      m->angle_mask, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(x_out, w.x, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FD_OK;
-}
-
-int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,
-                         void* hip_stream) {
-  if (!m || !out_dev) return fail(FD_E_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream;
-  launch_philox_fill(static_cast<float*>(out_dev), seed, t, seq_offset, B, L, m->cfg.n_features, s);
-  HIP_TRY(hipGetLastError());
-  return FD_OK;
-}
-
-int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L, const void* lens_dev, const void* item_off_dev,
-                      const float* offset, void* out_dev, void* hip_stream) {
-  if (!m || !traj_dev || !lens_dev || !item_off_dev || !out_dev) return fail(FD_E_INVALID, "null argument");
-  if (!m->finalized) return fail(FD_E_STATE, "fd_finalize has not been called");
-  if (rows < 1 || B < 1 || L < 1) return fail(FD_E_INVALID, "rows=%d B=%d L=%d must be positive", rows, B, L);
-  if ((long long)rows * B > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "rows x B = %lld blocks", (long long)rows * B);
-  HIP_TRY(hipSetDevice(m->device));
-  ShiftTrimArgs a;
-  memset(&a, 0, sizeof a);
-  a.traj = static_cast<const float*>(traj_dev); a.lens = static_cast<const int*>(lens_dev);
-  a.item_off = static_cast<const long long*>(item_off_dev); a.out = static_cast<float*>(out_dev);
-  a.rows = rows; a.B = B; a.L = L; a.F = m->cfg.n_features;
-  a.angle_mask = m->angle_mask;
-  a.has_offset = offset ? 1 : 0;
-  if (offset)
-    for (int f = 0; f < a.F; ++f) a.offset[f] = offset[f];
-  launch_shift_trim(a, hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream);
-  HIP_TRY(hipGetLastError());
-  return FD_OK;
 }
 
 int fd_profile_every(fd_model* m, int n) {

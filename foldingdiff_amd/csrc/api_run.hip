@@ -1,0 +1,748 @@
+// C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
+// single reverse steps, the sampling runs (plain, motif-conditioned, resampled) and their device-buffer pieces.  Host code
+// around api.hip's workspace, launch plan and step (model.h) only: every entry checks its arguments before its first HIP call,
+// and the paragraphs the entries share -- make the workspace current and upload, download and synchronise, the host-side
+// run, the one-copy staging of the loss entries -- are written once, below.
+// Boundary: include/fdmi.h (each entry point cites the reference function it replaces).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <initializer_list>
+#include <vector>
+
+#include "../../include/fdmi.h"
+#include "fdmi_kernels.h"
+#include "host_common.h"
+#include "model.h"
+
+using namespace fdmi;
+
+namespace {
+
+hipStream_t stream_of(fd_model* m, void* hip_stream) { return hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream; }
+
+// ---- the opening and the close of an entry that works on the current workspace
+struct Call {
+  Workspace* ws;
+  size_t n;  // B * L * F
+  hipStream_t s;
+};
+
+// the model's device and the (B, L) workspace become current
+int open_ws(fd_model* m, int B, int L, void* hip_stream, Call* c) {
+  HIP_TRY(hipSetDevice(m->device));
+  if (int rc = ensure_ws(m, B, L)) return rc;
+  *c = Call{&m->ws, (size_t)B * L * m->cfg.n_features, stream_of(m, hip_stream)};
+  return FD_OK;
+}
+
+// ... and x, lens and an optional [B] int vector (into t_seq) are on their way into it
+int open_call(fd_model* m, const void* x, const void* lens, const int32_t* per_seq, int B, int L, Call* c,
+              hipMemcpyKind kind = hipMemcpyHostToDevice, void* hip_stream = nullptr) {
+  if (int rc = open_ws(m, B, L, hip_stream, c)) return rc;
+  HIP_TRY(hipMemcpyAsync(c->ws->x, x, c->n * 4, kind, c->s));
+  HIP_TRY(hipMemcpyAsync(c->ws->lens, lens, (size_t)B * 4, kind, c->s));
+  if (per_seq) HIP_TRY(hipMemcpyAsync(c->ws->t_seq, per_seq, (size_t)B * 4, kind, c->s));
+  return FD_OK;
+}
+
+struct Download {
+  void* host;  // null: an optional output nobody asked for
+  const void* dev;
+  size_t bytes;
+};
+
+int download_sync(hipStream_t s, std::initializer_list<Download> list) {
+  for (const Download& d : list)
+    if (d.host) HIP_TRY(hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FD_OK;
+}
+
+int finish(fd_model* m, hipStream_t s, std::initializer_list<Download> list) {
+  if (int rc = download_sync(s, list)) return rc;
+  return check_flag(m);
+}
+
+// ---- one forward: fd_forward (t), fd_forward_t and fd_ar_forward (per_seq: a timestep or a target length per sequence)
+int forward(fd_model* m, const float* x, const int32_t* lens, const int32_t* per_seq, int t, StepMode mode, int B, int L, float* out) {
+  Call c;
+  if (int rc = open_call(m, x, lens, per_seq, B, L, &c)) return rc;
+  if (int rc = prepare_rows(m, c.s, 0)) return rc;  // the forward defines every position, masked ones included
+  if (per_seq) mode.t_seq = c.ws->t_seq;
+  else if (int rc = set_t(m, c.s, t)) return rc;
+  mode.forward_only = true;
+  if (int rc = run_step(m, c.s, mode)) return rc;
+  return finish(m, c.s, {{out, c.ws->eps, c.n * 4}});
+}
+
+// every t[b] of a per-sequence timestep vector lies in [0, T)
+int check_t_seq(const fd_model* m, const int32_t* t, int B) {
+  for (int b = 0; b < B; ++b)
+    if (t[b] < 0 || t[b] >= m->T) return fail(FD_E_INVALID, "timestep t[%d]=%d outside [0, %d)", b, t[b], m->T);
+  return FD_OK;
+}
+
+// the arguments fd_ar_forward and fd_ar_sample share, all checked before the first HIP call
+int check_ar(fd_model* m, const void* x, const int32_t* seq_lengths, const void* out, int B, int L, const char* who) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x || !seq_lengths || !out) return fail(FD_E_INVALID, "null argument");
+  if (!m->img)
+    return fail(FD_E_UNSUPPORTED, "%s: the autoregressive baseline runs on the row-image kernels only; finalize the model with "
+                "FD_PREC_F16X3 (the exact-fp32 mode has no autoregressive embedding)", who);
+  for (int b = 0; b < B; ++b)  // the length indexes the table fd_finalize was given in place of a timestep
+    if (seq_lengths[b] < 0 || seq_lengths[b] >= m->T)
+      return fail(FD_E_INVALID, "seq_lengths[%d]=%d outside [0, %d)", b, seq_lengths[b], m->T);
+  return FD_OK;
+}
+
+// ---- ONE upload of several host arrays: staged back to back (in 4-byte words) in a pageable vector of the caller's frame and
+// sent with a blocking copy, behind whatever an earlier asynchronous entry point left on the stream.  add() hands out the
+// segment's device address, good once send() has returned.
+class PackedUpload {
+ public:
+  explicit PackedUpload(float* dev) : dev_(dev) {}
+  const float* add(const void* host, size_t words) {  // host null: the segment stays zero
+    const size_t at = stage_.size();
+    stage_.resize(at + words, 0.f);
+    if (host) memcpy(stage_.data() + at, host, words * 4);
+    return dev_ + at;
+  }
+  int send(hipStream_t s) {
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(dev_, stage_.data(), stage_.size() * 4, hipMemcpyHostToDevice));
+    return FD_OK;
+  }
+
+ private:
+  float* dev_;
+  std::vector<float> stage_;
+};
+
+// What the two loss entries run between their upload and their own kernels: t and lens into place, x_t (x_t_dev; null: q(x_t | x_0)
+// on the device, with the wrap flags fd_finalize was given), then the forward with one timestep per sequence
+int loss_forward(fd_model* m, const Call& c, int B, int L, const float* x0_dev, const float* noise_dev, const float* keep_dev,
+                 const float* spread_dev, const float* x_t_dev, const float* t_dev, const float* lens_dev) {
+  Workspace& w = *c.ws;
+  HIP_TRY(hipMemcpyAsync(w.t_seq, t_dev, (size_t)B * 4, hipMemcpyDeviceToDevice, c.s));
+  HIP_TRY(hipMemcpyAsync(w.lens, lens_dev, (size_t)B * 4, hipMemcpyDeviceToDevice, c.s));
+  if (!x_t_dev) {
+    launch_q_sample(x0_dev, noise_dev, keep_dev, spread_dev, w.x, B, L, m->cfg.n_features, m->angle_mask, c.s);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemcpyAsync(w.x, x_t_dev, c.n * 4, hipMemcpyDeviceToDevice, c.s));
+  }
+  if (int rc = prepare_rows(m, c.s, 0)) return rc;
+  StepMode mode{};
+  mode.forward_only = true;
+  mode.t_seq = w.t_seq;
+  return run_step(m, c.s, mode);
+}
+
+// ---- motif-conditioned sampling: argument checks (before the first device call) and the workspace's staging buffer
+int check_inpaint(const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* lens, int B, int L, int F) {
+  if (!fixed) return fail(FD_E_INVALID, "fixed is null");
+  if (!known) return fail(FD_E_INVALID, "known is null (fixed is given)");
+  if (!known_coef) return fail(FD_E_INVALID, "known_coef is null");
+  for (int b = 0; b < B; ++b)
+    for (int l = lens[b]; l < L; ++l)
+      for (int f = 0; f < F; ++f)
+        if (fixed[((size_t)b * L + l) * F + f])
+          return fail(FD_E_INVALID, "fixed element beyond a length: sequence %d position %d feature %d, lens[%d] = %d", b, l, f, b, lens[b]);
+  return FD_OK;
+}
+
+// the host arrays of a conditioned call (fixed null: not conditioned)
+struct InpaintHost {
+  const float* known = nullptr;
+  const uint8_t* fixed = nullptr;
+  const float* known_coef = nullptr;
+};
+
+// ... and where they are on the device (all null: not conditioned)
+struct InpaintDev {
+  float *known = nullptr, *z_known = nullptr, *coef = nullptr;
+  unsigned char* fixed = nullptr;
+  void apply(StepMode* mode) const {  // one step by value: z_known = the one slab of its level
+    mode->known = known; mode->fixed = fixed; mode->known_coef = coef; mode->z_known = z_known;
+  }
+  void apply(UpdateDyn* dyn, const float* known_noise) const {  // a run: known_noise = every level's slab, or null (Philox)
+    dyn->known = known; dyn->fixed = fixed; dyn->known_coef = coef; dyn->known_noise = known_noise;
+  }
+  static void clear(UpdateDyn* dyn) { InpaintDev().apply(dyn, nullptr); }
+};
+
+// uploads known / fixed / known_coef into the current workspace's staging buffer (allocated on first use), stream-ordered on s
+int stage_inpaint(fd_model* m, hipStream_t s, const InpaintHost& h, InpaintDev* d) {
+  Workspace& w = m->ws;
+  const size_t n = (size_t)w.B * w.L * m->cfg.n_features, nc = 2 * ((size_t)m->T + 1);
+  if (!w.inpaint) HIP_TRY(hipMalloc((void**)&w.inpaint, (2 * n + nc) * 4 + n));
+  d->known = w.inpaint;
+  d->z_known = w.inpaint + n;
+  d->coef = w.inpaint + 2 * n;
+  d->fixed = reinterpret_cast<unsigned char*>(w.inpaint + 2 * n + nc);
+  HIP_TRY(hipMemcpyAsync(d->known, h.known, n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d->coef, h.known_coef, nc * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d->fixed, h.fixed, n, hipMemcpyHostToDevice, s));
+  return FD_OK;
+}
+
+// ---- one reverse step from host arrays: fd_p_sample_step, and with `cond` fd_p_sample_step_inpaint
+int p_sample_step(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
+                  const InpaintHost& cond, const float* z_known, float* x_out) {
+  Call c;
+  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
+  Workspace& w = *c.ws;
+  if (z) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
+  InpaintDev ip;
+  if (cond.fixed) {
+    if (int rc = stage_inpaint(m, c.s, cond, &ip)) return rc;
+    if (t > 0) HIP_TRY(hipMemcpyAsync(ip.z_known, z_known, c.n * 4, hipMemcpyHostToDevice, c.s));
+  }
+  if (int rc = prepare_rows(m, c.s, 0)) return rc;
+  if (int rc = set_t(m, c.s, t)) return rc;
+  StepMode mode{};
+  mode.noise = w.z;
+  mode.t_start = t;
+  mode.no_wrap = !wrap;
+  ip.apply(&mode);
+  if (int rc = run_step(m, c.s, mode)) return rc;
+  return finish(m, c.s, {{x_out, w.x, c.n * 4}});
+}
+
+// ---- resampling schedules: argument checks of fd_sample_inpaint_resample / fd_inpaint_jump
+uint64_t segment_seed(uint64_t seed, int s) { return seed + (uint64_t)s * 0x9E3779B97F4A7C15ull; }
+
+int check_jump_coef(float jk, float js, int jump) {
+  if (!std::isfinite(jk) || !std::isfinite(js) || jk < 0.f || jk > 1.f || js < 0.f || js > 1.f)
+    return fail(FD_E_INVALID, "jump_coef of jump %d: jk = %g, js = %g must be finite and within [0, 1]", jump, (double)jk, (double)js);
+  return FD_OK;
+}
+
+// the rules of a legal schedule; *n_jumps = the number of jumps in it
+int check_visits(const int32_t* visits, int n_visits, int t_start, const float* jump_coef, int* n_jumps) {
+  if (!visits) return fail(FD_E_INVALID, "visits is null");
+  if (n_visits < 1) return fail(FD_E_INVALID, "n_visits = %d must be positive", n_visits);
+  if (visits[0] != t_start) return fail(FD_E_INVALID, "visits[0] = %d, the run starts with step t_start = %d", visits[0], t_start);
+  int jumps = 0;
+  for (int i = 1; i < n_visits; ++i) {
+    if (visits[i] < 0 || visits[i] > t_start) return fail(FD_E_INVALID, "visits[%d] = %d outside [0, %d]", i, visits[i], t_start);
+    if (visits[i] == visits[i - 1] - 1) continue;
+    if (visits[i] < visits[i - 1])
+      return fail(FD_E_INVALID, "visits[%d] = %d follows %d: neither the next step down nor a jump up", i, visits[i], visits[i - 1]);
+    ++jumps;
+  }
+  if (visits[n_visits - 1] != 0) return fail(FD_E_INVALID, "visits[%d] = %d, the run ends with step 0", n_visits - 1, visits[n_visits - 1]);
+  if (jumps && !jump_coef) return fail(FD_E_INVALID, "jump_coef is null and the schedule has %d jumps", jumps);
+  for (int j = 0; j < jumps; ++j)
+    if (int rc = check_jump_coef(jump_coef[2 * j], jump_coef[2 * j + 1], j)) return rc;
+  *n_jumps = jumps;
+  return FD_OK;
+}
+
+// ---- a whole sampling run from host arrays (fd_sample_ex, fd_sample_inpaint, fd_sample_inpaint_resample); the entry has
+// checked every argument
+struct HostRun {
+  const float* x_init;
+  const int32_t* lens;
+  int B, L, t_start;
+  const float* noise;  // [t_start + 1][B][L][F], or null: Philox
+  uint64_t seed;
+  int64_t seq_offset;
+  float* out;
+  int full_history;
+  InpaintHost cond;                    // fixed null: a plain run
+  const float* known_noise = nullptr;  // [t_start + 2][B][L][F] (rows = levels 0 .. t_start + 1), or null: Philox
+  const int32_t* visits = nullptr;     // a resampling schedule, or null: the single descent t_start .. 0
+  int n_visits = 0;
+  const float* jump_coef = nullptr;
+};
+
+// the conditioning of a run just begun: the arrays staged, the start point's fixed elements at the start level, the fields of
+// the update kernels' per-run values (the captured step graph is the plain sampler's)
+int begin_conditioning(fd_model* m, hipStream_t s, const HostRun& a, const float* d_known_noise, InpaintDev* ip) {
+  if (int rc = stage_inpaint(m, s, a.cond, ip)) return rc;
+  const size_t n = (size_t)a.B * a.L * m->cfg.n_features;
+  // the start point enters step t_start, so it is at level t_start + 1
+  launch_inpaint_init(m->ws.x, ip->known, ip->fixed, d_known_noise ? d_known_noise + ((size_t)a.t_start + 1) * n : nullptr, ip->coef,
+                      m->T, a.t_start + 1, a.seed, a.seq_offset, a.B, a.L, m->cfg.n_features, m->angle_mask, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
+  ip->apply(&m->dyn_host, d_known_noise);
+  return FD_OK;
+}
+
+// a schedule's visits, one segment per pass: the jump that enters it (none in front of the first), then its descent.  Launches only.
+int walk_visits(fd_model* m, hipStream_t s, const HostRun& a, const InpaintDev& ip) {
+  for (int i = 0, seg = 0; i < a.n_visits; ++seg) {
+    int j = i + 1;
+    while (j < a.n_visits && a.visits[j] == a.visits[j - 1] - 1) ++j;
+    if (seg > 0) {
+      const uint64_t seed_s = segment_seed(a.seed, seg);
+      launch_inpaint_jump(m->ws.x, m->ws.lens, ip.known, ip.fixed, ip.coef, m->T, a.visits[i] + 1, a.jump_coef[2 * (seg - 1)],
+                          a.jump_coef[2 * (seg - 1) + 1], seed_s, a.seq_offset, a.B, a.L, m->cfg.n_features, m->angle_mask, s);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return fail(FD_E_HIP, "launch_inpaint_jump: %s", hipGetErrorString(e));
+      if (int rc = set_t(m, s, a.visits[i])) return rc;
+      m->run_t = a.visits[i];
+      m->dyn_host.seed = seed_s;
+    }
+    if (int rc = fd_sample_steps_dev(m, j - i, nullptr, 0, nullptr)) return rc;  // (re-sends dyn: the segment's seed)
+    i = j;
+  }
+  return FD_OK;
+}
+
+// A conditioned run is over (or failed, at any point behind fd_sample_begin_dev): it is closed, and a later run on this model,
+// plain or not, starts from cleared fields, on the host and on the device
+int close_conditioned_run(fd_model* m, hipStream_t s) {
+  m->run_open = false;
+  m->run_t = -1;
+  InpaintDev::clear(&m->dyn_host);
+  send_dyn(m, s, m->dyn_host);
+  HIP_TRY(hipStreamSynchronize(s));
+  return FD_OK;
+}
+
+int host_run(fd_model* m, const HostRun& a) {
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t n = (size_t)a.B * a.L * m->cfg.n_features;
+  const size_t nsteps = (size_t)a.t_start + 1;
+  // rows of `out`: 1 (final only), every state, or every full_history-th state plus the final one
+  const size_t out_rows = a.full_history ? (nsteps + a.full_history - 1) / a.full_history : 1;
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  const float *d_noise = nullptr, *d_known_noise = nullptr;
+  int* d_lens;
+  HIP_TRY(bufs.alloc(n * 4, &d_x));
+  HIP_TRY(bufs.alloc((size_t)a.B * 4, &d_lens));
+  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
+  HIP_TRY(hipMemcpy(d_x, a.x_init, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_lens, a.lens, (size_t)a.B * 4, hipMemcpyHostToDevice));
+  if (a.noise) HIP_TRY(bufs.upload(a.noise, nsteps * n * 4, &d_noise));
+  if (a.known_noise) HIP_TRY(bufs.upload(a.known_noise, (nsteps + 1) * n * 4, &d_known_noise));
+  if (int rc = fd_sample_begin_dev(m, d_x, d_lens, a.B, a.L, a.t_start, a.seed, a.seq_offset, d_out, a.full_history, nullptr)) return rc;
+  hipStream_t s = m->stream;
+  const bool conditioned = a.cond.fixed != nullptr;
+  InpaintDev ip;
+  int rc = conditioned ? begin_conditioning(m, s, a, d_known_noise, &ip) : FD_OK;
+  if (!rc) rc = a.visits ? walk_visits(m, s, a, ip) : fd_sample_steps_dev(m, a.t_start + 1, d_noise, 0, nullptr);
+  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
+  if (conditioned) {
+    if (int rc_close = close_conditioned_run(m, s)) return rc_close;
+  } else if (!rc) {
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(a.out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
+  return check_flag(m);
+}
+
+}  // namespace
+
+// ============================================================================ C ABI
+extern "C" {
+
+int fd_forward(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float* eps_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !eps_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  return forward(m, x, lens, nullptr, t, StepMode{}, B, L, eps_out);
+}
+
+int fd_forward_t(fd_model* m, const float* x, const int32_t* t, const int32_t* lens, int B, int L, float* eps_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x || !t || !lens || !eps_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_t_seq(m, t, B)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  return forward(m, x, lens, t, 0, StepMode{}, B, L, eps_out);
+}
+
+int fd_ar_forward(fd_model* m, const float* x, const int32_t* seq_lengths, const int32_t* key_lens, int B, int L, float* out) {
+  if (int rc = check_ar(m, x, seq_lengths, out, B, L, "fd_ar_forward")) return rc;
+  if (!key_lens) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_lens(key_lens, B, L)) return rc;
+  StepMode mode{};
+  mode.ar = true;
+  return forward(m, x, key_lens, seq_lengths, 0, mode, B, L, out);
+}
+
+int fd_ar_sample(fd_model* m, const float* seed, const int32_t* seq_lengths, int B, int L, int num_seed, float* out) {
+  if (int rc = check_ar(m, seed, seq_lengths, out, B, L, "fd_ar_sample")) return rc;
+  if (num_seed < 1)  // (no seed: the first step's keys would all be masked)
+    return fail(FD_E_INVALID, "num_seed=%d must be at least 1", num_seed);
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    if (seq_lengths[b] > L) return fail(FD_E_INVALID, "seq_lengths[%d]=%d exceeds L=%d", b, seq_lengths[b], L);
+    longest = seq_lengths[b] > longest ? seq_lengths[b] : longest;
+  }
+  Call c;
+  if (int rc = open_ws(m, B, L, nullptr, &c)) return rc;
+  Workspace& w = *c.ws;
+  const int F = m->cfg.n_features;
+  const size_t n = c.n, nb = (size_t)B;
+  hipStream_t s = c.s;
+  // ONE upload, seed | seq_lengths, through fd_denoise_loss's staging buffer (allocated at that entry's size, so that either may
+  // come first)
+  if (!w.loss_in) HIP_TRY(hipMalloc((void**)&w.loss_in, (2 * n + 4 * nb) * 4));
+  PackedUpload up(w.loss_in);
+  const float *seed_dev = up.add(seed, n), *lengths_dev = up.add(seq_lengths, nb);
+  if (int rc = up.send(s)) return rc;
+  HIP_TRY(hipMemcpyAsync(w.x, seed_dev, n * 4, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.t_seq, lengths_dev, nb * 4, hipMemcpyDeviceToDevice, s));
+  // Step i is a forward over the rows 0 .. i of every sequence with the keys 0 .. i-1 unmasked (rows > i are masked keys and
+  // queries nobody reads: they can influence nothing); its head writes eps[b][0 .. i], and row i of it becomes x[b][i].  The
+  // row count grows on the device, so the GEMMs run their slice-capable instantiation; everything else is plan_step's choice
+  const StepPlan plan = plan_step(m, w, false, true);
+  StepMode mode{};
+  mode.forward_only = true;
+  mode.t_seq = w.t_seq;
+  mode.ar = true;
+  auto tail = [&](int copy_pos, int rows_next) -> int {
+    launch_ar_step(w.x, w.eps, B, L, F, copy_pos, rows_next, w.cap, w.lens, w.nrow, w.seq_row0, w.rowinfo, w.dims, s);
+    HIP_TRY(hipGetLastError());
+    return FD_OK;
+  };
+  if (num_seed < longest)
+    if (int rc = tail(-1, num_seed + 1)) return rc;
+  for (int i = num_seed; i < longest; ++i) {
+    if (int rc = run_step_img(m, s, mode, plan)) return rc;
+    if (int rc = tail(i, i + 1 < longest ? i + 2 : 0)) return rc;
+  }
+  return finish(m, s, {{out, w.x, n * 4}});
+}
+
+int fd_denoise_loss(fd_model* m, const float* x0, const float* noise, const int32_t* t, const float* keep, const float* spread,
+                    const int32_t* lens, int B, int L, float beta_ang, float beta_lin, double* sums, float* corrupted_out,
+                    float* eps_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x0 || !noise || !t || !lens || !sums) return fail(FD_E_INVALID, "null argument");
+  if ((keep == nullptr) != (spread == nullptr)) return fail(FD_E_INVALID, "null argument: keep and spread go together");
+  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
+  if (int rc = check_t_seq(m, t, B)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  Call c;
+  if (int rc = open_ws(m, B, L, nullptr, &c)) return rc;
+  Workspace& w = *c.ws;
+  const int F = m->cfg.n_features;
+  const size_t n = c.n, nb = (size_t)B;
+  hipStream_t s = c.s;
+  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
+  if (!w.loss_in) HIP_TRY(hipMalloc((void**)&w.loss_in, (2 * n + 4 * nb) * 4));
+  if (!w.loss_sums) HIP_TRY(hipMalloc((void**)&w.loss_sums, nb * F * 8));
+  PackedUpload up(w.loss_in);  // x0 | noise | keep | spread | t | lens
+  const float *x0_dev = up.add(x0, n), *noise_dev = up.add(noise, n), *keep_dev = up.add(keep, nb), *spread_dev = up.add(spread, nb),
+              *t_dev = up.add(t, nb), *lens_dev = up.add(lens, nb);
+  if (int rc = up.send(s)) return rc;
+  // without keep and spread x0 is x_t already
+  if (int rc = loss_forward(m, c, B, L, x0_dev, noise_dev, keep_dev, spread_dev, keep ? nullptr : x0_dev, t_dev, lens_dev)) return rc;
+  launch_loss_terms(w.eps, noise_dev, w.lens, B, L, F, m->angle_mask, beta_ang, beta_lin, w.loss_sums, nullptr, s);
+  HIP_TRY(hipGetLastError());
+  return finish(m, s, {{sums, w.loss_sums, nb * F * 8}, {corrupted_out, w.x, n * 4}, {eps_out, w.eps, n * 4}});
+}
+
+int fd_denoise_loss_ex(fd_model* m, const float* x0, const float* corrupted, const float* noise, const int32_t* t,
+                       const float* keep, const float* spread, const int32_t* lens, int B, int L, int kind, float beta_ang,
+                       float beta_lin, const float* coef, const int32_t* feat_idx, double* sums, int64_t* turns,
+                       double* pair_sums, int64_t* pairs, float* corrupted_out, float* eps_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x0 || !noise || !t || !lens || !sums) return fail(FD_E_INVALID, "null argument");
+  if ((keep == nullptr) != (spread == nullptr)) return fail(FD_E_INVALID, "null argument: keep and spread go together");
+  if (!corrupted && !keep) return fail(FD_E_INVALID, "null argument: without corrupted the device noises x0 and needs keep and spread");
+  if (kind != 0 && kind != 1) return fail(FD_E_INVALID, "kind=%d: 0 (smooth_l1) or 1 (l1)", kind);
+  if (!(beta_ang > 0.f) || !(beta_lin > 0.f)) return fail(FD_E_INVALID, "beta_ang=%g beta_lin=%g must be > 0", beta_ang, beta_lin);
+  const int F = m->cfg.n_features;
+  if (pair_sums) {
+    if (!keep) return fail(FD_E_INVALID, "null argument: the pairwise term needs keep and spread");
+    if (!pairs || !feat_idx) return fail(FD_E_INVALID, "null argument: the pairwise term needs pairs and feat_idx");
+    if (int rc = check_pairwise(keep, coef, feat_idx, B, L, F)) return rc;
+  }
+  if (int rc = check_t_seq(m, t, B)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  Call c;
+  if (int rc = open_ws(m, B, L, nullptr, &c)) return rc;
+  Workspace& w = *c.ws;
+  const size_t n = c.n, nb = (size_t)B, nf = nb * F;
+  hipStream_t s = c.s;
+  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
+  if (!w.loss_ex_in) HIP_TRY(hipMalloc((void**)&w.loss_ex_in, (3 * n + 5 * nb) * 4));
+  if (!w.loss_ex_out) HIP_TRY(hipMalloc((void**)&w.loss_ex_out, (2 * nf + 2 * nb) * 8));
+  PackedUpload up(w.loss_ex_in);  // x0 | noise | corrupted | keep | spread | coef | t | lens
+  const float *x0_dev = up.add(x0, n), *noise_dev = up.add(noise, n), *corrupted_dev = up.add(corrupted, n), *keep_dev = up.add(keep, nb),
+              *spread_dev = up.add(spread, nb), *coef_dev = up.add(coef, nb), *t_dev = up.add(t, nb), *lens_dev = up.add(lens, nb);
+  if (int rc = up.send(s)) return rc;
+  if (int rc = loss_forward(m, c, B, L, x0_dev, noise_dev, keep_dev, spread_dev, corrupted ? corrupted_dev : nullptr, t_dev, lens_dev))
+    return rc;
+  double* sums_dev = w.loss_ex_out;
+  long long* turns_dev = (long long*)(w.loss_ex_out + nf);
+  double* pair_sums_dev = w.loss_ex_out + 2 * nf;
+  long long* pairs_dev = (long long*)(w.loss_ex_out + 2 * nf + nb);
+  launch_loss_terms_ex(w.eps, noise_dev, w.lens, B, L, F, m->angle_mask, kind, beta_ang, beta_lin, sums_dev, nullptr,
+                       turns ? turns_dev : nullptr, s);
+  HIP_TRY(hipGetLastError());
+  if (pair_sums) {  // the forward's x_t and prediction stay where they are: w.x, w.eps
+    const PairwiseFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5]};
+    launch_pairwise_dist(x0_dev, w.x, w.eps, keep_dev, spread_dev, coef ? coef_dev : nullptr, w.lens, B, L, F, fx, pair_sums_dev,
+                         pairs_dev, nullptr, s);
+    HIP_TRY(hipGetLastError());
+  }
+  // ONE download of what was asked for: sums [| turns] [| pair_sums | pairs] are contiguous up to the last one wanted
+  const size_t words = pair_sums ? 2 * nf + 2 * nb : turns ? 2 * nf : nf;
+  std::vector<double> back(words);
+  if (int rc = finish(m, s, {{back.data(), w.loss_ex_out, words * 8}, {corrupted_out, w.x, n * 4}, {eps_out, w.eps, n * 4}})) return rc;
+  memcpy(sums, back.data(), nf * 8);
+  if (turns) memcpy(turns, back.data() + nf, nf * 8);
+  if (pair_sums) {
+    memcpy(pair_sums, back.data() + 2 * nf, nb * 8);
+    memcpy(pairs, back.data() + 2 * nf + nb, nb * 8);
+  }
+  return FD_OK;
+}
+
+int fd_forward_ex(fd_model* m, const float* x, int t, const uint8_t* key_mask, const int32_t* position_ids, int B, int L,
+                  float* eps_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !eps_out) return fail(FD_E_INVALID, "null argument");
+  if (!key_mask && !position_ids) return fail(FD_E_INVALID, "fd_forward_ex without a mask and without position ids: use fd_forward");
+  if (!m->img) return fail(FD_E_UNSUPPORTED, "fd_forward_ex (arbitrary key masks / position ids) needs FD_PREC_F16X3");
+  const fd_config& cfg = m->cfg;
+  if (position_ids && cfg.pos_type == FD_POS_ABSOLUTE)
+    for (size_t i = 0; i < (size_t)B * L; ++i)
+      if (position_ids[i] < 0 || position_ids[i] >= cfg.max_pos)
+        return fail(FD_E_INVALID, "position_ids[%zu]=%d outside [0, %d)", i, position_ids[i], cfg.max_pos);
+  Call c;
+  if (int rc = open_ws(m, B, L, nullptr, &c)) return rc;
+  Workspace& w = *c.ws;
+  hipStream_t s = c.s;
+  // the lazily allocated buffers first: an out-of-memory return must not leave copies from this frame in flight
+  if (key_mask && !w.kmask) HIP_TRY(hipMalloc((void**)&w.kmask, (size_t)B * L));
+  if (position_ids && cfg.pos_type == FD_POS_ABSOLUTE && !w.pos_ids) HIP_TRY(hipMalloc((void**)&w.pos_ids, (size_t)B * L * 4));
+  std::vector<int32_t> lens(B, L);  // every position is a row and a key; what is attended to is the mask's business
+  // `lens` is a pageable vector of this frame, and the early returns below would destroy it under an asynchronous copy: a blocking
+  // one -- which goes through the NULL stream and is not ordered against work still queued on the model's non-blocking stream (an
+  // earlier asynchronous entry point reading w.lens), so that stream is drained first
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(w.lens, lens.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpyAsync(w.x, x, c.n * 4, hipMemcpyHostToDevice, s));
+  StepMode mode{};
+  mode.forward_only = true;
+  if (key_mask) {
+    HIP_TRY(hipMemcpyAsync(w.kmask, key_mask, (size_t)B * L, hipMemcpyHostToDevice, s));
+    mode.kmask = w.kmask;
+  }
+  // (relative position types: the reference's embeddings add no position embedding and HF's distance uses arange, so
+  // position_ids change nothing there -- modelling.py:157-166, BertSelfAttention)
+  if (position_ids && cfg.pos_type == FD_POS_ABSOLUTE) {
+    HIP_TRY(hipMemcpyAsync(w.pos_ids, position_ids, (size_t)B * L * 4, hipMemcpyHostToDevice, s));
+    mode.pos_ids = w.pos_ids;
+  }
+  if (int rc = prepare_rows(m, s, 0)) return rc;
+  if (int rc = set_t(m, s, t)) return rc;
+  if (int rc = run_step(m, s, mode)) return rc;
+  return finish(m, s, {{eps_out, w.eps, c.n * 4}});
+}
+
+int fd_p_sample_step(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
+                     float* x_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (t > 0 && !z) return fail(FD_E_INVALID, "z is required for t > 0");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  return p_sample_step(m, x, t, lens, B, L, z, wrap, InpaintHost{}, nullptr, x_out);
+}
+
+int fd_p_sample_step_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
+                             const float* known, const uint8_t* fixed, const float* known_coef, const float* z_known,
+                             float* x_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (t > 0 && !z) return fail(FD_E_INVALID, "z is required for t > 0");
+  if (t > 0 && !z_known) return fail(FD_E_INVALID, "z_known is required for t > 0");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  return p_sample_step(m, x, t, lens, B, L, z, wrap, InpaintHost{known, fixed, known_coef}, z_known, x_out);
+}
+
+int fd_sample_begin_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_start,
+                        uint64_t seed, int64_t seq_offset, void* out_dev, int full_history, void* hip_stream) {
+  if (int rc = check_shape(m, B, L, t_start)) return rc;
+  if (!x_init_dev || !lens_dev || !out_dev) return fail(FD_E_INVALID, "null argument");
+  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
+  Call c;
+  if (int rc = open_call(m, x_init_dev, lens_dev, nullptr, B, L, &c, hipMemcpyDeviceToDevice, hip_stream)) return rc;
+  Workspace& w = *c.ws;
+  hipStream_t s = c.s;
+  if (m->varlen && full_history)  // packed rows: positions beyond a sequence's length are never written
+    HIP_TRY(hipMemsetAsync(out_dev, 0, ((size_t)(t_start + full_history) / full_history) * c.n * 4, s));
+  if (int rc = prepare_rows(m, s, m->varlen)) return rc;
+  if (m->use_graph && !graph_current(m, w)) {
+    // first use of this (B, L): the warm-up step and the capture run on the model's stream and need the
+    // lengths / row table that were just queued on `s`
+    if (s != m->stream) HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = ensure_graph(m)) return rc;
+    HIP_TRY(hipStreamSynchronize(m->stream));
+  }
+  UpdateDyn& dyn = m->dyn_host;
+  memset(&dyn, 0, sizeof dyn);
+  dyn.hist = full_history ? static_cast<float*>(out_dev) : nullptr;
+  dyn.seed = seed;
+  dyn.seq_offset = seq_offset;
+  dyn.t_start = t_start;
+  dyn.hist_every = full_history;
+  m->run_t = t_start;
+  m->run_open = true;
+  m->run_B = B;
+  m->run_L = L;
+  if (int rc = set_t(m, s, t_start)) return rc;
+  return FD_OK;
+}
+
+int fd_sample_steps_dev(fd_model* m, int n_steps, const void* noise_dev, int noise_t0, void* hip_stream) {
+  if (!m || !m->finalized || m->ws.B == 0) return fail(FD_E_STATE, "fd_sample_steps_dev without fd_sample_begin_dev");
+  if (!m->run_open) return fail(FD_E_STATE, "fd_sample_steps_dev: no sampling run in progress (another call on this model has taken its workspace)");
+  if (m->ws.B != m->run_B || m->ws.L != m->run_L)
+    return fail(FD_E_STATE, "fd_sample_steps_dev: the workspace now holds B=%d L=%d, the run was begun with B=%d L=%d", m->ws.B, m->ws.L, m->run_B, m->run_L);
+  if (n_steps < 0 || n_steps > m->run_t + 1) return fail(FD_E_INVALID, "n_steps = %d with %d steps left", n_steps, m->run_t + 1);
+  if (noise_dev && (noise_t0 < 0 || noise_t0 > m->run_t - n_steps + 1))  // (the row of t = 0 is read too, and multiplied by sigma_0 = 0)
+    return fail(FD_E_INVALID, "noise rows start at t = %d, the steps run down to t = %d", noise_t0, m->run_t - n_steps + 1);
+  HIP_TRY(hipSetDevice(m->device));
+  Workspace& w = m->ws;
+  hipStream_t s = stream_of(m, hip_stream);
+  // the kernel reads the draw of step t at noise + t * (B L F): rebase the chunk (row 0 = step noise_t0)
+  const size_t n = (size_t)w.B * w.L * m->cfg.n_features;
+  UpdateDyn dyn = m->dyn_host;
+  dyn.noise = noise_dev ? static_cast<const float*>(noise_dev) - (ptrdiff_t)noise_t0 * (ptrdiff_t)n : nullptr;
+  send_dyn(m, s, dyn);
+  for (int i = 0; i < n_steps; ++i) {
+    const int done = m->dyn_host.t_start - m->run_t;  // steps already run
+    const bool prof = m->profile_every > 0 && (done % m->profile_every) == m->profile_every / 2;
+    if (m->use_graph && !prof) {
+      HIP_TRY(hipGraphLaunch(w.graph, s));
+    } else {
+      StepMode mode{};
+      mode.use_dyn = true;
+      mode.advance = true;
+      mode.profile = prof;
+      if (int rc = run_step(m, s, mode)) return rc;
+    }
+    --m->run_t;
+  }
+  return FD_OK;
+}
+
+int fd_sample_end_dev(fd_model* m, void* out_dev, void* hip_stream) {
+  if (!m || !m->finalized || m->ws.B == 0) return fail(FD_E_STATE, "fd_sample_end_dev without fd_sample_begin_dev");
+  if (!m->run_open) return fail(FD_E_STATE, "fd_sample_end_dev: no sampling run in progress (another call on this model has taken its workspace)");
+  if (m->run_t >= 0) return fail(FD_E_STATE, "%d reverse steps have not been run", m->run_t + 1);
+  if (m->ws.B != m->run_B || m->ws.L != m->run_L)
+    return fail(FD_E_STATE, "fd_sample_end_dev: the workspace now holds B=%d L=%d, the run was begun with B=%d L=%d", m->ws.B, m->ws.L, m->run_B, m->run_L);
+  HIP_TRY(hipSetDevice(m->device));
+  Workspace& w = m->ws;
+  hipStream_t s = stream_of(m, hip_stream);
+  const size_t n = (size_t)w.B * w.L * m->cfg.n_features;
+  if (!m->dyn_host.hist_every) HIP_TRY(hipMemcpyAsync(out_dev, w.x, n * 4, hipMemcpyDeviceToDevice, s));
+  m->run_open = false;
+  return FD_OK;
+}
+
+int fd_sample_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_start,
+                  const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev, int full_history,
+                  void* hip_stream) {
+  if (int rc = fd_sample_begin_dev(m, x_init_dev, lens_dev, B, L, t_start, seed, seq_offset, out_dev, full_history, hip_stream))
+    return rc;
+  if (int rc = fd_sample_steps_dev(m, t_start + 1, noise_dev, 0, hip_stream)) return rc;
+  return fd_sample_end_dev(m, out_dev, hip_stream);
+}
+
+int fd_sample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
+              uint64_t seed, float* out, int full_history) {
+  return fd_sample_ex(m, x_init, lens, B, L, t_start, noise, seed, 0, out, full_history);
+}
+
+int fd_sample_ex(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
+                 uint64_t seed, int64_t seq_offset, float* out, int full_history) {
+  if (int rc = check_shape(m, B, L, t_start)) return rc;
+  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  return host_run(m, HostRun{x_init, lens, B, L, t_start, noise, seed, seq_offset, out, full_history});
+}
+
+int fd_sample_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
+                      const float* known, const uint8_t* fixed, const float* known_coef, const float* known_noise,
+                      uint64_t seed, int64_t seq_offset, float* out, int full_history) {
+  if (int rc = check_shape(m, B, L, t_start)) return rc;
+  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  return host_run(m, HostRun{x_init, lens, B, L, t_start, noise, seed, seq_offset, out, full_history, {known, fixed, known_coef}, known_noise});
+}
+
+int fd_sample_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start,
+                               const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* visits,
+                               int n_visits, const float* jump_coef, uint64_t seed, int64_t seq_offset, float* out) {
+  if (int rc = check_shape(m, B, L, t_start)) return rc;
+  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  int n_jumps = 0;
+  if (int rc = check_visits(visits, n_visits, t_start, jump_coef, &n_jumps)) return rc;
+  return host_run(m, HostRun{x_init, lens, B, L, t_start, nullptr, seed, seq_offset, out, 0, {known, fixed, known_coef}, nullptr, visits,
+                             n_visits, jump_coef});
+}
+
+int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int L, int level_to, float jk, float js,
+                    const float* known, const uint8_t* fixed, const float* known_coef, uint64_t seed, int64_t seq_offset,
+                    float* x_out) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (level_to < 1 || level_to > m->T) return fail(FD_E_INVALID, "level_to = %d outside [1, %d]", level_to, m->T);
+  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  if (int rc = check_jump_coef(jk, js, 0)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  Call c;
+  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
+  Workspace& w = *c.ws;
+  InpaintDev ip;
+  if (int rc = stage_inpaint(m, c.s, InpaintHost{known, fixed, known_coef}, &ip)) return rc;
+  launch_inpaint_jump(w.x, w.lens, ip.known, ip.fixed, ip.coef, m->T, level_to, jk, js, seed, seq_offset, B, L, m->cfg.n_features,
+                      m->angle_mask, c.s);
+  HIP_TRY(hipGetLastError());
+  return download_sync(c.s, {{x_out, w.x, c.n * 4}});  // (nothing ran that raises the non-finite flag)
+}
+
+int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,
+                         void* hip_stream) {
+  if (!m || !out_dev) return fail(FD_E_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(m->device));
+  launch_philox_fill(static_cast<float*>(out_dev), seed, t, seq_offset, B, L, m->cfg.n_features, stream_of(m, hip_stream));
+  HIP_TRY(hipGetLastError());
+  return FD_OK;
+}
+
+int fd_shift_trim_dev(fd_model* m, const void* traj_dev, int rows, int B, int L, const void* lens_dev, const void* item_off_dev,
+                      const float* offset, void* out_dev, void* hip_stream) {
+  if (!m || !traj_dev || !lens_dev || !item_off_dev || !out_dev) return fail(FD_E_INVALID, "null argument");
+  if (!m->finalized) return fail(FD_E_STATE, "fd_finalize has not been called");
+  if (rows < 1 || B < 1 || L < 1) return fail(FD_E_INVALID, "rows=%d B=%d L=%d must be positive", rows, B, L);
+  if ((long long)rows * B > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "rows x B = %lld blocks", (long long)rows * B);
+  HIP_TRY(hipSetDevice(m->device));
+  ShiftTrimArgs a;
+  memset(&a, 0, sizeof a);
+  a.traj = static_cast<const float*>(traj_dev); a.lens = static_cast<const int*>(lens_dev);
+  a.item_off = static_cast<const long long*>(item_off_dev); a.out = static_cast<float*>(out_dev);
+  a.rows = rows; a.B = B; a.L = L; a.F = m->cfg.n_features;
+  a.angle_mask = m->angle_mask;
+  a.has_offset = offset ? 1 : 0;
+  if (offset)
+    for (int f = 0; f < a.F; ++f) a.offset[f] = offset[f];
+  launch_shift_trim(a, stream_of(m, hip_stream));
+  HIP_TRY(hipGetLastError());
+  return FD_OK;
+}
+
+}  // extern "C"

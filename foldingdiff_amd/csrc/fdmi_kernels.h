@@ -1,5 +1,5 @@
-// Internal launch interface between the C-ABI host code (api.hip: the model; api_structures.hip: fd_nerf and the
-// structure entries; api_hooks.hip: the fd_test_* hooks) and the gfx950 kernels.  Not installed; include/fdmi.h is the
+// Internal launch interface between the C-ABI host code (api.hip: the model; api_run.hip: the entries that run it;
+// api_structures.hip: fd_nerf and the structure entries; api_hooks.hip: the fd_test_* hooks) and the gfx950 kernels.  Not installed; include/fdmi.h is the
 // public boundary.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
-// Host-only helpers shared by the three C-ABI sources (api.hip: the model; api_structures.hip: the structure entries;
-// api_hooks.hip: the test hooks): the error string, the owner of device buffers that live for one call, the synchronous
-// round trip built on it, and the argument checks of the packed-chain entries.
+// Host-only helpers shared by the four C-ABI sources (api.hip: the model; api_run.hip: the entries that run it;
+// api_structures.hip: the structure entries; api_hooks.hip: the test hooks): the error string, the owner of device buffers
+// that live for one call, the synchronous round trip built on it, and the argument checks of the packed-chain entries.
 #pragma once
 #include <hip/hip_runtime.h>
 
