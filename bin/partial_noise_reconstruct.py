@@ -33,7 +33,7 @@ import logging
 import os
 import sys
 from pathlib import Path
-from typing import Collection, Dict, Tuple
+from typing import Collection, Dict, Optional, Tuple
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
@@ -83,30 +83,34 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--tmscore", action="store_true",
                         help='also write TM-scores ("tmscores", "tmscores_coord") of the same reconstructions')
     parser.add_argument("--lddt", action="store_true", help='also write lDDT scores ("lddt", "lddt_coord") of the same reconstructions')
+    parser.add_argument("--num_steps", type=int, default=None,
+                        help="denoise in this many network evaluations on a strided schedule with the DDIM update (default: every timestep)")
+    parser.add_argument("--eta", type=float, default=0.0, help="with --num_steps: 0 = DDIM .. 1 = the ancestral update of the respaced chain")
     return parser
 
 
-def get_reconstruction_error(pdb_files: Collection[str], timesteps: int, model: str,
-                             device: int = 0) -> Tuple[Dict[str, float], Dict[str, float]]:
+def get_reconstruction_error(pdb_files: Collection[str], timesteps: int, model: str, device: int = 0,
+                             num_steps: Optional[int] = None, eta: float = 0.0) -> Tuple[Dict[str, float], Dict[str, float]]:
     """(RMSD to the original angles' backbone, RMSD to the file's backbone) per file that entered the dataset."""
     assert os.path.isdir(model), f"Model path {model} is not a local directory"
     dset = load_dataset(pdb_files, Path(model))
     net = modelling.BertForDiffusionBase.from_dir(model).to(torch.device(f"cuda:{device}"))
     scores, coord_scores = sampling.get_reconstruction_error(net, dset=dset, noise_timesteps=timesteps,
-                                                             scorer=structures.RmsdScorer(device=device))
+                                                             scorer=structures.RmsdScorer(device=device), num_steps=num_steps, eta=eta)
     files = dset.filenames   # the dataset's (shuffled) order, which the scores follow
     logging.info(f"Reconstruction RMSD from t={timesteps}: {np.min(scores):.3f}-{np.max(scores):.3f} A")
     return ({f: float(s) for f, s in zip(files, scores)}, {f: float(s) for f, s in zip(files, coord_scores)})
 
 
 def get_reconstruction_scores(pdb_files: Collection[str], timesteps: int, model: str, device: int = 0,
-                              tmscore: bool = True, lddt: bool = False) -> Dict[str, Dict[str, float]]:
+                              tmscore: bool = True, lddt: bool = False, num_steps: Optional[int] = None,
+                              eta: float = 0.0) -> Dict[str, Dict[str, float]]:
     """One reconstruction per file, scored by the RMSD scorer and the chosen others: {"rmsd", "rmsd_coord" [, "tmscores",
     "tmscores_coord"] [, "lddt", "lddt_coord"]}, each {file: score} over the files that entered the dataset."""
     assert os.path.isdir(model), f"Model path {model} is not a local directory"
     dset = load_dataset(pdb_files, Path(model))
     net = modelling.BertForDiffusionBase.from_dir(model).to(torch.device(f"cuda:{device}"))
-    recon, truth, files = sampling.reconstruct(net, dset, noise_timesteps=timesteps)
+    recon, truth, files = sampling.reconstruct(net, dset, noise_timesteps=timesteps, num_steps=num_steps, eta=eta)
     out = {}
     scorers = [("rmsd", structures.RmsdScorer(device=device))]
     if tmscore:
@@ -125,15 +129,17 @@ def get_reconstruction_scores(pdb_files: Collection[str], timesteps: int, model:
 
 def main():
     args = build_parser().parse_args()
+    strided = {} if args.num_steps is None else {"num_steps": args.num_steps, "eta": args.eta}
     if args.tmscore or args.lddt:
         scores = get_reconstruction_scores(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device,
-                                           tmscore=args.tmscore, lddt=args.lddt)
+                                           tmscore=args.tmscore, lddt=args.lddt, num_steps=args.num_steps, eta=args.eta)
         with open(args.output_json, "w") as sink:
-            json.dump({"timesteps": args.timesteps, "model": args.model, **scores}, sink, indent=4)
+            json.dump({"timesteps": args.timesteps, "model": args.model, **strided, **scores}, sink, indent=4)
         return
-    rmsd, rmsd_coord = get_reconstruction_error(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device)
+    rmsd, rmsd_coord = get_reconstruction_error(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device,
+                                                num_steps=args.num_steps, eta=args.eta)
     with open(args.output_json, "w") as sink:
-        json.dump({"timesteps": args.timesteps, "model": args.model, "rmsd": rmsd, "rmsd_coord": rmsd_coord}, sink, indent=4)
+        json.dump({"timesteps": args.timesteps, "model": args.model, **strided, "rmsd": rmsd, "rmsd_coord": rmsd_coord}, sink, indent=4)
 
 
 if __name__ == "__main__":

@@ -81,6 +81,11 @@ def build_parser() -> argparse.ArgumentParser:
     psea.add_argument("--nopsea", action="store_true", help="accepted for compatibility: the P-SEA step runs only with --psea")
     parser.add_argument("--clashes", action="store_true",
                         help="count the van der Waals clashes of the sampled backbones (on the device) into clash_counts.json")
+    parser.add_argument("--num_steps", type=int, default=None,
+                        help="sample in this many network evaluations on a strided schedule with the DDIM update (default: every timestep, "
+                             "the reference's ancestral loop); the run's arguments then go to sampling_args.json")
+    parser.add_argument("--eta", type=float, default=0.0,
+                        help="with --num_steps: 0 = DDIM (deterministic given the start noise) .. 1 = the ancestral update of the respaced chain")
     parser.add_argument("--seed", type=int, default=SEED, help="Random seed")
     parser.add_argument("--device", type=str, default="cuda:0", help="Device to use")
     return parser
@@ -133,7 +138,10 @@ def main(argv=None) -> None:
 
     torch.manual_seed(args.seed)
     sampled = sampling.sample(model, train_dset, n=args.num, sweep_lengths=(sweep_min_len, sweep_max_len),
-                              batch_size=args.batchsize, final_only=not args.fullhistory)
+                              batch_size=args.batchsize, final_only=not args.fullhistory, num_steps=args.num_steps, eta=args.eta)
+    if rank == 0 and args.num_steps is not None:   # a strided run says so beside its samples
+        with open(outdir / "sampling_args.json", "w") as sink:
+            json.dump(vars(args), sink, indent=4)
     if rank == 0:
         names = train_dset.feature_names["angles"]
         sampled_dfs = [pd.DataFrame(s[-1], columns=names) for s in sampled]

@@ -648,6 +648,7 @@ UpdateArgs fill_update(const fd_model* m, const Workspace& w, const StepMode& mo
       u.noise = mode.noise;
       u.t_start = mode.t_start;
       u.known = mode.known; u.fixed = mode.fixed; u.known_noise = mode.z_known; u.known_coef = mode.known_coef;
+      u.strided = mode.strided ? 1 : 0; u.sa = mode.sa; u.sb = mode.sb; u.ss = mode.ss;
     }
   }
   if (mode.use_dyn) u.noise_stride = (long long)u.M * u.F;
@@ -702,7 +703,7 @@ int run_step(fd_model* m, hipStream_t s, const StepMode& mode) {
     u.g = w.g;
   }
   PROF(KC_HEAD_UPDATE, launch_head_update(u, s));
-  if (mode.advance) PROF(KC_ADVANCE, launch_step_advance(w.t_dev, s));
+  if (mode.advance) PROF(KC_ADVANCE, launch_step_advance(w.t_dev, mode.use_dyn ? w.dyn : nullptr, s));
   HIP_TRY(hipGetLastError());
   return FD_OK;
 }

@@ -1,5 +1,5 @@
 // C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
-// single reverse steps, the sampling runs (plain, motif-conditioned, resampled) and their device-buffer pieces.  Host code
+// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided) and their device-buffer pieces.  Host code
 // around api.hip's workspace, launch plan and step (model.h) only: every entry checks its arguments before its first HIP call,
 // and the paragraphs the entries share -- make the workspace current and upload, download and synchronise, the host-side
 // run, the one-copy staging of the loss entries -- are written once, below.
@@ -241,6 +241,44 @@ int check_visits(const int32_t* visits, int n_visits, int t_start, const float* 
   return FD_OK;
 }
 
+// ---- the opening of a sampling run on device arrays: n_steps reverse steps, the first of them step t_first.  The plain run
+// (fd_sample_begin_dev) has n_steps = t_first + 1; a strided run counts its visits.  m->run_t = the steps left, minus one --
+// in a plain run the next timestep
+int begin_run(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_first, int n_steps, uint64_t seed,
+              int64_t seq_offset, void* out_dev, int full_history, void* hip_stream) {
+  if (int rc = check_shape(m, B, L, t_first)) return rc;
+  if (!x_init_dev || !lens_dev || !out_dev) return fail(FD_E_INVALID, "null argument");
+  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
+  Call c;
+  if (int rc = open_call(m, x_init_dev, lens_dev, nullptr, B, L, &c, hipMemcpyDeviceToDevice, hip_stream)) return rc;
+  Workspace& w = *c.ws;
+  hipStream_t s = c.s;
+  if (m->varlen && full_history)  // packed rows: positions beyond a sequence's length are never written
+    HIP_TRY(hipMemsetAsync(out_dev, 0, ((size_t)(n_steps - 1 + full_history) / full_history) * c.n * 4, s));
+  if (int rc = prepare_rows(m, s, m->varlen)) return rc;
+  if (m->use_graph && !graph_current(m, w)) {
+    // first use of this (B, L): the warm-up step and the capture run on the model's stream and need the
+    // lengths / row table that were just queued on `s`
+    if (s != m->stream) HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = ensure_graph(m)) return rc;
+    HIP_TRY(hipStreamSynchronize(m->stream));
+  }
+  UpdateDyn& dyn = m->dyn_host;
+  memset(&dyn, 0, sizeof dyn);
+  dyn.hist = full_history ? static_cast<float*>(out_dev) : nullptr;
+  dyn.seed = seed;
+  dyn.seq_offset = seq_offset;
+  dyn.t_start = t_first;
+  dyn.hist_every = full_history;
+  m->run_t = n_steps - 1;
+  m->run_n = n_steps;
+  m->run_open = true;
+  m->run_B = B;
+  m->run_L = L;
+  if (int rc = set_t(m, s, t_first)) return rc;
+  return FD_OK;
+}
+
 // ---- a whole sampling run from host arrays (fd_sample_ex, fd_sample_inpaint, fd_sample_inpaint_resample); the entry has
 // checked every argument
 struct HostRun {
@@ -337,6 +375,83 @@ int host_run(fd_model* m, const HostRun& a) {
   if (rc) return rc;
   HIP_TRY(hipMemcpy(a.out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
   return check_flag(m);
+}
+
+// ---- strided (few-step) sampling: argument checks, all before the first device call
+int check_strided(const fd_model* m, const int32_t* visits, int n_visits, const float* coef) {
+  if (!visits) return fail(FD_E_INVALID, "visits is null");
+  if (!coef) return fail(FD_E_INVALID, "coef is null");
+  if (n_visits < 1) return fail(FD_E_INVALID, "n_visits = %d must be positive", n_visits);
+  for (int i = 0; i < n_visits; ++i) {
+    if (visits[i] < 0 || visits[i] >= m->T) return fail(FD_E_INVALID, "visits[%d] = %d outside [0, %d)", i, visits[i], m->T);
+    if (i > 0 && visits[i] >= visits[i - 1])
+      return fail(FD_E_INVALID, "visits[%d] = %d follows %d: a strided schedule is strictly descending", i, visits[i], visits[i - 1]);
+  }
+  for (int r = 0; r < 3; ++r)
+    for (int i = 0; i < n_visits; ++i)
+      if (!std::isfinite(coef[(size_t)r * n_visits + i]))
+        return fail(FD_E_INVALID, "coef[%d][%d] = %g is not finite", r, i, (double)coef[(size_t)r * n_visits + i]);
+  return FD_OK;
+}
+
+// where a strided run's tables are on the device (all null: no strided run)
+struct StridedDev {
+  const int *next_t = nullptr, *ord = nullptr;
+  const float* abs = nullptr;
+  void apply(UpdateDyn* dyn) const { dyn->next_t = next_t; dyn->ord = ord; dyn->abs = abs; }
+  static void clear(UpdateDyn* dyn) { StridedDev().apply(dyn); }
+};
+
+// the tables indexed by timestep, next_t | ord | a | b | s ([T] each), in ONE buffer of the call's lifetime (blocking upload);
+// a timestep the schedule does not visit holds next_t = -1 and zeros, and is never looked up
+int stage_strided(const fd_model* m, DeviceBufs* bufs, const int32_t* visits, int n_visits, const float* coef, StridedDev* d) {
+  const size_t T = (size_t)m->T;
+  std::vector<int32_t> tab(5 * T, 0);
+  for (size_t t = 0; t < T; ++t) tab[t] = -1;
+  for (int i = 0; i < n_visits; ++i) {
+    const size_t t = (size_t)visits[i];
+    tab[t] = i + 1 < n_visits ? visits[i + 1] : -1;
+    tab[T + t] = i;
+    for (int r = 0; r < 3; ++r) memcpy(&tab[(2 + r) * T + t], &coef[(size_t)r * n_visits + i], 4);
+  }
+  const int32_t* dev = nullptr;
+  HIP_TRY(bufs->upload(tab.data(), tab.size() * 4, &dev));
+  d->next_t = dev;
+  d->ord = dev + T;
+  d->abs = reinterpret_cast<const float*>(dev + 2 * T);
+  return FD_OK;
+}
+
+// A strided run on device arrays (the entry has checked every argument): the plain sampler's steps -- its captured graph
+// included -- with the tables in the update kernels' per-run values.  Returns with the stream drained and the fields cleared,
+// on the host and on the device, on every path: the tables die with this frame.
+int strided_run_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits, int n_visits,
+                    const float* coef, const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev, int full_history,
+                    void* hip_stream) {
+  HIP_TRY(hipSetDevice(m->device));
+  DeviceBufs bufs;
+  StridedDev sd;
+  if (int rc = stage_strided(m, &bufs, visits, n_visits, coef, &sd)) return rc;
+  if (int rc = begin_run(m, x_init_dev, lens_dev, B, L, visits[0], n_visits, seed, seq_offset, out_dev, full_history, hip_stream)) return rc;
+  hipStream_t s = stream_of(m, hip_stream);
+  sd.apply(&m->dyn_host);
+  int rc = fd_sample_steps_dev(m, n_visits, noise_dev, 0, hip_stream);  // (noise rows are per visit: row 0 = visit 0)
+  if (!rc) rc = fd_sample_end_dev(m, out_dev, hip_stream);
+  m->run_open = false;
+  m->run_t = -1;
+  StridedDev::clear(&m->dyn_host);
+  send_dyn(m, s, m->dyn_host);
+  HIP_TRY(hipStreamSynchronize(s));
+  return rc;
+}
+
+// ... and the checks the two entries share
+int check_strided_call(fd_model* m, const void* x_init, const void* lens, const void* out, int B, int L, const int32_t* visits,
+                       int n_visits, const float* coef, int full_history) {
+  if (int rc = check_shape(m, B, L, 0)) return rc;
+  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
+  return check_strided(m, visits, n_visits, coef);
 }
 
 }  // namespace
@@ -566,36 +681,7 @@ int fd_p_sample_step_inpaint(fd_model* m, const float* x, int t, const int32_t* 
 
 int fd_sample_begin_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_start,
                         uint64_t seed, int64_t seq_offset, void* out_dev, int full_history, void* hip_stream) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init_dev || !lens_dev || !out_dev) return fail(FD_E_INVALID, "null argument");
-  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
-  Call c;
-  if (int rc = open_call(m, x_init_dev, lens_dev, nullptr, B, L, &c, hipMemcpyDeviceToDevice, hip_stream)) return rc;
-  Workspace& w = *c.ws;
-  hipStream_t s = c.s;
-  if (m->varlen && full_history)  // packed rows: positions beyond a sequence's length are never written
-    HIP_TRY(hipMemsetAsync(out_dev, 0, ((size_t)(t_start + full_history) / full_history) * c.n * 4, s));
-  if (int rc = prepare_rows(m, s, m->varlen)) return rc;
-  if (m->use_graph && !graph_current(m, w)) {
-    // first use of this (B, L): the warm-up step and the capture run on the model's stream and need the
-    // lengths / row table that were just queued on `s`
-    if (s != m->stream) HIP_TRY(hipStreamSynchronize(s));
-    if (int rc = ensure_graph(m)) return rc;
-    HIP_TRY(hipStreamSynchronize(m->stream));
-  }
-  UpdateDyn& dyn = m->dyn_host;
-  memset(&dyn, 0, sizeof dyn);
-  dyn.hist = full_history ? static_cast<float*>(out_dev) : nullptr;
-  dyn.seed = seed;
-  dyn.seq_offset = seq_offset;
-  dyn.t_start = t_start;
-  dyn.hist_every = full_history;
-  m->run_t = t_start;
-  m->run_open = true;
-  m->run_B = B;
-  m->run_L = L;
-  if (int rc = set_t(m, s, t_start)) return rc;
-  return FD_OK;
+  return begin_run(m, x_init_dev, lens_dev, B, L, t_start, t_start + 1, seed, seq_offset, out_dev, full_history, hip_stream);
 }
 
 int fd_sample_steps_dev(fd_model* m, int n_steps, const void* noise_dev, int noise_t0, void* hip_stream) {
@@ -615,7 +701,7 @@ int fd_sample_steps_dev(fd_model* m, int n_steps, const void* noise_dev, int noi
   dyn.noise = noise_dev ? static_cast<const float*>(noise_dev) - (ptrdiff_t)noise_t0 * (ptrdiff_t)n : nullptr;
   send_dyn(m, s, dyn);
   for (int i = 0; i < n_steps; ++i) {
-    const int done = m->dyn_host.t_start - m->run_t;  // steps already run
+    const int done = m->run_n - 1 - m->run_t;  // steps already run
     const bool prof = m->profile_every > 0 && (done % m->profile_every) == m->profile_every / 2;
     if (m->use_graph && !prof) {
       HIP_TRY(hipGraphLaunch(w.graph, s));
@@ -713,6 +799,59 @@ int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int
                       m->angle_mask, c.s);
   HIP_TRY(hipGetLastError());
   return download_sync(c.s, {{x_out, w.x, c.n * 4}});  // (nothing ran that raises the non-finite flag)
+}
+
+int fd_sample_strided_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits,
+                          int n_visits, const float* coef, const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev,
+                          int full_history, void* hip_stream) {
+  if (int rc = check_strided_call(m, x_init_dev, lens_dev, out_dev, B, L, visits, n_visits, coef, full_history)) return rc;
+  return strided_run_dev(m, x_init_dev, lens_dev, B, L, visits, n_visits, coef, noise_dev, seed, seq_offset, out_dev, full_history,
+                         hip_stream);
+}
+
+int fd_sample_strided(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                      const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, float* out, int full_history) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, full_history)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  const size_t out_rows = full_history ? ((size_t)n_visits + full_history - 1) / full_history : 1;
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  const float* d_noise = nullptr;
+  int* d_lens;
+  HIP_TRY(bufs.upload(x_init, n * 4, &d_x));
+  HIP_TRY(bufs.upload(lens, (size_t)B * 4, &d_lens));
+  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
+  if (noise) HIP_TRY(bufs.upload(noise, (size_t)n_visits * n * 4, &d_noise));
+  if (int rc = strided_run_dev(m, d_x, d_lens, B, L, visits, n_visits, coef, d_noise, seed, seq_offset, d_out, full_history, nullptr))
+    return rc;
+  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
+  return check_flag(m);
+}
+
+int fd_p_sample_step_coef(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
+                          const float* z, int wrap, float* eps_out, float* x_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(s))
+    return fail(FD_E_INVALID, "a = %g, b = %g, s = %g: a coefficient is not finite", (double)a, (double)b, (double)s);
+  if (s != 0.f && !z) return fail(FD_E_INVALID, "z is required for s != 0");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  Call c;
+  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
+  Workspace& w = *c.ws;
+  if (s != 0.f) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
+  if (int rc = prepare_rows(m, c.s, 0)) return rc;
+  if (int rc = set_t(m, c.s, t)) return rc;
+  StepMode mode{};
+  mode.noise = w.z;
+  mode.t_start = t;
+  mode.no_wrap = !wrap;
+  mode.strided = true;
+  mode.sa = a; mode.sb = b; mode.ss = s;
+  if (int rc = run_step(m, c.s, mode)) return rc;
+  return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}});
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

@@ -64,6 +64,11 @@ struct UpdateDyn {
   const unsigned char* fixed;  // [M, F] != 0: the element is replaced after every step instead of updated
   const float* known_noise;    // [t_start+2, M, F] draws of the replacement (row j: level j) or null (Philox, tagged step word)
   const float* known_coef;     // [2, T+1] keep | spread per level
+  // strided (few-step) sampling: all null unless fd_sample_strided is running; indexed by the timestep t the kernel holds
+  // (a descending schedule visits each t at most once).  `noise` and `hist` rows are then per visit: row ord[t]
+  const int* next_t;           // [T] the next visit's t, -1 behind the last visit
+  const int* ord;              // [T] the visit's ordinal 0 .. K-1
+  const float* abs;            // [3, T] rows a | b | s of the visit:  x' = a x + b eps (+ s z where s != 0)
 };
 struct UpdateArgs {
   const UpdateDyn* dyn;  // device pointer; when non-null it overrides noise/hist/seed/seq_offset/t_start
@@ -94,6 +99,9 @@ struct UpdateArgs {
   const unsigned char* fixed;
   const float* known_noise;
   const float* known_coef;
+  // one strided update by value, without `dyn` (fd_p_sample_step_coef): x' = sa x + sb eps (+ ss z where ss != 0), z = `noise`
+  int strided;
+  float sa, sb, ss;
 };
 void launch_head_update(const UpdateArgs& a, hipStream_t s);
 // The replacement of the start point of a motif-conditioned run (inpaint_replace.h): x[o] = the level-`level` value of
@@ -162,8 +170,8 @@ void launch_backbone_clashes(const float* xyz, const int* offsets, const int* le
 void launch_lddt(const float* model, const float* ref, const int* offsets, const int* lens, int n_pairs, int atoms_per_res,
                  double radius, const LddtThresholds& thr, long long* counts_out, int* res_counts_out, hipStream_t s);
 
-// *t_dev -= 1  (last node of the per-step graph)
-void launch_step_advance(int* t_dev, hipStream_t s);
+// *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
+void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);
 
 // out[i] = Philox normal for (seed, t, element i of [B][L][F] with seq_offset)
 void launch_philox_fill(float* out, unsigned long long seed, int t, long long seq_offset, int B, int L, int F,

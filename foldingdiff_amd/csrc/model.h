@@ -160,7 +160,8 @@ struct fd_model {
   void* comm = nullptr;  // ncclComm_t (fd_comm_init)
   int comm_world = 0, comm_rank = 0;
   fdmi::UpdateDyn dyn_host{};  // per-run values of the sampling loop in progress (fd_sample_begin_dev .. fd_sample_end_dev)
-  int run_t = -1;        // next timestep of that run (-1: none left)
+  int run_t = -1;        // next timestep of that run (-1: none left); a strided run: its number of visits left, minus one
+  int run_n = 0;         // steps (visits) the run was begun with: the profiling ordinal counts from it
   bool run_open = false; // between fd_sample_begin_dev and fd_sample_end_dev, with no other call on the model in between
   int run_B = 0, run_L = 0;  // its shape: fd_sample_steps_dev / _end_dev refuse to run on another workspace
   // profiling
@@ -188,6 +189,9 @@ struct StepMode {
   // fd_p_sample_step_inpaint: the replacement's arrays (device; z_known = the one slab of level t), null otherwise
   const float *known = nullptr, *known_coef = nullptr, *z_known = nullptr;
   const unsigned char* fixed = nullptr;
+  // fd_p_sample_step_coef: one strided update x' = sa x + sb eps (+ ss z where ss != 0, z = `noise`) in place of p_sample's
+  bool strided = false;
+  float sa = 0.f, sb = 0.f, ss = 0.f;
   const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
   bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
 };

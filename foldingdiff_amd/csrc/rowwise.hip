@@ -13,6 +13,7 @@
 #include "fdmi_kernels.h"
 #include "inpaint_replace.h"
 #include "philox_normal.h"
+#include "strided_update.h"
 #include "wrap_pi.h"
 
 namespace fdmi {
@@ -427,12 +428,29 @@ __global__ __launch_bounds__(256) void head_update_kernel(UpdateArgs a) {
     hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
     known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
   }
+  // strided sampling (fd_sample_strided: the tables of `dyn`; fd_p_sample_step_coef: by value)
+  bool strided = a.strided != 0;
+  float sa = a.sa, sb = a.sb, ss = a.ss;
+  int ord = 0, t_next = -1;
+  if (a.dyn && a.dyn->next_t) {
+    strided = true;
+    t_next = a.dyn->next_t[t]; ord = a.dyn->ord[t];
+    sa = a.dyn->abs[t]; sb = a.dyn->abs[a.T + t]; ss = a.dyn->abs[2 * a.T + t];
+  }
   const float c1 = a.coef[t], bt = a.coef[a.T + t], c3 = a.coef[2 * a.T + t], sg = a.coef[3 * a.T + t];
   // model_mean = sqrt_recip_alphas_t * (x - betas_t * eps / sqrt_one_minus_alphas_cumprod_t)   (sampling.py:62-67)
   float xn;
   if (fixed && fixed[o]) {  // a fixed element leaves step t at level t, whatever the model predicted
     xn = inpaint_value(known, known_noise, known_coef, a.T, a.noise_stride, t, o, seed, seq_offset + tok / a.L, tok % a.L, lane,
                        (a.angle_mask >> lane) & 1u);
+  } else if (strided) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
+    xn = strided_mean(sa, a.x[o], sb, mine);
+    if (ss != 0.f) {
+      const float z = noise ? noise[(size_t)ord * a.noise_stride + o]
+                            : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, lane);
+      xn = strided_add_noise(xn, ss, z);
+    }
+    if ((a.angle_mask >> lane) & 1u) xn = wrap_pi(xn);
   } else {
     xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(bt, mine), c3)));
     if (t > 0) {  // sampling.py:69-75
@@ -443,8 +461,10 @@ __global__ __launch_bounds__(256) void head_update_kernel(UpdateArgs a) {
     if ((a.angle_mask >> lane) & 1u) xn = wrap_pi(xn);
   }
   a.x_out[o] = xn;
-  if (hist && ((t_start - t + 1) % hist_every == 0 || t == 0))  // state j = t_start - t goes to row j / hist_every
-    hist[(size_t)((t_start - t) / hist_every) * a.M * F + o] = xn;
+  const int state = strided ? ord : t_start - t;   // the state's ordinal in the run
+  const bool last = strided ? t_next < 0 : t == 0;
+  if (hist && ((state + 1) % hist_every == 0 || last))  // state j goes to row j / hist_every
+    hist[(size_t)(state / hist_every) * a.M * F + o] = xn;
 }
 
 template <int NV>
@@ -477,6 +497,15 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
     hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
     known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
   }
+  // strided sampling (fd_sample_strided: the tables of `dyn`; fd_p_sample_step_coef: by value)
+  bool strided = a.strided != 0;
+  float sa = a.sa, sb = a.sb, ss = a.ss;
+  int ord = 0, t_next = -1;
+  if (a.x_out && a.dyn && a.dyn->next_t) {
+    strided = true;
+    t_next = a.dyn->next_t[t]; ord = a.dyn->ord[t];
+    sa = a.dyn->abs[t]; sb = a.dyn->abs[a.T + t]; ss = a.dyn->abs[2 * a.T + t];
+  }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
   if (a.x_out) { c1 = a.coef[t]; btc = a.coef[a.T + t]; c3 = a.coef[2 * a.T + t]; sg = a.coef[3 * a.T + t]; }
   __syncthreads();
@@ -508,6 +537,14 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
         if (fixed && fixed[o]) {  // a fixed element leaves step t at level t, whatever the model predicted
           xn = inpaint_value(known, known_noise, known_coef, a.T, a.noise_stride, t, o, seed, seq_offset + tok / a.L,
                              tok % a.L, k, (a.angle_mask >> k) & 1u);
+        } else if (strided) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
+          xn = strided_mean(sa, a.x[o], sb, mine);
+          if (ss != 0.f) {
+            const float z = noise ? noise[(size_t)ord * a.noise_stride + o]
+                                  : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, k);
+            xn = strided_add_noise(xn, ss, z);
+          }
+          if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         } else {
           xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
           if (t > 0) {  // sampling.py:69-75
@@ -518,8 +555,10 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
           if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         }
         a.x_out[o] = xn;
-        if (hist && ((t_start - t + 1) % hist_every == 0 || t == 0))  // state j = t_start - t goes to row j / hist_every
-    hist[(size_t)((t_start - t) / hist_every) * a.M * F + o] = xn;
+        const int state = strided ? ord : t_start - t;   // the state's ordinal in the run
+        const bool last = strided ? t_next < 0 : t == 0;
+        if (hist && ((state + 1) % hist_every == 0 || last))  // state j goes to row j / hist_every
+          hist[(size_t)(state / hist_every) * a.M * F + o] = xn;
       }
     }
   }
@@ -577,8 +616,13 @@ void launch_inpaint_init(float* x, const float* known, const unsigned char* fixe
                      level, seed, seq_offset, n, L, F, angle_mask);
 }
 
-__global__ void step_advance_kernel(int* t_dev) { *t_dev -= 1; }
-void launch_step_advance(int* t_dev, hipStream_t s) { hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, t_dev); }
+__global__ void step_advance_kernel(int* t_dev, const UpdateDyn* dyn) {
+  if (dyn && dyn->next_t) *t_dev = dyn->next_t[*t_dev];  // a strided run: the next visit's t (-1 behind the last)
+  else *t_dev -= 1;
+}
+void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s) {
+  hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, t_dev, dyn);
+}
 
 void launch_wrap_test_f32(const float* in, float* out, long long n, hipStream_t s) {
   hipLaunchKernelGGL(wrap_test_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);

@@ -15,6 +15,7 @@
 #include "img_common.h"
 #include "inpaint_replace.h"
 #include "philox_normal.h"
+#include "strided_update.h"
 #include "wrap_pi.h"
 
 namespace fdmi {
@@ -510,6 +511,15 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
     hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
     known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
   }
+  // strided sampling (fd_sample_strided: the tables of `dyn`; fd_p_sample_step_coef: by value)
+  bool strided = a.strided != 0;
+  float sa = a.sa, sb = a.sb, ss = a.ss;
+  int ord = 0, t_next = -1;
+  if (a.x_out && a.dyn && a.dyn->next_t) {
+    strided = true;
+    t_next = a.dyn->next_t[t]; ord = a.dyn->ord[t];
+    sa = a.dyn->abs[t]; sb = a.dyn->abs[a.T + t]; ss = a.dyn->abs[2 * a.T + t];
+  }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
   if (a.x_out) { c1 = a.coef[t]; btc = a.coef[a.T + t]; c3 = a.coef[2 * a.T + t]; sg = a.coef[3 * a.T + t]; }
   __syncthreads();
@@ -565,6 +575,13 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
         if (fixed && fixed[o]) {  // a fixed element leaves step t at level t, whatever the model predicted
           xn = inpaint_value(known, known_noise, known_coef, a.T, a.noise_stride, t, o, seed, seq_offset + ri.x, ri.y, k,
                              (a.angle_mask >> k) & 1u);
+        } else if (strided) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
+          xn = strided_mean(sa, a.x[o], sb, mine);
+          if (ss != 0.f) {
+            const float z = noise ? noise[(size_t)ord * a.noise_stride + o] : philox_normal(seed, t, seq_offset + ri.x, ri.y, k);
+            xn = strided_add_noise(xn, ss, z);
+          }
+          if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         } else {
           xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
           if (t > 0) {  // sampling.py:69-75
@@ -574,13 +591,15 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
           if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
         }
         a.x_out[o] = xn;
-        if (hist && ((t_start - t + 1) % hist_every == 0 || t == 0))  // state j = t_start - t goes to row j / hist_every
-          hist[(size_t)((t_start - t) / hist_every) * BLF + o] = xn;
+        const int state = strided ? ord : t_start - t;   // the state's ordinal in the run
+        const bool last = strided ? t_next < 0 : t == 0;
+        if (hist && ((state + 1) % hist_every == 0 || last))  // state j goes to row j / hist_every
+          hist[(size_t)(state / hist_every) * BLF + o] = xn;
       }
     }
   }
   if (bad) atomicOr(ia.flag, 1);  // SURVEY 5 failure detection: a non-finite prediction poisons everything after it
-  if (ia.advance && blockIdx.x == 0 && threadIdx.x == 0) ia.tslot[0] = t - 1;  // next step (read by embed_img only)
+  if (ia.advance && blockIdx.x == 0 && threadIdx.x == 0) ia.tslot[0] = strided ? t_next : t - 1;  // next step (read by embed_img only)
 }
 
 // ---------------------------------------------------------------- converters (test hooks, debug dumps)

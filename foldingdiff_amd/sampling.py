@@ -232,6 +232,126 @@ _run_fd_sample_default = _run_fd_sample
 _NOISE_BUFFERS: dict = {}
 
 
+# --------------------------------------------------------------------------------- few-step (strided) sampling
+def ddim_visits(T: int, num_steps: int, t_first: Optional[int] = None) -> np.ndarray:
+    """int32 [num_steps]: the timesteps a strided run visits, evenly spaced from ``t_first`` (default ``T - 1``) down to 0,
+    strictly descending.  ``floor(x + 0.5)``, not ``np.round``: half-to-even gives duplicates at spacing 1 (1.5 and 2.5
+    both round to 2)."""
+    t_first = T - 1 if t_first is None else int(t_first)
+    if not 0 <= t_first < T:
+        raise ValueError(f"t_first={t_first} outside the {T}-step schedule")
+    if not 1 <= num_steps <= t_first + 1:
+        raise ValueError(f"num_steps={num_steps}: a schedule from t={t_first} has 1 .. {t_first + 1} distinct visits")
+    visits = np.floor(np.linspace(t_first, 0, num_steps) + 0.5).astype(np.int32)
+    assert visits[0] == t_first and (np.diff(visits) < 0).all()
+    return visits
+
+
+def _ddim_coefficients64(betas, visits, eta: float) -> np.ndarray:
+    """``ddim_coefficients`` before its one rounding: float64 [3, K]."""
+    b64 = torch.as_tensor(betas).detach().cpu().numpy().astype(np.float64)
+    visits = np.asarray(visits, dtype=np.int64).reshape(-1)
+    if len(visits) < 1 or visits.min() < 0 or visits.max() >= len(b64) or (np.diff(visits) >= 0).any():
+        raise ValueError(f"visits must be strictly descending within [0, {len(b64)}), got {visits.tolist()}")
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"eta={eta} outside [0, 1]")
+    acp = np.concatenate([[1.0], np.cumprod(1.0 - b64)])     # acp[j] = the product of the first j alphas: level j
+    p = visits + 1
+    q = np.concatenate([visits[1:] + 1, [0]])
+    r = acp[p] / acp[q]
+    s = eta * np.sqrt((1.0 - acp[q]) / (1.0 - acp[p])) * np.sqrt(1.0 - r)
+    a = np.sqrt(1.0 / r)
+    b = np.sqrt(np.maximum(1.0 - acp[q] - s * s, 0.0)) - a * np.sqrt(1.0 - acp[p])
+    return np.stack([a, b, s])
+
+
+def ddim_coefficients(betas, visits, eta: float = 0.0) -> np.ndarray:
+    """float32 [3, K], rows a | b | s: the update ``x' = a x + b eps + s z`` of every visit of a strided schedule
+    (``fd_sample_strided``'s ``coef``; Song et al. 2021, eq. 12 with sigma = eta * the posterior's).  Visit i takes the state
+    from level ``p = visits[i] + 1`` to level ``q = visits[i + 1] + 1`` (``q = 0`` behind the last visit; levels as in
+    ``inpaint_levels``).  With ``acp(0) = 1``, ``acp(j) = prod_{u<j} (1 - float64(betas[u]))`` and ``r = acp(p) / acp(q)``:
+    ``s = eta sqrt((1 - acp(q)) / (1 - acp(p))) sqrt(1 - r)``, ``a = sqrt(1 / r)``,
+    ``b = sqrt(max(1 - acp(q) - s^2, 0)) - a sqrt(1 - acp(p))``; float64 throughout, rounded once.  ``eta = 0`` is DDIM (every
+    s exactly 0), ``eta = 1`` the ancestral update of the respaced chain -- with all T visits ``p_sample`` itself."""
+    return np.ascontiguousarray(_ddim_coefficients64(betas, visits, eta).astype(np.float32))
+
+
+def _run_fd_sample_strided(h, x0: np.ndarray, lens: np.ndarray, visits: np.ndarray, coef: np.ndarray, zs: Optional[np.ndarray],
+                           seed: int, seq_offset: int, out: np.ndarray, full_history: int) -> None:
+    """The one call into libfdmi.so that runs a strided schedule on a host batch (fd_sample_strided).  Tests of the host
+    side replace exactly this function with a CPU stand-in."""
+    B, L, _ = x0.shape
+    _binding.check(_binding.load().fd_sample_strided(
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, _binding.ptr(visits), len(visits), _binding.ptr(coef), _binding.ptr(zs),
+        C.c_uint64(seed), C.c_int64(seq_offset), _binding.ptr(out), full_history))
+
+
+def _run_fd_sample_strided_device(model, h, x0: np.ndarray, lens: np.ndarray, visits: np.ndarray, coef: np.ndarray,
+                                  zs: Optional[np.ndarray], seed: int, seq_offset: int, rows: int, full_history: int) -> torch.Tensor:
+    """fd_sample_strided_dev on device copies of a host batch; the [rows, B, L, F] result stays on the device."""
+    dev = model.device
+    B, L, F = x0.shape
+    x_d, lens_d = torch.from_numpy(x0).to(dev), torch.from_numpy(lens).to(dev)
+    z_d = torch.from_numpy(zs).to(dev) if zs is not None else None
+    out_d = torch.empty((rows, B, L, F), dtype=torch.float32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    lib = _binding.load()
+    _binding.check(lib.fd_sample_strided_dev(h, C.c_void_p(x_d.data_ptr()), C.c_void_p(lens_d.data_ptr()), B, L, _binding.ptr(visits),
+                                             len(visits), _binding.ptr(coef), C.c_void_p(z_d.data_ptr()) if z_d is not None else None,
+                                             C.c_uint64(seed), C.c_int64(seq_offset), C.c_void_p(out_d.data_ptr()), full_history, None))
+    _binding.check(lib.fd_check_finite(h))
+    return out_d
+
+
+_run_fd_sample_strided_default = _run_fd_sample_strided
+
+
+def _draw_visit_noise(coef: np.ndarray, shape, rows: Optional[Tuple[int, int]] = None) -> Optional[np.ndarray]:
+    """Torch-order draws of a strided run, [K, b, L, F]: one ``torch.randn`` of the WHOLE batch shape per visit with
+    ``s != 0``, in visit order (the other rows stay zero and are not read); ``rows=(lo, hi)`` keeps that slice of the batch.
+    None when no visit draws (eta = 0)."""
+    if not (coef[2] != 0).any():
+        return None
+    lo, hi = rows if rows is not None else (0, shape[0])
+    zs = np.zeros((coef.shape[1], hi - lo) + tuple(shape[1:]), dtype=np.float32)
+    for i in range(coef.shape[1]):
+        if coef[2, i] != 0:
+            zs[i] = torch.randn(tuple(shape), dtype=torch.float32).numpy()[lo:hi]
+    return zs
+
+
+def _strided_loop(model, h, x0: np.ndarray, lens: np.ndarray, betas, t_first: int, num_steps: int, eta: float, final_only: bool,
+                  history_every: int, step_noise: Optional[np.ndarray], seed: Optional[int], seq_offset: int,
+                  draw_batch: Optional[Tuple[int, int, int]], device_out: bool) -> torch.Tensor:
+    """``num_steps`` visits from ``t_first`` down to 0 on a host batch: the schedule, its coefficients, the draws, the call."""
+    B, L, F = x0.shape
+    visits = ddim_visits(len(betas), num_steps, t_first)
+    coef = ddim_coefficients(betas, visits, eta)
+    K = len(visits)
+    if step_noise is not None:
+        zs = np.ascontiguousarray(step_noise, dtype=np.float32)
+        assert zs.shape == (K, B, L, F), f"step_noise of a strided run has one row per visit: {(K, B, L, F)}, got {zs.shape}"
+        seed = 0
+    elif seed is not None:
+        zs = None
+    elif NOISE_MODE == "torch":
+        b_all, lo, hi = draw_batch if draw_batch is not None else (B, 0, B)
+        assert hi - lo == B
+        zs, seed = _draw_visit_noise(coef, (b_all, L, F), (lo, hi)), 0
+    elif NOISE_MODE == "philox":
+        zs, seed = None, _draw_philox_seed()
+    else:
+        raise ValueError(f"NOISE_MODE={NOISE_MODE!r}")
+    rows = 1 if final_only else -(-K // history_every)
+    hist = 0 if final_only else history_every
+    on_gpu = _run_fd_sample_strided is _run_fd_sample_strided_default and getattr(getattr(model, "device", None), "type", "") == "cuda"
+    if device_out and on_gpu:
+        return _run_fd_sample_strided_device(model, h, x0, lens, visits, coef, zs, seed, seq_offset, rows, hist)
+    out = np.empty((rows, B, L, F), dtype=np.float32)
+    _run_fd_sample_strided(h, x0, lens, visits, coef, zs, seed, seq_offset, out, hist)
+    return torch.from_numpy(out)
+
+
 @torch.no_grad()
 def p_sample_loop(
     model,
@@ -248,13 +368,20 @@ def p_sample_loop(
     seq_offset: int = 0,
     draw_batch: Optional[Tuple[int, int, int]] = None,
     _device_out: bool = False,
+    num_steps: Optional[int] = None,
+    eta: float = 0.0,
 ) -> torch.Tensor:
     """Run the whole reverse process from ``noise``.  Returns a CPU tensor of shape
     (timesteps, batch_size, seq_len, n_ft) -- entry j is the state after step
     t = timesteps-1-j, last entry = the sample -- or (1, batch, seq_len, n_ft) holding
     only the final sample when ``final_only`` (extension; skips the history copy), or, with
     ``history_every=k > 1`` (extension), (ceil(timesteps / k), ...): every k-th state
-    (j = k-1, 2k-1, ...) with the sample in the last entry -- the history is thinned on the device."""
+    (j = k-1, 2k-1, ...) with the sample in the last entry -- the history is thinned on the device.
+
+    ``num_steps=K`` (extension; the reference has no such sampler): visit only the K timesteps ``ddim_visits(timesteps, K)``
+    with the update ``ddim_coefficients(betas, visits, eta)`` -- DDIM for ``eta=0`` (deterministic), the respaced ancestral
+    chain for ``eta=1``.  The history then has K (or ceil(K / k)) entries and ``step_noise``, when given, one row per visit.
+    ``None`` is the reference's loop."""
     assert history_every >= 1
     assert len(betas) == timesteps, f"{len(betas)} betas for {timesteps} timesteps"
     if not isinstance(is_angle, bool):
@@ -265,6 +392,9 @@ def p_sample_loop(
     B, L, F = x0.shape
     lens = _lens_array(lengths, B, L)
     logging.info(f"Starting from noise {tuple(noise.shape)} with angularity {is_angle} using {model.device}")
+    if num_steps is not None:
+        return _strided_loop(model, h, x0, lens, betas, timesteps - 1, num_steps, eta, final_only, history_every, step_noise, seed,
+                             seq_offset, draw_batch, _device_out)
     # per-step noise: given by the caller (a slice of a larger batch's draws), else drawn here
     if step_noise is not None:
         zs = np.ascontiguousarray(step_noise, dtype=np.float32)
@@ -317,6 +447,8 @@ def sample_on_device(
     full_history: Union[bool, int] = False,
     t_start: Optional[int] = None,
     sync: bool = True,
+    num_steps: Optional[int] = None,
+    eta: float = 0.0,
 ) -> torch.Tensor:
     """Device-resident variant: ``x_init`` [B, L, F] float32 and ``lens`` [B] int32 are
     CUDA tensors, the result is a CUDA tensor ([B, L, F], or [t_start+1, B, L, F] with
@@ -324,7 +456,10 @@ def sample_on_device(
     the final one); nothing touches the host.  Under a non-default torch stream the work is
     enqueued on that stream (asynchronous, stream-ordered).  Under torch's default (null)
     stream it runs on the model's own stream: pending torch work is waited for first and,
-    unless ``sync=False``, the call returns after the sampler finished."""
+    unless ``sync=False``, the call returns after the sampler finished.
+
+    ``num_steps=K``: the strided schedule ``ddim_visits(T, K, t_start)`` with ``ddim_coefficients(..., eta)`` (see
+    ``p_sample_loop``); the history and ``noise`` then have one row per visit, and the call returns with the run complete."""
     assert x_init.is_cuda and lens.is_cuda and x_init.dtype == torch.float32 and lens.dtype == torch.int32
     x_init, lens = x_init.contiguous(), lens.contiguous()
     h = model.prepare(betas, is_angle)
@@ -334,11 +469,13 @@ def sample_on_device(
     t_start = T - 1 if t_start is None else t_start
     hist = int(full_history)   # 0 final only, 1 every state, k every k-th state
     assert hist >= 0
-    shape = (-(-(t_start + 1) // hist), B, L, F) if hist else (B, L, F)
+    visits = None if num_steps is None else ddim_visits(T, num_steps, t_start)
+    n_states = t_start + 1 if visits is None else len(visits)
+    shape = (-(-n_states // hist), B, L, F) if hist else (B, L, F)
     out = torch.empty(shape, dtype=torch.float32, device=x_init.device)
     nptr = None
     if noise is not None:
-        assert noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (t_start + 1, B, L, F)
+        assert noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (n_states, B, L, F)
         noise = noise.contiguous()
         nptr = C.c_void_p(noise.data_ptr())
     ts = torch.cuda.current_stream(x_init.device)
@@ -346,6 +483,14 @@ def sample_on_device(
     if own_stream:
         ts.synchronize()
     lib = _binding.load()
+    if visits is not None:
+        coef = ddim_coefficients(betas, visits, eta)
+        _binding.check(lib.fd_sample_strided_dev(
+            h, C.c_void_p(x_init.data_ptr()), C.c_void_p(lens.data_ptr()), B, L, _binding.ptr(visits), len(visits), _binding.ptr(coef),
+            nptr, C.c_uint64(seed), C.c_int64(seq_offset), C.c_void_p(out.data_ptr()), hist,
+            None if own_stream else C.c_void_p(ts.cuda_stream)))
+        _binding.check(lib.fd_check_finite(h))
+        return out
     _binding.check(lib.fd_sample_dev(
         h, C.c_void_p(x_init.data_ptr()), C.c_void_p(lens.data_ptr()), B, L, t_start, nptr, C.c_uint64(seed),
         C.c_int64(seq_offset), C.c_void_p(out.data_ptr()), hist,
@@ -376,6 +521,8 @@ def sample(
     final_only: bool = False,
     history_every: int = 1,
     gather: str = "rank0",
+    num_steps: Optional[int] = None,
+    eta: float = 0.0,
 ) -> Optional[List[np.ndarray]]:
     """Sample ``n`` backbones per length in ``range(*sweep_lengths)`` (upper bound
     exclusive) -- or ``n`` backbones with lengths from ``train_dset.sample_length()``
@@ -383,6 +530,8 @@ def sample(
     (timesteps, seq_len, fts); index -1 is the sample.  ``final_only=True`` (extension)
     returns arrays of shape (1, seq_len, fts) and never materialises the history;
     ``history_every=k`` (extension) keeps every k-th state plus the sample (``p_sample_loop``).
+    ``num_steps=K`` (extension) samples in K network evaluations on a strided schedule with the DDIM update, ``eta`` in
+    [0, 1] (``p_sample_loop``); the arrays then have K (or ceil(K / k)) rows.
 
     ``train_dset`` needs ``sample_noise``, ``timesteps``, ``alpha_beta_terms``,
     ``feature_is_angular``, ``pad`` (and optionally ``sample_length``,
@@ -429,11 +578,13 @@ def sample(
     if offset is not None:
         logging.info(f"Shifting predicted values by original offset: {offset}")
     angular = np.asarray(train_dset.feature_is_angular[feature_key], dtype=bool)
-    on_gpu = _run_fd_sample is _run_fd_sample_default and getattr(getattr(model, "device", None), "type", "") == "cuda"
+    runner_is_default = _run_fd_sample is _run_fd_sample_default if num_steps is None else _run_fd_sample_strided is _run_fd_sample_strided_default
+    on_gpu = runner_is_default and getattr(getattr(model, "device", None), "type", "") == "cuda"
     # every rank finalises the model for THIS schedule and THIS angular mask before the first batch: the trim kernel reads
     # the mask of the finalised model, and a rank whose slice of a batch is empty never reaches p_sample_loop
     model.prepare(train_dset.alpha_beta_terms["betas"], train_dset.feature_is_angular[feature_key])
-    rows = 1 if final_only else -(-T // history_every)
+    n_states = T if num_steps is None else len(ddim_visits(T, num_steps))
+    rows = 1 if final_only else -(-n_states // history_every)
     F = model.n_inputs
     results: List[np.ndarray] = []
     for start in range(0, len(lengths), batch_size):
@@ -467,7 +618,7 @@ def sample(
                     model=model, lengths=these[lo:hi], noise=noise[lo:hi], timesteps=T,
                     betas=train_dset.alpha_beta_terms["betas"], is_angle=train_dset.feature_is_angular[feature_key],
                     disable_pbar=disable_pbar, final_only=final_only, history_every=history_every,
-                    seed=seed, seq_offset=lo, draw_batch=(B, lo, hi), _device_out=on_gpu)
+                    seed=seed, seq_offset=lo, draw_batch=(B, lo, hi), _device_out=on_gpu, num_steps=num_steps, eta=eta)
                 # this rank's items, cut to their lengths, shifted and re-wrapped where they are (the device), as one ragged buffer
                 flat = _shift_trim_flat(model, traj, these[lo:hi], offset, angular)
                 del traj
@@ -479,7 +630,9 @@ def sample(
                 if on_gpu:
                     model.set_option("rows_hint", 0)
                 model.set_option("varlen", prev_varlen if prev_varlen is not None else 0)
-        elif NOISE_MODE == "torch":  # an empty shard still advances the generator exactly as the other ranks do
+        elif NOISE_MODE == "torch" and num_steps is not None:  # an empty shard still advances the generator exactly as the other ranks do
+            _draw_visit_noise(ddim_coefficients(train_dset.alpha_beta_terms["betas"], ddim_visits(T, num_steps), eta), (B, L, F), (0, 0))
+        elif NOISE_MODE == "torch":
             _StepNoise(T - 1, (B, L, F), (0, 0)).materialize()
         if flat is None:
             flat = torch.zeros((0,), dtype=torch.float32, device=home)   # an empty slice, or a failed one (reported just below)
@@ -569,12 +722,13 @@ def _shift_trim(model, traj: torch.Tensor, lengths: Sequence[int], offset: Optio
 
 @torch.no_grad()
 def reverse_from(model, x_t: torch.Tensor, lengths: Sequence[int], t_start: int, betas: torch.Tensor,
-                 is_angle: Union[bool, List[bool]] = True) -> torch.Tensor:
+                 is_angle: Union[bool, List[bool]] = True, num_steps: Optional[int] = None, eta: float = 0.0) -> torch.Tensor:
     """Reverse steps t = t_start, t_start-1, ..., 0 from a partially noised ``x_t`` [B, L, F]; returns the
     final [B, L, F] on the CPU.  This is the loop of the reference's ``get_reconstruction_error``
     (foldingdiff/sampling.py:320-331): ``p_sample`` then ``modulo_with_wrapped_range(img)`` with its
     default bounds, i.e. EVERY feature is wrapped to [-pi, pi) (``is_angle=True``).  Per-step noise: the
-    reference's draw order from the global CPU generator (``NOISE_MODE="torch"``) or Philox."""
+    reference's draw order from the global CPU generator (``NOISE_MODE="torch"``) or Philox.  ``num_steps=K`` (extension):
+    the strided schedule ``ddim_visits(T, K, t_start)`` instead, as in ``p_sample_loop``."""
     T = len(betas)
     assert 0 <= t_start < T, f"t_start={t_start} outside the {T}-step schedule"
     h = model.prepare(betas, is_angle)
@@ -582,6 +736,8 @@ def reverse_from(model, x_t: torch.Tensor, lengths: Sequence[int], t_start: int,
     B, L, F = x0.shape
     assert F == model.n_inputs, f"{F} features, the model takes {model.n_inputs}"
     lens = _lens_array(lengths, B, L)
+    if num_steps is not None:
+        return _strided_loop(model, h, x0, lens, betas, t_start, num_steps, eta, True, 1, None, None, 0, None, False)[0]
     if NOISE_MODE == "torch":
         zs, seed = _draw_step_noise(t_start + 1, (B, L, F)), 0
     elif NOISE_MODE == "philox":
@@ -594,10 +750,11 @@ def reverse_from(model, x_t: torch.Tensor, lengths: Sequence[int], t_start: int,
 
 
 @torch.no_grad()
-def reconstruct(model, dset, noise_timesteps: int = 250, bs: int = 512):
+def reconstruct(model, dset, noise_timesteps: int = 250, bs: int = 512, num_steps: Optional[int] = None, eta: float = 0.0):
     """Device part of ``get_reconstruction_error`` (foldingdiff/sampling.py:287-341): forward-noise every
     item of ``dset`` (a ``NoisedAnglesDataset`` over real data) to ``t = noise_timesteps`` and denoise it
-    again.  Returns (reconstructed, truth, filenames): per item an array [len_i, F] each."""
+    again -- in ``num_steps`` strided visits when given (``reverse_from``).  Returns (reconstructed, truth, filenames): per
+    item an array [len_i, F] each."""
     recon, truth, files = [], [], []
     for start in range(0, len(dset), bs):
         idx_batch = list(range(start, min(start + bs, len(dset))))
@@ -607,14 +764,16 @@ def reconstruct(model, dset, noise_timesteps: int = 250, bs: int = 512):
         lengths = [int(torch.as_tensor(it["lengths"]).reshape(-1)[0]) for it in items]
         files.extend(dset.filenames[i] for i in idx_batch)
         # the reference iterates t = noise_timesteps-1 ... 0 whatever t the items were noised at
-        final = reverse_from(model, img, lengths, noise_timesteps - 1, dset.alpha_beta_terms["betas"], is_angle=True)
+        final = reverse_from(model, img, lengths, noise_timesteps - 1, dset.alpha_beta_terms["betas"], is_angle=True,
+                             num_steps=num_steps, eta=eta)
         for i, l in enumerate(lengths):
             recon.append(final[i, :l].numpy())
             truth.append(items[i]["angles"][:l].cpu().numpy())
     return recon, truth, files
 
 
-def get_reconstruction_error(model, dset, noise_timesteps: int = 250, bs: int = 512, scorer=None):
+def get_reconstruction_error(model, dset, noise_timesteps: int = 250, bs: int = 512, scorer=None, num_steps: Optional[int] = None,
+                             eta: float = 0.0):
     """Reference signature + ``scorer``: TM-align (an external binary) and the PDB writer are outside this
     path, so the caller supplies ``scorer(reconst_angles, truth_angles, truth_pdb_file) -> (score,
     score_coord)`` -- the role of the reference's ``_score_angles`` (foldingdiff/sampling.py:266-284).
@@ -624,7 +783,7 @@ def get_reconstruction_error(model, dset, noise_timesteps: int = 250, bs: int = 
     if scorer is None:
         raise NotImplementedError("pass scorer=...: structures.tm_scorer for the reference's TM-scores, "
                                   "structures.rmsd_scorer for RMSDs; use reconstruct() for the angle sets")
-    recon, truth, files = reconstruct(model, dset, noise_timesteps=noise_timesteps, bs=bs)
+    recon, truth, files = reconstruct(model, dset, noise_timesteps=noise_timesteps, bs=bs, num_steps=num_steps, eta=eta)
     if hasattr(scorer, "score_batch"):
         scores, coord_scores = scorer.score_batch(recon, truth, files)
         return np.asarray(scores), np.asarray(coord_scores)

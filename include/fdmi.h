@@ -49,6 +49,8 @@ extern "C" {
  *    term of the denoising loss) are additive too */
 /*    fd_sample_inpaint and fd_p_sample_step_inpaint (motif-conditioned sampling) are additive too */
 /*    fd_sample_inpaint_resample and fd_inpaint_jump (resampling schedules of motif-conditioned sampling) are additive too */
+/*    fd_sample_strided, fd_sample_strided_dev and fd_p_sample_step_coef (few-step sampling on a strided schedule) are additive
+ *    too: no existing entry or public struct changed, and the tests of the earlier additions pin the value 7 */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -332,6 +334,53 @@ int fd_sample_inpaint_resample(fd_model* m, const float* x_init, const int32_t* 
 int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int L, int level_to, float jk, float js,
                     const float* known, const uint8_t* fixed, const float* known_coef, uint64_t seed, int64_t seq_offset,
                     float* x_out);
+
+/* ---- few-step sampling on a strided schedule: the run visits a SUBSEQUENCE of the timesteps and takes the state from each
+ * visit's level straight to the next visit's with the DDIM update (Song et al. 2021) -- K network evaluations instead of T,
+ * from the same checkpoint.  The reference has no such sampler; like fd_sample_inpaint this is an extension.
+ *
+ * Levels are those of the inpainting block above: the state that enters step t is at level t + 1.  Visit i runs the network
+ * at t = visits[i] on a state at level p = visits[i] + 1 and leaves it at level q = visits[i+1] + 1 (q = 0 behind the last
+ * visit).  The library knows nothing of levels or eta: the caller's coefficients say where each visit lands.
+ *
+ * The update of visit i, for every element o = (b, l, f) with l < lens[b]:
+ *   x' = a[i] * x[o] + b[i] * eps[o]            each product and the sum rounded once, no contraction
+ *   x' = x' + s[i] * z                          only where s[i] != 0 (product and sum rounded once)
+ *   x' = wrap to [-pi, pi)                      where the model's feature f is an angle
+ * z = noise[i][o], or, noise NULL, the Philox draw of (seed, visits[i], seq_offset + b, l, f): the plain sampler's key.
+ * Where s[i] == 0 z is neither read nor drawn: a run with every s == 0 (DDIM, eta = 0) is a deterministic map of x_init,
+ * evaluates no Philox and needs no noise array.  sampling.ddim_coefficients gives, with acp(0) = 1, acp(j) =
+ * alphas_cumprod[j-1] and r = acp(p) / acp(q):
+ *   s = eta * sqrt((1 - acp(q)) / (1 - acp(p))) * sqrt(1 - r),  a = sqrt(1 / r),
+ *   b = sqrt(max(1 - acp(q) - s^2, 0)) - a * sqrt(1 - acp(p))
+ * computed in float64 and rounded once; eta = 1 with all T visits is p_sample's own update (its coefficients to 2.7e-13).
+ *
+ *   visits   int32[K], strictly descending, 0 <= visits[i] < T (host)
+ *   coef     float32 [3][K], rows a | b | s, all finite (host)
+ *   x_init   [B][L][F] the state that enters step visits[0]
+ *   noise    [K][B][L][F], row i = the draws of visit i (read only where s[i] != 0), or NULL (Philox)
+ *   out      full_history == 0: [B][L][F]; 1: [K][B][L][F] (row i = the state after visit i); k > 1: [ceil(K/k)] rows, the
+ *            states i = k-1, 2k-1, ... and the final one in the last row
+ * The tables live in device buffers of the call; the update kernels look them up by the timestep they hold, and the step
+ * counter advances to the next visit on the device.  The captured step graph is the plain sampler's and is not re-captured.
+ * A NULL visits or coef, n_visits < 1, a visit outside [0, T), visits[i] >= visits[i-1] or a coefficient that is not finite:
+ * FD_E_INVALID before any device call (fd_last_error() names the index), `out` untouched.  Options "use_graph" and "varlen"
+ * and both precisions as in fd_sample; a later fd_sample* is unaffected.  Not combined with motif conditioning. */
+int fd_sample_strided(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                      const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, float* out, int full_history);
+
+/* The same with x_init, lens, noise and out already in device memory (visits and coef stay host arrays), on `hip_stream`
+ * (NULL = the model's own stream).  Unlike fd_sample_dev it returns with the stream drained: the tables are freed with the
+ * call. */
+int fd_sample_strided_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits,
+                          int n_visits, const float* coef, const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev,
+                          int full_history, void* hip_stream);
+
+/* The parity hook of the above: ONE update at timestep t with explicit (a, b, s), all finite; z [B][L][F] is required exactly
+ * when s != 0.  eps_out (or NULL) receives the network's prediction, the bits of fd_forward's.  With wrap == 0 nothing is
+ * wrapped.  Host buffers. */
+int fd_p_sample_step_coef(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
+                          const float* z, int wrap, float* eps_out, float* x_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
