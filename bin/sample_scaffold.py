@@ -15,7 +15,8 @@ no such script; the flags and the output tree follow bin/sample.py:
 --motif_residues LO HI are 0-based residue indices into the file's parsed backbone, HI exclusive.  One backbone is
 generated per length in range(*--lengths), --num times.  Single device; the model must be a local directory, as for
 bin/sample.py.  --jump_length J --n_resample R (both off by default) run a resampling schedule: the run goes
-back up J noise levels and comes down again, R descents per stretch.  Whether the scaffolds are designable is not measured here: nothing in this repository folds a sequence.
+back up J noise levels and comes down again, R descents per stretch.  --num_steps K [--eta E] runs the conditioned chain in K
+network evaluations on a strided schedule with the DDIM update; --jump_length then counts visits.  Whether the scaffolds are designable is not measured here: nothing in this repository folds a sequence.
 """
 import argparse
 import json
@@ -75,6 +76,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--jump_length", type=int, default=None,
                         help="resampling: noise levels to go back up at every jump (default: off, the plain descent)")
     parser.add_argument("--n_resample", type=int, default=1, help="resampling: descents per stretch of --jump_length levels (1: off)")
+    parser.add_argument("--num_steps", type=int, default=None,
+                        help="few-step sampling: network evaluations per descent on a strided schedule (default: every timestep)")
+    parser.add_argument("--eta", type=float, default=0.0, help="few-step sampling: 0 = DDIM (deterministic), 1 = ancestral; needs --num_steps")
     parser.add_argument("-b", "--batchsize", type=int, default=512, help="Batch size to use when sampling")
     parser.add_argument("--outdir", "-o", type=str, default=os.getcwd(), help="Path to output directory")
     parser.add_argument("--seed", type=int, default=SEED, help="Random seed")
@@ -114,9 +118,14 @@ def main(argv=None) -> None:
     offsets = {"center": None, "random": "random"}.get(args.placement, args.placement)
     resample = {}
     n_visits = train_dset.timesteps
+    if args.num_steps is not None:
+        resample = dict(num_steps=args.num_steps, eta=args.eta)
+        n_visits = args.num_steps
+    elif args.eta != 0.0:
+        raise AssertionError("--eta applies to a strided run: give --num_steps")
     if args.jump_length is not None and args.n_resample > 1:
-        resample = dict(jump_length=args.jump_length, n_resample=args.n_resample)
-        n_visits = len(sampling.resample_schedule(train_dset.timesteps - 1, args.jump_length, args.n_resample))
+        resample.update(jump_length=args.jump_length, n_resample=args.n_resample)
+        n_visits = len(sampling.resample_schedule(n_visits - 1, args.jump_length, args.n_resample))   # (as many as over a grid of K)
     logging.info(f"{len(lengths)} chains, {n_visits} reverse steps (visits) per chain over {train_dset.timesteps} timesteps")
     sampled, offsets = sampling.scaffold(model, train_dset, motif, lengths, offsets=offsets, batch_size=args.batchsize, **resample)
 

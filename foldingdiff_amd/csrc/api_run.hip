@@ -1,8 +1,8 @@
 // C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
-// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided) and their device-buffer pieces.  Host code
-// around api.hip's workspace, launch plan and step (model.h) only: every entry checks its arguments before its first HIP call,
-// and the paragraphs the entries share -- make the workspace current and upload, download and synchronise, the host-side
-// run, the one-copy staging of the loss entries -- are written once, below.
+// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned) and their
+// device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry checks its
+// arguments before its first HIP call, and the paragraphs the entries share -- make the workspace current and upload, download
+// and synchronise, the host-side run, the one-copy staging of the loss entries -- are written once, below.
 // Boundary: include/fdmi.h (each entry point cites the reference function it replaces).
 #include <hip/hip_runtime.h>
 
@@ -312,18 +312,21 @@ int begin_conditioning(fd_model* m, hipStream_t s, const HostRun& a, const float
 }
 
 // a schedule's visits, one segment per pass: the jump that enters it (none in front of the first), then its descent.  Launches only.
-int walk_visits(fd_model* m, hipStream_t s, const HostRun& a, const InpaintDev& ip) {
-  for (int i = 0, seg = 0; i < a.n_visits; ++seg) {
+// descends(j): visit j follows visit j - 1 without a jump; steps_left(i): m->run_t once visit i is the next (plain ladder: its t)
+template <class Descends, class StepsLeft>
+int walk_visits(fd_model* m, hipStream_t s, const int32_t* visits, int n_visits, const float* jump_coef, uint64_t seed,
+                int64_t seq_offset, int B, int L, const InpaintDev& ip, Descends descends, StepsLeft steps_left) {
+  for (int i = 0, seg = 0; i < n_visits; ++seg) {
     int j = i + 1;
-    while (j < a.n_visits && a.visits[j] == a.visits[j - 1] - 1) ++j;
+    while (j < n_visits && descends(j)) ++j;
     if (seg > 0) {
-      const uint64_t seed_s = segment_seed(a.seed, seg);
-      launch_inpaint_jump(m->ws.x, m->ws.lens, ip.known, ip.fixed, ip.coef, m->T, a.visits[i] + 1, a.jump_coef[2 * (seg - 1)],
-                          a.jump_coef[2 * (seg - 1) + 1], seed_s, a.seq_offset, a.B, a.L, m->cfg.n_features, m->angle_mask, s);
+      const uint64_t seed_s = segment_seed(seed, seg);
+      launch_inpaint_jump(m->ws.x, m->ws.lens, ip.known, ip.fixed, ip.coef, m->T, visits[i] + 1, jump_coef[2 * (seg - 1)],
+                          jump_coef[2 * (seg - 1) + 1], seed_s, seq_offset, B, L, m->cfg.n_features, m->angle_mask, s);
       const hipError_t e = hipGetLastError();
       if (e != hipSuccess) return fail(FD_E_HIP, "launch_inpaint_jump: %s", hipGetErrorString(e));
-      if (int rc = set_t(m, s, a.visits[i])) return rc;
-      m->run_t = a.visits[i];
+      if (int rc = set_t(m, s, visits[i])) return rc;
+      m->run_t = steps_left(i);
       m->dyn_host.seed = seed_s;
     }
     if (int rc = fd_sample_steps_dev(m, j - i, nullptr, 0, nullptr)) return rc;  // (re-sends dyn: the segment's seed)
@@ -365,7 +368,13 @@ int host_run(fd_model* m, const HostRun& a) {
   const bool conditioned = a.cond.fixed != nullptr;
   InpaintDev ip;
   int rc = conditioned ? begin_conditioning(m, s, a, d_known_noise, &ip) : FD_OK;
-  if (!rc) rc = a.visits ? walk_visits(m, s, a, ip) : fd_sample_steps_dev(m, a.t_start + 1, d_noise, 0, nullptr);
+  if (!rc) {
+    if (a.visits)  // a descent goes one step down the ladder
+      rc = walk_visits(m, s, a.visits, a.n_visits, a.jump_coef, a.seed, a.seq_offset, a.B, a.L, ip,
+                       [&](int j) { return a.visits[j] == a.visits[j - 1] - 1; }, [&](int i) { return a.visits[i]; });
+    else
+      rc = fd_sample_steps_dev(m, a.t_start + 1, d_noise, 0, nullptr);
+  }
   if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
   if (conditioned) {
     if (int rc_close = close_conditioned_run(m, s)) return rc_close;
@@ -452,6 +461,111 @@ int check_strided_call(fd_model* m, const void* x_init, const void* lens, const 
   if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
   if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
   return check_strided(m, visits, n_visits, coef);
+}
+
+// ---- strided runs with motif conditioning: the strided tables and the conditioning in the same per-run values.
+// A visit at t then replaces its fixed elements at the level it lands on, next_t[t] + 1 (inpaint_replace.h).
+
+// where each timestep sits on a strided grid: pos[t] = its index, -1 off the grid
+std::vector<int> grid_positions(const fd_model* m, const int32_t* grid, int n_grid) {
+  std::vector<int> pos((size_t)m->T, -1);
+  for (int i = 0; i < n_grid; ++i) pos[(size_t)grid[i]] = i;
+  return pos;
+}
+
+// the rules of a legal resampled run over a (checked) grid; *n_jumps = the number of jumps in it
+int check_strided_visits(const fd_model* m, const int32_t* grid, int n_grid, const int32_t* run, int n_run, const float* jump_coef,
+                         int* n_jumps) {
+  if (!run) return fail(FD_E_INVALID, "run is null");
+  if (n_run < 1) return fail(FD_E_INVALID, "n_run = %d must be positive", n_run);
+  const std::vector<int> pos = grid_positions(m, grid, n_grid);
+  int jumps = 0;
+  for (int i = 0; i < n_run; ++i) {
+    if (run[i] < 0 || run[i] >= m->T || pos[(size_t)run[i]] < 0) return fail(FD_E_INVALID, "run[%d] = %d is not on the grid", i, run[i]);
+    if (i == 0) {
+      if (run[0] != grid[0]) return fail(FD_E_INVALID, "run[0] = %d, the run starts with the grid's first visit %d", run[0], grid[0]);
+      continue;
+    }
+    if (pos[(size_t)run[i]] == pos[(size_t)run[i - 1]] + 1) continue;
+    if (run[i] < run[i - 1])
+      return fail(FD_E_INVALID, "run[%d] = %d follows %d: neither the grid's next visit nor a jump up", i, run[i], run[i - 1]);
+    ++jumps;
+  }
+  if (run[n_run - 1] != grid[n_grid - 1])
+    return fail(FD_E_INVALID, "run[%d] = %d, the run ends with the grid's last visit %d", n_run - 1, run[n_run - 1], grid[n_grid - 1]);
+  if (jumps && !jump_coef) return fail(FD_E_INVALID, "jump_coef is null and the run has %d jumps", jumps);
+  for (int j = 0; j < jumps; ++j)
+    if (int rc = check_jump_coef(jump_coef[2 * j], jump_coef[2 * j + 1], j)) return rc;
+  *n_jumps = jumps;
+  return FD_OK;
+}
+
+// the host arrays of a strided conditioned run; the entry has checked every argument
+struct StridedHostRun {
+  const float* x_init;
+  const int32_t* lens;
+  int B, L;
+  const int32_t* grid;  // strictly descending
+  int n_grid;
+  const float* coef;    // [3][n_grid]
+  const float* noise;   // [n_grid][B][L][F], or null: Philox
+  InpaintHost cond;
+  const float* known_noise;  // [n_grid + 1][B][L][F] (row 0: the start point, row i + 1: the state visit i leaves), or null: Philox
+  uint64_t seed;
+  int64_t seq_offset;
+  float* out;
+  int full_history;
+  const int32_t* run = nullptr;  // a resampled run over the grid, or null: the grid once
+  int n_run = 0;
+  const float* jump_coef = nullptr;
+};
+
+// Returns with the stream drained and the strided and the conditioning fields cleared, on the host and on the device, on every
+// path behind begin_run: the tables and the draws die with this frame.
+int strided_host_run(fd_model* m, const StridedHostRun& a) {
+  HIP_TRY(hipSetDevice(m->device));
+  const int F = m->cfg.n_features;
+  const size_t n = (size_t)a.B * a.L * F;
+  const int n_visits = a.run ? a.n_run : a.n_grid;
+  const size_t out_rows = a.full_history ? ((size_t)a.n_grid + a.full_history - 1) / a.full_history : 1;
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  const float *d_noise = nullptr, *d_known_noise = nullptr;
+  int* d_lens;
+  HIP_TRY(bufs.upload(a.x_init, n * 4, &d_x));
+  HIP_TRY(bufs.upload(a.lens, (size_t)a.B * 4, &d_lens));
+  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
+  if (a.noise) HIP_TRY(bufs.upload(a.noise, (size_t)a.n_grid * n * 4, &d_noise));
+  if (a.known_noise) HIP_TRY(bufs.upload(a.known_noise, ((size_t)a.n_grid + 1) * n * 4, &d_known_noise));
+  StridedDev sd;
+  if (int rc = stage_strided(m, &bufs, a.grid, a.n_grid, a.coef, &sd)) return rc;
+  if (int rc = begin_run(m, d_x, d_lens, a.B, a.L, a.grid[0], n_visits, a.seed, a.seq_offset, d_out, a.full_history, nullptr)) return rc;
+  hipStream_t s = m->stream;
+  sd.apply(&m->dyn_host);
+  InpaintDev ip;
+  int rc = stage_inpaint(m, s, a.cond, &ip);
+  if (!rc) {  // the start point enters visit 0, so it is at level grid[0] + 1; its draws are row 0
+    launch_inpaint_init(m->ws.x, ip.known, ip.fixed, d_known_noise, ip.coef, m->T, a.grid[0] + 1, a.seed, a.seq_offset, a.B, a.L, F,
+                        m->angle_mask, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
+  }
+  if (!rc) {
+    ip.apply(&m->dyn_host, d_known_noise);
+    if (a.run) {  // a descent goes to the grid's next visit; a jump starts from the level the visit before it landed on
+      const std::vector<int> pos = grid_positions(m, a.grid, a.n_grid);
+      rc = walk_visits(m, s, a.run, a.n_run, a.jump_coef, a.seed, a.seq_offset, a.B, a.L, ip,
+                       [&](int j) { return pos[(size_t)a.run[j]] == pos[(size_t)a.run[j - 1]] + 1; }, [&](int i) { return a.n_run - 1 - i; });
+    } else {
+      rc = fd_sample_steps_dev(m, a.n_grid, d_noise, 0, nullptr);
+    }
+  }
+  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
+  StridedDev::clear(&m->dyn_host);
+  if (int rc_close = close_conditioned_run(m, s)) return rc_close;
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(a.out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
+  return check_flag(m);
 }
 
 }  // namespace
@@ -850,6 +964,64 @@ int fd_p_sample_step_coef(fd_model* m, const float* x, int t, const int32_t* len
   mode.no_wrap = !wrap;
   mode.strided = true;
   mode.sa = a; mode.sb = b; mode.ss = s;
+  if (int rc = run_step(m, c.s, mode)) return rc;
+  return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}});
+}
+
+int fd_sample_strided_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits,
+                              int n_visits, const float* coef, const float* noise, const float* known, const uint8_t* fixed,
+                              const float* known_coef, const float* known_noise, uint64_t seed, int64_t seq_offset, float* out,
+                              int full_history) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, full_history)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  return strided_host_run(m, StridedHostRun{x_init, lens, B, L, visits, n_visits, coef, noise, {known, fixed, known_coef}, known_noise,
+                                            seed, seq_offset, out, full_history});
+}
+
+int fd_sample_strided_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* grid,
+                                       int n_grid, const float* coef, const int32_t* run, int n_run, const float* jump_coef,
+                                       const float* known, const uint8_t* fixed, const float* known_coef, uint64_t seed,
+                                       int64_t seq_offset, float* out) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, grid, n_grid, coef, 0)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  int n_jumps = 0;
+  if (int rc = check_strided_visits(m, grid, n_grid, run, n_run, jump_coef, &n_jumps)) return rc;
+  return strided_host_run(m, StridedHostRun{x_init, lens, B, L, grid, n_grid, coef, nullptr, {known, fixed, known_coef}, nullptr, seed,
+                                            seq_offset, out, 0, run, n_run, jump_coef});
+}
+
+int fd_p_sample_step_coef_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
+                                  const float* z, int wrap, int level_out, const float* known, const uint8_t* fixed,
+                                  const float* known_coef, const float* z_known, float* eps_out, float* x_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(s))
+    return fail(FD_E_INVALID, "a = %g, b = %g, s = %g: a coefficient is not finite", (double)a, (double)b, (double)s);
+  if (s != 0.f && !z) return fail(FD_E_INVALID, "z is required for s != 0");
+  if (level_out < 0 || level_out > m->T) return fail(FD_E_INVALID, "level_out = %d outside [0, %d]", level_out, m->T);
+  if (level_out >= 1 && !z_known) return fail(FD_E_INVALID, "z_known is required for level_out >= 1");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  Call c;
+  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
+  Workspace& w = *c.ws;
+  if (s != 0.f) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
+  InpaintDev ip;
+  if (int rc = stage_inpaint(m, c.s, InpaintHost{known, fixed, known_coef}, &ip)) return rc;
+  if (level_out >= 1) HIP_TRY(hipMemcpyAsync(ip.z_known, z_known, c.n * 4, hipMemcpyHostToDevice, c.s));
+  if (int rc = prepare_rows(m, c.s, 0)) return rc;
+  if (int rc = set_t(m, c.s, t)) return rc;
+  StepMode mode{};
+  mode.noise = w.z;
+  mode.t_start = t;
+  mode.no_wrap = !wrap;
+  mode.strided = true;
+  mode.sa = a; mode.sb = b; mode.ss = s;
+  mode.level_out = level_out;
+  ip.apply(&mode);
   if (int rc = run_step(m, c.s, mode)) return rc;
   return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}});
 }

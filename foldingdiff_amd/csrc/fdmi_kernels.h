@@ -62,7 +62,8 @@ struct UpdateDyn {
   // motif-conditioned sampling (inpaint_replace.h): all null unless fd_sample_inpaint is running
   const float* known;          // [M, F] values of the fixed elements (model space)
   const unsigned char* fixed;  // [M, F] != 0: the element is replaced after every step instead of updated
-  const float* known_noise;    // [t_start+2, M, F] draws of the replacement (row j: level j) or null (Philox, tagged step word)
+  const float* known_noise;    // [t_start+2, M, F] draws of the replacement (row j: level j; a strided run: [K+1, M, F], row i+1 =
+                               // the state visit i leaves) or null (Philox, tagged step word)
   const float* known_coef;     // [2, T+1] keep | spread per level
   // strided (few-step) sampling: all null unless fd_sample_strided is running; indexed by the timestep t the kernel holds
   // (a descending schedule visits each t at most once).  `noise` and `hist` rows are then per visit: row ord[t]
@@ -102,6 +103,8 @@ struct UpdateArgs {
   // one strided update by value, without `dyn` (fd_p_sample_step_coef): x' = sa x + sb eps (+ ss z where ss != 0), z = `noise`
   int strided;
   float sa, sb, ss;
+  // ... and the level its fixed elements land on (fd_p_sample_step_coef_inpaint; known_noise = the one slab of that level)
+  int level_out;
 };
 void launch_head_update(const UpdateArgs& a, hipStream_t s);
 // The replacement of the start point of a motif-conditioned run (inpaint_replace.h): x[o] = the level-`level` value of

@@ -192,6 +192,7 @@ struct StepMode {
   // fd_p_sample_step_coef: one strided update x' = sa x + sb eps (+ ss z where ss != 0, z = `noise`) in place of p_sample's
   bool strided = false;
   float sa = 0.f, sb = 0.f, ss = 0.f;
+  int level_out = 0;  // fd_p_sample_step_coef_inpaint: the level the update lands on (z_known = the one slab of that level)
   const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
   bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
 };

@@ -515,9 +515,11 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
   bool strided = a.strided != 0;
   float sa = a.sa, sb = a.sb, ss = a.ss;
   int ord = 0, t_next = -1;
+  int level = strided ? a.level_out : t, known_row = level;  // what a fixed element leaves at, and its row of known_noise (inpaint_replace.h)
   if (a.x_out && a.dyn && a.dyn->next_t) {
     strided = true;
     t_next = a.dyn->next_t[t]; ord = a.dyn->ord[t];
+    level = t_next + 1; known_row = ord + 1;
     sa = a.dyn->abs[t]; sb = a.dyn->abs[a.T + t]; ss = a.dyn->abs[2 * a.T + t];
   }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
@@ -572,8 +574,8 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
       if (a.x_out) {
         // model_mean = sqrt_recip_alphas_t * (x - betas_t * eps / sqrt_one_minus_alphas_cumprod_t)   (sampling.py:62-67)
         float xn;
-        if (fixed && fixed[o]) {  // a fixed element leaves step t at level t, whatever the model predicted
-          xn = inpaint_value(known, known_noise, known_coef, a.T, a.noise_stride, t, o, seed, seq_offset + ri.x, ri.y, k,
+        if (fixed && fixed[o]) {  // a fixed element leaves step t at level t (a strided visit: where it lands), whatever the model predicted
+          xn = inpaint_value_row(known, known_noise, known_coef, a.T, a.noise_stride, level, known_row, o, seed, seq_offset + ri.x, ri.y, k,
                              (a.angle_mask >> k) & 1u);
         } else if (strided) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
           xn = strided_mean(sa, a.x[o], sb, mine);

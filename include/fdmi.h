@@ -365,7 +365,7 @@ int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int
  * counter advances to the next visit on the device.  The captured step graph is the plain sampler's and is not re-captured.
  * A NULL visits or coef, n_visits < 1, a visit outside [0, T), visits[i] >= visits[i-1] or a coefficient that is not finite:
  * FD_E_INVALID before any device call (fd_last_error() names the index), `out` untouched.  Options "use_graph" and "varlen"
- * and both precisions as in fd_sample; a later fd_sample* is unaffected.  Not combined with motif conditioning. */
+ * and both precisions as in fd_sample; a later fd_sample* is unaffected.  With motif conditioning: fd_sample_strided_inpaint. */
 int fd_sample_strided(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
                       const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, float* out, int full_history);
 
@@ -381,6 +381,47 @@ int fd_sample_strided_dev(fd_model* m, const void* x_init_dev, const void* lens_
  * wrapped.  Host buffers. */
 int fd_p_sample_step_coef(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
                           const float* z, int wrap, float* eps_out, float* x_out);
+
+/* ---- few-step motif scaffolding: a strided run with replacement, and resampling jumps over visits.
+ *
+ * Levels are those of the two blocks above.  Visit i of a grid g_0 > g_1 > ... > g_{K-1} runs the network at t = g_i on a state
+ * at level g_i + 1 and leaves it at level q_i = g_{i+1} + 1, q_{K-1} = 0.  An element with fixed[o] != 0 leaves visit i as the
+ * replacement AT LEVEL q_i (not g_i: the level the state has just reached): keep[q_i] * known[o] + spread[q_i] * z, wrapped
+ * where angular, with z = known_noise[i + 1][o] or the Philox draw of (seed, 0x80000000 | q_i, seq_offset + b, l, f); q_i = 0
+ * gives the bits of known[o].  It reads or draws no z of the update's own.  Every other element takes fd_sample_strided's
+ * statement unchanged, and so do the history rows and the step counter.  x_init's fixed elements are replaced at level
+ * g_0 + 1 first (known_noise row 0).  No launch is added to a step and the captured step graph is the plain sampler's.
+ *
+ *   visits, coef, noise, out, full_history   as in fd_sample_strided
+ *   known, fixed, known_coef                 as in fd_sample_inpaint
+ *   known_noise  [n_visits + 1][B][L][F]: row 0 = the draws of the start point, row i + 1 = those of the state visit i leaves
+ *                (the last row is never read: level 0), or NULL (Philox).  Rows are per VISIT here, not per level.
+ * With fixed all zero the result is fd_sample_strided's.  Everything fd_sample_strided or fd_sample_inpaint rejects:
+ * FD_E_INVALID before any device call, `out` untouched.  A later fd_sample* on the same model is unaffected. */
+int fd_sample_strided_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits,
+                              int n_visits, const float* coef, const float* noise, const float* known, const uint8_t* fixed,
+                              const float* known_coef, const float* known_noise, uint64_t seed, int64_t seq_offset, float* out,
+                              int full_history);
+
+/* The same over a resampled run.  grid [n_grid] and coef [3][n_grid] are fd_sample_strided's visits and coefficients; run
+ * [n_run] is the timestep of every visit in the order run.  Legal: run[0] == grid[0], run[n_run - 1] == grid[n_grid - 1],
+ * every entry on the grid, and for i > 0 either run[i] is the grid's successor of run[i-1] (a descent) or run[i] >= run[i-1]
+ * (a JUMP: the state visit run[i-1] left at level a -- its q, 0 behind the grid's last visit -- is forward-noised to level
+ * b = run[i] + 1 > a).  Segments, their seeds seed + s * 0x9E3779B97F4A7C15, the jump's statement and its streams are
+ * fd_sample_inpaint_resample's; jump_coef [n_jumps][2] = (jk, js) between those a and b.  A run without a jump is
+ * fd_sample_strided_inpaint's bit for bit.  Philox only, final state only; launches only between upload and download.
+ * An illegal run (fd_last_error() names the index), a NULL run, n_run < 1, a NULL jump_coef with a jump, jk / js outside
+ * [0, 1] or anything the entry above rejects: FD_E_INVALID; T >= 2^30: FD_E_UNSUPPORTED; before any device call. */
+int fd_sample_strided_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* grid,
+                                       int n_grid, const float* coef, const int32_t* run, int n_run, const float* jump_coef,
+                                       const float* known, const uint8_t* fixed, const float* known_coef, uint64_t seed,
+                                       int64_t seq_offset, float* out);
+
+/* The parity hook of a conditioned visit: fd_p_sample_step_coef, with the fixed elements replaced at level level_out
+ * (0 .. T) with the draws z_known [B][L][F] (required for level_out >= 1; level 0 writes known's bits).  x is taken as given. */
+int fd_p_sample_step_coef_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
+                                  const float* z, int wrap, int level_out, const float* known, const uint8_t* fixed,
+                                  const float* known_coef, const float* z_known, float* eps_out, float* x_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
