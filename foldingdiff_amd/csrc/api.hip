@@ -433,7 +433,8 @@ int fdmi::ensure_ws(fd_model* m, int B, int L) {
   HIP_TRY(al((void**)&w.dyn, sizeof(UpdateDyn)));
   if (m->img) {
     // Row images: sequences start at multiples of 8 rows, the row count is rounded up to whole 128-row tiles.
-    // Everything is zeroed once: padding rows / never-written key slots stay finite for ever.
+    // Everything is zeroed here: padding rows and never-written key slots start finite, and stay finite as long as every call's
+    // values are.  A call that produced an inf / NaN ends in check_flag, which zeroes them again.
     const size_t Lr = (size_t)(L + 7) / 8 * 8;
     const size_t cap = (B * Lr + 127) / 128 * 128;
     const int T = L > 128 ? 4 : (L + 31) / 32;
@@ -981,6 +982,20 @@ int check_flag(fd_model* m) {
   HIP_TRY(hipMemcpy(&v, w.flag, 4, hipMemcpyDeviceToHost));
   if (!v) return FD_OK;
   HIP_TRY(hipMemset(w.flag, 0, 4));
+  // The inf / NaN may sit where no later call writes: padding rows of the images, key / value slots behind the rows of a
+  // sequence that is shorter next time (a masked key's p = 0 still meets the slot in the P V product: 0 * NaN).  Back to
+  // the zeros of allocation (ensure_ws), on the error path only.
+  {
+    const fd_config& c = m->cfg;
+    const size_t d = c.d_model, gmax = c.d_ff > c.d_model ? c.d_ff : c.d_model, cap = (size_t)w.cap;
+    const size_t qkv = (size_t)w.B * sub_heads(c) * w.LTOT * 128;
+    const std::pair<void*, size_t> zero[] = {{w.himg, cap * d * 4}, {w.aimg, cap * d * 4}, {w.cimg, cap * d * 4}, {w.gimg, cap * gmax * 4},
+                                             {d > 384 ? (void*)w.tmp : nullptr, cap * d * 4}, {w.qbuf, qkv}, {w.kbuf, qkv}, {w.vbuf, qkv},
+                                             {w.eps, (size_t)w.B * w.L * c.n_features * 4}};
+    for (const auto& z : zero)
+      if (z.first) HIP_TRY(hipMemsetAsync(z.first, 0, z.second, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+  }
   return fail(FD_E_NONFINITE, "the model produced a non-finite value (inf/NaN in the predicted noise)");
 }
 
