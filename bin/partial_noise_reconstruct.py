@@ -86,17 +86,27 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--num_steps", type=int, default=None,
                         help="denoise in this many network evaluations on a strided schedule with the DDIM update (default: every timestep)")
     parser.add_argument("--eta", type=float, default=0.0, help="with --num_steps: 0 = DDIM .. 1 = the ancestral update of the respaced chain")
+    parser.add_argument("--solver", type=str, default=None, choices=["ddim", "dpm2m"],
+                        help="with --num_steps: the update of a visit, ddim (default) or dpm2m, a second-order multistep solver (needs --eta 0)")
+    parser.add_argument("--spacing", type=str, default=None, choices=["uniform", "logsnr"],
+                        help="with --num_steps: visits spaced evenly in t (default) or in log-SNR")
+    parser.add_argument("--lambda_min", type=float, default=None,
+                        help="with --spacing logsnr: the log-SNR below which the visits are not spread (default: the library's, -3)")
     return parser
 
 
+FEW_STEP_FLAGS = ("solver", "spacing", "lambda_min")   # passed on, and recorded, only when given
+
+
 def get_reconstruction_error(pdb_files: Collection[str], timesteps: int, model: str, device: int = 0,
-                             num_steps: Optional[int] = None, eta: float = 0.0) -> Tuple[Dict[str, float], Dict[str, float]]:
+                             num_steps: Optional[int] = None, eta: float = 0.0, **few_step) -> Tuple[Dict[str, float], Dict[str, float]]:
     """(RMSD to the original angles' backbone, RMSD to the file's backbone) per file that entered the dataset."""
     assert os.path.isdir(model), f"Model path {model} is not a local directory"
     dset = load_dataset(pdb_files, Path(model))
     net = modelling.BertForDiffusionBase.from_dir(model).to(torch.device(f"cuda:{device}"))
     scores, coord_scores = sampling.get_reconstruction_error(net, dset=dset, noise_timesteps=timesteps,
-                                                             scorer=structures.RmsdScorer(device=device), num_steps=num_steps, eta=eta)
+                                                             scorer=structures.RmsdScorer(device=device), num_steps=num_steps, eta=eta,
+                                                             **few_step)
     files = dset.filenames   # the dataset's (shuffled) order, which the scores follow
     logging.info(f"Reconstruction RMSD from t={timesteps}: {np.min(scores):.3f}-{np.max(scores):.3f} A")
     return ({f: float(s) for f, s in zip(files, scores)}, {f: float(s) for f, s in zip(files, coord_scores)})
@@ -104,13 +114,13 @@ def get_reconstruction_error(pdb_files: Collection[str], timesteps: int, model: 
 
 def get_reconstruction_scores(pdb_files: Collection[str], timesteps: int, model: str, device: int = 0,
                               tmscore: bool = True, lddt: bool = False, num_steps: Optional[int] = None,
-                              eta: float = 0.0) -> Dict[str, Dict[str, float]]:
+                              eta: float = 0.0, **few_step) -> Dict[str, Dict[str, float]]:
     """One reconstruction per file, scored by the RMSD scorer and the chosen others: {"rmsd", "rmsd_coord" [, "tmscores",
     "tmscores_coord"] [, "lddt", "lddt_coord"]}, each {file: score} over the files that entered the dataset."""
     assert os.path.isdir(model), f"Model path {model} is not a local directory"
     dset = load_dataset(pdb_files, Path(model))
     net = modelling.BertForDiffusionBase.from_dir(model).to(torch.device(f"cuda:{device}"))
-    recon, truth, files = sampling.reconstruct(net, dset, noise_timesteps=timesteps, num_steps=num_steps, eta=eta)
+    recon, truth, files = sampling.reconstruct(net, dset, noise_timesteps=timesteps, num_steps=num_steps, eta=eta, **few_step)
     out = {}
     scorers = [("rmsd", structures.RmsdScorer(device=device))]
     if tmscore:
@@ -129,15 +139,16 @@ def get_reconstruction_scores(pdb_files: Collection[str], timesteps: int, model:
 
 def main():
     args = build_parser().parse_args()
-    strided = {} if args.num_steps is None else {"num_steps": args.num_steps, "eta": args.eta}
+    few_step = {k: getattr(args, k) for k in FEW_STEP_FLAGS if getattr(args, k) is not None}
+    strided = {} if args.num_steps is None else {"num_steps": args.num_steps, "eta": args.eta, **few_step}
     if args.tmscore or args.lddt:
         scores = get_reconstruction_scores(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device,
-                                           tmscore=args.tmscore, lddt=args.lddt, num_steps=args.num_steps, eta=args.eta)
+                                           tmscore=args.tmscore, lddt=args.lddt, num_steps=args.num_steps, eta=args.eta, **few_step)
         with open(args.output_json, "w") as sink:
             json.dump({"timesteps": args.timesteps, "model": args.model, **strided, **scores}, sink, indent=4)
         return
     rmsd, rmsd_coord = get_reconstruction_error(args.pdb_files, timesteps=args.timesteps, model=args.model, device=args.device,
-                                                num_steps=args.num_steps, eta=args.eta)
+                                                num_steps=args.num_steps, eta=args.eta, **few_step)
     with open(args.output_json, "w") as sink:
         json.dump({"timesteps": args.timesteps, "model": args.model, **strided, "rmsd": rmsd, "rmsd_coord": rmsd_coord}, sink, indent=4)
 

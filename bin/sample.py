@@ -86,9 +86,18 @@ def build_parser() -> argparse.ArgumentParser:
                              "the reference's ancestral loop); the run's arguments then go to sampling_args.json")
     parser.add_argument("--eta", type=float, default=0.0,
                         help="with --num_steps: 0 = DDIM (deterministic given the start noise) .. 1 = the ancestral update of the respaced chain")
+    parser.add_argument("--solver", type=str, default=None, choices=["ddim", "dpm2m"],
+                        help="with --num_steps: the update of a visit, ddim (default) or dpm2m, a second-order multistep solver (needs --eta 0)")
+    parser.add_argument("--spacing", type=str, default=None, choices=["uniform", "logsnr"],
+                        help="with --num_steps: visits spaced evenly in t (default) or in log-SNR")
+    parser.add_argument("--lambda_min", type=float, default=None,
+                        help="with --spacing logsnr: the log-SNR below which the visits are not spread (default: the library's, -3)")
     parser.add_argument("--seed", type=int, default=SEED, help="Random seed")
     parser.add_argument("--device", type=str, default="cuda:0", help="Device to use")
     return parser
+
+
+FEW_STEP_FLAGS = ("solver", "spacing", "lambda_min")   # passed on, and recorded, only when given
 
 
 def main(argv=None) -> None:
@@ -136,12 +145,14 @@ def main(argv=None) -> None:
     assert sweep_min_len < sweep_max_len
     assert sweep_max_len <= train_dset.dset.pad
 
+    few_step = {k: getattr(args, k) for k in FEW_STEP_FLAGS if getattr(args, k) is not None}
     torch.manual_seed(args.seed)
     sampled = sampling.sample(model, train_dset, n=args.num, sweep_lengths=(sweep_min_len, sweep_max_len),
-                              batch_size=args.batchsize, final_only=not args.fullhistory, num_steps=args.num_steps, eta=args.eta)
-    if rank == 0 and args.num_steps is not None:   # a strided run says so beside its samples
+                              batch_size=args.batchsize, final_only=not args.fullhistory, num_steps=args.num_steps, eta=args.eta,
+                              **few_step)
+    if rank == 0 and args.num_steps is not None:   # a strided run says so beside its samples; the solver's flags only when given
         with open(outdir / "sampling_args.json", "w") as sink:
-            json.dump(vars(args), sink, indent=4)
+            json.dump({k: v for k, v in vars(args).items() if k not in FEW_STEP_FLAGS or v is not None}, sink, indent=4)
     if rank == 0:
         names = train_dset.feature_names["angles"]
         sampled_dfs = [pd.DataFrame(s[-1], columns=names) for s in sampled]

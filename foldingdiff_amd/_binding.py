@@ -71,6 +71,10 @@ _SIGNATURES = {
                                                      C.c_uint64, C.c_int64, _P]),
     "fd_p_sample_step_coef_inpaint": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P, C.c_int,
                                                 C.c_int, _P, _P, _P, _P, _P, _P]),
+    "fd_sample_solver": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int]),
+    "fd_sample_solver_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
+    "fd_p_sample_step_solver": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          _P, C.c_int, _P, _P, _P]),
     "fd_sample_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_begin_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_steps_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),

@@ -1,5 +1,5 @@
 // C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
-// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned) and their
+// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned, solver) and their
 // device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry checks its
 // arguments before its first HIP call, and the paragraphs the entries share -- make the workspace current and upload, download
 // and synchronise, the host-side run, the one-copy staging of the loss entries -- are written once, below.
@@ -431,36 +431,100 @@ int stage_strided(const fd_model* m, DeviceBufs* bufs, const int32_t* visits, in
   return FD_OK;
 }
 
+// ---- second-order multistep solver: a strided run with s = 0 whose update also reads the visit's (c, u, v) and
+// the previous visit's prediction of the clean state
+int check_solver(const fd_model* m, const int32_t* visits, int n_visits, const float* coef) {
+  if (int rc = check_strided(m, visits, n_visits, coef)) return rc;  // the visits; rows a | b | c finite
+  for (int r = 3; r < 5; ++r)
+    for (int i = 0; i < n_visits; ++i)
+      if (!std::isfinite(coef[(size_t)r * n_visits + i]))
+        return fail(FD_E_INVALID, "coef[%d][%d] = %g is not finite", r, i, (double)coef[(size_t)r * n_visits + i]);
+  if (coef[(size_t)2 * n_visits] != 0.f)
+    return fail(FD_E_INVALID, "coef[2][0] = %g: the first visit has no earlier prediction, its c is 0", (double)coef[(size_t)2 * n_visits]);
+  return FD_OK;
+}
+
+// where a solver run's table and its previous prediction are on the device (both null: no solver run)
+struct SolverDev {
+  const float* cuv = nullptr;
+  float* x0_prev = nullptr;
+  void apply(UpdateDyn* dyn) const { dyn->cuv = cuv; dyn->x0_prev = x0_prev; }
+  static void clear(UpdateDyn* dyn) { SolverDev().apply(dyn); }
+};
+
+// coef [5][K] a | b | c | u | v: the strided tables with a | b | 0, the table c | u | v ([3][T], zeros off the schedule) and the
+// [n] previous prediction (uninitialised: the first visit's c is 0 and does not read it), in buffers of the call's lifetime
+int stage_solver(const fd_model* m, DeviceBufs* bufs, const int32_t* visits, int n_visits, const float* coef, size_t n, StridedDev* sd,
+                 SolverDev* d) {
+  const size_t T = (size_t)m->T, K = (size_t)n_visits;
+  std::vector<float> abs(3 * K, 0.f), cuv(3 * T, 0.f);
+  memcpy(abs.data(), coef, 2 * K * 4);
+  if (int rc = stage_strided(m, bufs, visits, n_visits, abs.data(), sd)) return rc;
+  for (size_t i = 0; i < K; ++i)
+    for (size_t r = 0; r < 3; ++r) cuv[r * T + (size_t)visits[i]] = coef[(2 + r) * K + i];
+  HIP_TRY(bufs->upload(cuv.data(), cuv.size() * 4, &d->cuv));
+  HIP_TRY(bufs->alloc(n * 4, &d->x0_prev));
+  return FD_OK;
+}
+
 // A strided run on device arrays (the entry has checked every argument): the plain sampler's steps -- its captured graph
-// included -- with the tables in the update kernels' per-run values.  Returns with the stream drained and the fields cleared,
-// on the host and on the device, on every path: the tables die with this frame.
+// included -- with the tables in the update kernels' per-run values.  `solver`: coef is [5][K] and the run is the solver's, its
+// noise_dev null.  Returns with the stream drained and the fields cleared, on the host and on the device, on every path: the
+// tables (and the solver's previous prediction) die with this frame.
 int strided_run_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits, int n_visits,
-                    const float* coef, const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev, int full_history,
-                    void* hip_stream) {
+                    const float* coef, bool solver, const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev,
+                    int full_history, void* hip_stream) {
   HIP_TRY(hipSetDevice(m->device));
   DeviceBufs bufs;
   StridedDev sd;
-  if (int rc = stage_strided(m, &bufs, visits, n_visits, coef, &sd)) return rc;
+  SolverDev sv;
+  if (solver) {
+    if (int rc = stage_solver(m, &bufs, visits, n_visits, coef, (size_t)B * L * m->cfg.n_features, &sd, &sv)) return rc;
+  } else if (int rc = stage_strided(m, &bufs, visits, n_visits, coef, &sd)) {
+    return rc;
+  }
   if (int rc = begin_run(m, x_init_dev, lens_dev, B, L, visits[0], n_visits, seed, seq_offset, out_dev, full_history, hip_stream)) return rc;
   hipStream_t s = stream_of(m, hip_stream);
   sd.apply(&m->dyn_host);
+  sv.apply(&m->dyn_host);
   int rc = fd_sample_steps_dev(m, n_visits, noise_dev, 0, hip_stream);  // (noise rows are per visit: row 0 = visit 0)
   if (!rc) rc = fd_sample_end_dev(m, out_dev, hip_stream);
   m->run_open = false;
   m->run_t = -1;
   StridedDev::clear(&m->dyn_host);
+  SolverDev::clear(&m->dyn_host);
   send_dyn(m, s, m->dyn_host);
   HIP_TRY(hipStreamSynchronize(s));
   return rc;
 }
 
-// ... and the checks the two entries share
+// the same from host arrays (noise [K][B][L][F] or null)
+int strided_run_host(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                     const float* coef, bool solver, const float* noise, uint64_t seed, int64_t seq_offset, float* out, int full_history) {
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  const size_t out_rows = full_history ? ((size_t)n_visits + full_history - 1) / full_history : 1;
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  const float* d_noise = nullptr;
+  int* d_lens;
+  HIP_TRY(bufs.upload(x_init, n * 4, &d_x));
+  HIP_TRY(bufs.upload(lens, (size_t)B * 4, &d_lens));
+  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
+  if (noise) HIP_TRY(bufs.upload(noise, (size_t)n_visits * n * 4, &d_noise));
+  if (int rc = strided_run_dev(m, d_x, d_lens, B, L, visits, n_visits, coef, solver, d_noise, seed, seq_offset, d_out, full_history, nullptr))
+    return rc;
+  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
+  return check_flag(m);
+}
+
+// ... and the checks the entries share
 int check_strided_call(fd_model* m, const void* x_init, const void* lens, const void* out, int B, int L, const int32_t* visits,
-                       int n_visits, const float* coef, int full_history) {
+                       int n_visits, const float* coef, int full_history, bool solver = false) {
   if (int rc = check_shape(m, B, L, 0)) return rc;
   if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
   if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
-  return check_strided(m, visits, n_visits, coef);
+  return solver ? check_solver(m, visits, n_visits, coef) : check_strided(m, visits, n_visits, coef);
 }
 
 // ---- strided runs with motif conditioning: the strided tables and the conditioning in the same per-run values.
@@ -919,29 +983,15 @@ int fd_sample_strided_dev(fd_model* m, const void* x_init_dev, const void* lens_
                           int n_visits, const float* coef, const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev,
                           int full_history, void* hip_stream) {
   if (int rc = check_strided_call(m, x_init_dev, lens_dev, out_dev, B, L, visits, n_visits, coef, full_history)) return rc;
-  return strided_run_dev(m, x_init_dev, lens_dev, B, L, visits, n_visits, coef, noise_dev, seed, seq_offset, out_dev, full_history,
-                         hip_stream);
+  return strided_run_dev(m, x_init_dev, lens_dev, B, L, visits, n_visits, coef, false, noise_dev, seed, seq_offset, out_dev,
+                         full_history, hip_stream);
 }
 
 int fd_sample_strided(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
                       const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, float* out, int full_history) {
   if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, full_history)) return rc;
   if (int rc = check_lens(lens, B, L)) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  const size_t out_rows = full_history ? ((size_t)n_visits + full_history - 1) / full_history : 1;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  const float* d_noise = nullptr;
-  int* d_lens;
-  HIP_TRY(bufs.upload(x_init, n * 4, &d_x));
-  HIP_TRY(bufs.upload(lens, (size_t)B * 4, &d_lens));
-  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
-  if (noise) HIP_TRY(bufs.upload(noise, (size_t)n_visits * n * 4, &d_noise));
-  if (int rc = strided_run_dev(m, d_x, d_lens, B, L, visits, n_visits, coef, d_noise, seed, seq_offset, d_out, full_history, nullptr))
-    return rc;
-  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
-  return check_flag(m);
+  return strided_run_host(m, x_init, lens, B, L, visits, n_visits, coef, false, noise, seed, seq_offset, out, full_history);
 }
 
 int fd_p_sample_step_coef(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
@@ -1024,6 +1074,55 @@ int fd_p_sample_step_coef_inpaint(fd_model* m, const float* x, int t, const int3
   ip.apply(&mode);
   if (int rc = run_step(m, c.s, mode)) return rc;
   return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}});
+}
+
+int fd_sample_solver_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits,
+                         int n_visits, const float* coef, void* out_dev, int full_history, void* hip_stream) {
+  if (int rc = check_strided_call(m, x_init_dev, lens_dev, out_dev, B, L, visits, n_visits, coef, full_history, true)) return rc;
+  return strided_run_dev(m, x_init_dev, lens_dev, B, L, visits, n_visits, coef, true, nullptr, 0, 0, out_dev, full_history, hip_stream);
+}
+
+int fd_sample_solver(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                     const float* coef, float* out, int full_history) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, full_history, true)) return rc;
+  if (int rc = check_lens(lens, B, L)) return rc;
+  return strided_run_host(m, x_init, lens, B, L, visits, n_visits, coef, true, nullptr, 0, 0, out, full_history);
+}
+
+int fd_p_sample_step_solver(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float c, float u,
+                            float v, const float* x0_prev, int wrap, float* eps_out, float* x0_out, float* x_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c) || !std::isfinite(u) || !std::isfinite(v))
+    return fail(FD_E_INVALID, "a = %g, b = %g, c = %g, u = %g, v = %g: a coefficient is not finite", (double)a, (double)b, (double)c,
+                (double)u, (double)v);
+  if (c != 0.f && !x0_prev) return fail(FD_E_INVALID, "x0_prev is required for c != 0");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  // the previous and the new prediction in buffers of the call, allocated (and the previous one uploaded, blocking) before
+  // anything of this frame is queued; a given x0_prev is uploaded whatever c is, and not read where c == 0
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  DeviceBufs bufs;
+  float *d_prev, *d_x0;
+  HIP_TRY(bufs.alloc(n * 4, &d_prev));
+  HIP_TRY(bufs.alloc(n * 4, &d_x0));
+  if (x0_prev) HIP_TRY(hipMemcpy(d_prev, x0_prev, n * 4, hipMemcpyHostToDevice));
+  Call cl;
+  if (int rc = open_call(m, x, lens, nullptr, B, L, &cl)) return rc;
+  Workspace& w = *cl.ws;
+  HIP_TRY(hipMemsetAsync(d_x0, 0, n * 4, cl.s));  // (a position the kernel does not take as a row is not written)
+  if (int rc = prepare_rows(m, cl.s, 0)) return rc;
+  if (int rc = set_t(m, cl.s, t)) return rc;
+  StepMode mode{};
+  mode.t_start = t;
+  mode.no_wrap = !wrap;
+  mode.strided = true;
+  mode.sa = a; mode.sb = b;
+  mode.sc = c; mode.su = u; mode.sv = v;
+  mode.x0_prev = d_prev;
+  mode.x0_out = d_x0;
+  if (int rc = run_step(m, cl.s, mode)) return rc;
+  return finish(m, cl.s, {{x_out, w.x, cl.n * 4}, {eps_out, w.eps, cl.n * 4}, {x0_out, d_x0, cl.n * 4}});
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

@@ -70,6 +70,9 @@ struct UpdateDyn {
   const int* next_t;           // [T] the next visit's t, -1 behind the last visit
   const int* ord;              // [T] the visit's ordinal 0 .. K-1
   const float* abs;            // [3, T] rows a | b | s of the visit:  x' = a x + b eps (+ s z where s != 0)
+  // second-order multistep solver (solver_update.h): both null unless fd_sample_solver is running (a strided run with s = 0)
+  const float* cuv;            // [3, T] rows c | u | v of the visit, indexed by t like `abs`
+  float* x0_prev;              // [M, F] the previous visit's prediction of the clean state, indexed like x (packed rows too)
 };
 struct UpdateArgs {
   const UpdateDyn* dyn;  // device pointer; when non-null it overrides noise/hist/seed/seq_offset/t_start
@@ -105,6 +108,11 @@ struct UpdateArgs {
   float sa, sb, ss;
   // ... and the level its fixed elements land on (fd_p_sample_step_coef_inpaint; known_noise = the one slab of that level)
   int level_out;
+  // one solver update by value, without `dyn` (fd_p_sample_step_solver; x0_out non-null selects it, with `strided` set and
+  // ss = 0): solver_update.h with (sa, sb, sc, su, sv); x0_prev [M, F] is read only where sc != 0, x0_out [M, F] receives x0
+  float sc, su, sv;
+  const float* x0_prev;
+  float* x0_out;
 };
 void launch_head_update(const UpdateArgs& a, hipStream_t s);
 // The replacement of the start point of a motif-conditioned run (inpaint_replace.h): x[o] = the level-`level` value of

@@ -193,6 +193,11 @@ struct StepMode {
   bool strided = false;
   float sa = 0.f, sb = 0.f, ss = 0.f;
   int level_out = 0;  // fd_p_sample_step_coef_inpaint: the level the update lands on (z_known = the one slab of that level)
+  // fd_p_sample_step_solver: one update of the second-order solver (solver_update.h) with (sa, sb, sc, su, sv); x0_out non-null
+  // selects it (device; x0_prev is read only where sc != 0)
+  float sc = 0.f, su = 0.f, sv = 0.f;
+  const float* x0_prev = nullptr;
+  float* x0_out = nullptr;
   const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
   bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
 };

@@ -15,6 +15,7 @@
 #include "img_common.h"
 #include "inpaint_replace.h"
 #include "philox_normal.h"
+#include "solver_update.h"
 #include "strided_update.h"
 #include "wrap_pi.h"
 
@@ -515,12 +516,22 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
   bool strided = a.strided != 0;
   float sa = a.sa, sb = a.sb, ss = a.ss;
   int ord = 0, t_next = -1;
+  // ... of the second-order solver (fd_sample_solver: `dyn`'s cuv and x0_prev; fd_p_sample_step_solver: by value)
+  bool solver = a.x0_out != nullptr;
+  float sc = a.sc, su = a.su, sv = a.sv;
+  const float* x0_prev = a.x0_prev;
+  float* x0_out = a.x0_out;
   int level = strided ? a.level_out : t, known_row = level;  // what a fixed element leaves at, and its row of known_noise (inpaint_replace.h)
   if (a.x_out && a.dyn && a.dyn->next_t) {
     strided = true;
     t_next = a.dyn->next_t[t]; ord = a.dyn->ord[t];
     level = t_next + 1; known_row = ord + 1;
     sa = a.dyn->abs[t]; sb = a.dyn->abs[a.T + t]; ss = a.dyn->abs[2 * a.T + t];
+    if (a.dyn->cuv) {
+      solver = true;
+      sc = a.dyn->cuv[t]; su = a.dyn->cuv[a.T + t]; sv = a.dyn->cuv[2 * a.T + t];
+      x0_prev = x0_out = a.dyn->x0_prev;
+    }
   }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
   if (a.x_out) { c1 = a.coef[t]; btc = a.coef[a.T + t]; c3 = a.coef[2 * a.T + t]; sg = a.coef[3 * a.T + t]; }
@@ -577,13 +588,15 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
         if (fixed && fixed[o]) {  // a fixed element leaves step t at level t (a strided visit: where it lands), whatever the model predicted
           xn = inpaint_value_row(known, known_noise, known_coef, a.T, a.noise_stride, level, known_row, o, seed, seq_offset + ri.x, ri.y, k,
                              (a.angle_mask >> k) & 1u);
-        } else if (strided) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
+        } else if (strided && !solver) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
           xn = strided_mean(sa, a.x[o], sb, mine);
           if (ss != 0.f) {
             const float z = noise ? noise[(size_t)ord * a.noise_stride + o] : philox_normal(seed, t, seq_offset + ri.x, ri.y, k);
             xn = strided_add_noise(xn, ss, z);
           }
           if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
+        } else if (strided) {  // solver_update.h: the strided mean, corrected by c * wrap(x0 - prev); no draw
+          xn = solver_update(sa, a.x[o], sb, mine, sc, su, sv, x0_prev + o, x0_out + o, (a.angle_mask >> k) & 1u);
         } else {
           xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
           if (t > 0) {  // sampling.py:69-75

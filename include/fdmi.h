@@ -51,6 +51,7 @@ extern "C" {
 /*    fd_sample_inpaint_resample and fd_inpaint_jump (resampling schedules of motif-conditioned sampling) are additive too */
 /*    fd_sample_strided, fd_sample_strided_dev and fd_p_sample_step_coef (few-step sampling on a strided schedule) are additive
  *    too: no existing entry or public struct changed, and the tests of the earlier additions pin the value 7 */
+/*    fd_sample_solver, fd_sample_solver_dev and fd_p_sample_step_solver (the second-order multistep solver) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -422,6 +423,46 @@ int fd_sample_strided_inpaint_resample(fd_model* m, const float* x_init, const i
 int fd_p_sample_step_coef_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
                                   const float* z, int wrap, int level_out, const float* known, const uint8_t* fixed,
                                   const float* known_coef, const float* z_known, float* eps_out, float* x_out);
+
+/* ---- few-step sampling with a second-order multistep solver, in the manner of DPM-Solver++(2M) (Lu et al. 2022): a strided
+ * run without noise whose update also uses the previous visit's prediction of the clean state.  K network evaluations, one
+ * [B][L][F] buffer more.  The reference has no such sampler; like fd_sample_strided this is an extension.
+ *
+ * Visits and levels are fd_sample_strided's.  The update of visit i with (a, b, c, u, v) = coef[.][i], for every element
+ * o = (b, l, f) with l < lens[b]; `angular`: the model's feature f is an angle; every product and every sum rounded once, no
+ * contraction:
+ *   m  = a * x[o] + b * eps[o]                                   fd_sample_strided's mean
+ *   x0 = u * x[o] + v * eps[o];   angular: x0 = wrap(x0)          the prediction of the clean state
+ *   c != 0:  d = x0 - prev[o];    angular: d = wrap(d);   m = m + c * d
+ *   angular: m = wrap(m)
+ *   prev[o] = x0;  x'[o] = m
+ * wrap = to [-pi, pi).  The difference is wrapped: two predictions of an angle either side of +-pi are close on the circle and
+ * about 2 pi apart as numbers.  Where c == 0, prev[o] is NOT read (the first visit finds it uninitialised).  Nothing is drawn:
+ * the run is a deterministic map of x_init.  sampling.solver_coefficients gives a and b of ddim_coefficients(eta = 0),
+ * u = 1 / alpha_p, v = -sigma_p / alpha_p and, with lam = log(alpha / sigma), h = lam_q - lam_p, r = (lam_p - lam_p') / h
+ * (p' = the level visit i - 1 ran at): c = alpha_q (1 - exp(-h)) / (2 r); c = 0 for the first visit, for the last (level 0
+ * has infinite log-SNR) and everywhere at order 1, where the run is fd_sample_strided's with every s == 0, bit for bit.
+ *
+ *   visits   as in fd_sample_strided
+ *   coef     float32 [5][K], rows a | b | c | u | v, all finite, c[0] == 0 (host)
+ *   x_init, out, full_history   as in fd_sample_strided
+ * prev and the tables live in device buffers of the call.  The captured step graph is the plain sampler's and is not
+ * re-captured.  Everything fd_sample_strided rejects, a coefficient that is not finite or c[0] != 0: FD_E_INVALID before any
+ * device call (fd_last_error() names the index), `out` untouched.  Options "use_graph" and "varlen" and both precisions as in
+ * fd_sample; a later fd_sample* is unaffected.  Not offered with motif conditioning. */
+int fd_sample_solver(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                     const float* coef, float* out, int full_history);
+
+/* The same with x_init, lens and out already in device memory (visits and coef stay host arrays), on `hip_stream` (NULL = the
+ * model's own stream).  Like fd_sample_strided_dev it returns with the stream drained. */
+int fd_sample_solver_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits,
+                         int n_visits, const float* coef, void* out_dev, int full_history, void* hip_stream);
+
+/* The parity hook of the above: ONE update at timestep t with explicit (a, b, c, u, v), all finite.  x0_prev [B][L][F] is
+ * required exactly when c != 0 (given with c == 0 it is not read).  eps_out (or NULL) receives the network's prediction, the
+ * bits of fd_forward's; x0_out (or NULL) the visit's x0.  With wrap == 0 nothing is wrapped.  Host buffers. */
+int fd_p_sample_step_solver(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float c, float u,
+                            float v, const float* x0_prev, int wrap, float* eps_out, float* x0_out, float* x_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
