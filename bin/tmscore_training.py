@@ -6,7 +6,11 @@ bin/tmscore_training.py (same -d / -n arguments).
 Every generated backbone is aligned to every training chain by foldingdiff_amd.structures.max_tm_across_refs (the
 TM-align-style search restated on the device in place of one TMalign subprocess per pair), normalised by the training
 chain's length.  Writes tm_scores.json ({sample name: best score}) and tm_scores_ref.json ({sample name: the best
-matching training file}) into the directory of generated structures, like compute_training_tm_scores.
+matching training file}) into the directory of generated structures, like compute_training_tm_scores, and
+tm_scores_settings.json ({"starts": ...}; the keys of the other two are the sample names).
+
+--starts all searches every pair from all five of TM-align's starts instead of two (fd_tm_align_ex): slower, never a
+lower score, so never a higher novelty.
 
 What differs: the training set is named with --train (a directory of .pdb / .pdb.gz files, or a text file listing one
 path per line); the reference builds the CATH training split, whose data pipeline is not here.  Files that cannot be
@@ -28,6 +32,9 @@ if REPO not in sys.path:
 from foldingdiff_amd import structures  # noqa: E402
 
 
+STARTS = {"two": ("threading", "ss"), "all": "all"}
+
+
 def training_files(train: str):
     if os.path.isdir(train):
         return sorted(glob(os.path.join(train, "*.pdb")) + glob(os.path.join(train, "*.pdb.gz")))
@@ -43,6 +50,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--train", type=str, required=True,
                         help="Training structures: a directory of PDB files, or a file listing one PDB path per line")
     parser.add_argument("--device", type=int, default=0, help="GPU index")
+    parser.add_argument("--starts", choices=sorted(STARTS), default="two",
+                        help="Starts of the alignment search: two (threading, secondary structure) or all five")
     return parser
 
 
@@ -59,8 +68,10 @@ def main(argv=None) -> None:
     train = training_files(args.train)
     assert train, f"{args.train} names no training structures"
     logging.info(f"Calculating tm scores against {len(train)} training structures...")
-    scores, refs = structures.training_tm_scores(generated, train, device=args.device)
+    scores, refs = structures.training_tm_scores(generated, train, device=args.device, starts=STARTS[args.starts])
     outdir = Path(args.dirname)
+    with open(outdir / "tm_scores_settings.json", "w") as sink:
+        json.dump({"starts": args.starts}, sink, indent=4)
     with open(outdir / "tm_scores.json", "w") as sink:
         json.dump(scores, sink, indent=4)
     with open(outdir / "tm_scores_ref.json", "w") as sink:

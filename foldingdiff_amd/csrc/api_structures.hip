@@ -1,4 +1,4 @@
-// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, clash_lddt.hip), of
+// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
 // the loss arithmetic on its own (loss.hip, loss_variants.hip) and of the angle histograms (angle_stats.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
@@ -95,9 +95,11 @@ int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, con
                           });
 }
 
-int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
-                const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens, int n_pairs, int max_iter,
-                double* tm_out, double* transform_out, int32_t* n_ali_out, const int64_t* map_offsets, int32_t* map_out) {
+// fd_tm_align (starts = 0: tm_align_kernel, starts 1 and 2) and fd_tm_align_ex (a bit set of starts: tm_starts_kernel)
+static int tm_align_roundtrip(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                              const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens, int n_pairs, int max_iter,
+                              double* tm_out, double* transform_out, int32_t* n_ali_out, const int64_t* map_offsets,
+                              int32_t* map_out, uint32_t starts, double* start_tm_out) {
   if (!ca || !offsets || !lens || !pair_a || !pair_b || !tm_out) return fail(FD_E_INVALID, "null argument");
   if ((map_offsets == nullptr) != (map_out == nullptr))
     return fail(FD_E_INVALID, "null argument: map_offsets and map_out go together");
@@ -131,16 +133,38 @@ int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const i
       {{ca, na * 3 * 8}, {cent.data(), nc * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}, {pair_a, np * 4}, {pair_b, np * 4},
        {norm.data(), np * 4}, {map_offsets ? map_offsets : &no_offsets, map_offsets ? np * 8 : 8}},
       {{nullptr, na}, {nullptr, nc * 2 * 4}, {tm_out, np * 8}, {transform_out, np * 12 * 8}, {n_ali_out, np * 4},
-       {map_out, map_bytes}},
+       {map_out, map_bytes}, {start_tm_out, start_tm_out ? np * 5 * 8 : 8}},
       [&](const RoundtripBufs& d) {
-        // the labels of every chain first (start 2 reads them), then the pairs; both on the null stream, in order
+        // the labels of every chain first (starts 2 and 3 read them), then the pairs; both on the null stream, in order
         launch_psea(d.in(0), d.in(2), d.in(3), n_chains, max_len, d.out(0), d.out(1), nullptr);
         const long long* map_off = d.in(7);
         int* map = d.out(5);
-        return launch_tm_align(d.in(0), d.in(1), d.in(2), d.in(3), d.out(0), d.in(4), d.in(5), d.in(6),
-                               map_out ? map_off : nullptr, n_pairs, max_iter, max_len, d.out(2), d.out(3), d.out(4),
-                               map_out ? map : nullptr, nullptr);
+        double* start_tm = d.out(6);
+        if (starts == 0)
+          return launch_tm_align(d.in(0), d.in(1), d.in(2), d.in(3), d.out(0), d.in(4), d.in(5), d.in(6),
+                                 map_out ? map_off : nullptr, n_pairs, max_iter, max_len, d.out(2), d.out(3), d.out(4),
+                                 map_out ? map : nullptr, nullptr);
+        return launch_tm_starts(d.in(0), d.in(1), d.in(2), d.in(3), d.out(0), d.in(4), d.in(5), d.in(6),
+                                map_out ? map_off : nullptr, n_pairs, max_iter, max_len, starts, d.out(2), d.out(3), d.out(4),
+                                map_out ? map : nullptr, start_tm_out ? start_tm : nullptr, nullptr);
       });
+}
+
+int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens, int n_pairs, int max_iter,
+                double* tm_out, double* transform_out, int32_t* n_ali_out, const int64_t* map_offsets, int32_t* map_out) {
+  return tm_align_roundtrip(device_id, ca, offsets, lens, n_chains, pair_a, pair_b, norm_lens, n_pairs, max_iter, tm_out,
+                            transform_out, n_ali_out, map_offsets, map_out, 0, nullptr);
+}
+
+int fd_tm_align_ex(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                   const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens, int n_pairs, int max_iter,
+                   double* tm_out, double* transform_out, int32_t* n_ali_out, const int64_t* map_offsets, int32_t* map_out,
+                   uint32_t starts, double* start_tm_out) {
+  if (starts == 0 || starts > FDMI_ALIGN_STARTS_ALL)
+    return fail(FD_E_INVALID, "starts=%u: a non-empty set of the bits 1, 2, 4, 8, 16", starts);
+  return tm_align_roundtrip(device_id, ca, offsets, lens, n_chains, pair_a, pair_b, norm_lens, n_pairs, max_iter, tm_out,
+                            transform_out, n_ali_out, map_offsets, map_out, starts, start_tm_out);
 }
 
 int fd_loss_terms(int device_id, const float* pred, const float* target, const int32_t* lens, int B, int L, int F,

@@ -166,6 +166,13 @@ hipError_t launch_tm_align(const double* ca, const double* cent, const int* offs
                            const int* pair_a, const int* pair_b, const int* norm_lens, const long long* map_offsets,
                            int n_pairs, int max_iter, int max_len, double* tm_out, double* transform_out, int* n_ali_out,
                            int* map_out, hipStream_t s);
+// The same search from the starts of the bit set `starts` (tm_align_starts.hip; 1 threading, 2 secondary structure, 4
+// secondary structure plus distance, 8 local superposition, 16 fragment threading); start_tm_out [n_pairs][5] or null: the
+// best TM reached from each start, -1 where it was not requested or was skipped.
+hipError_t launch_tm_starts(const double* ca, const double* cent, const int* offsets, const int* lens, const signed char* sse,
+                            const int* pair_a, const int* pair_b, const int* norm_lens, const long long* map_offsets,
+                            int n_pairs, int max_iter, int max_len, unsigned starts, double* tm_out, double* transform_out,
+                            int* n_ali_out, int* map_out, double* start_tm_out, hipStream_t s);
 
 // Integer pair counts over all atom pairs of a structure (clash_lddt.hip), one workgroup per structure, float32
 // coordinates packed like launch_internal_coords'.  Clashes: xyz [n_res][3][3] -> counts_out [n_chains] (atoms that clash),

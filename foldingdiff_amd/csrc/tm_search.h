@@ -1,5 +1,5 @@
 // The seed-and-extend TM-score search of one lane, shared by tm_score_kernel (tm_score.hip: residue-paired traces) and
-// tm_align_kernel (tm_align.hip: the aligned pairs of a residue alignment).  The rules are in the header of
+// tm_align_kernel and tm_starts_kernel (tm_align.hip, tm_align_starts.hip: the aligned pairs of a residue alignment).  The rules are in the header of
 // tm_score.hip and in DESIGN.md "TM-score".
 #pragma once
 #include "horn_fit.h"

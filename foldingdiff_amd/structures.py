@@ -20,7 +20,8 @@ The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
 * ``tmalign.run_tmalign`` / ``max_tm_across_refs`` (foldingdiff/tmalign.py:22-83) and ``get_pairwise_tmscores``
   (bin/hclust_structures.py:38-69), which run one TM-align subprocess per pair of chains whose residues do not
   correspond: ``tm_align``, ``pairwise_tm``, ``max_tm_across_refs`` and ``pairwise_tmscores`` search the residue
-  alignment and the superposition on the device (``fd_tm_align``, one workgroup per pair).
+  alignment and the superposition on the device (``fd_tm_align``, one workgroup per pair; ``starts=`` chooses among
+  TM-align's five starts through ``fd_tm_align_ex``).
 
 * ``count_clashes`` / ``count_clashes_parallel`` (foldingdiff/vdw_clashes.py:34-78), a Python double loop over atom pairs
   in one process per file, and ``lddt`` / ``lddt_sampled_folded`` (foldingdiff/lddt.py:32-100), one OpenStructure
@@ -691,9 +692,34 @@ def _align_traces(chains: Sequence[np.ndarray], what: str = "chain") -> List[np.
     return _ca_traces(chains, ALIGN_MAX_LEN, what)
 
 
+ALIGN_STARTS = ("threading", "ss", "ss_dist", "local", "fragment")   # bit k of FDMI_ALIGN_START_*: 1 << k
+_DEFAULT_STARTS = ("threading", "ss")
+
+
+def align_start_bits(starts=_DEFAULT_STARTS) -> int:
+    """The ``starts`` bit set of ``fd_tm_align_ex`` for a selection of ``ALIGN_STARTS`` names; ``"all"`` is all five.
+    An unknown name, an empty selection and a repeated name raise ValueError."""
+    if isinstance(starts, str):
+        starts = ALIGN_STARTS if starts == "all" else (starts,)
+    names = list(starts)
+    if not names:
+        raise ValueError("starts: empty selection")
+    bits = 0
+    for name in names:
+        if name not in ALIGN_STARTS:
+            raise ValueError(f"starts: unknown start {name!r}; expected \"all\" or names from {ALIGN_STARTS}")
+        if bits & (1 << ALIGN_STARTS.index(name)):
+            raise ValueError(f"starts: {name!r} is named twice")
+        bits |= 1 << ALIGN_STARTS.index(name)
+    return bits
+
+
 def _align_indexed(chains: List[np.ndarray], pair_a: np.ndarray, pair_b: np.ndarray, norm_lens, max_iter: int, device: int,
-                   want_map: bool):
-    """One ``fd_tm_align`` call over already-checked float64 traces: (tm [P], T [P, 12], n_ali [P], maps or None)."""
+                   want_map: bool, starts=_DEFAULT_STARTS, want_start_tms: bool = False):
+    """One ``fd_tm_align`` call (``fd_tm_align_ex`` for any but the default starts, or when the per-start scores are
+    wanted) over already-checked float64 traces: (tm [P], T [P, 12], n_ali [P], maps or None), and the [P, 5] per-start
+    scores with ``want_start_tms``."""
+    bits = align_start_bits(starts)
     X, offsets, lens = _pack(chains)
     P = len(pair_a)
     pa, pb = np.ascontiguousarray(pair_a, dtype=np.int32), np.ascontiguousarray(pair_b, dtype=np.int32)
@@ -705,17 +731,21 @@ def _align_indexed(chains: List[np.ndarray], pair_a: np.ndarray, pair_b: np.ndar
     tm = np.empty((P,), dtype=np.float64)
     T = np.empty((P, 12), dtype=np.float64)
     n_ali = np.empty((P,), dtype=np.int32)
+    start_tms = np.empty((P, len(ALIGN_STARTS)), dtype=np.float64) if want_start_tms else None
     if P == 0:
-        return tm, T, n_ali, ([] if want_map else None)
+        return (tm, T, n_ali, ([] if want_map else None)) + ((start_tms,) if want_start_tms else ())
     map_off = flat = None
     if want_map:
         map_off = np.concatenate([[0], np.cumsum(lens[pa], dtype=np.int64)[:-1]]).astype(np.int64)
         flat = np.empty((int(lens[pa].sum()),), dtype=np.int32)
-    _binding.check(_binding.load().fd_tm_align(
-        device, ptr(X), ptr(offsets), ptr(lens), len(chains), ptr(pa), ptr(pb), ptr(nl), P, int(max_iter), ptr(tm), ptr(T),
-        ptr(n_ali), ptr(map_off), ptr(flat)))
+    args = (device, ptr(X), ptr(offsets), ptr(lens), len(chains), ptr(pa), ptr(pb), ptr(nl), P, int(max_iter), ptr(tm), ptr(T),
+            ptr(n_ali), ptr(map_off), ptr(flat))
+    if bits == align_start_bits(_DEFAULT_STARTS) and not want_start_tms:
+        _binding.check(_binding.load().fd_tm_align(*args))
+    else:
+        _binding.check(_binding.load().fd_tm_align_ex(*args, bits, ptr(start_tms)))
     maps = [flat[o: o + lens[i]].copy() for o, i in zip(map_off, pa)] if want_map else None
-    return tm, T, n_ali, maps
+    return (tm, T, n_ali, maps) + ((start_tms,) if want_start_tms else ())
 
 
 def _polish(chains, pa, pb, nl, maps, device):
@@ -727,7 +757,7 @@ def _polish(chains, pa, pb, nl, maps, device):
 
 def tm_align(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], norm_lens: Optional[Sequence[int]] = None,
              max_iter: int = 10, return_transform: bool = False, return_map: bool = False, polish: bool = False,
-             device: int = 0):
+             device: int = 0, starts=_DEFAULT_STARTS, return_start_tms: bool = False):
     """TM-score of each pair of CA traces (a[i] [n1, 3], b[i] [n2, 3], 1 <= n <= 512) whose residues need not
     correspond, in one ``fd_tm_align`` call: float64 [len(a_list)], normalised by ``norm_lens[i]`` (>= min(n1, n2);
     default n2, the "Chain_2" number ``tmalign.run_tmalign`` returns).  With ``return_transform`` also R [n, 3, 3] and
@@ -741,6 +771,13 @@ def tm_align(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], norm_le
     "TM-align-style alignment" states the rules).  It is not pinned to the TMalign binary; with fewer starts than
     TM-align's five it is a lower bound on the optimum TM-align looks for.
 
+    ``starts``: the starts to search from, names from ``ALIGN_STARTS`` ("threading", "ss", "ss_dist": labels plus
+    distances under the threading's superposition, "local": the best of up to 128 fragment-pair superpositions,
+    "fragment": threading of the longest stretch without a chain break) or ``"all"``; any but the default goes through
+    ``fd_tm_align_ex``.  More starts never score lower.  With ``return_start_tms`` also (last) a float64 [n, 5] array:
+    the best score reached from each start (at the coarse stride, with ``polish`` too), -1 where it was not requested
+    or does not apply to the pair.
+
     ``polish``: the aligned pairs are scored again by ``tm_score`` at stride 1.  Stride 1's seeds contain the coarse
     stride's, so the polished score (and its transform) is never lower."""
     if len(a_list) != len(b_list):
@@ -748,21 +785,24 @@ def tm_align(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], norm_le
     a, b = _align_traces(a_list, "a"), _align_traces(b_list, "b")
     n = len(a)
     pa, pb = np.arange(n, dtype=np.int32), np.arange(n, 2 * n, dtype=np.int32)
-    tm, T, _, maps = _align_indexed(a + b, pa, pb, norm_lens, max_iter, device, return_map or polish)
+    got = _align_indexed(a + b, pa, pb, norm_lens, max_iter, device, return_map or polish, starts, return_start_tms)
+    tm, T, _, maps = got[:4]
+    start_tms = got[4] if return_start_tms else None
     R, t = T[:, :9].reshape(n, 3, 3).copy(), T[:, 9:].copy()
     if polish and n:
         nl = [len(y) for y in b] if norm_lens is None else list(norm_lens)
         tm, R, t = _polish(a + b, pa, pb, nl, maps, device)
-    out = (tm,) + ((R, t) if return_transform else ()) + ((maps,) if return_map else ())
+    out = (tm,) + ((R, t) if return_transform else ()) + ((maps,) if return_map else ()) + ((start_tms,) if return_start_tms else ())
     return out if len(out) > 1 else tm
 
 
 def pairwise_tm(chains: Sequence[np.ndarray], pairs=None, norm_lens: Optional[Sequence[int]] = None, max_iter: int = 10,
-                polish: bool = False, chunk: int = 1 << 16, device: int = 0) -> np.ndarray:
+                polish: bool = False, chunk: int = 1 << 16, device: int = 0, starts=_DEFAULT_STARTS) -> np.ndarray:
     """``tm_align`` scores of ``pairs`` (an [P, 2] list of (i, j) indices into ``chains``: chain i aligned to chain j,
     normalised by chain j's length unless ``norm_lens`` says otherwise; default every i < j in row order): float64 [P].
     The pair list is cut into chunks of ``chunk`` pairs and every call uploads only the chains its chunk names, so the
-    host and device buffers stay bounded however long the list is."""
+    host and device buffers stay bounded however long the list is.  ``starts`` as in ``tm_align``."""
+    align_start_bits(starts)
     ca = _align_traces(chains)
     if pairs is None:
         iu = np.triu_indices(len(ca), k=1)
@@ -784,7 +824,7 @@ def pairwise_tm(chains: Sequence[np.ndarray], pairs=None, norm_lens: Optional[Se
         inv = inv.reshape(sub.shape)
         local = [ca[i] for i in used]
         sub_nl = None if nl is None else nl[lo: lo + len(sub)]
-        tm, _, _, maps = _align_indexed(local, inv[:, 0], inv[:, 1], sub_nl, max_iter, device, polish)
+        tm, _, _, maps = _align_indexed(local, inv[:, 0], inv[:, 1], sub_nl, max_iter, device, polish, starts)
         if polish:
             pnl = [len(local[j]) for j in inv[:, 1]] if sub_nl is None else list(sub_nl)
             tm = _polish(local, inv[:, 0], inv[:, 1], pnl, maps, device)[0]
@@ -793,17 +833,19 @@ def pairwise_tm(chains: Sequence[np.ndarray], pairs=None, norm_lens: Optional[Se
 
 
 def max_tm_across_refs(query_ca: Sequence[np.ndarray], refs_ca: Sequence[np.ndarray], max_iter: int = 10,
-                       polish: bool = False, chunk: int = 1 << 16, device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+                       polish: bool = False, chunk: int = 1 << 16, device: int = 0,
+                       starts=_DEFAULT_STARTS) -> Tuple[np.ndarray, np.ndarray]:
     """(max, argmax) over the references of the ``tm_align`` score of every query against every reference, normalised
     by the reference's length: ``tmalign.max_tm_across_refs`` (foldingdiff/tmalign.py:57-83) for many queries at once.
-    float64 [n_queries] and int64 [n_queries] (the first reference on a tie)."""
+    float64 [n_queries] and int64 [n_queries] (the first reference on a tie).  ``starts`` as in ``tm_align``."""
+    align_start_bits(starts)
     q, r = _align_traces(query_ca, "query"), _align_traces(refs_ca, "reference")
     if not r:
         raise ValueError("no references")
     nq, nr = len(q), len(r)
     qi, ri = np.meshgrid(np.arange(nq), np.arange(nr), indexing="ij")
     pairs = np.stack([qi.ravel(), nq + ri.ravel()], axis=1)
-    tm = pairwise_tm(q + r, pairs, max_iter=max_iter, polish=polish, chunk=chunk, device=device).reshape(nq, nr)
+    tm = pairwise_tm(q + r, pairs, max_iter=max_iter, polish=polish, chunk=chunk, device=device, starts=starts).reshape(nq, nr)
     best = tm.argmax(axis=1) if nq else np.zeros((0,), np.int64)
     return tm[np.arange(nq), best], best.astype(np.int64)
 
@@ -824,31 +866,33 @@ def _alignable_files(fnames: Sequence[str]) -> Tuple[List[str], List[np.ndarray]
     return kept, traces
 
 
-def pairwise_tmscores(fnames: Sequence[str], max_iter: int = 10, device: int = 0) -> pd.DataFrame:
+def pairwise_tmscores(fnames: Sequence[str], max_iter: int = 10, device: int = 0, starts=_DEFAULT_STARTS) -> pd.DataFrame:
     """The symmetric table of ``get_pairwise_tmscores`` (bin/hclust_structures.py:38-69): index and columns are the
     files' base names without extension, the diagonal is 1.0, and for k before v in ``fnames`` the score of k aligned
-    to v (normalised by v's length) goes on both sides."""
+    to v (normalised by v's length) goes on both sides.  ``starts`` as in ``tm_align``."""
+    align_start_bits(starts)
     kept, traces = _alignable_files(list(fnames))
     logging.info(f"Computing pairwise distances between {len(kept)} pdb files")
     bnames = [os.path.splitext(os.path.basename(f))[0] for f in kept]
     vals = np.ones((len(kept), len(kept)), dtype=np.float64)
     if len(kept) > 1:
         iu = np.triu_indices(len(kept), k=1)
-        tm = pairwise_tm(traces, np.stack(iu, axis=1), max_iter=max_iter, device=device)
+        tm = pairwise_tm(traces, np.stack(iu, axis=1), max_iter=max_iter, device=device, starts=starts)
         vals[iu] = tm
         vals[(iu[1], iu[0])] = tm
     return pd.DataFrame(vals, index=bnames, columns=bnames)
 
 
 def training_tm_scores(pdb_files: Sequence[str], train_files: Sequence[str], max_iter: int = 10,
-                       device: int = 0) -> Tuple[dict, dict]:
+                       device: int = 0, starts=_DEFAULT_STARTS) -> Tuple[dict, dict]:
     """``compute_training_tm_scores`` (bin/tmscore_training.py:22-42) without the files it writes: ({sample name: the
-    largest score against the training chains}, {sample name: that training file})."""
+    largest score against the training chains}, {sample name: that training file}).  ``starts`` as in ``tm_align``."""
+    align_start_bits(starts)
     samples, q = _alignable_files(list(pdb_files))
     refs, r = _alignable_files(list(train_files))
     if not refs:
         raise ValueError("no usable training structure")
-    best, which = max_tm_across_refs(q, r, max_iter=max_iter, device=device) if q else ([], [])
+    best, which = max_tm_across_refs(q, r, max_iter=max_iter, device=device, starts=starts) if q else ([], [])
     names = [os.path.splitext(os.path.basename(f))[0] for f in samples]
     return ({k: float(v) for k, v in zip(names, best)}, {k: refs[int(j)] for k, j in zip(names, which)})
 

@@ -52,6 +52,7 @@ extern "C" {
 /*    fd_sample_strided, fd_sample_strided_dev and fd_p_sample_step_coef (few-step sampling on a strided schedule) are additive
  *    too: no existing entry or public struct changed, and the tests of the earlier additions pin the value 7 */
 /*    fd_sample_solver, fd_sample_solver_dev and fd_p_sample_step_solver (the second-order multistep solver) are additive too */
+/*    fd_tm_align_ex (the alignment search from a chosen set of TM-align's five starts) is additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -579,6 +580,32 @@ int fd_tm_align(int device_id, const double* ca, const int32_t* offsets, const i
                 int n_pairs, int max_iter, double* tm_out, double* transform_out /* null or [n_pairs][12] */,
                 int32_t* n_ali_out /* null ok */, const int64_t* map_offsets, int32_t* map_out /* both null, or
                 map_out[map_offsets[p] + i] = j or -1 for i < lens[pair_a[p]] */);
+
+/* The starts of fd_tm_align_ex's search, a bit set.  fd_tm_align searches from the first two. */
+#define FDMI_ALIGN_START_THREADING 1u /* the best gapless threading */
+#define FDMI_ALIGN_START_SSE 2u       /* a dynamic programme over the P-SEA labels */
+#define FDMI_ALIGN_START_SSE_DIST 4u  /* labels plus the distances under start 1's superposition */
+#define FDMI_ALIGN_START_LOCAL 8u     /* the best of up to 128 fragment-pair superpositions; chains of >= 12 residues */
+#define FDMI_ALIGN_START_FRAGMENT 16u /* threading of the longest stretch without a chain break (CA-CA step >= 4.25 A) */
+#define FDMI_ALIGN_STARTS_ALL 31u
+
+/* fd_tm_align from a chosen set of TM-align's five starts (DESIGN.md "TM-align-style alignment" has the exact rules of
+ * each; like the first two, the three further ones restate the published method and are not pinned to the TMalign
+ * binary).  The first 15 arguments and their checks are fd_tm_align's.
+ *   starts        a non-empty set of the FDMI_ALIGN_START_* bits; anything else is FD_E_INVALID.  Every requested start
+ *                 that applies to the pair is refined as in fd_tm_align and the best candidate wins, the first on a tie in
+ *                 start order: more starts never score lower, and FDMI_ALIGN_START_THREADING | FDMI_ALIGN_START_SSE
+ *                 returns bit for bit what fd_tm_align returns.
+ *   start_tm_out  NULL, or float64 [n_pairs][5]: the best TM reached from each start, -1 where the start was not
+ *                 requested or was skipped (LOCAL below 12 residues, FRAGMENT without a chain break).
+ * A pair to which no requested start applies has no candidate: tm_out = -1, the identity transform, n_ali_out = 0 and a
+ * map of -1.
+ * Synchronous; the result of a pair does not depend on the other pairs of the call. */
+int fd_tm_align_ex(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
+                   const int32_t* pair_a, const int32_t* pair_b, const int32_t* norm_lens /* null: lens[pair_b] */,
+                   int n_pairs, int max_iter, double* tm_out, double* transform_out /* null or [n_pairs][12] */,
+                   int32_t* n_ali_out /* null ok */, const int64_t* map_offsets, int32_t* map_out /* both null or neither */,
+                   uint32_t starts, double* start_tm_out /* null or [n_pairs][5] */);
 
 /* Most atoms of one structure fd_backbone_clashes and fd_lddt take (the per-atom pair counters are 32-bit). */
 #define FDMI_PAIRCOUNT_MAX_ATOMS 65536
