@@ -40,6 +40,19 @@ class FdConfig(C.Structure):
     ]
 
 
+class FdSteerParams(C.Structure):
+    """``fd_steer_params`` of include/fdmi.h."""
+    _fields_ = [
+        ("weights", C.c_double * 4),
+        ("lam", C.c_double),
+        ("ess_frac", C.c_double),
+        ("clash_alpha", C.c_double),
+        ("feat_idx", C.c_int32 * 9),
+        ("has_offset", C.c_int32),
+        ("offset", C.c_float * 16),
+    ]
+
+
 # every symbol include/fdmi.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -75,6 +88,12 @@ _SIGNATURES = {
     "fd_sample_solver_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     "fd_p_sample_step_solver": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                           _P, C.c_int, _P, _P, _P]),
+    "fd_sample_steered": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.c_int64, _P, C.c_int,
+                                    C.POINTER(FdSteerParams), _P, _P, _P, _P, _P, _P]),
+    "fd_p_sample_step_coef_x0": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                           _P, C.c_int, _P, _P, _P]),
+    "fd_steer_rewards": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P]),
+    "fd_steer_resample": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P]),
     "fd_sample_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_begin_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_steps_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),

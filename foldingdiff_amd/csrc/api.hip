@@ -649,7 +649,7 @@ UpdateArgs fill_update(const fd_model* m, const Workspace& w, const StepMode& mo
       u.noise = mode.noise;
       u.t_start = mode.t_start;
       u.known = mode.known; u.fixed = mode.fixed; u.known_noise = mode.z_known; u.known_coef = mode.known_coef;
-      u.strided = mode.strided ? 1 : 0; u.sa = mode.sa; u.sb = mode.sb; u.ss = mode.ss;
+      u.strided = mode.strided ? (mode.x0_only ? 2 : 1) : 0; u.sa = mode.sa; u.sb = mode.sb; u.ss = mode.ss;
       u.level_out = mode.level_out;
       u.sc = mode.sc; u.su = mode.su; u.sv = mode.sv; u.x0_prev = mode.x0_prev; u.x0_out = mode.x0_out;
     }

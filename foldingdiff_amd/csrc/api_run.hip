@@ -1,5 +1,5 @@
 // C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
-// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned, solver) and their
+// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned, solver, steered) and their
 // device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry checks its
 // arguments before its first HIP call, and the paragraphs the entries share -- make the workspace current and upload, download
 // and synchronise, the host-side run, the one-copy staging of the loss entries -- are written once, below.
@@ -632,6 +632,147 @@ int strided_host_run(fd_model* m, const StridedHostRun& a) {
   return check_flag(m);
 }
 
+// ---- steered sampling: a strided run whose visits also write their prediction of the clean state, with an
+// event -- shift, rewards, resample, gather (steer.hip) -- between the step segments, as walk_visits puts jumps between them
+struct SteeredHostRun {
+  const float* x_init;
+  const int32_t* lens;
+  int B, L;
+  const int32_t* visits;
+  int n_visits;
+  const float* coef;   // [5][K] a | b | s | u | v
+  const float* noise;  // [K][B][L][F], or null: Philox
+  uint64_t seed;
+  int64_t seq_offset;
+  const uint8_t* event;  // [K]
+  int n_events;
+  int P;
+  const fd_steer_params* params;
+  const double* u;  // [n_events][B / P]
+  float* out;
+  double *terms_out, *reward_out, *logw_out;
+  int32_t* ancestors_out;  // [n_events][B], or null
+};
+
+// where a steered run's table u | v and its prediction buffer are on the device (both null: no steered run)
+struct SteerDev {
+  const float* uv = nullptr;
+  float* x0 = nullptr;
+  void apply(UpdateDyn* dyn) const { dyn->uv = uv; dyn->x0_steer = x0; }
+  static void clear(UpdateDyn* dyn) { SteerDev().apply(dyn); }
+};
+
+// Returns with the stream drained and the strided and the steering fields cleared, on the host and on the device, on every
+// path behind begin_run: the tables and the buffers die with this frame.  The entry has checked every argument.
+int steered_host_run(fd_model* m, const SteeredHostRun& a) {
+  HIP_TRY(hipSetDevice(m->device));
+  const int F = m->cfg.n_features, B = a.B, L = a.L, K = a.n_visits, G = a.B / a.P;
+  const size_t n = (size_t)B * L * F, nr = (size_t)B * L, nb = (size_t)B, T = (size_t)m->T;
+  const fd_steer_params& sp = *a.params;
+  DeviceBufs bufs;
+  float *d_x, *d_out, *d_ang, *d_tmp;
+  const float* d_noise = nullptr;
+  int* d_lens;
+  HIP_TRY(bufs.upload(a.x_init, n * 4, &d_x));
+  HIP_TRY(bufs.upload(a.lens, nb * 4, &d_lens));
+  HIP_TRY(bufs.alloc(n * 4, &d_out));
+  HIP_TRY(bufs.alloc(n * 4, &d_ang));
+  HIP_TRY(bufs.alloc(n * 4, &d_tmp));
+  if (a.noise) HIP_TRY(bufs.upload(a.noise, (size_t)K * n * 4, &d_noise));
+  StridedDev sd;
+  if (int rc = stage_strided(m, &bufs, a.visits, K, a.coef, &sd)) return rc;  // (rows a | b | s are the first three of coef)
+  SteerDev sv;
+  std::vector<float> uv(2 * T, 0.f);
+  for (int i = 0; i < K; ++i)
+    for (size_t r = 0; r < 2; ++r) uv[r * T + (size_t)a.visits[i]] = a.coef[(3 + r) * (size_t)K + i];
+  HIP_TRY(bufs.upload(uv.data(), uv.size() * 4, &sv.uv));
+  HIP_TRY(bufs.zeros(n * 4, &sv.x0));  // (packed rows: a position beyond a length is never written, and never read)
+  // the rewards pass's buffers, the weights' state and the uniforms
+  SteerWork wk{};
+  std::vector<int32_t> offsets(nb);
+  int max_len = 0;
+  for (int b = 0; b < B; ++b) {
+    offsets[(size_t)b] = b * L;
+    max_len = a.lens[b] > max_len ? a.lens[b] : max_len;
+  }
+  HIP_TRY(bufs.alloc(nr * 9 * 8, &wk.coords));
+  HIP_TRY(bufs.alloc(nr * 9 * 4, &wk.xyz));
+  HIP_TRY(bufs.alloc(nr * 3 * 8, &wk.ca));
+  HIP_TRY(bufs.alloc(nr, &wk.sse));
+  HIP_TRY(bufs.alloc(nb * 2 * 4, &wk.sse_runs));
+  HIP_TRY(bufs.alloc(nb * 4, &wk.clashes));
+  HIP_TRY(bufs.upload(offsets.data(), nb * 4, &wk.offsets));
+  double *d_terms, *d_reward, *d_logw, *d_rprev;
+  const double* d_u = nullptr;
+  int* d_anc;
+  unsigned char* d_flags;
+  const size_t ne = a.n_events > 0 ? (size_t)a.n_events : 1;
+  HIP_TRY(bufs.alloc(nb * 4 * 8, &d_terms));
+  HIP_TRY(bufs.alloc(nb * 8, &d_reward));
+  HIP_TRY(bufs.zeros(nb * 8, &d_logw));
+  HIP_TRY(bufs.zeros(nb * 8, &d_rprev));
+  HIP_TRY(bufs.alloc(ne * nb * 4, &d_anc));
+  HIP_TRY(bufs.alloc((size_t)G, &d_flags));
+  if (a.n_events > 0) HIP_TRY(bufs.upload(a.u, ne * (size_t)G * 8, &d_u));
+  const NerfFeatures fx{sp.feat_idx[0], sp.feat_idx[1], sp.feat_idx[2], sp.feat_idx[3], sp.feat_idx[4],
+                        sp.feat_idx[5], sp.feat_idx[6], sp.feat_idx[7], sp.feat_idx[8]};
+  SteerWeights wt{};
+  for (int k = 0; k < 4; ++k) wt.w[k] = sp.weights[k];
+  SteerOffset off{};
+  off.has_offset = sp.has_offset ? 1 : 0;
+  for (int f = 0; sp.has_offset && f < F; ++f) off.offset[f] = sp.offset[f];
+
+  if (int rc = begin_run(m, d_x, d_lens, B, L, a.visits[0], K, a.seed, a.seq_offset, d_out, 0, nullptr)) return rc;
+  hipStream_t s = m->stream;
+  Workspace& w = m->ws;
+  sd.apply(&m->dyn_host);
+  sv.apply(&m->dyn_host);
+  auto rewards_of = [&](const float* state) -> int {  // shift + rewards of a [B][L][F] state in model space
+    launch_steer_shift(state, w.lens, B, L, F, off, m->angle_mask, d_ang, s);
+    launch_steer_rewards(d_ang, w.lens, B, L, F, fx, wt, sp.clash_alpha, max_len, wk, d_terms, d_reward, s);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? fail(FD_E_HIP, "launch_steer_rewards: %s", hipGetErrorString(e)) : FD_OK;
+  };
+  int rc = FD_OK;
+  for (int i = 0, e = 0; !rc && i < K;) {  // a segment ends with a visit that has an event, or with the last visit
+    int j = i + 1;
+    while (j < K && !a.event[j - 1]) ++j;
+    rc = fd_sample_steps_dev(m, j - i, d_noise, 0, nullptr);  // (noise rows are per visit, whatever the segment)
+    if (!rc && a.event[j - 1]) {
+      rc = rewards_of(sv.x0);
+      if (!rc) {
+        int* anc = d_anc + (size_t)e * nb;
+        launch_steer_resample(d_reward, d_logw, d_rprev, G, a.P, sp.lambda, sp.ess_frac, d_u + (size_t)e * G, anc, d_flags, s);
+        launch_steer_gather(w.x, anc, d_tmp, B, (long long)L * F, s);
+        const hipError_t he = hipGetLastError();
+        if (he != hipSuccess) rc = fail(FD_E_HIP, "launch_steer_resample: %s", hipGetErrorString(he));
+      }
+      if (!rc) {
+        const hipError_t he = hipMemcpyAsync(w.x, d_tmp, n * 4, hipMemcpyDeviceToDevice, s);
+        if (he != hipSuccess) rc = fail(FD_E_HIP, "hipMemcpyAsync: %s", hipGetErrorString(he));
+      }
+      ++e;
+    }
+    i = j;
+  }
+  if (!rc) rc = rewards_of(w.x);  // the final state's
+  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
+  m->run_open = false;
+  m->run_t = -1;
+  StridedDev::clear(&m->dyn_host);
+  SteerDev::clear(&m->dyn_host);
+  send_dyn(m, s, m->dyn_host);
+  HIP_TRY(hipStreamSynchronize(s));
+  if (rc) return rc;
+  if (int rc_flag = check_flag(m)) return rc_flag;
+  HIP_TRY(hipMemcpy(a.out, d_out, n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(a.terms_out, d_terms, nb * 4 * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(a.reward_out, d_reward, nb * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(a.logw_out, d_logw, nb * 8, hipMemcpyDeviceToHost));
+  if (a.ancestors_out && a.n_events > 0) HIP_TRY(hipMemcpy(a.ancestors_out, d_anc, ne * nb * 4, hipMemcpyDeviceToHost));
+  return FD_OK;
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -1123,6 +1264,71 @@ int fd_p_sample_step_solver(fd_model* m, const float* x, int t, const int32_t* l
   mode.x0_out = d_x0;
   if (int rc = run_step(m, cl.s, mode)) return rc;
   return finish(m, cl.s, {{x_out, w.x, cl.n * 4}, {eps_out, w.eps, cl.n * 4}, {x0_out, d_x0, cl.n * 4}});
+}
+
+int fd_p_sample_step_coef_x0(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
+                             float u, float v, const float* z, int wrap, float* eps_out, float* x0_out, float* x_out) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out || !x0_out) return fail(FD_E_INVALID, "null argument");
+  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(s) || !std::isfinite(u) || !std::isfinite(v))
+    return fail(FD_E_INVALID, "a = %g, b = %g, s = %g, u = %g, v = %g: a coefficient is not finite", (double)a, (double)b, (double)s,
+                (double)u, (double)v);
+  if (s != 0.f && !z) return fail(FD_E_INVALID, "z is required for s != 0");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t n = (size_t)B * L * m->cfg.n_features;
+  DeviceBufs bufs;
+  float* d_x0;
+  HIP_TRY(bufs.alloc(n * 4, &d_x0));  // (before anything of this frame is queued)
+  Call c;
+  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
+  Workspace& w = *c.ws;
+  HIP_TRY(hipMemsetAsync(d_x0, 0, n * 4, c.s));  // (a position the kernel does not take as a row is not written)
+  if (s != 0.f) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
+  if (int rc = prepare_rows(m, c.s, 0)) return rc;
+  if (int rc = set_t(m, c.s, t)) return rc;
+  StepMode mode{};
+  mode.noise = w.z;
+  mode.t_start = t;
+  mode.no_wrap = !wrap;
+  mode.strided = true;
+  mode.sa = a; mode.sb = b; mode.ss = s;
+  mode.su = u; mode.sv = v;
+  mode.x0_out = d_x0;
+  mode.x0_only = true;
+  if (int rc = run_step(m, c.s, mode)) return rc;
+  return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}, {x0_out, d_x0, c.n * 4}});
+}
+
+int fd_sample_steered(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                      const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, const uint8_t* event,
+                      int n_particles, const fd_steer_params* params, const double* u, float* out, double* terms_out,
+                      double* reward_out, double* logw_out, int32_t* ancestors_out) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;  // (rows a | b | s too)
+  for (int r = 3; r < 5; ++r)
+    for (int i = 0; i < n_visits; ++i)
+      if (!std::isfinite(coef[(size_t)r * n_visits + i]))
+        return fail(FD_E_INVALID, "coef[%d][%d] = %g is not finite", r, i, (double)coef[(size_t)r * n_visits + i]);
+  if (!event || !u || !params) return fail(FD_E_INVALID, "null argument: event, u and params are required");
+  if (!terms_out || !reward_out || !logw_out) return fail(FD_E_INVALID, "null argument: terms_out, reward_out and logw_out are required");
+  if (n_particles < 1 || n_particles > kSteerMaxParticles)
+    return fail(FD_E_INVALID, "n_particles = %d outside [1, %d]", n_particles, kSteerMaxParticles);
+  if (B % n_particles != 0) return fail(FD_E_INVALID, "B = %d is not a multiple of n_particles = %d", B, n_particles);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  for (int b = 0; b < B; ++b)
+    if (lens[b] != lens[b - b % n_particles])
+      return fail(FD_E_INVALID, "lens[%d] = %d, the first particle of its group has %d: a group shares one length", b, lens[b],
+                  lens[b - b % n_particles]);
+  if (!std::isfinite(params->lambda)) return fail(FD_E_INVALID, "lambda = %g must be finite", params->lambda);
+  if (!(params->ess_frac >= 0.0)) return fail(FD_E_INVALID, "ess_frac = %g must be >= 0", params->ess_frac);
+  if (int rc = check_steer(lens, B, L, m->cfg.n_features, params->feat_idx, params->weights, params->clash_alpha,
+                           params->has_offset ? params->offset : nullptr))
+    return rc;
+  int n_events = 0;
+  for (int i = 0; i < n_visits; ++i) n_events += event[i] ? 1 : 0;
+  if (int rc = check_steer_u(u, (size_t)n_events * (size_t)(B / n_particles))) return rc;
+  return steered_host_run(m, SteeredHostRun{x_init, lens, B, L, visits, n_visits, coef, noise, seed, seq_offset, event, n_events,
+                                            n_particles, params, u, out, terms_out, reward_out, logw_out, ancestors_out});
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

@@ -1,5 +1,5 @@
 // C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
-// the loss arithmetic on its own (loss.hip, loss_variants.hip) and of the angle histograms (angle_stats.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) and of the steering kernels on their own (steer.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
 #include <cstring>
@@ -281,6 +281,67 @@ int fd_lddt(int device_id, const float* model, const float* ref, const int32_t* 
                             int* res_dev = d.out(1);
                             launch_lddt(d.in(0), d.in(1), d.in(2), d.in(3), n_pairs, A, radius, thr, d.out(0),
                                         res_counts_out ? res_dev : nullptr, nullptr);
+                          });
+}
+
+int fd_steer_rewards(int device_id, const float* x, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                     const float* offset, const uint8_t* is_angle, const double* weights, double clash_alpha,
+                     double* terms_out, double* reward_out) {
+  if (!x || !lens || !feat_idx || !weights || !terms_out || !reward_out) return fail(FD_E_INVALID, "null argument");
+  if (offset && !is_angle) return fail(FD_E_INVALID, "null argument: an offset needs is_angle");
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if (int rc = check_steer(lens, B, L, F, feat_idx, weights, clash_alpha, offset)) return rc;
+  for (int b = 0; b < B; ++b)
+    for (size_t i = (size_t)b * L * F; i < ((size_t)b * L + lens[b]) * F; ++i)
+      if (!std::isfinite(x[i])) return fail(FD_E_INVALID, "x is not finite at sequence %d, position %d", b, (int)(i / F - (size_t)b * L));
+  const NerfFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5], feat_idx[6], feat_idx[7], feat_idx[8]};
+  SteerOffset off{};
+  SteerWeights wt{};
+  unsigned angle_mask = 0;
+  int max_len = 0;
+  std::vector<int32_t> offsets((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    offsets[b] = b * L;
+    max_len = std::max(max_len, (int)lens[b]);
+  }
+  for (int k = 0; k < 4; ++k) wt.w[k] = weights[k];
+  off.has_offset = offset ? 1 : 0;
+  for (int f = 0; offset && f < F; ++f) {
+    off.offset[f] = offset[f];
+    if (is_angle[f]) angle_mask |= 1u << f;
+  }
+  const size_t n = (size_t)B * L * F, nr = (size_t)B * L, nb = (size_t)B;
+  return device_roundtrip(device_id, {{x, n * 4}, {lens, nb * 4}, {offsets.data(), nb * 4}},
+                          {{nullptr, n * 4}, {nullptr, nr * 9 * 8}, {nullptr, nr * 9 * 4}, {nullptr, nr * 3 * 8}, {nullptr, nr},
+                           {nullptr, nb * 2 * 4}, {nullptr, nb * 4}, {terms_out, nb * 4 * 8}, {reward_out, nb * 8}},
+                          [&](const RoundtripBufs& d) {
+                            float* ang = d.out(0);
+                            const SteerWork wk{d.out(1), d.out(2), d.out(3), d.out(4), d.out(5), d.out(6), d.in(2)};
+                            launch_steer_shift(d.in(0), d.in(1), B, L, F, off, angle_mask, ang, nullptr);
+                            launch_steer_rewards(ang, d.in(1), B, L, F, fx, wt, clash_alpha, max_len, wk, d.out(7), d.out(8), nullptr);
+                          });
+}
+
+int fd_steer_resample(int device_id, const double* reward, double* logw, double* r_prev, int G, int P, double lambda,
+                      double ess_frac, const double* u, int32_t* ancestors_out, uint8_t* resampled_out) {
+  if (!reward || !logw || !r_prev || !u || !ancestors_out || !resampled_out) return fail(FD_E_INVALID, "null argument");
+  if (G < 1) return fail(FD_E_INVALID, "G=%d must be >= 1", G);
+  if (P < 1 || P > kSteerMaxParticles) return fail(FD_E_INVALID, "P=%d outside [1, %d]", P, kSteerMaxParticles);
+  if ((long long)G * P > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "G * P = %lld particles, at most 2^31 - 1", (long long)G * P);
+  if (!std::isfinite(lambda)) return fail(FD_E_INVALID, "lambda=%g must be finite", lambda);
+  if (!(ess_frac >= 0.0)) return fail(FD_E_INVALID, "ess_frac=%g must be >= 0", ess_frac);
+  if (int rc = check_steer_u(u, (size_t)G)) return rc;
+  const size_t nb = (size_t)G * P;
+  return device_roundtrip(device_id, {{reward, nb * 8}, {logw, nb * 8}, {r_prev, nb * 8}, {u, (size_t)G * 8}},
+                          {{logw, nb * 8}, {r_prev, nb * 8}, {ancestors_out, nb * 4}, {resampled_out, (size_t)G}},
+                          [&](const RoundtripBufs& d) -> hipError_t {
+                            double *logw_dev = d.out(0), *r_prev_dev = d.out(1);
+                            const double *logw_in = d.in(1), *r_prev_in = d.in(2);
+                            if (hipError_t e = hipMemcpyAsync(logw_dev, logw_in, nb * 8, hipMemcpyDeviceToDevice, nullptr)) return e;
+                            if (hipError_t e = hipMemcpyAsync(r_prev_dev, r_prev_in, nb * 8, hipMemcpyDeviceToDevice, nullptr)) return e;
+                            launch_steer_resample(d.in(0), logw_dev, r_prev_dev, G, P, lambda, ess_frac, d.in(3), d.out(2), d.out(3),
+                                                  nullptr);
+                            return hipSuccess;
                           });
 }
 

@@ -73,6 +73,10 @@ struct UpdateDyn {
   // second-order multistep solver (solver_update.h): both null unless fd_sample_solver is running (a strided run with s = 0)
   const float* cuv;            // [3, T] rows c | u | v of the visit, indexed by t like `abs`
   float* x0_prev;              // [M, F] the previous visit's prediction of the clean state, indexed like x (packed rows too)
+  // steered sampling (fd_sample_steered): both null otherwise.  A strided visit that is not the solver's then also writes its
+  // prediction of the clean state, solver_update.h's x0 = u x + v eps (wrapped where angular); x' is unchanged
+  const float* uv;             // [2, T] rows u | v of the visit, indexed by t like `abs`
+  float* x0_steer;             // [M, F] the visit's prediction, indexed like x (packed rows too); never set together with cuv
 };
 struct UpdateArgs {
   const UpdateDyn* dyn;  // device pointer; when non-null it overrides noise/hist/seed/seq_offset/t_start
@@ -108,11 +112,13 @@ struct UpdateArgs {
   float sa, sb, ss;
   // ... and the level its fixed elements land on (fd_p_sample_step_coef_inpaint; known_noise = the one slab of that level)
   int level_out;
-  // one solver update by value, without `dyn` (fd_p_sample_step_solver; x0_out non-null selects it, with `strided` set and
+  // one solver update by value, without `dyn` (fd_p_sample_step_solver; x0_out non-null selects it, with `strided` == 1 and
   // ss = 0): solver_update.h with (sa, sb, sc, su, sv); x0_prev [M, F] is read only where sc != 0, x0_out [M, F] receives x0
   float sc, su, sv;
   const float* x0_prev;
   float* x0_out;
+  // ... and one strided update by value that also writes the visit's prediction of the clean state (fd_p_sample_step_coef_x0):
+  // strided == 2 selects it; (sa, sb, ss) as for strided == 1, x0_out [M, F] = su x + sv eps, wrapped where angular
 };
 void launch_head_update(const UpdateArgs& a, hipStream_t s);
 // The replacement of the start point of a motif-conditioned run (inpaint_replace.h): x[o] = the level-`level` value of
@@ -187,6 +193,40 @@ void launch_backbone_clashes(const float* xyz, const int* offsets, const int* le
                              int* counts_out, unsigned char* flags_out, hipStream_t s);
 void launch_lddt(const float* model, const float* ref, const int* offsets, const int* lens, int n_pairs, int atoms_per_res,
                  double radius, const LddtThresholds& thr, long long* counts_out, int* res_counts_out, hipStream_t s);
+
+// ---- steering by particle resampling (steer.hip; the statements are in its header and in include/fdmi.h)
+struct SteerOffset {
+  int has_offset;              // 0: the values are taken as they are (neither shift nor wrap)
+  float offset[kMaxFeat];
+};
+// ang[b][l][f] = x0 + offset[f], rounded once, wrapped where bit f of angle_mask is set (launch_shift_trim's statement without
+// the trim); positions l >= lens[b] get 0
+void launch_steer_shift(const float* x0, const int* lens, int B, int L, int F, const SteerOffset& off, unsigned angle_mask,
+                        float* ang, hipStream_t s);
+// the device buffers of one rewards pass over B particles of padded length L; the caller owns them
+struct SteerWork {
+  double* coords;              // [B][3L][3] launch_nerf's output
+  float* xyz;                  // [B][L][3][3] the same rounded to float32 (launch_backbone_clashes' input)
+  double* ca;                  // [B][L][3] the CA atoms (launch_psea's input)
+  signed char* sse;            // [B][L] launch_psea's labels
+  int* sse_runs;               // [B][2] launch_psea's run counts (not used further)
+  int* clashes;                // [B] launch_backbone_clashes' counts
+  const int* offsets;          // [B] = b * L: particle b's first residue in xyz / ca / sse
+};
+struct SteerWeights {
+  double w[4];                 // clashes | radius of gyration | helix fraction | strand fraction
+};
+// terms [B][4] and reward [B] of the backbones of ang [B][L][F] (model features already shifted): launch_nerf (center = 0),
+// launch_backbone_clashes and launch_psea as they are, then one wave per particle.  max_len = the longest particle (<= 2048)
+void launch_steer_rewards(const float* ang, const int* lens, int B, int L, int F, const NerfFeatures& fx, const SteerWeights& wt,
+                          double alpha, int max_len, const SteerWork& wk, double* terms, double* reward, hipStream_t s);
+constexpr int kSteerMaxParticles = 1024;
+// one workgroup per group of P consecutive particles: the reweighting and the systematic resampling of include/fdmi.h;
+// ancestors [G * P] hold global indices, resampled [G] 0 / 1
+void launch_steer_resample(const double* reward, double* logw, double* r_prev, int G, int P, double lambda, double ess_frac,
+                           const double* u, int* ancestors, unsigned char* resampled, hipStream_t s);
+// x_new[b] = x[ancestors[b]], whole [row] blocks (row = L * F floats); x_new must not alias x
+void launch_steer_gather(const float* x, const int* ancestors, float* x_new, int B, long long row, hipStream_t s);
 
 // *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);

@@ -200,4 +200,28 @@ inline int check_pairwise(const float* keep, const float* coef, const int32_t* f
   return FD_OK;
 }
 
+// what fd_steer_rewards and fd_sample_steered ask of a rewards pass: lengths the P-SEA kernel takes, a feature count the
+// shift kernel takes, fd_nerf's columns, finite weights and offsets, a positive clash factor
+inline int check_steer(const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, const double* weights, double clash_alpha,
+                       const float* offset) {
+  if (F < 3 || F > 16) return fail(FD_E_INVALID, "F=%d outside [3, 16]", F);
+  if ((long long)B * L * F > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * F = %lld elements, at most 2^31 - 1", (long long)B * L * F);
+  if (int rc = check_lens(lens, B, L < FDMI_SSE_MAX_LEN ? L : FDMI_SSE_MAX_LEN)) return rc;
+  for (int i = 0; i < 9; ++i)
+    if (feat_idx[i] >= F || (i < 3 && feat_idx[i] < 0)) return fail(FD_E_INVALID, "feat_idx[%d]=%d (F=%d)", i, feat_idx[i], F);
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(weights[k])) return fail(FD_E_INVALID, "weights[%d]=%g must be finite", k, weights[k]);
+  if (!(clash_alpha > 0.0) || !std::isfinite(clash_alpha)) return fail(FD_E_INVALID, "clash_alpha=%g must be > 0 and finite", clash_alpha);
+  for (int f = 0; offset && f < F; ++f)
+    if (!std::isfinite(offset[f])) return fail(FD_E_INVALID, "offset[%d]=%g must be finite", f, (double)offset[f]);
+  return FD_OK;
+}
+
+// the uniforms of systematic resampling: each in [0, 1)
+inline int check_steer_u(const double* u, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!(u[i] >= 0.0 && u[i] < 1.0)) return fail(FD_E_INVALID, "u[%zu]=%g outside [0, 1)", i, u[i]);
+  return FD_OK;
+}
+
 }  // namespace fdmi

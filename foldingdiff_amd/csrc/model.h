@@ -198,6 +198,9 @@ struct StepMode {
   float sc = 0.f, su = 0.f, sv = 0.f;
   const float* x0_prev = nullptr;
   float* x0_out = nullptr;
+  // fd_p_sample_step_coef_x0: the strided update (sa, sb, ss) of fd_p_sample_step_coef, which also writes the visit's prediction
+  // of the clean state su x + sv eps, wrapped where angular, to x0_out (not the solver's update)
+  bool x0_only = false;
   const int* t_seq = nullptr;            // fd_forward_t / fd_denoise_loss: [B] one timestep per sequence (device), forward only; null: *t_dev
   bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
 };

@@ -434,7 +434,7 @@ __global__ __launch_bounds__(256) void head_update_kernel(UpdateArgs a) {
   float sa = a.sa, sb = a.sb, ss = a.ss;
   int ord = 0, t_next = -1;
   // ... of the second-order solver (fd_sample_solver: `dyn`'s cuv and x0_prev; fd_p_sample_step_solver: by value)
-  bool solver = a.x0_out != nullptr;
+  bool solver = a.x0_out != nullptr && a.strided != 2;  // (strided == 2: a steered visit, which only writes x0 to x0_out)
   float sc = a.sc, su = a.su, sv = a.sv;
   const float* x0_prev = a.x0_prev;
   float* x0_out = a.x0_out;
@@ -448,6 +448,9 @@ __global__ __launch_bounds__(256) void head_update_kernel(UpdateArgs a) {
       solver = true;
       sc = a.dyn->cuv[t]; su = a.dyn->cuv[a.T + t]; sv = a.dyn->cuv[2 * a.T + t];
       x0_prev = x0_out = a.dyn->x0_prev;
+    } else if (a.dyn->uv) {  // a steered run (fd_sample_steered): the visit also writes its x0
+      su = a.dyn->uv[t]; sv = a.dyn->uv[a.T + t];
+      x0_out = a.dyn->x0_steer;
     }
   }
   const float c1 = a.coef[t], bt = a.coef[a.T + t], c3 = a.coef[2 * a.T + t], sg = a.coef[3 * a.T + t];
@@ -458,6 +461,11 @@ __global__ __launch_bounds__(256) void head_update_kernel(UpdateArgs a) {
                        (a.angle_mask >> lane) & 1u);
   } else if (strided && !solver) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
     xn = strided_mean(sa, a.x[o], sb, mine);
+    if (x0_out) {  // a steered visit: solver_update.h's x0 statement; x' does not depend on it
+      float p0 = strided_mean(su, a.x[o], sv, mine);
+      if ((a.angle_mask >> lane) & 1u) p0 = wrap_pi(p0);
+      x0_out[o] = p0;
+    }
     if (ss != 0.f) {
       const float z = noise ? noise[(size_t)ord * a.noise_stride + o]
                             : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, lane);
@@ -517,7 +525,7 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
   float sa = a.sa, sb = a.sb, ss = a.ss;
   int ord = 0, t_next = -1;
   // ... of the second-order solver (fd_sample_solver: `dyn`'s cuv and x0_prev; fd_p_sample_step_solver: by value)
-  bool solver = a.x0_out != nullptr;
+  bool solver = a.x0_out != nullptr && a.strided != 2;  // (strided == 2: a steered visit, which only writes x0 to x0_out)
   float sc = a.sc, su = a.su, sv = a.sv;
   const float* x0_prev = a.x0_prev;
   float* x0_out = a.x0_out;
@@ -531,6 +539,9 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
       solver = true;
       sc = a.dyn->cuv[t]; su = a.dyn->cuv[a.T + t]; sv = a.dyn->cuv[2 * a.T + t];
       x0_prev = x0_out = a.dyn->x0_prev;
+    } else if (a.dyn->uv) {  // a steered run (fd_sample_steered): the visit also writes its x0
+      su = a.dyn->uv[t]; sv = a.dyn->uv[a.T + t];
+      x0_out = a.dyn->x0_steer;
     }
   }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
@@ -566,6 +577,11 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
                              tok % a.L, k, (a.angle_mask >> k) & 1u);
         } else if (strided && !solver) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
           xn = strided_mean(sa, a.x[o], sb, mine);
+          if (x0_out) {  // a steered visit: solver_update.h's x0 statement; x' does not depend on it
+            float p0 = strided_mean(su, a.x[o], sv, mine);
+            if ((a.angle_mask >> k) & 1u) p0 = wrap_pi(p0);
+            x0_out[o] = p0;
+          }
           if (ss != 0.f) {
             const float z = noise ? noise[(size_t)ord * a.noise_stride + o]
                                   : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, k);

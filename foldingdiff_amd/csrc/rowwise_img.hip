@@ -517,7 +517,7 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
   float sa = a.sa, sb = a.sb, ss = a.ss;
   int ord = 0, t_next = -1;
   // ... of the second-order solver (fd_sample_solver: `dyn`'s cuv and x0_prev; fd_p_sample_step_solver: by value)
-  bool solver = a.x0_out != nullptr;
+  bool solver = a.x0_out != nullptr && a.strided != 2;  // (strided == 2: a steered visit, which only writes x0 to x0_out)
   float sc = a.sc, su = a.su, sv = a.sv;
   const float* x0_prev = a.x0_prev;
   float* x0_out = a.x0_out;
@@ -531,6 +531,9 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
       solver = true;
       sc = a.dyn->cuv[t]; su = a.dyn->cuv[a.T + t]; sv = a.dyn->cuv[2 * a.T + t];
       x0_prev = x0_out = a.dyn->x0_prev;
+    } else if (a.dyn->uv) {  // a steered run (fd_sample_steered): the visit also writes its x0
+      su = a.dyn->uv[t]; sv = a.dyn->uv[a.T + t];
+      x0_out = a.dyn->x0_steer;
     }
   }
   float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
@@ -590,6 +593,11 @@ __global__ __launch_bounds__(256) void head_update_img_kernel(UpdateArgs a, Head
                              (a.angle_mask >> k) & 1u);
         } else if (strided && !solver) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
           xn = strided_mean(sa, a.x[o], sb, mine);
+          if (x0_out) {  // a steered visit: solver_update.h's x0 statement; x' does not depend on it
+            float p0 = strided_mean(su, a.x[o], sv, mine);
+            if ((a.angle_mask >> k) & 1u) p0 = wrap_pi(p0);
+            x0_out[o] = p0;
+          }
           if (ss != 0.f) {
             const float z = noise ? noise[(size_t)ord * a.noise_stride + o] : philox_normal(seed, t, seq_offset + ri.x, ri.y, k);
             xn = strided_add_noise(xn, ss, z);

@@ -25,6 +25,18 @@ _SLOT = {"phi": 0, "psi": 1, "omega": 2, "tau": 3, "N:CA:C": 3, "CA:C:1N": 4, "C
          "0C:1N": 6, "N:CA": 7, "CA:C": 8}
 
 
+def feature_columns(feature_names: Sequence[str]) -> np.ndarray:
+    """int32 [9]: ``fd_nerf``'s ``feat_idx`` for these column names, -1 for a bond angle or length that is not a feature."""
+    for req in ("phi", "psi", "omega"):
+        assert req in feature_names, f"NeRF needs the dihedral {req!r}"
+    idx = np.full(9, -1, dtype=np.int32)
+    for col, name in enumerate(feature_names):
+        if name not in _SLOT:
+            raise ValueError(f"Unrecognized feature: {name}")
+        idx[_SLOT[name]] = col
+    return idx
+
+
 def build_backbones(
     angles: Union[np.ndarray, Sequence[np.ndarray]],
     feature_names: Sequence[str],
@@ -40,13 +52,7 @@ def build_backbones(
     chains = [np.asarray(a, dtype=np.float32) for a in (angles if not isinstance(angles, np.ndarray) or angles.ndim != 3 else list(angles))]
     F = len(feature_names)
     assert all(c.ndim == 2 and c.shape[1] == F for c in chains), "each chain must be [len, F]"
-    for req in ("phi", "psi", "omega"):
-        assert req in feature_names, f"NeRF needs the dihedral {req!r}"
-    idx = np.full(9, -1, dtype=np.int32)
-    for col, name in enumerate(feature_names):
-        if name not in _SLOT:
-            raise ValueError(f"Unrecognized feature: {name}")
-        idx[_SLOT[name]] = col
+    idx = feature_columns(feature_names)
     B, L = len(chains), max(len(c) for c in chains)
     feats = np.zeros((B, L, F), dtype=np.float32)
     lens = np.zeros(B, dtype=np.int32)

@@ -1304,6 +1304,180 @@ def scaffold(model, dset, motif: np.ndarray, total_lengths: Sequence[int], offse
     return inpaint(model, dset, known, fixed, feature_key=feature_key, **kwargs), offs
 
 
+# --------------------------------------------------------------------------------- steering by particle resampling
+REWARD_TERMS = ("clashes", "rg", "helix", "strand")
+DEFAULT_REWARD = {"clashes": -1.0, "rg": 0.0, "helix": 0.0, "strand": 0.0}
+
+
+def reward_weights(reward) -> np.ndarray:
+    """float64 [4]: the weights of ``REWARD_TERMS`` from a dict (missing terms weigh 0; an unknown or non-finite one raises)."""
+    reward = DEFAULT_REWARD if reward is None else reward
+    unknown = sorted(set(reward) - set(REWARD_TERMS))
+    if unknown:
+        raise ValueError(f"reward terms {unknown}: expected some of {REWARD_TERMS}")
+    w = np.array([float(reward.get(k, 0.0)) for k in REWARD_TERMS], dtype=np.float64)
+    if not np.isfinite(w).all():
+        raise ValueError(f"reward weights must be finite, got {dict(reward)}")
+    return w
+
+
+def steer_events(visits, steer_from: int, every: int = 1) -> np.ndarray:
+    """uint8 [K]: the visits of a steered run that are followed by an event (``fd_sample_steered``'s ``event``).  Among the
+    visits with ``t < steer_from``, counted from the first, every ``every``-th is one; if there is any such visit the last
+    visit of the run is one too, so that the final states have been resampled on their own rewards."""
+    visits = np.asarray(visits, dtype=np.int64).reshape(-1)
+    if int(every) < 1:
+        raise ValueError(f"every={every} must be at least 1")
+    event = np.zeros(len(visits), dtype=np.uint8)
+    late = np.nonzero(visits < int(steer_from))[0]
+    if len(late):
+        event[late[int(every) - 1:: int(every)]] = 1
+        event[len(visits) - 1] = 1
+    return event
+
+
+def steer_coefficients(betas, visits, eta: float = 1.0) -> np.ndarray:
+    """float32 [5, K], rows a | b | s | u | v (``fd_sample_steered``'s ``coef``): rows 0-2 are the bits of
+    ``ddim_coefficients(betas, visits, eta)``, rows 3-4 those of ``solver_coefficients``' u and v, which give a visit's
+    prediction of the clean state ``x0 = u x + v eps``."""
+    abs_ = ddim_coefficients(betas, visits, eta)
+    uv = solver_coefficients(betas, visits, order=1)[3:5]
+    return np.ascontiguousarray(np.concatenate([abs_, uv]), dtype=np.float32)
+
+
+def steer_params(weights, lam: float, ess_frac: float, clash_alpha: float, feature_names: Sequence[str],
+                 offset: Optional[np.ndarray]) -> "_binding.FdSteerParams":
+    """``fd_steer_params`` from Python values; the feature columns are named as for ``nerf.build_backbones``."""
+    from . import nerf
+    p = _binding.FdSteerParams()
+    p.weights[:] = [float(w) for w in weights]
+    p.lam, p.ess_frac, p.clash_alpha = float(lam), float(ess_frac), float(clash_alpha)
+    p.feat_idx[:] = [int(i) for i in nerf.feature_columns(feature_names)]
+    p.has_offset = 0 if offset is None else 1
+    if offset is not None:
+        off = np.asarray(offset, dtype=np.float32).reshape(-1)
+        if len(off) != len(feature_names) or len(off) > 16:
+            raise ValueError(f"offset has {len(off)} entries for {len(feature_names)} features (at most 16)")
+        p.offset[: len(off)] = off.tolist()
+    return p
+
+
+def _run_fd_sample_steered(h, x0: np.ndarray, lens: np.ndarray, visits: np.ndarray, coef: np.ndarray, zs: Optional[np.ndarray],
+                           seed: int, seq_offset: int, event: np.ndarray, n_particles: int, params, u: np.ndarray, out: np.ndarray,
+                           terms: np.ndarray, reward: np.ndarray, logw: np.ndarray, ancestors: Optional[np.ndarray]) -> None:
+    """The one call into libfdmi.so that runs a steered schedule on a host batch (fd_sample_steered)."""
+    B, L, _ = x0.shape
+    _binding.check(_binding.load().fd_sample_steered(
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, _binding.ptr(visits), len(visits), _binding.ptr(coef), _binding.ptr(zs),
+        C.c_uint64(seed), C.c_int64(seq_offset), _binding.ptr(event), int(n_particles), C.byref(params), _binding.ptr(u),
+        _binding.ptr(out), _binding.ptr(terms), _binding.ptr(reward), _binding.ptr(logw), _binding.ptr(ancestors)))
+
+
+@torch.no_grad()
+def steer(model, dset, lengths: Sequence[int], n_particles: int = 8, reward=None, lam: float = 1.0, ess_frac: float = 0.5,
+          steer_from: Optional[int] = None, every: int = 1, num_steps: Optional[int] = None, eta: float = 1.0,
+          spacing: str = "uniform", select: str = "best", seed: Optional[int] = None, batch_size: int = 512,
+          feature_key: str = "angles", clash_alpha: float = 0.63):
+    """Sample one backbone per entry of ``lengths`` from the model's distribution tilted toward a reward, without gradients
+    (``fd_sample_steered``): ``n_particles`` particles per backbone run the noisy strided sampler together, and
+    after the visits ``steer_events`` marks they are scored on their predicted clean structure and resampled in proportion to
+    ``exp(lam * (reward now - reward before))``.
+
+    ``reward``: weights of ``"clashes"`` (clashing backbone atoms at ``clash_alpha``), ``"rg"`` (radius of gyration of the CA
+    atoms, Angstrom), ``"helix"`` and ``"strand"`` (P-SEA fractions); the default, ``{"clashes": -1}``, asks for backbones
+    without clashes.  ``ess_frac``: an event resamples when the effective sample size falls below that share of the
+    particles (``>= 1``: always, ``0``: never).  ``steer_from`` (default ``T // 2``) and ``every`` choose the events;
+    ``num_steps`` (default: all T), ``eta`` and ``spacing`` the schedule, as in ``sample``.  ``eta = 0`` with more than one
+    particle raises ``ValueError``: nothing would be drawn, and the copies of a particle would stay identical.
+
+    The start noise and the Philox seed of the steps are drawn as in ``sample`` (``torch.manual_seed`` reproducible); the
+    uniforms of the resampling come from ``numpy.random.Generator(numpy.random.Philox(seed))``, ``seed`` drawn from torch's
+    CPU generator when None.  ``batch_size`` bounds the particles of one call.  Single device.
+
+    ``select="best"`` returns ``(samples, info)`` with one ``[len, F]`` array per requested length, the particle of the
+    highest final reward, shifted by the training mean offset and trimmed like ``sample``'s final states; ``"all"`` returns
+    every particle, group after group.  ``info``: ``terms`` float64 ``[n, 4]`` (``REWARD_TERMS``), ``reward`` and ``logw``
+    ``[n]`` of the returned samples, ``index`` (the particle each is), ``ancestors`` (per batch, int32 ``[events, B]``),
+    ``events`` and ``visits``."""
+    if select not in ("best", "all"):
+        raise ValueError(f"select={select!r}: expected 'best' or 'all'")
+    if spacing not in SPACINGS:
+        raise ValueError(f"spacing={spacing!r}: expected one of {SPACINGS}")
+    P = int(n_particles)
+    if not 1 <= P <= 1024:
+        raise ValueError(f"n_particles={n_particles} outside [1, 1024]")
+    if eta == 0 and P > 1:
+        raise ValueError("eta=0 draws nothing: the copies of a resampled particle would stay identical; use eta > 0 or one particle")
+    if not np.isfinite(lam) or not ess_frac >= 0 or not clash_alpha > 0:
+        raise ValueError(f"lam={lam} must be finite, ess_frac={ess_frac} >= 0 and clash_alpha={clash_alpha} > 0")
+    weights = reward_weights(reward)
+    lengths = [int(l) for l in lengths]
+    pad = dset.pad
+    if not lengths or min(lengths) < 1 or max(lengths) > min(pad, 2048):
+        raise ValueError(f"lengths must be non-empty and lie in [1, {min(pad, 2048)}]")
+    if int(batch_size) < P:
+        raise ValueError(f"batch_size={batch_size} is below n_particles={P}")
+    T = dset.timesteps
+    betas = dset.alpha_beta_terms["betas"]
+    steer_from = T // 2 if steer_from is None else int(steer_from)
+    visits = _few_step_visits(betas, T if num_steps is None else int(num_steps), None, spacing, -3.0)
+    coef = steer_coefficients(betas, visits, eta)
+    event = steer_events(visits, steer_from, every)
+    n_events = int(event.sum())
+    inner = getattr(dset, "dset", None)
+    offset = None
+    if inner is not None and hasattr(inner, "get_masked_means"):
+        try:
+            offset = inner.get_masked_means()
+        except NotImplementedError:
+            offset = None
+    angular = np.asarray(dset.feature_is_angular[feature_key], dtype=bool)
+    names = list(dset.feature_names[feature_key])
+    F = model.n_inputs
+    params = steer_params(weights, lam, ess_frac, clash_alpha, names, offset)
+    h = model.prepare(betas, dset.feature_is_angular[feature_key])
+    on_gpu = getattr(getattr(model, "device", None), "type", "") == "cuda"
+    rng = np.random.Generator(np.random.Philox(_draw_philox_seed() if seed is None else int(seed)))
+    groups = max(1, int(batch_size) // P)
+    samples: List[np.ndarray] = []
+    info = {"terms": [], "reward": [], "logw": [], "index": [], "ancestors": [], "events": event, "visits": visits}
+    for start in range(0, len(lengths), groups):
+        these = lengths[start: start + groups]
+        G, L = len(these), max(these)
+        B = G * P
+        per_particle = [l for l in these for _ in range(P)]
+        x0 = _as_f32(dset.sample_noise(torch.zeros((B, pad, F), dtype=torch.float32))[:, :L, :])
+        philox_seed = _draw_philox_seed()
+        u = np.ascontiguousarray(rng.random((n_events, G)), dtype=np.float64)
+        out = np.empty((B, L, F), dtype=np.float32)
+        terms, rew, logw = np.empty((B, 4), np.float64), np.empty(B, np.float64), np.empty(B, np.float64)
+        anc = np.empty((n_events, B), dtype=np.int32)
+        prev_varlen = model.set_option("varlen", 1)   # positions beyond an item's length are cut away below, as in sample()
+        try:
+            if on_gpu:
+                model.set_option("rows_hint", sum((l + 7) // 8 * 8 for l in per_particle))
+            _run_fd_sample_steered(h, x0, _lens_array(per_particle, B, L), visits, coef, None, philox_seed, 0, event, P, params, u, out,
+                                   terms, rew, logw, anc)
+        finally:
+            if on_gpu:
+                model.set_option("rows_hint", 0)
+            model.set_option("varlen", prev_varlen if prev_varlen is not None else 0)
+        if select == "best":   # (np.argmax: the first of equals)
+            keep = np.array([g * P + int(np.argmax(rew[g * P: (g + 1) * P])) for g in range(G)], dtype=np.int64)
+        else:
+            keep = np.arange(B, dtype=np.int64)
+        kept = _shift_trim(model, torch.from_numpy(np.ascontiguousarray(out[keep][None])), [per_particle[k] for k in keep], offset, angular)
+        samples.extend(s[0] for s in kept)
+        info["terms"].append(terms[keep])
+        info["reward"].append(rew[keep])
+        info["logw"].append(logw[keep])
+        info["index"].append(keep + start * P)
+        info["ancestors"].append(anc)
+    for k in ("terms", "reward", "logw", "index"):
+        info[k] = np.concatenate(info[k])
+    return samples, info
+
+
 def sample_simple(model_dir: str, n: int = 10, sweep_lengths: Tuple[int, int] = (50, 128)):
     """Load model + dummy dataset from ``model_dir`` and return one DataFrame of final
     angles per sampled backbone."""

@@ -938,6 +938,42 @@ def count_clashes(chains: Sequence[np.ndarray], alpha: float = 0.63, device: int
     return counts.astype(np.int64)
 
 
+def steer_terms(angles: Union[np.ndarray, Sequence[np.ndarray]], feature_names: Sequence[str], reward=None,
+                offset: Optional[np.ndarray] = None, is_angle: Optional[Sequence[bool]] = None, alpha: float = 0.63,
+                device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """The reward terms of steered sampling (``sampling.steer``) for a batch of backbones given as angles, in one
+    ``fd_steer_rewards`` call: float64 ``[B, 4]`` -- the clashing atoms at ``alpha`` (``count_clashes``), the radius of
+    gyration of the CA atoms in Angstrom, the helix and the strand fraction (``annotate_sse``) -- and float64 ``[B]``, their
+    sum weighted by ``reward`` (a dict over ``sampling.REWARD_TERMS``; default ``{"clashes": -1}``), left to right.
+
+    ``angles``: ``[B, L, F]`` or a list of ``[len_i, F]`` arrays, columns named by ``feature_names`` as for
+    ``nerf.build_backbones``.  With ``offset`` (float32 ``[F]``) the values are first shifted by it and the columns of
+    ``is_angle`` wrapped to [-pi, pi), as ``sampling.sample`` does with the training mean offset; without, they are taken as
+    they are."""
+    from . import nerf, sampling
+    chains = [np.asarray(a, dtype=np.float32) for a in (angles if not isinstance(angles, np.ndarray) or angles.ndim != 3 else list(angles))]
+    F = len(feature_names)
+    if not chains or any(c.ndim != 2 or c.shape[1] != F or len(c) == 0 for c in chains):
+        raise ValueError(f"each backbone must be [len >= 1, {F}]")
+    if offset is not None and is_angle is None:
+        raise ValueError("an offset needs is_angle: the columns to wrap after the shift")
+    weights = sampling.reward_weights(reward)
+    idx = nerf.feature_columns(feature_names)
+    B, L = len(chains), max(len(c) for c in chains)
+    feats = np.zeros((B, L, F), dtype=np.float32)
+    lens = np.array([len(c) for c in chains], dtype=np.int32)
+    for i, c in enumerate(chains):
+        feats[i, : len(c)] = c
+    off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float32).reshape(-1)
+    ang = None if is_angle is None else np.ascontiguousarray(np.asarray(is_angle, dtype=bool).reshape(-1).astype(np.uint8))
+    if (off is not None and len(off) != F) or (ang is not None and len(ang) != F):
+        raise ValueError(f"offset and is_angle must have {F} entries")
+    terms, rew = np.empty((B, 4), dtype=np.float64), np.empty((B,), dtype=np.float64)
+    _binding.check(_binding.load().fd_steer_rewards(device, ptr(feats), ptr(lens), B, L, F, ptr(idx), ptr(off), ptr(ang), ptr(weights),
+                                                    float(alpha), ptr(terms), ptr(rew)))
+    return terms, rew
+
+
 def count_clashes_parallel(filenames: Sequence[str], nthreads: Optional[int] = None, device: int = 0) -> dict:
     """``count_clashes_parallel`` (foldingdiff/vdw_clashes.py:71-78): {file name: clash count} with the reference's
     default ``alpha``, the files parsed on the host by ``read_backbone`` and counted in one launch.  ``nthreads`` is

@@ -53,6 +53,8 @@ extern "C" {
  *    too: no existing entry or public struct changed, and the tests of the earlier additions pin the value 7 */
 /*    fd_sample_solver, fd_sample_solver_dev and fd_p_sample_step_solver (the second-order multistep solver) are additive too */
 /*    fd_tm_align_ex (the alignment search from a chosen set of TM-align's five starts) is additive too */
+/*    fd_sample_steered, fd_p_sample_step_coef_x0, fd_steer_rewards and fd_steer_resample (steering a few-step run by particle
+ *    resampling on device rewards) and the struct fd_steer_params are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -464,6 +466,92 @@ int fd_sample_solver_dev(fd_model* m, const void* x_init_dev, const void* lens_d
  * bits of fd_forward's; x0_out (or NULL) the visit's x0.  With wrap == 0 nothing is wrapped.  Host buffers. */
 int fd_p_sample_step_solver(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float c, float u,
                             float v, const float* x0_prev, int wrap, float* eps_out, float* x0_out, float* x_out);
+
+/* ---- steering a few-step run by particle resampling on device rewards, in the manner of Feynman-Kac steering (Singhal et
+ * al. 2025) and twisted sequential Monte Carlo: no gradient, no backward pass.  The reference has no such sampler; like
+ * fd_sample_strided this is an extension.
+ *
+ * The run carries P = n_particles particles for each of G = B / P requested backbones; the particles of group g are the
+ * sequences g P .. g P + P - 1 and share one length.  Every visit is fd_sample_strided's visit (noise included: with every
+ * s == 0 the copies of a particle would stay identical) and also writes its prediction of the clean state, the x0 of
+ * fd_sample_solver's statement: x0 = u[i] * x[o] + v[i] * eps[o], product and sum rounded once, wrapped where angular.  A
+ * visit with event[i] != 0 is followed by an EVENT, four launches on the state the visit left:
+ *   shift     ang = x0 + offset[f] in float32, rounded once, wrapped where the model's feature f is an angle
+ *             (fd_shift_trim_dev's statement without the trim; has_offset == 0: ang = x0 as it is)
+ *   rewards   fd_nerf's coordinates of ang (center = 0), fp64 [B][3L][3]; per particle b of length len:
+ *               terms[b][0] = fd_backbone_clashes' count of the coordinates rounded to float32, with clash_alpha
+ *               terms[b][1] = the radius of gyration of the CA atoms in Angstrom, sqrt(sum |ca_i - mean|^2 / len), fp64
+ *               terms[b][2], terms[b][3] = the residues fd_annotate_sse labels helix (1) and strand (2), divided by len
+ *               reward[b] = w0 terms[b][0] + w1 terms[b][1] + w2 terms[b][2] + w3 terms[b][3], summed left to right, every
+ *                           product and sum rounded once
+ *   resample  per group, with every sum in index order:
+ *               logw[b] += lambda * (reward[b] - r_prev[b]);  r_prev[b] = reward[b]
+ *               mx = max logw;  w_j = exp(logw_j - mx);  W = sum w_j;  ESS = W W / sum w_j^2
+ *               resample iff ess_frac >= 1, or ESS < ess_frac * P; never if W is not finite or not > 0:
+ *                 target_k = (u[g] + k) / P * W, k = 0 .. P - 1
+ *                 anc[k] = the smallest j with (w_0 + .. + w_j) > target_k   (P - 1 if none)
+ *                 r_prev[k] <- r_prev[anc[k]];  logw[k] <- 0
+ *               else anc[k] = k
+ *   gather    x[b] <- x[g P + anc[b - g P]], the whole [L][F] block of a sequence
+ * r_prev and logw start at 0, so the product of an unresampled particle's potentials telescopes to exp(lambda * reward of its
+ * latest event).  After the last visit terms_out and reward_out are the rewards statement on the FINAL state (shifted in the
+ * same way) and logw_out is what the last event left.
+ *
+ *   visits, noise, seed, seq_offset, x_init   as in fd_sample_strided
+ *   coef           float32 [5][K], rows a | b | s | u | v, all finite (host): a | b | s are fd_sample_strided's, u | v
+ *                  fd_sample_solver's
+ *   event          uint8[K]
+ *   params         weights, lambda (finite), ess_frac (>= 0), clash_alpha (> 0), feat_idx as in fd_nerf, the offset
+ *   u              double [n_events][G], each in [0, 1): row e belongs to the e-th visit with event != 0
+ *   out            [B][L][F] the final state
+ *   terms_out [B][4], reward_out [B], logw_out [B]   doubles (host)
+ *   ancestors_out  int32 [n_events][B] global indices g P + anc, or NULL
+ * Only launches happen between the upload and the download; the steps replay the plain sampler's captured graph, which is not
+ * captured again.  Everything fd_sample_strided rejects, a NULL event / u / params / terms_out / reward_out / logw_out,
+ * n_particles outside [1, 1024], B not a multiple of n_particles, unequal lengths within a group, a length above 2048, fewer
+ * than 3 or more than 16 features, a bad feat_idx, a u outside [0, 1) or a u / v / weight / lambda / offset that is not
+ * finite, ess_frac < 0, clash_alpha <= 0: FD_E_INVALID before any device call, `out` untouched.  Options "use_graph" and
+ * "varlen" and both precisions as in fd_sample_strided; a later fd_sample* is unaffected.  Final state only; not offered with
+ * motif conditioning or with the second-order solver. */
+typedef struct fd_steer_params {
+  double weights[4];   /* clashes | radius of gyration | helix fraction | strand fraction */
+  double lambda;
+  double ess_frac;
+  double clash_alpha;
+  int32_t feat_idx[9];
+  int32_t has_offset;
+  float offset[16];    /* the first F are read, and only where has_offset != 0 */
+} fd_steer_params;
+int fd_sample_steered(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                      const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, const uint8_t* event,
+                      int n_particles, const fd_steer_params* params, const double* u, float* out, double* terms_out,
+                      double* reward_out, double* logw_out, int32_t* ancestors_out);
+
+/* The parity hook of a steered visit: fd_p_sample_step_coef plus u, v (both finite) and x0_out [B][L][F] (required), which
+ * receives the visit's prediction of the clean state.  x_out and eps_out are the bits of fd_p_sample_step_coef's. */
+int fd_p_sample_step_coef_x0(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
+                             float u, float v, const float* z, int wrap, float* eps_out, float* x0_out, float* x_out);
+
+/* The shift and rewards statements above on host arrays, model-free and synchronous like fd_nerf.
+ *   x          float32 [B][L][F] (host); finite on the rows l < lens[b]
+ *   lens       int32[B], 1 <= lens[b] <= min(L, 2048)
+ *   feat_idx   int32[9] as in fd_nerf; 3 <= F <= 16
+ *   offset     float32[F], or NULL: x is taken as it is; is_angle uint8[F] (required with an offset): the features to wrap
+ *   weights    double[4], finite; clash_alpha > 0
+ *   terms_out  double [B][4], reward_out double [B]
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs untouched. */
+int fd_steer_rewards(int device_id, const float* x, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                     const float* offset, const uint8_t* is_angle, const double* weights, double clash_alpha,
+                     double* terms_out, double* reward_out);
+
+/* The resample statement above on host arrays, model-free and synchronous: G groups of P consecutive particles.
+ *   reward         double [G P]
+ *   logw, r_prev   double [G P], in and out
+ *   lambda finite, ess_frac >= 0, 1 <= P <= 1024, u double[G] each in [0, 1)
+ *   ancestors_out  int32 [G P] global indices, resampled_out uint8 [G]
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs and logw / r_prev untouched. */
+int fd_steer_resample(int device_id, const double* reward, double* logw, double* r_prev, int G, int P, double lambda,
+                      double ess_frac, const double* u, int32_t* ancestors_out, uint8_t* resampled_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
