@@ -94,6 +94,9 @@ _SIGNATURES = {
                                            _P, C.c_int, _P, _P, _P]),
     "fd_steer_rewards": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P]),
     "fd_steer_resample": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P]),
+    "fd_sample_repeat": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.c_int64, _P, _P]),
+    "fd_tie_repeats": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, _P, C.c_uint64, C.c_int, C.c_int64,
+                                 _P]),
     "fd_sample_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_begin_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_steps_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),

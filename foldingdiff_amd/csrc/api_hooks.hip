@@ -126,6 +126,38 @@ int fd_test_wrap(int device_id, int which, const float* in, int64_t n, float* ou
   return FD_OK;
 }
 
+int fd_tie_repeats(int device_id, const float* x, const int32_t* lens, const int32_t* tie, int B, int L, int F,
+                   const uint8_t* is_angle, int init, float s, const float* z, uint64_t seed, int t, int64_t seq_offset, float* out) {
+  if (!x || !lens || !tie || !is_angle || !out) return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1 || F < 1) return fail(FD_E_INVALID, "bad argument: B=%d L=%d F=%d must be positive", B, L, F);
+  if (F > 32) return fail(FD_E_UNSUPPORTED, "F=%d: at most 32 features", F);
+  if ((long long)B * L * F > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * F = %lld elements, at most 2^31 - 1", (long long)B * L * F);
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_tie(tie, lens, B)) return rc;
+  if (!std::isfinite(s)) return fail(FD_E_INVALID, "s = %g is not finite", (double)s);
+  unsigned angle_mask = 0;
+  for (int f = 0; f < F; ++f)
+    if (is_angle[f]) angle_mask |= 1u << f;
+  const size_t n = (size_t)B * L * F;
+  const bool draws = !init && s != 0.f && z;  // (the slab is read only then)
+  std::vector<float> state_host(n);  // the rows at or beyond a length are not the kernel's: `out` keeps what it held there
+  const int rc = device_roundtrip(device_id, {{x, n * 4}, {lens, (size_t)B * 4}, {tie, (size_t)B * 3 * 4}, {draws ? z : x, draws ? n * 4 : 4}},
+                          {{state_host.data(), n * 4}}, [&](const RoundtripBufs& d) -> hipError_t {
+                            float* state = d.out(0);
+                            const float* x_dev = d.in(0);
+                            const float* z_dev = d.in(3);
+                            const hipError_t e = hipMemcpyAsync(state, x_dev, n * 4, hipMemcpyDeviceToDevice, nullptr);
+                            if (e != hipSuccess) return e;
+                            launch_repeat_tie(state, d.in(1), d.in(2), B, L, F, angle_mask, init ? 1 : 0, s, draws ? z_dev : nullptr, seed,
+                                              t, seq_offset, nullptr);
+                            return hipSuccess;
+                          });
+  if (rc) return rc;
+  for (int b = 0; b < B; ++b)
+    memcpy(out + (size_t)b * L * F, state_host.data() + (size_t)b * L * F, (size_t)lens[b] * F * 4);
+  return FD_OK;
+}
+
 int fd_test_gemm(int device_id, int precision, int epilogue, const float* A, const float* W, const float* bias,
                  const float* resid, float* C, int M, int N, int K) {
   if (!A || !W || !bias || !C || M < 1 || N < 1 || K < 16 || K % 32) return fail(FD_E_INVALID, "bad argument");

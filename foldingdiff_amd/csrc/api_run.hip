@@ -773,6 +773,55 @@ int steered_host_run(fd_model* m, const SteeredHostRun& a) {
   return FD_OK;
 }
 
+// ---- repeat sampling: a strided run whose visits leave wrap(a x + b eps) -- the tables' row s is zero -- with
+// one tie launch (repeat_tie.hip) behind every visit, which averages the copies of a unit row and adds the visit's draw, the
+// same one to every copy.  The entry has checked every argument.  Returns with the stream drained and the strided fields
+// cleared, on the host and on the device, on every path behind begin_run: the tables die with this frame.
+int repeat_host_run(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int K, const float* coef,
+                    const float* noise, uint64_t seed, int64_t seq_offset, const int32_t* tie, float* out) {
+  HIP_TRY(hipSetDevice(m->device));
+  const int F = m->cfg.n_features;
+  const size_t n = (size_t)B * L * F;
+  DeviceBufs bufs;
+  float *d_x, *d_out;
+  const float* d_noise = nullptr;
+  int* d_lens;
+  const int* d_tie;
+  HIP_TRY(bufs.upload(x_init, n * 4, &d_x));
+  HIP_TRY(bufs.upload(lens, (size_t)B * 4, &d_lens));
+  HIP_TRY(bufs.upload(tie, (size_t)B * 3 * 4, &d_tie));
+  HIP_TRY(bufs.alloc(n * 4, &d_out));
+  if (noise) HIP_TRY(bufs.upload(noise, (size_t)K * n * 4, &d_noise));
+  std::vector<float> ab0(3 * (size_t)K, 0.f);  // a | b | 0: the draw is the tie launch's
+  memcpy(ab0.data(), coef, 2 * (size_t)K * 4);
+  StridedDev sd;
+  if (int rc = stage_strided(m, &bufs, visits, K, ab0.data(), &sd)) return rc;
+  if (int rc = begin_run(m, d_x, d_lens, B, L, visits[0], K, seed, seq_offset, d_out, 0, nullptr)) return rc;
+  hipStream_t s = m->stream;
+  Workspace& w = m->ws;
+  sd.apply(&m->dyn_host);
+  auto tie_state = [&](int init, float sz, const float* z, int t) -> int {
+    launch_repeat_tie(w.x, w.lens, d_tie, B, L, F, m->angle_mask, init, sz, z, seed, t, seq_offset, s);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? fail(FD_E_HIP, "launch_repeat_tie: %s", hipGetErrorString(e)) : FD_OK;
+  };
+  int rc = tie_state(1, 0.f, nullptr, 0);  // the start point: every copy is copy 0
+  for (int i = 0; !rc && i < K; ++i) {
+    rc = fd_sample_steps_dev(m, 1, nullptr, 0, nullptr);
+    if (!rc) rc = tie_state(0, coef[2 * (size_t)K + i], d_noise ? d_noise + (size_t)i * n : nullptr, visits[i]);
+  }
+  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
+  m->run_open = false;
+  m->run_t = -1;
+  StridedDev::clear(&m->dyn_host);
+  send_dyn(m, s, m->dyn_host);
+  HIP_TRY(hipStreamSynchronize(s));
+  if (rc) return rc;
+  if (int rc_flag = check_flag(m)) return rc_flag;
+  HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
+  return FD_OK;
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -1329,6 +1378,15 @@ int fd_sample_steered(fd_model* m, const float* x_init, const int32_t* lens, int
   if (int rc = check_steer_u(u, (size_t)n_events * (size_t)(B / n_particles))) return rc;
   return steered_host_run(m, SteeredHostRun{x_init, lens, B, L, visits, n_visits, coef, noise, seed, seq_offset, event, n_events,
                                             n_particles, params, u, out, terms_out, reward_out, logw_out, ancestors_out});
+}
+
+int fd_sample_repeat(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                     const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, const int32_t* tie, float* out) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;
+  if (!tie) return fail(FD_E_INVALID, "null argument: tie is required");
+  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_tie(tie, lens, B)) return rc;
+  return repeat_host_run(m, x_init, lens, B, L, visits, n_visits, coef, noise, seed, seq_offset, tie, out);
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

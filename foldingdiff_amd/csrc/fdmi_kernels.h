@@ -228,6 +228,12 @@ void launch_steer_resample(const double* reward, double* logw, double* r_prev, i
 // x_new[b] = x[ancestors[b]], whole [row] blocks (row = L * F floats); x_new must not alias x
 void launch_steer_gather(const float* x, const int* ancestors, float* x_new, int B, long long row, hipStream_t s);
 
+// ---- tying the rows of repeat units (repeat_tie.hip; the statement is in its header and in include/fdmi.h).  In place on
+// x [B][L][F]; tie int32 [B][3] = start | period | units per sequence, checked by the host: start + period * units <= lens[b].
+// init != 0: every copy <- copy 0 and nothing else.  z: the visit's [B][L][F] draws, or null: Philox (seed, t, seq_offset)
+void launch_repeat_tie(float* x, const int* lens, const int* tie, int B, int L, int F, unsigned angle_mask, int init, float s,
+                       const float* z, unsigned long long seed, int t, long long seq_offset, hipStream_t st);
+
 // *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);
 

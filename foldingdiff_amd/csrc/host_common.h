@@ -224,4 +224,18 @@ inline int check_steer_u(const double* u, size_t n) {
   return FD_OK;
 }
 
+// the ties of fd_tie_repeats and fd_sample_repeat (check_lens has passed): tie[b] = start | period | units with start >= 0,
+// period >= 1, units >= 1 and the tied rows [start, start + period * units) below lens[b]
+inline int check_tie(const int32_t* tie, const int32_t* lens, int B) {
+  for (int b = 0; b < B; ++b) {
+    const int32_t start = tie[3 * b], period = tie[3 * b + 1], units = tie[3 * b + 2];
+    if (start < 0 || period < 1 || units < 1)
+      return fail(FD_E_INVALID, "tie[%d] = (%d, %d, %d): start >= 0, period >= 1 and units >= 1", b, start, period, units);
+    if ((long long)start + (long long)period * units > lens[b])
+      return fail(FD_E_INVALID, "tie[%d] = (%d, %d, %d) ends at row %lld, beyond lens[%d] = %d", b, start, period, units,
+                  (long long)start + (long long)period * units, b, lens[b]);
+  }
+  return FD_OK;
+}
+
 }  // namespace fdmi

@@ -1478,6 +1478,99 @@ def steer(model, dset, lengths: Sequence[int], n_particles: int = 8, reward=None
     return samples, info
 
 
+def _per_length(value, n: int, what: str) -> List[int]:
+    """A scalar for every length, or one value per length."""
+    if np.ndim(value) == 0:
+        return [int(value)] * n
+    vals = [int(v) for v in value]
+    if len(vals) != n:
+        raise ValueError(f"{what} has {len(vals)} entries for {n} lengths")
+    return vals
+
+
+def repeat_ties(lengths: Sequence[int], period, units, start=0) -> np.ndarray:
+    """int32 ``[n, 3]`` rows ``start | period | units`` of ``fd_sample_repeat``, one per length; ``ValueError`` for a sequence
+    of another length than ``lengths`` or a tie that does not fit: ``start >= 0``, ``period >= 1``, ``units >= 1`` and
+    ``start + period * units <= length``."""
+    lengths = [int(l) for l in lengths]
+    n = len(lengths)
+    cols = [_per_length(v, n, what) for v, what in ((start, "start"), (period, "period"), (units, "units"))]
+    ties = np.ascontiguousarray(np.array(cols, dtype=np.int64).T.reshape(n, 3))
+    for l, (s, p, r) in zip(lengths, ties.tolist()):
+        if s < 0 or p < 1 or r < 1 or s + p * r > l:
+            raise ValueError(f"tie (start={s}, period={p}, units={r}) does not fit a length of {l}")
+    return ties.astype(np.int32)
+
+
+def _run_fd_sample_repeat(h, x0: np.ndarray, lens: np.ndarray, visits: np.ndarray, coef: np.ndarray, zs: Optional[np.ndarray],
+                          seed: int, seq_offset: int, tie: np.ndarray, out: np.ndarray) -> None:
+    """The one call into libfdmi.so that runs a repeat schedule on a host batch (fd_sample_repeat)."""
+    B, L, _ = x0.shape
+    _binding.check(_binding.load().fd_sample_repeat(
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, _binding.ptr(visits), len(visits), _binding.ptr(coef), _binding.ptr(zs),
+        C.c_uint64(seed), C.c_int64(seq_offset), _binding.ptr(tie), _binding.ptr(out)))
+
+
+@torch.no_grad()
+def sample_repeats(model, dset, lengths: Sequence[int], period, units, start=0, num_steps: Optional[int] = None, eta: float = 1.0,
+                   spacing: str = "uniform", batch_size: int = 512, feature_key: str = "angles") -> List[np.ndarray]:
+    """Sample one backbone per entry of ``lengths`` with an internal repeat (``fd_sample_repeat``): the angle
+    rows ``[start, start + period * units)`` are tied across the ``units`` copies of a ``period``-row unit, so that they come
+    out periodic bit for bit.  A residue's features are internal angles, so the tied stretch has exact screw symmetry
+    (``structures.repeat_rmsd``); the rows outside it are free flanks.  At every visit the copies' predictions are averaged
+    and the same draw is added to every copy.  ``period``, ``units`` and ``start`` are scalars or one value per length;
+    ``units=1`` ties nothing.
+
+    ``num_steps`` (default: all T), ``eta`` and ``spacing`` choose the schedule as in ``sample``; the start noise and the
+    Philox seed of the steps are drawn as in ``steer`` (``torch.manual_seed`` reproducible).  Returns one ``[len, F]`` array per
+    length, shifted by the training mean offset and trimmed like ``sample``'s final states.  ``ValueError``, before any device
+    call, for a tie that does not fit its length, a ``period`` / ``units`` / ``start`` sequence of another length than
+    ``lengths``, and a ``spacing`` the samplers reject.  Single device; not combined with motif conditioning, the
+    second-order solver or steering."""
+    _check_few_step(None, spacing, num_steps, eta)
+    lengths = [int(l) for l in lengths]
+    pad = dset.pad
+    if not lengths or min(lengths) < 1 or max(lengths) > pad:
+        raise ValueError(f"lengths must be non-empty and lie in [1, {pad}]")
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size={batch_size} must be positive")
+    ties = repeat_ties(lengths, period, units, start)
+    T = dset.timesteps
+    betas = dset.alpha_beta_terms["betas"]
+    visits = _few_step_visits(betas, T if num_steps is None else int(num_steps), None, spacing, -3.0)
+    coef = ddim_coefficients(betas, visits, eta)
+    inner = getattr(dset, "dset", None)
+    offset = None
+    if inner is not None and hasattr(inner, "get_masked_means"):
+        try:
+            offset = inner.get_masked_means()
+        except NotImplementedError:
+            offset = None
+    angular = np.asarray(dset.feature_is_angular[feature_key], dtype=bool)
+    F = model.n_inputs
+    h = model.prepare(betas, dset.feature_is_angular[feature_key])
+    on_gpu = getattr(getattr(model, "device", None), "type", "") == "cuda"
+    samples: List[np.ndarray] = []
+    for lo in range(0, len(lengths), int(batch_size)):
+        these = lengths[lo: lo + int(batch_size)]
+        B, L = len(these), max(these)
+        x0 = _as_f32(dset.sample_noise(torch.zeros((B, pad, F), dtype=torch.float32))[:, :L, :])
+        philox_seed = _draw_philox_seed()
+        out = np.empty((B, L, F), dtype=np.float32)
+        prev_varlen = model.set_option("varlen", 1)   # positions beyond an item's length are cut away below, as in sample()
+        try:
+            if on_gpu:
+                model.set_option("rows_hint", sum((l + 7) // 8 * 8 for l in these))
+            _run_fd_sample_repeat(h, x0, _lens_array(these, B, L), visits, coef, None, philox_seed, 0,
+                                  np.ascontiguousarray(ties[lo: lo + B]), out)
+        finally:
+            if on_gpu:
+                model.set_option("rows_hint", 0)
+            model.set_option("varlen", prev_varlen if prev_varlen is not None else 0)
+        samples.extend(s[0] for s in _shift_trim(model, torch.from_numpy(out[None]), these, offset, angular))
+    return samples
+
+
 def sample_simple(model_dir: str, n: int = 10, sweep_lengths: Tuple[int, int] = (50, 128)):
     """Load model + dummy dataset from ``model_dir`` and return one DataFrame of final
     angles per sampled backbone."""

@@ -413,6 +413,33 @@ def motif_rmsd(backbones: Sequence[np.ndarray], motif_backbone: np.ndarray, offs
     return superposed_rmsd(parts, [ref] * len(parts), device=device)
 
 
+def repeat_rmsd(backbones: Sequence[np.ndarray], start, period, units, device: int = 0) -> np.ndarray:
+    """How exactly the repeat units of a backbone superpose (``sampling.sample_repeats``): for every backbone
+    (``[3 len_i, 3]``, N / CA / C per residue, ``nerf.build_backbones``) the RMSD in Angstrom, after optimal superposition,
+    of the atoms of the tied residues ``[start + 1, start + (units - 1) * period)`` onto the same range shifted by
+    ``period`` -- all units but the last onto all units but the first; float64 ``[len(backbones)]`` from one
+    ``superposed_rmsd`` call.  The first tied residue is left out: NeRF reads the N-CA-C angle of residue ``i`` from row
+    ``i - 1``, which for residue ``start`` is a free row (for residue 0: the fixed seed), while its images in the later units
+    read a tied row.  Every other residue of the range is built from tied rows alone.  ``start``, ``period`` and ``units``
+    are scalars or one value per backbone.  NaN where ``units == 1`` (nothing is tied) or the range is empty."""
+    n = len(backbones)
+    per = [np.broadcast_to(np.asarray(v, dtype=np.int64), (n,)) for v in (start, period, units)]
+    out = np.full((n,), np.nan, dtype=np.float64)
+    a_parts, b_parts, where = [], [], []
+    for i, (bb, s, p, r) in enumerate(zip(backbones, *per)):
+        bb = np.asarray(bb, dtype=np.float64).reshape(-1, 3)
+        if s < 0 or p < 1 or r < 1 or 3 * (s + p * r) > len(bb):
+            raise ValueError(f"backbone {i}: {len(bb) // 3} residues, tie (start={s}, period={p}, units={r})")
+        lo, hi = int(s) + 1, int(s + (r - 1) * p)
+        if r > 1 and hi > lo:
+            a_parts.append(bb[3 * lo: 3 * hi])
+            b_parts.append(bb[3 * (lo + int(p)): 3 * (hi + int(p))])
+            where.append(i)
+    if where:
+        out[where] = superposed_rmsd(a_parts, b_parts, device=device)
+    return out
+
+
 class RmsdScorer:
     """A ``scorer=`` for ``sampling.get_reconstruction_error``: per item (RMSD of NeRF(reconstruction) to NeRF(truth),
     RMSD of NeRF(reconstruction) to the backbone of the item's PDB file), in Angstrom after optimal superposition --

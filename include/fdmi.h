@@ -55,6 +55,7 @@ extern "C" {
 /*    fd_tm_align_ex (the alignment search from a chosen set of TM-align's five starts) is additive too */
 /*    fd_sample_steered, fd_p_sample_step_coef_x0, fd_steer_rewards and fd_steer_resample (steering a few-step run by particle
  *    resampling on device rewards) and the struct fd_steer_params are additive too */
+/*    fd_sample_repeat and fd_tie_repeats (few-step sampling with the angle rows tied across repeat units) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -552,6 +553,45 @@ int fd_steer_rewards(int device_id, const float* x, const int32_t* lens, int B, 
  * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs and logw / r_prev untouched. */
 int fd_steer_resample(int device_id, const double* reward, double* logw, double* r_prev, int G, int P, double lambda,
                       double ess_frac, const double* u, int32_t* ancestors_out, uint8_t* resampled_out);
+
+/* ---- repeat proteins: a few-step run whose angle rows are tied across the units of an internal repeat.  A
+ * residue's features are internal angles, so a chain whose rows are periodic has exact screw symmetry (all but residue 0, which
+ * NeRF seeds from fixed coordinates).  Sequence b has a tie (start, period, units): the tied region is the rows
+ * [start, start + period * units), row start + k * period + j is copy k of unit row j, and units == 1 ties nothing.
+ * The tie statement, in place on a [B][L][F] state, every product, sum and quotient rounded once in float32; for a tied element
+ * with x_k its value in copy k:
+ *     d_k = x_k - x_0, wrapped to [-pi, pi) where the feature is angular            k = 1 .. units - 1
+ *     m   = x_0 + (d_1 + d_2 + ... + d_{units-1}) / float(units)                    summed left to right
+ *     m   = m + s * z  where s != 0;   m = wrap(m) where angular;   every copy <- m
+ * and for an element of a row below lens[b] outside the region: m = x, then the same + s z and wrap.  z is the entry of the
+ * visit's draws at the copy-0 position (b, start + j, f), or without draws philox_normal(seed, t, seq_offset + b, start + j, f):
+ * what the update kernel would have drawn there (a free element: its own position).  Rows at or beyond lens[b] are neither
+ * read nor written.  The `init` statement: every copy <- x_0, nothing else.
+ *
+ * fd_sample_repeat is fd_sample_strided (final state only) with the ties enforced at every visit: the init statement on the
+ * start point, then per visit i the strided update without its draw -- wrap(a x + b eps) -- followed by the tie statement with
+ * s = coef[2][i], t = visits[i] and row i of `noise`.  The copies therefore start equal, see the mean of the units'
+ * predictions and receive the same draw: they stay bit-identical.
+ *   visits, coef [3][K], noise [K][B][L][F] or NULL, seed, seq_offset, x_init, lens   as in fd_sample_strided
+ *   tie            int32 [B][3] start | period | units (host): start >= 0, period >= 1, units >= 1,
+ *                  start + period * units <= lens[b]
+ *   out            [B][L][F] the final state
+ * One tie launch sits between two replays of the plain sampler's captured step graph; nothing is asked of the host between the
+ * upload and the download.  Everything fd_sample_strided rejects, a NULL tie or a tie outside its sequence: FD_E_INVALID before
+ * any device call, `out` untouched.  Options "use_graph" and "varlen" and both precisions as in fd_sample_strided; a later
+ * fd_sample* is unaffected.  Not offered with motif conditioning, the second-order solver or steering. */
+int fd_sample_repeat(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                     const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, const int32_t* tie, float* out);
+
+/* The tie statement above on host arrays, model-free and synchronous like fd_nerf.
+ *   x          float32 [B][L][F] (host); lens int32[B] in [1, L]; tie int32 [B][3] as above; 1 <= F <= 32
+ *   is_angle   uint8[F]: the features to wrap
+ *   init       != 0: the init statement (s, z, seed, t and seq_offset are not looked at)
+ *   s          finite; z float32 [B][L][F], or NULL: Philox with (seed, t, seq_offset); neither is looked at where s == 0
+ *   out        float32 [B][L][F]: the rows below lens[b]; the others keep what they held
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), `out` untouched. */
+int fd_tie_repeats(int device_id, const float* x, const int32_t* lens, const int32_t* tie, int B, int L, int F,
+                   const uint8_t* is_angle, int init, float s, const float* z, uint64_t seed, int t, int64_t seq_offset, float* out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
