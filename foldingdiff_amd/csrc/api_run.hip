@@ -1,12 +1,16 @@
 // C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
-// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned, solver, steered) and their
-// device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry checks its
-// arguments before its first HIP call, and the paragraphs the entries share -- make the workspace current and upload, download
-// and synchronise, the host-side run, the one-copy staging of the loss entries -- are written once, below.
+// single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned, solver, steered,
+// repeat) and their device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry
+// checks its arguments before its first HIP call, and the paragraphs the entries share are written once, below: make the
+// workspace current and upload (open_call), download and synchronise (finish), the one-copy staging of the loss entries
+// (PackedUpload), one reverse step from host arrays (host_step), the owner of a run from host arrays (HostRun: stage, begin,
+// the family's own steps, finish), the ONE close of a run (close_run: nothing of a finished run stays on the handle or in the
+// device's UpdateDyn, whichever family ran and however it ended) and the ONE stager of the per-timestep tables (stage_tables).
 // Boundary: include/fdmi.h (each entry point cites the reference function it replaces).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <initializer_list>
 #include <vector>
@@ -53,14 +57,14 @@ struct Download {
   size_t bytes;
 };
 
-int download_sync(hipStream_t s, std::initializer_list<Download> list) {
+int download_sync(hipStream_t s, const std::vector<Download>& list) {
   for (const Download& d : list)
     if (d.host) HIP_TRY(hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return FD_OK;
 }
 
-int finish(fd_model* m, hipStream_t s, std::initializer_list<Download> list) {
+int finish(fd_model* m, hipStream_t s, const std::vector<Download>& list) {
   if (int rc = download_sync(s, list)) return rc;
   return check_flag(m);
 }
@@ -188,27 +192,65 @@ int stage_inpaint(fd_model* m, hipStream_t s, const InpaintHost& h, InpaintDev* 
   return FD_OK;
 }
 
-// ---- one reverse step from host arrays: fd_p_sample_step, and with `cond` fd_p_sample_step_inpaint
-int p_sample_step(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
-                  const InpaintHost& cond, const float* z_known, float* x_out) {
+// ---- ONE reverse step from host arrays: the six fd_p_sample_step* entries, each of which has checked its arguments, allocated
+// its call-lifetime buffers (mode.x0_prev, mode.x0_out) and filled the StepMode fields of its update
+struct StepHost {
+  const float* x;
+  int t;
+  const int32_t* lens;
+  int B, L, wrap;
+  const float* z = nullptr;        // the draw to upload, or null: none is read (t = 0, s = 0)
+  bool draws = true;               // the update takes its draw from the workspace's slab (false: it has none, the solver's)
+  InpaintHost cond;                // fixed null: not conditioned
+  const float* z_known = nullptr;  // the replacement's draw to upload, or null: none is read
+};
+
+// x_out, eps_out and x0_out (null: not asked for) are the one download list: the state, the prediction and mode.x0_out
+int host_step(fd_model* m, const StepHost& h, StepMode mode, float* x_out, float* eps_out, float* x0_out) {
   Call c;
-  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
+  if (int rc = open_call(m, h.x, h.lens, nullptr, h.B, h.L, &c)) return rc;
   Workspace& w = *c.ws;
-  if (z) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
+  if (mode.x0_out) HIP_TRY(hipMemsetAsync(mode.x0_out, 0, c.n * 4, c.s));  // (a position the kernel does not take as a row is not written)
+  if (h.z) HIP_TRY(hipMemcpyAsync(w.z, h.z, c.n * 4, hipMemcpyHostToDevice, c.s));
   InpaintDev ip;
-  if (cond.fixed) {
-    if (int rc = stage_inpaint(m, c.s, cond, &ip)) return rc;
-    if (t > 0) HIP_TRY(hipMemcpyAsync(ip.z_known, z_known, c.n * 4, hipMemcpyHostToDevice, c.s));
+  if (h.cond.fixed) {
+    if (int rc = stage_inpaint(m, c.s, h.cond, &ip)) return rc;
+    if (h.z_known) HIP_TRY(hipMemcpyAsync(ip.z_known, h.z_known, c.n * 4, hipMemcpyHostToDevice, c.s));
   }
   if (int rc = prepare_rows(m, c.s, 0)) return rc;
-  if (int rc = set_t(m, c.s, t)) return rc;
-  StepMode mode{};
-  mode.noise = w.z;
-  mode.t_start = t;
-  mode.no_wrap = !wrap;
+  if (int rc = set_t(m, c.s, h.t)) return rc;
+  if (h.draws) mode.noise = w.z;
+  mode.t_start = h.t;
+  mode.no_wrap = !h.wrap;
   ip.apply(&mode);
   if (int rc = run_step(m, c.s, mode)) return rc;
-  return finish(m, c.s, {{x_out, w.x, c.n * 4}});
+  return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}, {x0_out, mode.x0_out, c.n * 4}});
+}
+
+// one strided update by value: x' = a x + b eps (+ s z where s != 0)
+StepMode strided_mode(float a, float b, float s) {
+  StepMode mode{};
+  mode.strided = true;
+  mode.sa = a; mode.sb = b; mode.ss = s;
+  return mode;
+}
+
+// the opening checks the step entries share ...
+int check_step_call(fd_model* m, const void* x, const void* lens, const void* x_out, int B, int L, int t) {
+  if (int rc = check_shape(m, B, L, t)) return rc;
+  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  return FD_OK;
+}
+
+// ... and the finiteness of the coefficients by value: names = one letter per value
+int check_finite_coef(const char* names, std::initializer_list<float> values) {
+  bool finite = true;
+  for (float v : values) finite = finite && std::isfinite(v);
+  if (finite) return FD_OK;
+  char list[160];
+  int at = 0;
+  for (float v : values) at += snprintf(list + at, sizeof list - (size_t)at, "%s%c = %g", at ? ", " : "", *names++, (double)v);
+  return fail(FD_E_INVALID, "%s: a coefficient is not finite", list);
 }
 
 // ---- resampling schedules: argument checks of fd_sample_inpaint_resample / fd_inpaint_jump
@@ -279,32 +321,95 @@ int begin_run(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, 
   return FD_OK;
 }
 
-// ---- a whole sampling run from host arrays (fd_sample_ex, fd_sample_inpaint, fd_sample_inpaint_resample); the entry has
-// checked every argument
-struct HostRun {
+// ---- THE close of a sampling run whose family put pointers into the update kernels' per-run values (every run but the plain
+// sampler's device entries): the run is over -- or failed, at any point behind begin_run -- and a later run on this model, of
+// whatever family, starts from cleared fields, on the host and on the device.  The device-side UpdateDyn is what the captured
+// step graph reads; the buffers those pointers named die with the caller's frame, hence the drain.
+int close_run(fd_model* m, hipStream_t s) {
+  m->run_open = false;
+  m->run_t = -1;
+  clear_run_pointers(&m->dyn_host);
+  send_dyn(m, s, m->dyn_host);
+  HIP_TRY(hipStreamSynchronize(s));
+  return FD_OK;
+}
+
+// the host arrays every run family takes; the entry has checked every argument
+struct RunArrays {
   const float* x_init;
   const int32_t* lens;
-  int B, L, t_start;
-  const float* noise;  // [t_start + 1][B][L][F], or null: Philox
+  int B, L;
+  size_t states;             // the states a run without jumps goes through (plain: t_start + 1, strided: the grid's visits)
+  const float* noise;        // [states][B][L][F], or null: Philox
+  const float* known_noise;  // [states + 1][B][L][F], or null: Philox (or not conditioned)
   uint64_t seed;
   int64_t seq_offset;
-  float* out;
+  float* out;                // rows: 1 (final only), every state, or every full_history-th state plus the final one
   int full_history;
-  InpaintHost cond;                    // fixed null: a plain run
-  const float* known_noise = nullptr;  // [t_start + 2][B][L][F] (rows = levels 0 .. t_start + 1), or null: Philox
-  const int32_t* visits = nullptr;     // a resampling schedule, or null: the single descent t_start .. 0
-  int n_visits = 0;
-  const float* jump_coef = nullptr;
 };
 
-// the conditioning of a run just begun: the arrays staged, the start point's fixed elements at the start level, the fields of
-// the update kernels' per-run values (the captured step graph is the plain sampler's)
-int begin_conditioning(fd_model* m, hipStream_t s, const HostRun& a, const float* d_known_noise, InpaintDev* ip) {
-  if (int rc = stage_inpaint(m, s, a.cond, ip)) return rc;
-  const size_t n = (size_t)a.B * a.L * m->cfg.n_features;
-  // the start point enters step t_start, so it is at level t_start + 1
-  launch_inpaint_init(m->ws.x, ip->known, ip->fixed, d_known_noise ? d_known_noise + ((size_t)a.t_start + 1) * n : nullptr, ip->coef,
-                      m->T, a.t_start + 1, a.seed, a.seq_offset, a.B, a.L, m->cfg.n_features, m->angle_mask, s);
+// ---- THE owner of a sampling run from host arrays, on the model's stream.  stage(): x_init, lens, out and the draws into
+// buffers of the call's lifetime, blocking -- as is whatever the family adds to `bufs` (its tables, its work buffers) before
+// begin() queues the first copy.  Between begin() and finish() the family sets its fields of m->dyn_host and runs its steps.
+// finish(rc) ends the run where rc is FD_OK, closes it (close_run) whatever rc is, and then downloads `out` and the family's
+// further outputs and reads the non-finite flag -- in that order for every family, so a run that answers FD_E_NONFINITE has
+// written its (unusable, include/fdmi.h) outputs.  A frame left between begin() and finish() is closed by the destructor.
+class HostRun {
+ public:
+  HostRun(fd_model* m, const RunArrays& a) : n((size_t)a.B * a.L * m->cfg.n_features), m_(m), a_(a) {}
+  HostRun(const HostRun&) = delete;
+  HostRun& operator=(const HostRun&) = delete;
+  ~HostRun() {
+    if (open_) (void)close_run(m_, m_->stream);
+  }
+  int stage() {
+    HIP_TRY(hipSetDevice(m_->device));
+    out_bytes_ = (a_.full_history ? (a_.states + a_.full_history - 1) / a_.full_history : 1) * n * 4;
+    HIP_TRY(bufs.upload(a_.x_init, n * 4, &x));
+    HIP_TRY(bufs.upload(a_.lens, (size_t)a_.B * 4, &lens));
+    HIP_TRY(bufs.alloc(out_bytes_, &out));
+    if (a_.noise) HIP_TRY(bufs.upload(a_.noise, a_.states * n * 4, &noise));
+    if (a_.known_noise) HIP_TRY(bufs.upload(a_.known_noise, (a_.states + 1) * n * 4, &known_noise));
+    return FD_OK;
+  }
+  int begin(int t_first, int n_steps) {
+    if (int rc = begin_run(m_, x, lens, a_.B, a_.L, t_first, n_steps, a_.seed, a_.seq_offset, out, a_.full_history, nullptr)) return rc;
+    open_ = true;
+    return FD_OK;
+  }
+  int finish(int rc, std::initializer_list<Download> more = {}) {
+    if (!rc) rc = fd_sample_end_dev(m_, out, nullptr);
+    open_ = false;
+    if (int rc_close = close_run(m_, m_->stream)) return rc_close;
+    return rc ? rc : download(more);
+  }
+  int download(std::initializer_list<Download> more = {}) {  // (on its own: behind a run that strided_run_dev has closed)
+    std::vector<Download> list{{a_.out, out, out_bytes_}};
+    list.insert(list.end(), more);
+    return ::finish(m_, m_->stream, list);
+  }
+
+  DeviceBufs bufs;
+  const size_t n;  // B * L * F
+  float *x = nullptr, *out = nullptr;
+  int* lens = nullptr;
+  const float *noise = nullptr, *known_noise = nullptr;
+
+ private:
+  fd_model* m_;
+  const RunArrays a_;
+  size_t out_bytes_ = 0;
+  bool open_ = false;
+};
+
+// the conditioning of a run just begun: the arrays staged, the start point's fixed elements at the level it enters the first
+// step with (start_draws: that level's slab, or null: Philox), the fields of the update kernels' per-run values (the captured
+// step graph is the plain sampler's)
+int begin_conditioning(fd_model* m, hipStream_t s, const InpaintHost& cond, const RunArrays& a, int level, const float* start_draws,
+                       const float* d_known_noise, InpaintDev* ip) {
+  if (int rc = stage_inpaint(m, s, cond, ip)) return rc;
+  launch_inpaint_init(m->ws.x, ip->known, ip->fixed, start_draws, ip->coef, m->T, level, a.seed, a.seq_offset, a.B, a.L,
+                      m->cfg.n_features, m->angle_mask, s);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
   ip->apply(&m->dyn_host, d_known_noise);
@@ -335,58 +440,47 @@ int walk_visits(fd_model* m, hipStream_t s, const int32_t* visits, int n_visits,
   return FD_OK;
 }
 
-// A conditioned run is over (or failed, at any point behind fd_sample_begin_dev): it is closed, and a later run on this model,
-// plain or not, starts from cleared fields, on the host and on the device
-int close_conditioned_run(fd_model* m, hipStream_t s) {
-  m->run_open = false;
-  m->run_t = -1;
-  InpaintDev::clear(&m->dyn_host);
-  send_dyn(m, s, m->dyn_host);
-  HIP_TRY(hipStreamSynchronize(s));
-  return FD_OK;
-}
+// ---- a whole run down the ladder t_start .. 0 from host arrays (fd_sample_ex, fd_sample_inpaint, fd_sample_inpaint_resample); the
+// entry has checked every argument.  A plain run goes through the same close as every other: one more stream-ordered copy of
+// the small UpdateDyn, and a drained stream on the error paths too.
+struct LadderRun {
+  RunArrays arrays;
+  int t_start;
+  InpaintHost cond;                 // fixed null: a plain run
+  const int32_t* visits = nullptr;  // a resampling schedule, or null: the single descent t_start .. 0
+  int n_visits = 0;
+  const float* jump_coef = nullptr;
+};
 
-int host_run(fd_model* m, const HostRun& a) {
-  HIP_TRY(hipSetDevice(m->device));
-  const size_t n = (size_t)a.B * a.L * m->cfg.n_features;
-  const size_t nsteps = (size_t)a.t_start + 1;
-  // rows of `out`: 1 (final only), every state, or every full_history-th state plus the final one
-  const size_t out_rows = a.full_history ? (nsteps + a.full_history - 1) / a.full_history : 1;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  const float *d_noise = nullptr, *d_known_noise = nullptr;
-  int* d_lens;
-  HIP_TRY(bufs.alloc(n * 4, &d_x));
-  HIP_TRY(bufs.alloc((size_t)a.B * 4, &d_lens));
-  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
-  HIP_TRY(hipMemcpy(d_x, a.x_init, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_lens, a.lens, (size_t)a.B * 4, hipMemcpyHostToDevice));
-  if (a.noise) HIP_TRY(bufs.upload(a.noise, nsteps * n * 4, &d_noise));
-  if (a.known_noise) HIP_TRY(bufs.upload(a.known_noise, (nsteps + 1) * n * 4, &d_known_noise));
-  if (int rc = fd_sample_begin_dev(m, d_x, d_lens, a.B, a.L, a.t_start, a.seed, a.seq_offset, d_out, a.full_history, nullptr)) return rc;
+int host_run(fd_model* m, const LadderRun& a) {
+  HostRun r(m, a.arrays);
+  if (int rc = r.stage()) return rc;
+  if (int rc = r.begin(a.t_start, a.t_start + 1)) return rc;
   hipStream_t s = m->stream;
-  const bool conditioned = a.cond.fixed != nullptr;
   InpaintDev ip;
-  int rc = conditioned ? begin_conditioning(m, s, a, d_known_noise, &ip) : FD_OK;
+  int rc = FD_OK;
+  if (a.cond.fixed)  // the start point enters step t_start, so it is at level t_start + 1
+    rc = begin_conditioning(m, s, a.cond, a.arrays, a.t_start + 1,
+                            r.known_noise ? r.known_noise + ((size_t)a.t_start + 1) * r.n : nullptr, r.known_noise, &ip);
   if (!rc) {
     if (a.visits)  // a descent goes one step down the ladder
-      rc = walk_visits(m, s, a.visits, a.n_visits, a.jump_coef, a.seed, a.seq_offset, a.B, a.L, ip,
+      rc = walk_visits(m, s, a.visits, a.n_visits, a.jump_coef, a.arrays.seed, a.arrays.seq_offset, a.arrays.B, a.arrays.L, ip,
                        [&](int j) { return a.visits[j] == a.visits[j - 1] - 1; }, [&](int i) { return a.visits[i]; });
     else
-      rc = fd_sample_steps_dev(m, a.t_start + 1, d_noise, 0, nullptr);
+      rc = fd_sample_steps_dev(m, a.t_start + 1, r.noise, 0, nullptr);
   }
-  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
-  if (conditioned) {
-    if (int rc_close = close_conditioned_run(m, s)) return rc_close;
-  } else if (!rc) {
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(a.out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
-  return check_flag(m);
+  return r.finish(rc);
 }
 
 // ---- strided (few-step) sampling: argument checks, all before the first device call
+int check_coef_rows(const float* coef, int n_visits, int r0, int r1) {  // rows r0 .. r1 - 1 of a [.][n_visits] table are finite
+  for (int r = r0; r < r1; ++r)
+    for (int i = 0; i < n_visits; ++i)
+      if (!std::isfinite(coef[(size_t)r * n_visits + i]))
+        return fail(FD_E_INVALID, "coef[%d][%d] = %g is not finite", r, i, (double)coef[(size_t)r * n_visits + i]);
+  return FD_OK;
+}
+
 int check_strided(const fd_model* m, const int32_t* visits, int n_visits, const float* coef) {
   if (!visits) return fail(FD_E_INVALID, "visits is null");
   if (!coef) return fail(FD_E_INVALID, "coef is null");
@@ -396,38 +490,41 @@ int check_strided(const fd_model* m, const int32_t* visits, int n_visits, const 
     if (i > 0 && visits[i] >= visits[i - 1])
       return fail(FD_E_INVALID, "visits[%d] = %d follows %d: a strided schedule is strictly descending", i, visits[i], visits[i - 1]);
   }
-  for (int r = 0; r < 3; ++r)
-    for (int i = 0; i < n_visits; ++i)
-      if (!std::isfinite(coef[(size_t)r * n_visits + i]))
-        return fail(FD_E_INVALID, "coef[%d][%d] = %g is not finite", r, i, (double)coef[(size_t)r * n_visits + i]);
-  return FD_OK;
+  return check_coef_rows(coef, n_visits, 0, 3);
 }
 
-// where a strided run's tables are on the device (all null: no strided run)
-struct StridedDev {
-  const int *next_t = nullptr, *ord = nullptr;
-  const float* abs = nullptr;
-  void apply(UpdateDyn* dyn) const { dyn->next_t = next_t; dyn->ord = ord; dyn->abs = abs; }
-  static void clear(UpdateDyn* dyn) { StridedDev().apply(dyn); }
+// where a strided run's tables are on the device: next_t | ord | the rows it asked for, [T] each
+struct VisitTables {
+  const int32_t* dev = nullptr;
+  size_t T = 0;
+  const float* row(size_t r) const { return reinterpret_cast<const float*>(dev + (2 + r) * T); }
+  void apply(UpdateDyn* dyn) const {  // rows 0 .. 2 are a | b | s of every family
+    dyn->next_t = dev;
+    dyn->ord = dev + T;
+    dyn->abs = row(0);
+  }
 };
 
-// the tables indexed by timestep, next_t | ord | a | b | s ([T] each), in ONE buffer of the call's lifetime (blocking upload);
-// a timestep the schedule does not visit holds next_t = -1 and zeros, and is never looked up
-int stage_strided(const fd_model* m, DeviceBufs* bufs, const int32_t* visits, int n_visits, const float* coef, StridedDev* d) {
+// THE stager of the tables indexed by timestep, in ONE buffer of the call's lifetime (blocking upload): next_t | ord | one
+// [T] row per entry of `rows`, a [K] host row whose element i goes to index visits[i] (null: a row of zeros).  A timestep the
+// schedule does not visit holds next_t = -1 and zeros, and is never looked up.
+int stage_tables(const fd_model* m, DeviceBufs* bufs, const int32_t* visits, int n_visits, std::initializer_list<const float*> rows,
+                 VisitTables* d) {
   const size_t T = (size_t)m->T;
-  std::vector<int32_t> tab(5 * T, 0);
+  std::vector<int32_t> tab((2 + rows.size()) * T, 0);
   for (size_t t = 0; t < T; ++t) tab[t] = -1;
   for (int i = 0; i < n_visits; ++i) {
     const size_t t = (size_t)visits[i];
     tab[t] = i + 1 < n_visits ? visits[i + 1] : -1;
     tab[T + t] = i;
-    for (int r = 0; r < 3; ++r) memcpy(&tab[(2 + r) * T + t], &coef[(size_t)r * n_visits + i], 4);
+    size_t r = 2;
+    for (const float* row : rows) {
+      if (row) memcpy(&tab[r * T + t], &row[i], 4);
+      ++r;
+    }
   }
-  const int32_t* dev = nullptr;
-  HIP_TRY(bufs->upload(tab.data(), tab.size() * 4, &dev));
-  d->next_t = dev;
-  d->ord = dev + T;
-  d->abs = reinterpret_cast<const float*>(dev + 2 * T);
+  d->T = T;
+  HIP_TRY(bufs->upload(tab.data(), tab.size() * 4, &d->dev));
   return FD_OK;
 }
 
@@ -435,90 +532,68 @@ int stage_strided(const fd_model* m, DeviceBufs* bufs, const int32_t* visits, in
 // the previous visit's prediction of the clean state
 int check_solver(const fd_model* m, const int32_t* visits, int n_visits, const float* coef) {
   if (int rc = check_strided(m, visits, n_visits, coef)) return rc;  // the visits; rows a | b | c finite
-  for (int r = 3; r < 5; ++r)
-    for (int i = 0; i < n_visits; ++i)
-      if (!std::isfinite(coef[(size_t)r * n_visits + i]))
-        return fail(FD_E_INVALID, "coef[%d][%d] = %g is not finite", r, i, (double)coef[(size_t)r * n_visits + i]);
+  if (int rc = check_coef_rows(coef, n_visits, 3, 5)) return rc;
   if (coef[(size_t)2 * n_visits] != 0.f)
     return fail(FD_E_INVALID, "coef[2][0] = %g: the first visit has no earlier prediction, its c is 0", (double)coef[(size_t)2 * n_visits]);
   return FD_OK;
 }
 
-// where a solver run's table and its previous prediction are on the device (both null: no solver run)
-struct SolverDev {
-  const float* cuv = nullptr;
-  float* x0_prev = nullptr;
-  void apply(UpdateDyn* dyn) const { dyn->cuv = cuv; dyn->x0_prev = x0_prev; }
-  static void clear(UpdateDyn* dyn) { SolverDev().apply(dyn); }
-};
-
-// coef [5][K] a | b | c | u | v: the strided tables with a | b | 0, the table c | u | v ([3][T], zeros off the schedule) and the
-// [n] previous prediction (uninitialised: the first visit's c is 0 and does not read it), in buffers of the call's lifetime
-int stage_solver(const fd_model* m, DeviceBufs* bufs, const int32_t* visits, int n_visits, const float* coef, size_t n, StridedDev* sd,
-                 SolverDev* d) {
-  const size_t T = (size_t)m->T, K = (size_t)n_visits;
-  std::vector<float> abs(3 * K, 0.f), cuv(3 * T, 0.f);
-  memcpy(abs.data(), coef, 2 * K * 4);
-  if (int rc = stage_strided(m, bufs, visits, n_visits, abs.data(), sd)) return rc;
-  for (size_t i = 0; i < K; ++i)
-    for (size_t r = 0; r < 3; ++r) cuv[r * T + (size_t)visits[i]] = coef[(2 + r) * K + i];
-  HIP_TRY(bufs->upload(cuv.data(), cuv.size() * 4, &d->cuv));
-  HIP_TRY(bufs->alloc(n * 4, &d->x0_prev));
-  return FD_OK;
-}
-
 // A strided run on device arrays (the entry has checked every argument): the plain sampler's steps -- its captured graph
-// included -- with the tables in the update kernels' per-run values.  `solver`: coef is [5][K] and the run is the solver's, its
-// noise_dev null.  Returns with the stream drained and the fields cleared, on the host and on the device, on every path: the
-// tables (and the solver's previous prediction) die with this frame.
+// included -- with the tables in the update kernels' per-run values.  `solver`: coef is [5][K] a | b | c | u | v, the run is the
+// solver's and its noise_dev null: the tables hold a | b | 0 and c | u | v, and the [n] previous prediction is a buffer of this
+// frame (uninitialised: the first visit's c is 0 and does not read it).  Returns closed (close_run) on every path behind
+// begin_run: the tables and the previous prediction die with this frame.
 int strided_run_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits, int n_visits,
                     const float* coef, bool solver, const void* noise_dev, uint64_t seed, int64_t seq_offset, void* out_dev,
                     int full_history, void* hip_stream) {
   HIP_TRY(hipSetDevice(m->device));
+  const size_t K = (size_t)n_visits;
   DeviceBufs bufs;
-  StridedDev sd;
-  SolverDev sv;
+  VisitTables tb;
+  float* x0_prev = nullptr;
   if (solver) {
-    if (int rc = stage_solver(m, &bufs, visits, n_visits, coef, (size_t)B * L * m->cfg.n_features, &sd, &sv)) return rc;
-  } else if (int rc = stage_strided(m, &bufs, visits, n_visits, coef, &sd)) {
+    if (int rc = stage_tables(m, &bufs, visits, n_visits, {coef, coef + K, nullptr, coef + 2 * K, coef + 3 * K, coef + 4 * K}, &tb)) return rc;
+    HIP_TRY(bufs.alloc((size_t)B * L * m->cfg.n_features * 4, &x0_prev));
+  } else if (int rc = stage_tables(m, &bufs, visits, n_visits, {coef, coef + K, coef + 2 * K}, &tb)) {
     return rc;
   }
   if (int rc = begin_run(m, x_init_dev, lens_dev, B, L, visits[0], n_visits, seed, seq_offset, out_dev, full_history, hip_stream)) return rc;
-  hipStream_t s = stream_of(m, hip_stream);
-  sd.apply(&m->dyn_host);
-  sv.apply(&m->dyn_host);
+  tb.apply(&m->dyn_host);
+  if (solver) {
+    m->dyn_host.cuv = tb.row(3);
+    m->dyn_host.x0_prev = x0_prev;
+  }
   int rc = fd_sample_steps_dev(m, n_visits, noise_dev, 0, hip_stream);  // (noise rows are per visit: row 0 = visit 0)
   if (!rc) rc = fd_sample_end_dev(m, out_dev, hip_stream);
-  m->run_open = false;
-  m->run_t = -1;
-  StridedDev::clear(&m->dyn_host);
-  SolverDev::clear(&m->dyn_host);
-  send_dyn(m, s, m->dyn_host);
-  HIP_TRY(hipStreamSynchronize(s));
-  return rc;
+  const int rc_close = close_run(m, stream_of(m, hip_stream));
+  return rc_close ? rc_close : rc;
 }
 
 // the same from host arrays (noise [K][B][L][F] or null)
-int strided_run_host(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
-                     const float* coef, bool solver, const float* noise, uint64_t seed, int64_t seq_offset, float* out, int full_history) {
-  HIP_TRY(hipSetDevice(m->device));
-  const size_t n = (size_t)B * L * m->cfg.n_features;
-  const size_t out_rows = full_history ? ((size_t)n_visits + full_history - 1) / full_history : 1;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  const float* d_noise = nullptr;
-  int* d_lens;
-  HIP_TRY(bufs.upload(x_init, n * 4, &d_x));
-  HIP_TRY(bufs.upload(lens, (size_t)B * 4, &d_lens));
-  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
-  if (noise) HIP_TRY(bufs.upload(noise, (size_t)n_visits * n * 4, &d_noise));
-  if (int rc = strided_run_dev(m, d_x, d_lens, B, L, visits, n_visits, coef, solver, d_noise, seed, seq_offset, d_out, full_history, nullptr))
+int strided_run_host(fd_model* m, const RunArrays& a, const int32_t* visits, const float* coef, bool solver) {
+  HostRun r(m, a);
+  if (int rc = r.stage()) return rc;
+  if (int rc = strided_run_dev(m, r.x, r.lens, a.B, a.L, visits, (int)a.states, coef, solver, r.noise, a.seed, a.seq_offset, r.out,
+                               a.full_history, nullptr))
     return rc;
-  HIP_TRY(hipMemcpy(out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
-  return check_flag(m);
+  return r.download();
 }
 
-// ... and the checks the entries share
+// ---- the opening checks the run entries share, in the order the contract tests pin.  The ladder runs ...
+int check_run_call(fd_model* m, const void* x_init, const int32_t* lens, const void* out, int B, int L, int t_start, int full_history) {
+  if (int rc = check_shape(m, B, L, t_start)) return rc;
+  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
+  return check_lens(lens, B, L);
+}
+
+// ... an entry with jumps ...
+int check_jump_tag(const fd_model* m) {
+  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  return FD_OK;
+}
+
+// ... and the strided runs, on host or device arrays (a host entry checks its lengths next)
 int check_strided_call(fd_model* m, const void* x_init, const void* lens, const void* out, int B, int L, const int32_t* visits,
                        int n_visits, const float* coef, int full_history, bool solver = false) {
   if (int rc = check_shape(m, B, L, 0)) return rc;
@@ -566,134 +641,77 @@ int check_strided_visits(const fd_model* m, const int32_t* grid, int n_grid, con
 
 // the host arrays of a strided conditioned run; the entry has checked every argument
 struct StridedHostRun {
-  const float* x_init;
-  const int32_t* lens;
-  int B, L;
+  RunArrays arrays;     // states = n_grid; known_noise row 0: the start point, row i + 1: the state visit i leaves
   const int32_t* grid;  // strictly descending
-  int n_grid;
   const float* coef;    // [3][n_grid]
-  const float* noise;   // [n_grid][B][L][F], or null: Philox
   InpaintHost cond;
-  const float* known_noise;  // [n_grid + 1][B][L][F] (row 0: the start point, row i + 1: the state visit i leaves), or null: Philox
-  uint64_t seed;
-  int64_t seq_offset;
-  float* out;
-  int full_history;
   const int32_t* run = nullptr;  // a resampled run over the grid, or null: the grid once
   int n_run = 0;
   const float* jump_coef = nullptr;
 };
 
-// Returns with the stream drained and the strided and the conditioning fields cleared, on the host and on the device, on every
-// path behind begin_run: the tables and the draws die with this frame.
 int strided_host_run(fd_model* m, const StridedHostRun& a) {
-  HIP_TRY(hipSetDevice(m->device));
-  const int F = m->cfg.n_features;
-  const size_t n = (size_t)a.B * a.L * F;
-  const int n_visits = a.run ? a.n_run : a.n_grid;
-  const size_t out_rows = a.full_history ? ((size_t)a.n_grid + a.full_history - 1) / a.full_history : 1;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  const float *d_noise = nullptr, *d_known_noise = nullptr;
-  int* d_lens;
-  HIP_TRY(bufs.upload(a.x_init, n * 4, &d_x));
-  HIP_TRY(bufs.upload(a.lens, (size_t)a.B * 4, &d_lens));
-  HIP_TRY(bufs.alloc(out_rows * n * 4, &d_out));
-  if (a.noise) HIP_TRY(bufs.upload(a.noise, (size_t)a.n_grid * n * 4, &d_noise));
-  if (a.known_noise) HIP_TRY(bufs.upload(a.known_noise, ((size_t)a.n_grid + 1) * n * 4, &d_known_noise));
-  StridedDev sd;
-  if (int rc = stage_strided(m, &bufs, a.grid, a.n_grid, a.coef, &sd)) return rc;
-  if (int rc = begin_run(m, d_x, d_lens, a.B, a.L, a.grid[0], n_visits, a.seed, a.seq_offset, d_out, a.full_history, nullptr)) return rc;
+  const RunArrays& h = a.arrays;
+  const int n_grid = (int)h.states;
+  HostRun r(m, h);
+  if (int rc = r.stage()) return rc;
+  VisitTables tb;
+  if (int rc = stage_tables(m, &r.bufs, a.grid, n_grid, {a.coef, a.coef + n_grid, a.coef + 2 * (size_t)n_grid}, &tb)) return rc;
+  if (int rc = r.begin(a.grid[0], a.run ? a.n_run : n_grid)) return rc;
   hipStream_t s = m->stream;
-  sd.apply(&m->dyn_host);
-  InpaintDev ip;
-  int rc = stage_inpaint(m, s, a.cond, &ip);
-  if (!rc) {  // the start point enters visit 0, so it is at level grid[0] + 1; its draws are row 0
-    launch_inpaint_init(m->ws.x, ip.known, ip.fixed, d_known_noise, ip.coef, m->T, a.grid[0] + 1, a.seed, a.seq_offset, a.B, a.L, F,
-                        m->angle_mask, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(FD_E_HIP, "launch_inpaint_init: %s", hipGetErrorString(e));
-  }
+  tb.apply(&m->dyn_host);
+  InpaintDev ip;  // the start point enters visit 0, so it is at level grid[0] + 1; its draws are row 0
+  int rc = begin_conditioning(m, s, a.cond, h, a.grid[0] + 1, r.known_noise, r.known_noise, &ip);
   if (!rc) {
-    ip.apply(&m->dyn_host, d_known_noise);
     if (a.run) {  // a descent goes to the grid's next visit; a jump starts from the level the visit before it landed on
-      const std::vector<int> pos = grid_positions(m, a.grid, a.n_grid);
-      rc = walk_visits(m, s, a.run, a.n_run, a.jump_coef, a.seed, a.seq_offset, a.B, a.L, ip,
+      const std::vector<int> pos = grid_positions(m, a.grid, n_grid);
+      rc = walk_visits(m, s, a.run, a.n_run, a.jump_coef, h.seed, h.seq_offset, h.B, h.L, ip,
                        [&](int j) { return pos[(size_t)a.run[j]] == pos[(size_t)a.run[j - 1]] + 1; }, [&](int i) { return a.n_run - 1 - i; });
     } else {
-      rc = fd_sample_steps_dev(m, a.n_grid, d_noise, 0, nullptr);
+      rc = fd_sample_steps_dev(m, n_grid, r.noise, 0, nullptr);
     }
   }
-  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
-  StridedDev::clear(&m->dyn_host);
-  if (int rc_close = close_conditioned_run(m, s)) return rc_close;
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(a.out, d_out, out_rows * n * 4, hipMemcpyDeviceToHost));
-  return check_flag(m);
+  return r.finish(rc);
 }
 
 // ---- steered sampling: a strided run whose visits also write their prediction of the clean state, with an
 // event -- shift, rewards, resample, gather (steer.hip) -- between the step segments, as walk_visits puts jumps between them
 struct SteeredHostRun {
-  const float* x_init;
-  const int32_t* lens;
-  int B, L;
+  RunArrays arrays;  // states = K, final state only
   const int32_t* visits;
-  int n_visits;
-  const float* coef;   // [5][K] a | b | s | u | v
-  const float* noise;  // [K][B][L][F], or null: Philox
-  uint64_t seed;
-  int64_t seq_offset;
+  const float* coef;     // [5][K] a | b | s | u | v
   const uint8_t* event;  // [K]
   int n_events;
   int P;
   const fd_steer_params* params;
   const double* u;  // [n_events][B / P]
-  float* out;
   double *terms_out, *reward_out, *logw_out;
   int32_t* ancestors_out;  // [n_events][B], or null
 };
 
-// where a steered run's table u | v and its prediction buffer are on the device (both null: no steered run)
-struct SteerDev {
-  const float* uv = nullptr;
-  float* x0 = nullptr;
-  void apply(UpdateDyn* dyn) const { dyn->uv = uv; dyn->x0_steer = x0; }
-  static void clear(UpdateDyn* dyn) { SteerDev().apply(dyn); }
-};
-
-// Returns with the stream drained and the strided and the steering fields cleared, on the host and on the device, on every
-// path behind begin_run: the tables and the buffers die with this frame.  The entry has checked every argument.
+// The entry has checked every argument.  The tables, the prediction buffer and the rewards pass's buffers die with this frame.
 int steered_host_run(fd_model* m, const SteeredHostRun& a) {
-  HIP_TRY(hipSetDevice(m->device));
-  const int F = m->cfg.n_features, B = a.B, L = a.L, K = a.n_visits, G = a.B / a.P;
-  const size_t n = (size_t)B * L * F, nr = (size_t)B * L, nb = (size_t)B, T = (size_t)m->T;
+  const RunArrays& h = a.arrays;
+  const int F = m->cfg.n_features, B = h.B, L = h.L, K = (int)h.states, G = B / a.P;
+  const size_t nr = (size_t)B * L, nb = (size_t)B, Kz = h.states;
   const fd_steer_params& sp = *a.params;
-  DeviceBufs bufs;
-  float *d_x, *d_out, *d_ang, *d_tmp;
-  const float* d_noise = nullptr;
-  int* d_lens;
-  HIP_TRY(bufs.upload(a.x_init, n * 4, &d_x));
-  HIP_TRY(bufs.upload(a.lens, nb * 4, &d_lens));
-  HIP_TRY(bufs.alloc(n * 4, &d_out));
+  HostRun r(m, h);
+  if (int rc = r.stage()) return rc;
+  const size_t n = r.n;
+  DeviceBufs& bufs = r.bufs;
+  float *d_ang, *d_tmp, *d_x0;
   HIP_TRY(bufs.alloc(n * 4, &d_ang));
   HIP_TRY(bufs.alloc(n * 4, &d_tmp));
-  if (a.noise) HIP_TRY(bufs.upload(a.noise, (size_t)K * n * 4, &d_noise));
-  StridedDev sd;
-  if (int rc = stage_strided(m, &bufs, a.visits, K, a.coef, &sd)) return rc;  // (rows a | b | s are the first three of coef)
-  SteerDev sv;
-  std::vector<float> uv(2 * T, 0.f);
-  for (int i = 0; i < K; ++i)
-    for (size_t r = 0; r < 2; ++r) uv[r * T + (size_t)a.visits[i]] = a.coef[(3 + r) * (size_t)K + i];
-  HIP_TRY(bufs.upload(uv.data(), uv.size() * 4, &sv.uv));
-  HIP_TRY(bufs.zeros(n * 4, &sv.x0));  // (packed rows: a position beyond a length is never written, and never read)
+  VisitTables tb;
+  if (int rc = stage_tables(m, &bufs, a.visits, K, {a.coef, a.coef + Kz, a.coef + 2 * Kz, a.coef + 3 * Kz, a.coef + 4 * Kz}, &tb)) return rc;
+  HIP_TRY(bufs.zeros(n * 4, &d_x0));  // (packed rows: a position beyond a length is never written, and never read)
   // the rewards pass's buffers, the weights' state and the uniforms
   SteerWork wk{};
   std::vector<int32_t> offsets(nb);
   int max_len = 0;
   for (int b = 0; b < B; ++b) {
     offsets[(size_t)b] = b * L;
-    max_len = a.lens[b] > max_len ? a.lens[b] : max_len;
+    max_len = h.lens[b] > max_len ? h.lens[b] : max_len;
   }
   HIP_TRY(bufs.alloc(nr * 9 * 8, &wk.coords));
   HIP_TRY(bufs.alloc(nr * 9 * 4, &wk.xyz));
@@ -722,11 +740,12 @@ int steered_host_run(fd_model* m, const SteeredHostRun& a) {
   off.has_offset = sp.has_offset ? 1 : 0;
   for (int f = 0; sp.has_offset && f < F; ++f) off.offset[f] = sp.offset[f];
 
-  if (int rc = begin_run(m, d_x, d_lens, B, L, a.visits[0], K, a.seed, a.seq_offset, d_out, 0, nullptr)) return rc;
+  if (int rc = r.begin(a.visits[0], K)) return rc;
   hipStream_t s = m->stream;
   Workspace& w = m->ws;
-  sd.apply(&m->dyn_host);
-  sv.apply(&m->dyn_host);
+  tb.apply(&m->dyn_host);
+  m->dyn_host.uv = tb.row(3);
+  m->dyn_host.x0_steer = d_x0;
   auto rewards_of = [&](const float* state) -> int {  // shift + rewards of a [B][L][F] state in model space
     launch_steer_shift(state, w.lens, B, L, F, off, m->angle_mask, d_ang, s);
     launch_steer_rewards(d_ang, w.lens, B, L, F, fx, wt, sp.clash_alpha, max_len, wk, d_terms, d_reward, s);
@@ -737,9 +756,9 @@ int steered_host_run(fd_model* m, const SteeredHostRun& a) {
   for (int i = 0, e = 0; !rc && i < K;) {  // a segment ends with a visit that has an event, or with the last visit
     int j = i + 1;
     while (j < K && !a.event[j - 1]) ++j;
-    rc = fd_sample_steps_dev(m, j - i, d_noise, 0, nullptr);  // (noise rows are per visit, whatever the segment)
+    rc = fd_sample_steps_dev(m, j - i, r.noise, 0, nullptr);  // (noise rows are per visit, whatever the segment)
     if (!rc && a.event[j - 1]) {
-      rc = rewards_of(sv.x0);
+      rc = rewards_of(d_x0);
       if (!rc) {
         int* anc = d_anc + (size_t)e * nb;
         launch_steer_resample(d_reward, d_logw, d_rprev, G, a.P, sp.lambda, sp.ess_frac, d_u + (size_t)e * G, anc, d_flags, s);
@@ -756,70 +775,38 @@ int steered_host_run(fd_model* m, const SteeredHostRun& a) {
     i = j;
   }
   if (!rc) rc = rewards_of(w.x);  // the final state's
-  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
-  m->run_open = false;
-  m->run_t = -1;
-  StridedDev::clear(&m->dyn_host);
-  SteerDev::clear(&m->dyn_host);
-  send_dyn(m, s, m->dyn_host);
-  HIP_TRY(hipStreamSynchronize(s));
-  if (rc) return rc;
-  if (int rc_flag = check_flag(m)) return rc_flag;
-  HIP_TRY(hipMemcpy(a.out, d_out, n * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(a.terms_out, d_terms, nb * 4 * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(a.reward_out, d_reward, nb * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(a.logw_out, d_logw, nb * 8, hipMemcpyDeviceToHost));
-  if (a.ancestors_out && a.n_events > 0) HIP_TRY(hipMemcpy(a.ancestors_out, d_anc, ne * nb * 4, hipMemcpyDeviceToHost));
-  return FD_OK;
+  return r.finish(rc, {{a.terms_out, d_terms, nb * 4 * 8},
+                       {a.reward_out, d_reward, nb * 8},
+                       {a.logw_out, d_logw, nb * 8},
+                       {a.n_events > 0 ? a.ancestors_out : nullptr, d_anc, ne * nb * 4}});
 }
 
-// ---- repeat sampling: a strided run whose visits leave wrap(a x + b eps) -- the tables' row s is zero -- with
-// one tie launch (repeat_tie.hip) behind every visit, which averages the copies of a unit row and adds the visit's draw, the
-// same one to every copy.  The entry has checked every argument.  Returns with the stream drained and the strided fields
-// cleared, on the host and on the device, on every path behind begin_run: the tables die with this frame.
-int repeat_host_run(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int K, const float* coef,
-                    const float* noise, uint64_t seed, int64_t seq_offset, const int32_t* tie, float* out) {
-  HIP_TRY(hipSetDevice(m->device));
-  const int F = m->cfg.n_features;
-  const size_t n = (size_t)B * L * F;
-  DeviceBufs bufs;
-  float *d_x, *d_out;
-  const float* d_noise = nullptr;
-  int* d_lens;
+// ---- repeat sampling: a strided run whose visits leave wrap(a x + b eps) -- the tables' row s is zero, the draw
+// is the tie launch's -- with one tie launch (repeat_tie.hip) behind every visit, which averages the copies of a unit row and
+// adds the visit's draw, the same one to every copy.  The entry has checked every argument; a.states = K, final state only.
+int repeat_host_run(fd_model* m, const RunArrays& a, const int32_t* visits, const float* coef, const int32_t* tie) {
+  const int F = m->cfg.n_features, B = a.B, L = a.L, K = (int)a.states;
+  HostRun r(m, a);
+  if (int rc = r.stage()) return rc;
   const int* d_tie;
-  HIP_TRY(bufs.upload(x_init, n * 4, &d_x));
-  HIP_TRY(bufs.upload(lens, (size_t)B * 4, &d_lens));
-  HIP_TRY(bufs.upload(tie, (size_t)B * 3 * 4, &d_tie));
-  HIP_TRY(bufs.alloc(n * 4, &d_out));
-  if (noise) HIP_TRY(bufs.upload(noise, (size_t)K * n * 4, &d_noise));
-  std::vector<float> ab0(3 * (size_t)K, 0.f);  // a | b | 0: the draw is the tie launch's
-  memcpy(ab0.data(), coef, 2 * (size_t)K * 4);
-  StridedDev sd;
-  if (int rc = stage_strided(m, &bufs, visits, K, ab0.data(), &sd)) return rc;
-  if (int rc = begin_run(m, d_x, d_lens, B, L, visits[0], K, seed, seq_offset, d_out, 0, nullptr)) return rc;
+  HIP_TRY(r.bufs.upload(tie, (size_t)B * 3 * 4, &d_tie));
+  VisitTables tb;
+  if (int rc = stage_tables(m, &r.bufs, visits, K, {coef, coef + a.states, nullptr}, &tb)) return rc;
+  if (int rc = r.begin(visits[0], K)) return rc;
   hipStream_t s = m->stream;
   Workspace& w = m->ws;
-  sd.apply(&m->dyn_host);
+  tb.apply(&m->dyn_host);
   auto tie_state = [&](int init, float sz, const float* z, int t) -> int {
-    launch_repeat_tie(w.x, w.lens, d_tie, B, L, F, m->angle_mask, init, sz, z, seed, t, seq_offset, s);
+    launch_repeat_tie(w.x, w.lens, d_tie, B, L, F, m->angle_mask, init, sz, z, a.seed, t, a.seq_offset, s);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? fail(FD_E_HIP, "launch_repeat_tie: %s", hipGetErrorString(e)) : FD_OK;
   };
   int rc = tie_state(1, 0.f, nullptr, 0);  // the start point: every copy is copy 0
   for (int i = 0; !rc && i < K; ++i) {
     rc = fd_sample_steps_dev(m, 1, nullptr, 0, nullptr);
-    if (!rc) rc = tie_state(0, coef[2 * (size_t)K + i], d_noise ? d_noise + (size_t)i * n : nullptr, visits[i]);
+    if (!rc) rc = tie_state(0, coef[2 * a.states + i], r.noise ? r.noise + (size_t)i * r.n : nullptr, visits[i]);
   }
-  if (!rc) rc = fd_sample_end_dev(m, d_out, nullptr);
-  m->run_open = false;
-  m->run_t = -1;
-  StridedDev::clear(&m->dyn_host);
-  send_dyn(m, s, m->dyn_host);
-  HIP_TRY(hipStreamSynchronize(s));
-  if (rc) return rc;
-  if (int rc_flag = check_flag(m)) return rc_flag;
-  HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
-  return FD_OK;
+  return r.finish(rc);
 }
 
 }  // namespace
@@ -1028,23 +1015,22 @@ int fd_forward_ex(fd_model* m, const float* x, int t, const uint8_t* key_mask, c
 
 int fd_p_sample_step(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
                      float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_step_call(m, x, lens, x_out, B, L, t)) return rc;
   if (t > 0 && !z) return fail(FD_E_INVALID, "z is required for t > 0");
   if (int rc = check_lens(lens, B, L)) return rc;
-  return p_sample_step(m, x, t, lens, B, L, z, wrap, InpaintHost{}, nullptr, x_out);
+  return host_step(m, StepHost{x, t, lens, B, L, wrap, z}, StepMode{}, x_out, nullptr, nullptr);
 }
 
 int fd_p_sample_step_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, const float* z, int wrap,
                              const float* known, const uint8_t* fixed, const float* known_coef, const float* z_known,
                              float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_step_call(m, x, lens, x_out, B, L, t)) return rc;
   if (t > 0 && !z) return fail(FD_E_INVALID, "z is required for t > 0");
   if (t > 0 && !z_known) return fail(FD_E_INVALID, "z_known is required for t > 0");
   if (int rc = check_lens(lens, B, L)) return rc;
   if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  return p_sample_step(m, x, t, lens, B, L, z, wrap, InpaintHost{known, fixed, known_coef}, z_known, x_out);
+  return host_step(m, StepHost{x, t, lens, B, L, wrap, z, true, {known, fixed, known_coef}, t > 0 ? z_known : nullptr}, StepMode{}, x_out,
+                   nullptr, nullptr);
 }
 
 int fd_sample_begin_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, int t_start,
@@ -1116,36 +1102,29 @@ int fd_sample(fd_model* m, const float* x_init, const int32_t* lens, int B, int 
 
 int fd_sample_ex(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
                  uint64_t seed, int64_t seq_offset, float* out, int full_history) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
-  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
-  if (int rc = check_lens(lens, B, L)) return rc;
-  return host_run(m, HostRun{x_init, lens, B, L, t_start, noise, seed, seq_offset, out, full_history});
+  if (int rc = check_run_call(m, x_init, lens, out, B, L, t_start, full_history)) return rc;
+  return host_run(m, LadderRun{{x_init, lens, B, L, (size_t)t_start + 1, noise, nullptr, seed, seq_offset, out, full_history}, t_start});
 }
 
 int fd_sample_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start, const float* noise,
                       const float* known, const uint8_t* fixed, const float* known_coef, const float* known_noise,
                       uint64_t seed, int64_t seq_offset, float* out, int full_history) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
-  if (full_history < 0) return fail(FD_E_INVALID, "full_history = %d", full_history);
-  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_run_call(m, x_init, lens, out, B, L, t_start, full_history)) return rc;
   if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  return host_run(m, HostRun{x_init, lens, B, L, t_start, noise, seed, seq_offset, out, full_history, {known, fixed, known_coef}, known_noise});
+  return host_run(m, LadderRun{{x_init, lens, B, L, (size_t)t_start + 1, noise, known_noise, seed, seq_offset, out, full_history},
+                               t_start, {known, fixed, known_coef}});
 }
 
 int fd_sample_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, int t_start,
                                const float* known, const uint8_t* fixed, const float* known_coef, const int32_t* visits,
                                int n_visits, const float* jump_coef, uint64_t seed, int64_t seq_offset, float* out) {
-  if (int rc = check_shape(m, B, L, t_start)) return rc;
-  if (!x_init || !lens || !out) return fail(FD_E_INVALID, "null argument");
-  if (int rc = check_lens(lens, B, L)) return rc;
+  if (int rc = check_run_call(m, x_init, lens, out, B, L, t_start, 0)) return rc;
   if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  if (int rc = check_jump_tag(m)) return rc;
   int n_jumps = 0;
   if (int rc = check_visits(visits, n_visits, t_start, jump_coef, &n_jumps)) return rc;
-  return host_run(m, HostRun{x_init, lens, B, L, t_start, nullptr, seed, seq_offset, out, 0, {known, fixed, known_coef}, nullptr, visits,
-                             n_visits, jump_coef});
+  return host_run(m, LadderRun{{x_init, lens, B, L, (size_t)t_start + 1, nullptr, nullptr, seed, seq_offset, out, 0}, t_start,
+                               {known, fixed, known_coef}, visits, n_visits, jump_coef});
 }
 
 int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int L, int level_to, float jk, float js,
@@ -1154,7 +1133,7 @@ int fd_inpaint_jump(fd_model* m, const float* x, const int32_t* lens, int B, int
   if (int rc = check_shape(m, B, L, 0)) return rc;
   if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
   if (level_to < 1 || level_to > m->T) return fail(FD_E_INVALID, "level_to = %d outside [1, %d]", level_to, m->T);
-  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  if (int rc = check_jump_tag(m)) return rc;
   if (int rc = check_jump_coef(jk, js, 0)) return rc;
   if (int rc = check_lens(lens, B, L)) return rc;
   if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
@@ -1181,31 +1160,16 @@ int fd_sample_strided(fd_model* m, const float* x_init, const int32_t* lens, int
                       const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, float* out, int full_history) {
   if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, full_history)) return rc;
   if (int rc = check_lens(lens, B, L)) return rc;
-  return strided_run_host(m, x_init, lens, B, L, visits, n_visits, coef, false, noise, seed, seq_offset, out, full_history);
+  return strided_run_host(m, {x_init, lens, B, L, (size_t)n_visits, noise, nullptr, seed, seq_offset, out, full_history}, visits, coef, false);
 }
 
 int fd_p_sample_step_coef(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
                           const float* z, int wrap, float* eps_out, float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
-  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(s))
-    return fail(FD_E_INVALID, "a = %g, b = %g, s = %g: a coefficient is not finite", (double)a, (double)b, (double)s);
+  if (int rc = check_step_call(m, x, lens, x_out, B, L, t)) return rc;
+  if (int rc = check_finite_coef("abs", {a, b, s})) return rc;
   if (s != 0.f && !z) return fail(FD_E_INVALID, "z is required for s != 0");
   if (int rc = check_lens(lens, B, L)) return rc;
-  Call c;
-  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
-  Workspace& w = *c.ws;
-  if (s != 0.f) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
-  if (int rc = prepare_rows(m, c.s, 0)) return rc;
-  if (int rc = set_t(m, c.s, t)) return rc;
-  StepMode mode{};
-  mode.noise = w.z;
-  mode.t_start = t;
-  mode.no_wrap = !wrap;
-  mode.strided = true;
-  mode.sa = a; mode.sb = b; mode.ss = s;
-  if (int rc = run_step(m, c.s, mode)) return rc;
-  return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}});
+  return host_step(m, StepHost{x, t, lens, B, L, wrap, s != 0.f ? z : nullptr}, strided_mode(a, b, s), x_out, eps_out, nullptr);
 }
 
 int fd_sample_strided_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits,
@@ -1215,8 +1179,8 @@ int fd_sample_strided_inpaint(fd_model* m, const float* x_init, const int32_t* l
   if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, full_history)) return rc;
   if (int rc = check_lens(lens, B, L)) return rc;
   if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  return strided_host_run(m, StridedHostRun{x_init, lens, B, L, visits, n_visits, coef, noise, {known, fixed, known_coef}, known_noise,
-                                            seed, seq_offset, out, full_history});
+  return strided_host_run(m, StridedHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, known_noise, seed, seq_offset, out, full_history},
+                                            visits, coef, {known, fixed, known_coef}});
 }
 
 int fd_sample_strided_inpaint_resample(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* grid,
@@ -1226,44 +1190,28 @@ int fd_sample_strided_inpaint_resample(fd_model* m, const float* x_init, const i
   if (int rc = check_strided_call(m, x_init, lens, out, B, L, grid, n_grid, coef, 0)) return rc;
   if (int rc = check_lens(lens, B, L)) return rc;
   if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  if (m->T >= (1 << 30)) return fail(FD_E_UNSUPPORTED, "T = %d: the jump's stream is tagged with bit 30 of the step word", m->T);
+  if (int rc = check_jump_tag(m)) return rc;
   int n_jumps = 0;
   if (int rc = check_strided_visits(m, grid, n_grid, run, n_run, jump_coef, &n_jumps)) return rc;
-  return strided_host_run(m, StridedHostRun{x_init, lens, B, L, grid, n_grid, coef, nullptr, {known, fixed, known_coef}, nullptr, seed,
-                                            seq_offset, out, 0, run, n_run, jump_coef});
+  return strided_host_run(m, StridedHostRun{{x_init, lens, B, L, (size_t)n_grid, nullptr, nullptr, seed, seq_offset, out, 0}, grid, coef,
+                                            {known, fixed, known_coef}, run, n_run, jump_coef});
 }
 
 int fd_p_sample_step_coef_inpaint(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
                                   const float* z, int wrap, int level_out, const float* known, const uint8_t* fixed,
                                   const float* known_coef, const float* z_known, float* eps_out, float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
-  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(s))
-    return fail(FD_E_INVALID, "a = %g, b = %g, s = %g: a coefficient is not finite", (double)a, (double)b, (double)s);
+  if (int rc = check_step_call(m, x, lens, x_out, B, L, t)) return rc;
+  if (int rc = check_finite_coef("abs", {a, b, s})) return rc;
   if (s != 0.f && !z) return fail(FD_E_INVALID, "z is required for s != 0");
   if (level_out < 0 || level_out > m->T) return fail(FD_E_INVALID, "level_out = %d outside [0, %d]", level_out, m->T);
   if (level_out >= 1 && !z_known) return fail(FD_E_INVALID, "z_known is required for level_out >= 1");
   if (int rc = check_lens(lens, B, L)) return rc;
   if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  Call c;
-  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
-  Workspace& w = *c.ws;
-  if (s != 0.f) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
-  InpaintDev ip;
-  if (int rc = stage_inpaint(m, c.s, InpaintHost{known, fixed, known_coef}, &ip)) return rc;
-  if (level_out >= 1) HIP_TRY(hipMemcpyAsync(ip.z_known, z_known, c.n * 4, hipMemcpyHostToDevice, c.s));
-  if (int rc = prepare_rows(m, c.s, 0)) return rc;
-  if (int rc = set_t(m, c.s, t)) return rc;
-  StepMode mode{};
-  mode.noise = w.z;
-  mode.t_start = t;
-  mode.no_wrap = !wrap;
-  mode.strided = true;
-  mode.sa = a; mode.sb = b; mode.ss = s;
+  StepMode mode = strided_mode(a, b, s);
   mode.level_out = level_out;
-  ip.apply(&mode);
-  if (int rc = run_step(m, c.s, mode)) return rc;
-  return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}});
+  return host_step(m, StepHost{x, t, lens, B, L, wrap, s != 0.f ? z : nullptr, true, {known, fixed, known_coef},
+                               level_out >= 1 ? z_known : nullptr},
+                   mode, x_out, eps_out, nullptr);
 }
 
 int fd_sample_solver_dev(fd_model* m, const void* x_init_dev, const void* lens_dev, int B, int L, const int32_t* visits,
@@ -1276,16 +1224,13 @@ int fd_sample_solver(fd_model* m, const float* x_init, const int32_t* lens, int 
                      const float* coef, float* out, int full_history) {
   if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, full_history, true)) return rc;
   if (int rc = check_lens(lens, B, L)) return rc;
-  return strided_run_host(m, x_init, lens, B, L, visits, n_visits, coef, true, nullptr, 0, 0, out, full_history);
+  return strided_run_host(m, {x_init, lens, B, L, (size_t)n_visits, nullptr, nullptr, 0, 0, out, full_history}, visits, coef, true);
 }
 
 int fd_p_sample_step_solver(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float c, float u,
                             float v, const float* x0_prev, int wrap, float* eps_out, float* x0_out, float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out) return fail(FD_E_INVALID, "null argument");
-  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c) || !std::isfinite(u) || !std::isfinite(v))
-    return fail(FD_E_INVALID, "a = %g, b = %g, c = %g, u = %g, v = %g: a coefficient is not finite", (double)a, (double)b, (double)c,
-                (double)u, (double)v);
+  if (int rc = check_step_call(m, x, lens, x_out, B, L, t)) return rc;
+  if (int rc = check_finite_coef("abcuv", {a, b, c, u, v})) return rc;
   if (c != 0.f && !x0_prev) return fail(FD_E_INVALID, "x0_prev is required for c != 0");
   if (int rc = check_lens(lens, B, L)) return rc;
   HIP_TRY(hipSetDevice(m->device));
@@ -1297,56 +1242,31 @@ int fd_p_sample_step_solver(fd_model* m, const float* x, int t, const int32_t* l
   HIP_TRY(bufs.alloc(n * 4, &d_prev));
   HIP_TRY(bufs.alloc(n * 4, &d_x0));
   if (x0_prev) HIP_TRY(hipMemcpy(d_prev, x0_prev, n * 4, hipMemcpyHostToDevice));
-  Call cl;
-  if (int rc = open_call(m, x, lens, nullptr, B, L, &cl)) return rc;
-  Workspace& w = *cl.ws;
-  HIP_TRY(hipMemsetAsync(d_x0, 0, n * 4, cl.s));  // (a position the kernel does not take as a row is not written)
-  if (int rc = prepare_rows(m, cl.s, 0)) return rc;
-  if (int rc = set_t(m, cl.s, t)) return rc;
-  StepMode mode{};
-  mode.t_start = t;
-  mode.no_wrap = !wrap;
-  mode.strided = true;
-  mode.sa = a; mode.sb = b;
+  StepMode mode = strided_mode(a, b, 0.f);
   mode.sc = c; mode.su = u; mode.sv = v;
   mode.x0_prev = d_prev;
   mode.x0_out = d_x0;
-  if (int rc = run_step(m, cl.s, mode)) return rc;
-  return finish(m, cl.s, {{x_out, w.x, cl.n * 4}, {eps_out, w.eps, cl.n * 4}, {x0_out, d_x0, cl.n * 4}});
+  StepHost h{x, t, lens, B, L, wrap};
+  h.draws = false;
+  return host_step(m, h, mode, x_out, eps_out, x0_out);
 }
 
 int fd_p_sample_step_coef_x0(fd_model* m, const float* x, int t, const int32_t* lens, int B, int L, float a, float b, float s,
                              float u, float v, const float* z, int wrap, float* eps_out, float* x0_out, float* x_out) {
-  if (int rc = check_shape(m, B, L, t)) return rc;
-  if (!x || !lens || !x_out || !x0_out) return fail(FD_E_INVALID, "null argument");
-  if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(s) || !std::isfinite(u) || !std::isfinite(v))
-    return fail(FD_E_INVALID, "a = %g, b = %g, s = %g, u = %g, v = %g: a coefficient is not finite", (double)a, (double)b, (double)s,
-                (double)u, (double)v);
+  if (int rc = check_step_call(m, x, lens, x_out, B, L, t)) return rc;
+  if (!x0_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_finite_coef("absuv", {a, b, s, u, v})) return rc;
   if (s != 0.f && !z) return fail(FD_E_INVALID, "z is required for s != 0");
   if (int rc = check_lens(lens, B, L)) return rc;
   HIP_TRY(hipSetDevice(m->device));
-  const size_t n = (size_t)B * L * m->cfg.n_features;
   DeviceBufs bufs;
   float* d_x0;
-  HIP_TRY(bufs.alloc(n * 4, &d_x0));  // (before anything of this frame is queued)
-  Call c;
-  if (int rc = open_call(m, x, lens, nullptr, B, L, &c)) return rc;
-  Workspace& w = *c.ws;
-  HIP_TRY(hipMemsetAsync(d_x0, 0, n * 4, c.s));  // (a position the kernel does not take as a row is not written)
-  if (s != 0.f) HIP_TRY(hipMemcpyAsync(w.z, z, c.n * 4, hipMemcpyHostToDevice, c.s));
-  if (int rc = prepare_rows(m, c.s, 0)) return rc;
-  if (int rc = set_t(m, c.s, t)) return rc;
-  StepMode mode{};
-  mode.noise = w.z;
-  mode.t_start = t;
-  mode.no_wrap = !wrap;
-  mode.strided = true;
-  mode.sa = a; mode.sb = b; mode.ss = s;
+  HIP_TRY(bufs.alloc((size_t)B * L * m->cfg.n_features * 4, &d_x0));  // (before anything of this frame is queued)
+  StepMode mode = strided_mode(a, b, s);
   mode.su = u; mode.sv = v;
   mode.x0_out = d_x0;
   mode.x0_only = true;
-  if (int rc = run_step(m, c.s, mode)) return rc;
-  return finish(m, c.s, {{x_out, w.x, c.n * 4}, {eps_out, w.eps, c.n * 4}, {x0_out, d_x0, c.n * 4}});
+  return host_step(m, StepHost{x, t, lens, B, L, wrap, s != 0.f ? z : nullptr}, mode, x_out, eps_out, x0_out);
 }
 
 int fd_sample_steered(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
@@ -1354,10 +1274,7 @@ int fd_sample_steered(fd_model* m, const float* x_init, const int32_t* lens, int
                       int n_particles, const fd_steer_params* params, const double* u, float* out, double* terms_out,
                       double* reward_out, double* logw_out, int32_t* ancestors_out) {
   if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;  // (rows a | b | s too)
-  for (int r = 3; r < 5; ++r)
-    for (int i = 0; i < n_visits; ++i)
-      if (!std::isfinite(coef[(size_t)r * n_visits + i]))
-        return fail(FD_E_INVALID, "coef[%d][%d] = %g is not finite", r, i, (double)coef[(size_t)r * n_visits + i]);
+  if (int rc = check_coef_rows(coef, n_visits, 3, 5)) return rc;
   if (!event || !u || !params) return fail(FD_E_INVALID, "null argument: event, u and params are required");
   if (!terms_out || !reward_out || !logw_out) return fail(FD_E_INVALID, "null argument: terms_out, reward_out and logw_out are required");
   if (n_particles < 1 || n_particles > kSteerMaxParticles)
@@ -1376,8 +1293,8 @@ int fd_sample_steered(fd_model* m, const float* x_init, const int32_t* lens, int
   int n_events = 0;
   for (int i = 0; i < n_visits; ++i) n_events += event[i] ? 1 : 0;
   if (int rc = check_steer_u(u, (size_t)n_events * (size_t)(B / n_particles))) return rc;
-  return steered_host_run(m, SteeredHostRun{x_init, lens, B, L, visits, n_visits, coef, noise, seed, seq_offset, event, n_events,
-                                            n_particles, params, u, out, terms_out, reward_out, logw_out, ancestors_out});
+  return steered_host_run(m, SteeredHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, nullptr, seed, seq_offset, out, 0}, visits, coef,
+                                            event, n_events, n_particles, params, u, terms_out, reward_out, logw_out, ancestors_out});
 }
 
 int fd_sample_repeat(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
@@ -1386,7 +1303,7 @@ int fd_sample_repeat(fd_model* m, const float* x_init, const int32_t* lens, int 
   if (!tie) return fail(FD_E_INVALID, "null argument: tie is required");
   if (int rc = check_lens(lens, B, L)) return rc;
   if (int rc = check_tie(tie, lens, B)) return rc;
-  return repeat_host_run(m, x_init, lens, B, L, visits, n_visits, coef, noise, seed, seq_offset, tie, out);
+  return repeat_host_run(m, {x_init, lens, B, L, (size_t)n_visits, noise, nullptr, seed, seq_offset, out, 0}, visits, coef, tie);
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

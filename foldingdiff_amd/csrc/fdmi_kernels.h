@@ -78,6 +78,15 @@ struct UpdateDyn {
   const float* uv;             // [2, T] rows u | v of the visit, indexed by t like `abs`
   float* x0_steer;             // [M, F] the visit's prediction, indexed like x (packed rows too); never set together with cuv
 };
+// Every pointer member above that a run family sets for one run (`noise` and `hist` are rewritten by every run's opening and
+// every step segment): back to null, so that a closed run leaves nothing pointing into its call-lifetime buffers.  A new
+// per-run pointer member belongs here.
+inline void clear_run_pointers(UpdateDyn* d) {
+  d->known = nullptr; d->fixed = nullptr; d->known_noise = nullptr; d->known_coef = nullptr;
+  d->next_t = nullptr; d->ord = nullptr; d->abs = nullptr;
+  d->cuv = nullptr; d->x0_prev = nullptr;
+  d->uv = nullptr; d->x0_steer = nullptr;
+}
 struct UpdateArgs {
   const UpdateDyn* dyn;  // device pointer; when non-null it overrides noise/hist/seed/seq_offset/t_start
   const float* g;        // [M, d]

@@ -6,7 +6,8 @@ A model handle keeps state between calls ("What a handle carries be
 after a call A on one handle and compare B's result BIT FOR BIT with the same call made first on a fresh handle.  So that a
 stale row table, a stale key / value slot or a stale graph can show, every kind has its own lengths: a distinct permutation
 of LENGTHS.  Two different permutations of the same numbers differ somewhere upwards and somewhere downwards, so for any
-ordered pair of kinds some sequence gets shorter and some gets longer.
+ordered pair of kinds some sequence gets shorter and some gets longer.  (One kind, "steered", cannot have a permutation: its
+particles share a length.  What it keeps of the rule is stated at STEERED_LEN.)
 """
 import itertools
 
@@ -38,16 +39,49 @@ KINDS = (
     ("loss_ex", True),                      # fd_denoise_loss_ex with the pairwise term
     ("run_left_open", False),               # fd_sample_begin_dev + two steps, never ended
     ("refused", False),                     # calls refused for an argument error
+    # the run families and step hooks that came later (appended: lens_of goes by index, the kinds above keep their lengths).
+    # Their grids are the three visits 3, 1, 0 of "strided"
+    ("solver", True),                       # fd_sample_solver, every state
+    ("strided_inpaint", True),              # fd_sample_strided_inpaint, no jumps, the caller's known_noise, every state
+    ("steered", True),                      # fd_sample_steered, two events, ONE group of five particles (see lens_of)
+    ("repeat", True),                       # fd_sample_repeat, the caller's draws
+    ("step_coef_inpaint", True),            # fd_p_sample_step_coef_inpaint
+    ("step_solver", True),                  # fd_p_sample_step_solver, c != 0
+    ("step_coef_x0", True),                 # fd_p_sample_step_coef_x0
 )
 A_KINDS = tuple(k for k, _ in KINDS)
 B_KINDS = tuple(k for k, second in KINDS if second)
+LATER_KINDS = A_KINDS[A_KINDS.index("refused") + 1:]
+# The matrix of 25 x 23 kinds makes twice the calls of the 18 x 16 it was, so the later kinds run under three of the five plans
+# (DESIGN.md 2): the default, both fusions off, and several items per workgroup
+LATER_PLANS = ("auto", "unfused", "attn1_ffn2_grid2")
 
 _PERMS = sorted(itertools.permutations(LENGTHS))
+# fd_sample_steered wants one length per particle group, and B = 5 is one group of five or five groups of one (no steering): the
+# kind stays on the (5, 101) workspace every other kind uses, with all five lengths at 64 -- 5 * 64 = 320 packed rows like the
+# others.  Against any permutation of LENGTHS some sequence still gets shorter and some longer, either way round; of the five
+# edges it cannot cross leaves_96 as a first call, nor leaves_tile and enters_96 as a second (STEERED_EDGES)
+STEERED_LEN = 64
+STEERED_EDGES = {"first": ("rows_shrink", "rows_grow", "leaves_tile", "enters_96"), "second": ("rows_shrink", "rows_grow", "leaves_96")}
 
 
 def lens_of(kind: str) -> tuple:
-    """The kind's lengths: permutation 7 i (mod 120) of the sorted list, i = the kind's index (7 and 120 are coprime)."""
+    """The kind's lengths: permutation 7 i (mod 120) of the sorted list, i = the kind's index (7 and 120 are coprime); the
+    one exception is "steered", whose five particles share STEERED_LEN."""
+    if kind == "steered":
+        return (STEERED_LEN,) * B
     return _PERMS[(7 * A_KINDS.index(kind)) % len(_PERMS)]
+
+
+def kinds_under(plan: str, kinds: tuple) -> tuple:
+    """`kinds` without the later ones under a plan that does not run them."""
+    return tuple(k for k in kinds if plan in LATER_PLANS or k not in LATER_KINDS)
+
+
+def repeat_ties(lens) -> tuple:
+    """(start, period, units) per sequence of the "repeat" kind: three units behind a lead-in row, whatever the length
+    (7: rows 1 .. 6 in units of 2; 101: rows 1 .. 99 in units of 33)."""
+    return tuple((1, (n - 1) // 3, 3) for n in lens)
 
 
 # the reduced matrices of the other models

@@ -10,11 +10,26 @@ def test_every_kind_has_its_own_permutation_of_the_lengths():
     seen = {}
     for kind in cases.A_KINDS:
         lens = cases.lens_of(kind)
-        assert sorted(lens) == sorted(cases.LENGTHS), kind
+        if kind == "steered":     # one group of five particles: one length, inside the range of the others and with their 320 rows
+            assert lens == (cases.STEERED_LEN,) * cases.B and min(cases.LENGTHS) < cases.STEERED_LEN < max(cases.LENGTHS)
+            assert cases.STEERED_LEN in cases.LENGTHS and cases.B * cases.ceil8(cases.STEERED_LEN) == 320
+        else:
+            assert sorted(lens) == sorted(cases.LENGTHS), kind
         assert lens not in seen, (kind, seen.get(lens))
         seen[lens] = kind
     assert set(cases.B_KINDS) < set(cases.A_KINDS) and set(cases.A_KINDS) - set(cases.B_KINDS) == {"run_left_open", "refused"}
-    assert len(cases.A_KINDS) == 18 and len(cases.B_KINDS) == 16
+    assert len(cases.A_KINDS) == 25 and len(cases.B_KINDS) == 23
+    # the kinds that were there first keep their place, and with it their lengths
+    assert cases.A_KINDS[:18] == ("forward", "forward_t", "forward_ex", "step", "step_inpaint", "step_coef", "run_history", "run_packed",
+                                  "run_host_noise", "inpaint", "inpaint_resample", "strided", "strided_inpaint_resample", "ar_forward",
+                                  "ar_sample", "loss_ex", "run_left_open", "refused")
+    assert cases.LATER_KINDS == ("solver", "strided_inpaint", "steered", "repeat", "step_coef_inpaint", "step_solver", "step_coef_x0")
+    assert set(cases.LATER_PLANS) < set(cases.PLANS)
+    for plan in cases.PLANS:
+        got = cases.kinds_under(plan, cases.B_KINDS)
+        assert got == (cases.B_KINDS if plan in cases.LATER_PLANS else cases.B_KINDS[:16]), plan
+    for n, (start, period, units) in zip(cases.lens_of("repeat"), cases.repeat_ties(cases.lens_of("repeat"))):
+        assert start >= 0 and period >= 1 and units >= 2 and start + period * units <= n, (n, start, period, units)
     for reduced in (cases.WIDE_KINDS, cases.ABS_KINDS, cases.F32_REFUSED):
         assert set(reduced) <= set(cases.B_KINDS)
     assert max(cases.LENGTHS) == cases.L <= 128 and max(cases.LENGTHS) < cases.T     # (fd_ar_*: seq_lengths < T)
@@ -43,14 +58,15 @@ def test_the_pairs_include_every_edge_for_every_first_kind():
                 met |= {e for e in edges if tr[e]}
                 for e in edges:
                     count[e] += tr[e]
-        assert met == set(edges), (a, set(edges) - met)
+        # (five equal lengths cannot cross every edge: "steered" crosses the ones call_history_cases.STEERED_EDGES names)
+        assert met == set(cases.STEERED_EDGES["first"] if a == "steered" else edges), (a, set(edges) - met)
     for b in cases.B_KINDS:
         met = set()
         for a in cases.A_KINDS:
             if a != b:
                 tr = cases.transitions(cases.lens_of(a), cases.lens_of(b))
                 met |= {e for e in edges if tr[e]}
-        assert met == set(edges), (b, set(edges) - met)
+        assert met == set(cases.STEERED_EDGES["second"] if b == "steered" else edges), (b, set(edges) - met)
     n_pairs = len(cases.A_KINDS) * len(cases.B_KINDS) - len(cases.B_KINDS)
     assert all(c >= n_pairs // 2 for c in count.values()), (count, n_pairs)     # and most pairs do
 

@@ -15,6 +15,12 @@ Every element of every output is compared -- every entry here defines all of the
 every position, masked ones included; a padded run evolves every position; a packed run (varlen = 1) leaves x_init at and
 behind a length in the final state and zeros in the history rows; fd_ar_sample returns the seed at and behind
 max(seq_lengths).  The outputs start at a sentinel and the solo check finds none left.
+
+The run families and step hooks that came after the first matrix -- the solver, the strided conditioned run without jumps,
+the steered run, the repeat run, fd_p_sample_step_coef_inpaint, _solver and _coef_x0 -- are kinds of their own
+(cases.LATER_KINDS), under three of the five plans (cases.LATER_PLANS).  They are the paths that share one close
+(api_run.hip: close_run), and what the matrix checks for them is that nothing of a finished run of any family is left on
+the handle or in the device's UpdateDyn for the next call of any other.
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -26,14 +32,18 @@ import torch
 import ar_reference
 import call_history_cases as cases
 import inpaint_reference as ipr
+import solver_reference as vref
+import strided_inpaint_reference as sir
 import strided_reference as sref
 from foldingdiff_amd import _binding, beta_schedules, losses, modelling, sampling
 from oracle import ref_sampling
 from test_gpu_parity import FWD_TOL, STEP_TOL, _inputs, _mask, _pair
 from test_inpaint_gpu import ANG, F, _bits, _masks, _sample_inpaint
 from test_resample_gpu import _resample
+from test_solver_gpu import _solver, _step_solver
+from test_steer_gpu import _params, _steered, _step_x0
 from test_strided_gpu import SENTINEL, _step_coef, _strided
-from test_strided_inpaint_gpu import _strided_resample
+from test_strided_inpaint_gpu import _step_coef_inpaint, _strided_inpaint, _strided_resample
 
 pytestmark = pytest.mark.gpu
 P = _binding.ptr
@@ -63,8 +73,11 @@ def _const():
         visits = np.array([3, 2, 1, 2, 1, 0], dtype=np.int32)           # one jump: from level 1 back to level 3
         _CONST.update(betas=betas, kcoef=sampling.inpaint_levels(betas), grid=grid, coef=sampling.ddim_coefficients(betas, grid, 1.0),
                       rgrid=rgrid, rcoef=sampling.ddim_coefficients(betas, rgrid, 0.5), run=run,
-                      rjc=sampling.strided_jump_coef(betas, rgrid, run), visits=visits, jc=sampling.resample_jump_coef(betas, visits))
+                      rjc=sampling.strided_jump_coef(betas, rgrid, run), visits=visits, jc=sampling.resample_jump_coef(betas, visits),
+                      scoef=sampling.solver_coefficients(betas, grid), stcoef=sampling.steer_coefficients(betas, grid, 1.0),
+                      event=np.array([1, 0, 1], dtype=np.uint8), steer=_params())
         assert len(_CONST["jc"]) == 1 and len(_CONST["rjc"]) == 1 and (_CONST["coef"][2, :-1] != 0).all()
+        assert _CONST["scoef"][2, 1] != 0 and np.array_equal(_CONST["stcoef"][:3], _CONST["coef"])     # the middle visit has a c
     return SimpleNamespace(**_CONST)
 
 
@@ -138,6 +151,12 @@ def _case(kind, lens, nb=B, nl=L, salt=0, absolute=False):
     k = _const().kcoef
     c.keep, c.spread = np.ascontiguousarray(k[0, c.tv + 1]), np.ascontiguousarray(k[1, c.tv + 1])
     c.pair_coef = np.ascontiguousarray(np.linspace(0.5, 1.5, nb).astype(np.float32))
+    # the later kinds (drawn last: the inputs above are what they were): the replacement's draws of a three-visit grid's four
+    # levels, the three visits' draws, the uniforms of two events for one group, the ties
+    n_grid = len(_const().grid)
+    c.knoise, c.gnoise = rn(n_grid + 1, nb, nl, F), rn(n_grid, nb, nl, F)
+    c.u = np.ascontiguousarray(torch.rand(2, 1, generator=g, dtype=torch.float64).numpy())
+    c.ties = np.ascontiguousarray(np.asarray(cases.repeat_ties(lens), dtype=np.int32))
     return c
 
 
@@ -286,9 +305,55 @@ def _k_refused(H, c):
     return 0, {}
 
 
+def _k_solver(H, c):
+    k = _const()
+    rc, out = _solver(H.h, c.x, c.lens_list, k.grid, k.scoef, 1)
+    return rc, {"x": out}
+
+
+def _k_strided_inpaint(H, c):
+    k = _const()
+    rc, out = _strided_inpaint(H.h, c.x, c.lens_list, k.grid, k.coef, c.known, c.fixed, k.kcoef, c.seed, 1, known_noise=c.knoise)
+    return rc, {"x": out}
+
+
+def _k_steered(H, c):
+    """One group of five particles, events behind the first and the last visit."""
+    k = _const()
+    rc, out, terms, reward, logw, anc = _steered(H.h, c.x, c.lens_list, k.grid, k.stcoef, None, c.seed, k.event, c.B, k.steer, c.u)
+    return rc, {"x": out, "terms": terms, "reward": reward, "logw": logw, "ancestors": anc}
+
+
+def _k_repeat(H, c):
+    k = _const()
+    out = _new(c)
+    rc = _lib().fd_sample_repeat(H.h, P(c.x), P(c.lens), c.B, c.L, P(k.grid), len(k.grid), P(k.coef), P(c.gnoise), C.c_uint64(c.seed),
+                                 C.c_int64(0), P(c.ties), P(out))
+    return rc, {"x": out}
+
+
+def _k_step_coef_inpaint(H, c):
+    k = _const()
+    a, b, s = k.coef[:, 0]
+    rc, eps, out = _step_coef_inpaint(H.h, c.x, T_START, c.lens_list, a, b, s, c.z, int(k.grid[1]) + 1, c.known, c.fixed, k.kcoef, c.zk)
+    return rc, {"eps": eps, "x": out}
+
+
+def _k_step_solver(H, c):
+    """The middle visit of the grid: the one whose c is not 0, so the previous prediction (c.known stands in) is read."""
+    k = _const()
+    rc, eps, x0, out = _step_solver(H.h, c.x, int(k.grid[1]), c.lens_list, *k.scoef[:, 1], c.known)
+    return rc, {"eps": eps, "x0": x0, "x": out}
+
+
+def _k_step_coef_x0(H, c):
+    rc, eps, x0, out = _step_x0(H.h, c.x, T_START, c.lens_list, *_const().stcoef[:, 0], c.z)
+    return rc, {"eps": eps, "x0": x0, "x": out}
+
+
 RUN = {k: globals()["_k_" + k] for k in cases.A_KINDS}
 FORWARD_KINDS = ("forward", "forward_t", "forward_ex", "ar_forward", "loss_ex")
-STEP_KINDS = ("step", "step_inpaint", "step_coef")
+STEP_KINDS = ("step", "step_inpaint", "step_coef", "step_coef_inpaint", "step_solver", "step_coef_x0")
 
 
 def _same(got, want):
@@ -349,23 +414,36 @@ def _oracle_gap(model, kind, c, out):
         elif kind == "step_coef":
             a, b, s = k.coef[:, 0]
             want = sref.update(c.x, sref.forward(o32, c.x, T_START, c.lens_list).numpy(), a, b, s, c.z, ANG)
+        elif kind == "step_coef_inpaint":
+            a, b, s = k.coef[:, 0]
+            want = sir.visit(c.x, sref.forward(o32, c.x, T_START, c.lens_list).numpy(), a, b, s, c.z, c.known, c.fixed, int(k.grid[1]) + 1,
+                             k.kcoef, c.zk, ANG)
+        elif kind == "step_solver":
+            want = vref.update(c.x, sref.forward(o32, c.x, int(k.grid[1]), c.lens_list).numpy(), c.known, *k.scoef[:, 1], ANG)[0]
+        elif kind == "step_coef_x0":    # the state is fd_p_sample_step_coef's: the prediction of the clean state is a further output
+            a, b, s = k.stcoef[:3, 0]
+            want = sref.update(c.x, sref.forward(o32, c.x, T_START, c.lens_list).numpy(), a, b, s, c.z, ANG)
     if kind in STEP_KINDS:
         return float(ref_sampling.circ_dist(out["x"], want).max()), STEP_TOL
     return float(np.abs(out["eps"].astype(np.float64) - want).max()), FWD_TOL
 
 
-def _kinds_of(model):
-    return {"main": cases.B_KINDS, "wide": cases.WIDE_KINDS, "abs": cases.ABS_KINDS, "f32": cases.B_KINDS}[model]
+def _kinds_of(model, plan="auto"):
+    """The second kinds of a model's matrix under a plan, in KINDS' order (the later kinds: under cases.LATER_PLANS only)."""
+    kinds = {"main": cases.B_KINDS, "wide": cases.WIDE_KINDS, "abs": cases.ABS_KINDS, "f32": cases.B_KINDS}[model]
+    return cases.kinds_under(plan, kinds)
 
 
-def _first_kinds_of(model):
-    return _kinds_of(model) + (("run_left_open", "refused") if model in ("main", "f32") else ())
+def _first_kinds_of(model, plan="auto"):
+    if model not in ("main", "f32"):
+        return _kinds_of(model, plan)
+    return cases.kinds_under(plan, cases.A_KINDS)
 
 
 @pytest.mark.parametrize("model,plan", [("main", p) for p in cases.PLANS] + [("wide", "auto"), ("abs", "auto"), ("f32", "auto")])
 def test_solo_results_are_reproducible_and_not_vacuous(gpu, model, plan):
     results = {}
-    for kind in _kinds_of(model):
+    for kind in _kinds_of(model, plan):
         rc, out = _solo(model, plan, kind)
         if _refused_by(model, kind):
             assert rc == UNSUPPORTED, (kind, rc, _lib().fd_last_error())
@@ -384,7 +462,7 @@ def test_solo_results_are_reproducible_and_not_vacuous(gpu, model, plan):
             print(f"{model} {plan} {kind}: {gap:.3e} against the fp32 oracle (bound {tol:g})")
             assert gap <= tol, (kind, gap)
     if model == "f32":
-        assert set(_kinds_of(model)) - set(results) == set(cases.F32_REFUSED)
+        assert set(_kinds_of(model, plan)) - set(results) == set(cases.F32_REFUSED)
     main = lambda o: o["x"] if "x" in o else o["eps"] if "eps" in o else o["out"]   # noqa: E731
     for a in results:
         for b in results:
@@ -400,7 +478,7 @@ def test_solo_results_are_reproducible_and_not_vacuous(gpu, model, plan):
 def _row(model, plan, a):
     """One handle; for every second kind b: a, then b, and b carries its solo bits.  The history accumulates on purpose.
     Where a itself has a solo result it is compared too (it follows the previous b)."""
-    seconds = _kinds_of(model)
+    seconds = _kinds_of(model, plan)
     for b in seconds:      # the solo results first: at most one other handle alive while the row's own is
         _solo(model, plan, b)
     if a in seconds:
@@ -422,9 +500,9 @@ def _row(model, plan, a):
             assert diff == "", f"{model} / {plan}: {b} after {a} is not its solo result: {diff}"
 
 
-@pytest.mark.parametrize("plan", list(cases.PLANS))
-@pytest.mark.parametrize("a", cases.A_KINDS)
+@pytest.mark.parametrize("a,plan", [(a, plan) for plan in cases.PLANS for a in _first_kinds_of("main", plan)])
 def test_transition_matrix_row(gpu, a, plan):
+    """25 first kinds x 23 second kinds under the plans of cases.LATER_PLANS, the 18 x 16 that came first under the other two."""
     _row("main", plan, a)
 
 
