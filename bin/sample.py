@@ -11,6 +11,11 @@ reference's ``bin/sample.py`` (same flags, same files):
     with --psea: plots/ss_cooccurrence_sampled.json  {generated_{i}.pdb: [n_alpha, n_beta]} of the final backbones and
                  plots/ss_cooccurrence_sampled.pdf   their 2-D histogram, when matplotlib is installed (:456-469)
 
+    with --dssp: dssp.json  {generated_{i}.pdb: {"dssp": the DSSP label string, "n_hbonds": kept backbone hydrogen bonds,
+                 "n_helix": runs of H, "n_strand": runs of E, "hbonds_per_residue": n_hbonds / residues}} of the final backbones,
+                 oxygens placed on the device (structures.add_oxygens, structures.dssp: DESIGN.md 6t); without --dssp the
+                 output tree is unchanged
+
     with --clashes: clash_counts.json               {generated_{i}.pdb: van der Waals clash count} of the final backbones
                     (structures.count_clashes on the coordinates as written: what bin/vdw_clashes.py gives on the files;
                     without --clashes the output tree is unchanged)
@@ -79,6 +84,8 @@ def build_parser() -> argparse.ArgumentParser:
     psea.add_argument("--psea", action="store_true",
                       help="count the helices and strands of the sampled backbones (P-SEA on the device) into plots/ss_cooccurrence_sampled.json [.pdf]")
     psea.add_argument("--nopsea", action="store_true", help="accepted for compatibility: the P-SEA step runs only with --psea")
+    parser.add_argument("--dssp", action="store_true",
+                        help="label the sampled backbones with DSSP states from their backbone hydrogen bonds (on the device) into dssp.json")
     parser.add_argument("--clashes", action="store_true",
                         help="count the van der Waals clashes of the sampled backbones (on the device) into clash_counts.json")
     parser.add_argument("--num_steps", type=int, default=None,
@@ -186,6 +193,17 @@ def main(argv=None) -> None:
             counts = structures.count_secondary_structures([coords_as_written(xyz[1::3]) for _, xyz in kept], device=device_index)
             structures.write_ss_cooccurrence([name for name, _ in kept], counts, json_file=str(plotdir / "ss_cooccurrence_sampled.json"),
                                              outpdf=str(plotdir / "ss_cooccurrence_sampled.pdf"), title="Secondary structure co-occurrence, sampled")
+        if args.dssp:
+            # the three-decimal coordinates of the files just written, oxygens added on the device
+            kept = [(os.path.basename(f), xyz) for f, xyz in zip(pdb_files, final_coords) if f]
+            device_index = torch.device(args.device).index or 0
+            chains = structures.add_oxygens([coords_as_written(xyz) for _, xyz in kept], device=device_index)
+            labels = structures.dssp(chains, device=device_index)
+            counts = structures.dssp_counts(chains, device=device_index)
+            with open(outdir / "dssp.json", "w") as sink:
+                json.dump({name: {"dssp": "".join(lab), "n_hbonds": int(c[0]), "n_helix": int(c[1]), "n_strand": int(c[2]),
+                                  "hbonds_per_residue": int(c[0]) / len(lab)}
+                           for (name, _), lab, c in zip(kept, labels, counts)}, sink, indent=4)
         if args.clashes:
             # what bin/vdw_clashes.py counts on the files just written: their three-decimal coordinates as float32
             kept = [(os.path.basename(f), xyz) for f, xyz in zip(pdb_files, final_coords) if f]

@@ -111,6 +111,8 @@ _SIGNATURES = {
     "fd_superpose_rmsd": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "fd_tm_score": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "fd_annotate_sse": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "fd_backbone_oxygens": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "fd_dssp": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "fd_tm_align": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fd_tm_align_ex": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P]),
     "fd_backbone_clashes": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_double, _P, _P]),

@@ -70,6 +70,31 @@ def write_coords_to_pdb(coords: np.ndarray, out_fname: str) -> str:
     return out_fname
 
 
+def write_backbone_with_o_pdb(coords4: np.ndarray, out_fname: str) -> str:
+    """Write [n, 4, 3] backbone coordinates (N, CA, C, O per residue: ``structures.add_oxygens``) as a PDB file in
+    ``write_coords_to_pdb``'s column layout, O after C; a residue whose O is NaN (a chain's last) gets no O record.
+    CONECT records join each C to the next residue's N.  Returns ``out_fname``."""
+    coords4 = np.asarray(coords4, dtype=np.float64)
+    assert coords4.ndim == 3 and coords4.shape[1:] == (4, 3), f"Expected [n, 4, 3] coords, got {coords4.shape}"
+    lines, c_ids, n_ids = [], [], []
+    serial = 0
+    for r, residue in enumerate(coords4):
+        for (name, element), (x, y, z) in zip(_ATOMS + (("O", "O"),), residue):
+            if name == "O" and np.isnan([x, y, z]).any():
+                continue
+            serial += 1
+            (n_ids if name == "N" else c_ids if name == "C" else []).append(serial)
+            lines.append(
+                f"ATOM  {((serial - 1) % 99999 + 1):>5d}  {name:<3} GLY A{(r % 9999 + 1):>4d}    "
+                f"{x:>8.3f}{y:>8.3f}{z:>8.3f}{1.0:>6.2f}{5.0:>6.2f}          {element:>2}  ")
+    for c, n in zip(c_ids[:-1], n_ids[1:]):   # peptide bonds, both directions
+        lines.append(f"CONECT{c:>5d}{n:>5d}")
+        lines.append(f"CONECT{n:>5d}{c:>5d}")
+    with open(out_fname, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return out_fname
+
+
 def read_pdb_backbone(fname: str) -> np.ndarray:
     """[3N, 3] coordinates of the ATOM records of a backbone PDB (fixed columns 31-54)."""
     out = []

@@ -1,4 +1,4 @@
-// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
+// C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, dssp.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
 // the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) and of the steering kernels on their own (steer.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
@@ -92,6 +92,46 @@ int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, con
   return device_roundtrip(device_id, {{ca, na * 3 * 8}, {offsets, nc * 4}, {lens, nc * 4}},
                           {{sse_out, na}, {counts_out, nc * 2 * 4}}, [&](const RoundtripBufs& d) {
                             launch_psea(d.in(0), d.in(1), d.in(2), n_chains, max_len, d.out(0), d.out(1), nullptr);
+                          });
+}
+
+int fd_backbone_oxygens(int device_id, const double* nca_c, const int32_t* offsets, const int32_t* lens, int n_chains,
+                        int reference_torsion, double* out) {
+  if (!nca_c || !offsets || !lens || !out) return fail(FD_E_INVALID, "null argument");
+  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
+  if (int rc = check_lens(lens, n_chains, FDMI_DSSP_MAX_LEN)) return rc;
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 12, &n_res)) return rc;
+  if (int rc = check_backbone(nca_c, offsets, lens, n_chains, 3)) return rc;
+  const size_t nr = (size_t)n_res, nc = (size_t)n_chains;
+  return device_roundtrip(device_id, {{nca_c, nr * 9 * 8}, {offsets, nc * 4}, {lens, nc * 4}}, {{out, nr * 12 * 8}},
+                          [&](const RoundtripBufs& d) {
+                            launch_backbone_oxygens(d.in(0), d.in(1), d.in(2), n_chains, reference_torsion, d.out(0), nullptr);
+                          });
+}
+
+int fd_dssp(int device_id, const double* bb, const uint8_t* flags, const int32_t* offsets, const int32_t* lens, int n_chains,
+            int8_t* state_out, int32_t* acc_out, double* energy_out, int32_t* counts_out) {
+  if (!bb || !offsets || !lens || !state_out) return fail(FD_E_INVALID, "null argument");
+  if ((acc_out == nullptr) != (energy_out == nullptr))
+    return fail(FD_E_INVALID, "null argument: acc_out and energy_out go together");
+  if (n_chains < 1) return fail(FD_E_INVALID, "n_chains=%d must be >= 1", n_chains);
+  int max_len = 0;
+  if (int rc = check_lens(lens, n_chains, FDMI_DSSP_MAX_LEN, &max_len)) return rc;
+  long long n_res = 0;
+  if (int rc = check_packed(offsets, lens, n_chains, 0x7fffffffLL / 12, &n_res)) return rc;
+  if (int rc = check_backbone(bb, offsets, lens, n_chains, 4, 3)) return rc;
+  const size_t nr = (size_t)n_res, nc = (size_t)n_chains;
+  static const uint8_t no_flags = 0;
+  return device_roundtrip(device_id, {{bb, nr * 12 * 8}, {offsets, nc * 4}, {lens, nc * 4}, {flags ? flags : &no_flags, flags ? nr : 1}},
+                          {{state_out, nr}, {acc_out, acc_out ? nr * 2 * 4 : 4}, {energy_out, energy_out ? nr * 2 * 8 : 8},
+                           {counts_out, nc * 3 * 4}},
+                          [&](const RoundtripBufs& d) {
+                            const unsigned char* flags_dev = d.in(3);
+                            int* acc_dev = d.out(1);
+                            double* energy_dev = d.out(2);
+                            launch_dssp(d.in(0), flags ? flags_dev : nullptr, d.in(1), d.in(2), n_chains, max_len, d.out(0),
+                                        acc_out ? acc_dev : nullptr, acc_out ? energy_dev : nullptr, d.out(3), nullptr);
                           });
 }
 

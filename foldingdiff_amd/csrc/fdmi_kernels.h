@@ -173,6 +173,16 @@ hipError_t launch_tm_score(const double* a, const double* b, const double* cent,
 // of LDS per residue).
 void launch_psea(const double* ca, const int* offsets, const int* lens, int n_chains, int max_len, signed char* sse_out,
                  int* counts_out, hipStream_t s);
+// Backbone oxygens (dssp.hip), one workgroup per chain: out [sum lens][4][3] = N, CA, C of nca_c [sum lens][3][3] copied, then O
+// (NaN on a chain's last residue); reference_torsion != 0 places O at the next N's torsion instead of trans to it.
+void launch_backbone_oxygens(const double* nca_c, const int* offsets, const int* lens, int n_chains, int reference_torsion,
+                             double* out, hipStream_t s);
+// DSSP states of N / CA / C / O backbones bb [sum lens][4][3] (dssp.hip), one workgroup per chain: state_out [sum lens]
+// (0 '-', 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S); acc_out [sum lens][2] and energy_out [sum lens][2] (the kept acceptors of each donor) or
+// both null; counts_out [n_chains][3] (kept bonds, runs of H, runs of E) or null; flags [sum lens] (bit 0 no donor, bit 1 no
+// acceptor) or null.  max_len = the longest chain (<= 1024: 54 bytes of LDS per residue).
+void launch_dssp(const double* bb, const unsigned char* flags, const int* offsets, const int* lens, int n_chains, int max_len,
+                 signed char* state_out, int* acc_out, double* energy_out, int* counts_out, hipStream_t s);
 // TM-align-style alignment search (tm_align.hip), one workgroup per pair on a persistent grid: pair p = chains pair_a[p],
 // pair_b[p] of the packed traces `ca` (cent = [n_chains][3] centroids, sse = launch_psea's labels of the same chains,
 // max_len = the longest chain, <= 512).  tm_out [n_pairs], transform_out [n_pairs][12], n_ali_out [n_pairs]; map_out

@@ -163,6 +163,20 @@ inline int check_coords(const double* xyz, const int32_t* offsets, const int32_t
   return FD_OK;
 }
 
+// packed float64 backbones with `per` atoms to a residue ([sum lens][per][3], check_packed has passed): every coordinate finite
+// and within 1e6 A; with nan_atom >= 0 that atom's coordinates may also be NaN (a residue without it)
+inline int check_backbone(const double* xyz, const int32_t* offsets, const int32_t* lens, int n, int per, int nan_atom = -1) {
+  for (int c = 0; c < n; ++c)
+    for (int i = offsets[c]; i < offsets[c] + lens[c]; ++i)
+      for (int a = 0; a < per; ++a)
+        for (int d = 0; d < 3; ++d) {
+          const double u = xyz[((size_t)i * per + a) * 3 + d];
+          if (!(std::fabs(u) <= 1e6) && !(a == nan_atom && std::isnan(u)))
+            return fail(FD_E_INVALID, "coordinate %d of atom %d of residue %d (chain %d) is not finite or beyond 1e6: %g", d, a, i, c, u);
+        }
+  return FD_OK;
+}
+
 // the same for packed float32 coordinates with `per` atoms to an entry ([sum lens][per][3]); names the atom and its chain
 inline int check_coords_f32(const float* xyz, const int32_t* offsets, const int32_t* lens, int n, int per) {
   for (int c = 0; c < n; ++c)

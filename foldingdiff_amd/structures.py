@@ -28,6 +28,11 @@ The inverse of ``angles_and_coords`` / ``nerf``.  Restates, without biotite:
   container per pair: ``count_clashes``, ``count_clashes_parallel``, ``lddt`` and ``lddt_scorer`` count the atom pairs on
   the device (``fd_backbone_clashes``, ``fd_lddt``: one workgroup per structure, integer results).
 
+* ``add_oxygen_to_backbone`` (bin/add_oxygen_to_backbone.py:42-83), one biotite atom at a time: ``add_oxygens`` places the
+  carbonyl oxygens of every backbone of a call in one launch (``fd_backbone_oxygens``), and ``dssp`` / ``dssp_counts`` /
+  ``dssp_from_backbones`` / ``dssp_of_pdb`` label N / CA / C / O backbones with the DSSP states from their backbone hydrogen
+  bonds (``fd_dssp``, one workgroup per chain).  The reference has no DSSP of its own (it shells out to mkdssp).
+
 PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PDBFile`` for them):
 
 1. a file with more than one MODEL record is rejected (``None``), as the reference does;
@@ -689,6 +694,137 @@ def ss_cooccurrence(pdb_files: Sequence[str], json_file: str = "", outpdf: str =
                           outpdf=outpdf, title=title, **kwargs)
     counts = np.array([c for _, c in kept], dtype=np.int64).reshape(-1, 2)
     return counts[:, 0], counts[:, 1]
+
+
+# ---------------------------------------------------------------------------------------------------- oxygens, DSSP
+DSSP_MAX_LEN = 1024   # FDMI_DSSP_MAX_LEN
+DSSP_STATES = np.array(list("-HBEGITS"))   # fd_dssp's state codes 0 .. 7
+DSSP_NO_DONOR, DSSP_NO_ACCEPTOR = 1, 2     # fd_dssp's flag bits
+_BACKBONE_O = _BACKBONE + ("O",)
+
+
+def read_backbone_atoms(fname: str) -> Optional[Tuple[np.ndarray, List[str]]]:
+    """N, CA, C and O of every residue of a ``.pdb`` / ``.pdb.gz`` file: (float64 [n, 4, 3], the n residue names), or
+    ``None`` for a file ``read_backbone`` rejects.  The same rules 1-7 (the module docstring); O is optional: the O row of
+    a residue without an O record (a generated backbone, or the last residue of ``write_backbone_with_o_pdb``'s files)
+    is NaN."""
+    n_models = 0
+    atoms, names, order = {}, {}, []
+    with _open(fname) as fh:
+        for line in fh:
+            rec = line[:6]
+            if rec == "MODEL ":
+                n_models += 1
+                continue
+            if rec != "ATOM  " and not (rec == "HETATM" and line[17:20] == "MSE"):
+                continue
+            name = line[12:16].strip()
+            if name not in _BACKBONE_O:
+                continue
+            rid = (line[21], line[22:26].strip(), line[26].strip())
+            res = atoms.get(rid)
+            if res is None:
+                res = atoms[rid] = {}
+                names[rid] = line[17:20].strip()
+                order.append(rid)
+            if name not in res:
+                res[name] = (float(line[30:38]), float(line[38:46]), float(line[46:54]))
+    if n_models > 1 or not order or any(a not in atoms[rid] for rid in order for a in _BACKBONE):
+        logging.debug(f"{fname}: several models, no backbone atoms or a residue without N / CA / C - skipping")
+        return None
+    nan = (np.nan, np.nan, np.nan)
+    xyz = np.array([[atoms[rid].get(a, nan) for a in _BACKBONE_O] for rid in order], dtype=np.float64)
+    return xyz, [names[rid] for rid in order]
+
+
+def _residue_arrays(chains: Sequence[np.ndarray], atoms: int, what: str) -> List[np.ndarray]:
+    """The chains as float64 [n, atoms, 3] arrays (an [atoms n, 3] array is reshaped), 1 <= n <= DSSP_MAX_LEN."""
+    out = []
+    for i, x in enumerate(chains):
+        x = np.asarray(x, dtype=np.float64)
+        ok = (x.ndim == 2 and x.shape[1] == 3 and len(x) % atoms == 0) or (x.ndim == 3 and x.shape[1:] == (atoms, 3))
+        if not ok or not 1 <= x.size // (3 * atoms) <= DSSP_MAX_LEN:
+            raise ValueError(f"{what} {i}: {x.shape}; expected [n, {atoms}, 3] or [{atoms} n, 3] with 1 <= n <= {DSSP_MAX_LEN}")
+        out.append(x.reshape(-1, atoms, 3))
+    return out
+
+
+def add_oxygens(backbones: Sequence[np.ndarray], reference_torsion: bool = False, device: int = 0) -> List[np.ndarray]:
+    """The carbonyl oxygens of N / CA / C backbones (each [3n, 3] or [n, 3, 3], 1 <= n <= 1024), all of them in one
+    ``fd_backbone_oxygens`` launch: float64 [n, 4, 3] per backbone, N, CA, C copied and O placed at the CA-C-O angle
+    2.0992622 rad and C=O length 1.2359372 A of the reference's bin/add_oxygen_to_backbone.py, trans to the next residue's
+    N (torsion psi + pi).  ``reference_torsion``: the torsion psi that script passes, which puts the O where the next N
+    is.  The last residue has no psi; its O row is NaN, as the reference gives it no oxygen."""
+    xs = _residue_arrays(backbones, 3, "backbone")
+    if not xs:
+        return []
+    X, offsets, lens = _pack(xs)
+    out = np.empty((len(X), 4, 3), dtype=np.float64)
+    _binding.check(_binding.load().fd_backbone_oxygens(device, ptr(X), ptr(offsets), ptr(lens), len(xs), int(bool(reference_torsion)),
+                                                       ptr(out)))
+    return [out[o: o + n] for o, n in zip(offsets, lens)]
+
+
+def _dssp(chains, flags, device: int, want_bonds: bool):
+    """One ``fd_dssp`` call: (int8 states per chain, int32 [n_chains, 3] counts, (acc, energy) per chain or None)."""
+    xs = _residue_arrays(chains, 4, "chain")
+    n = len(xs)
+    counts = np.zeros((n, 3), dtype=np.int32)
+    if n == 0:
+        return [], counts, ([] if want_bonds else None)
+    X, offsets, lens = _pack(xs)
+    fl = None
+    if flags is not None:
+        if len(flags) != n or any(len(np.reshape(f, -1)) != m for f, m in zip(flags, lens)):
+            raise ValueError("flags: expected one uint8 array of the chain's length per chain")
+        fl = np.ascontiguousarray(np.concatenate([np.reshape(f, -1) for f in flags]), dtype=np.uint8)
+    state = np.empty((len(X),), dtype=np.int8)
+    acc = np.empty((len(X), 2), dtype=np.int32) if want_bonds else None
+    energy = np.empty((len(X), 2), dtype=np.float64) if want_bonds else None
+    _binding.check(_binding.load().fd_dssp(device, ptr(X), ptr(fl), ptr(offsets), ptr(lens), n, ptr(state), ptr(acc), ptr(energy),
+                                           ptr(counts)))
+    cut = lambda a: [a[o: o + m] for o, m in zip(offsets, lens)]   # noqa: E731
+    return cut(state), counts, (list(zip(cut(acc), cut(energy))) if want_bonds else None)
+
+
+def dssp(chains: Sequence[np.ndarray], flags: Optional[Sequence[np.ndarray]] = None, device: int = 0, return_hbonds: bool = False):
+    """DSSP states of N / CA / C / O backbones (each [n, 4, 3] or [4n, 3], 1 <= n <= 1024; an O row of NaN is a residue
+    without oxygen), all chains in one ``fd_dssp`` launch: a ``'U1'`` array of ``-HBEGITS`` per chain.  With
+    ``return_hbonds`` also a list of ``(acc int32 [n, 2], energy float64 [n, 2])``: per donor residue its two kept
+    acceptors (chain-local, -1 where none) and their energies in kcal/mol.
+
+    ``flags``: per chain a uint8 [n] array, bit 0 (``DSSP_NO_DONOR``) for a residue without an amide hydrogen (proline),
+    bit 1 (``DSSP_NO_ACCEPTOR``) for one that accepts nothing.
+
+    The rules are Kabsch & Sander's (1983), restated in DESIGN.md 6t; beta-bulges and sheet labels are not built, and
+    the labels are not pinned to the mkdssp binary."""
+    states, _, bonds = _dssp(chains, flags, device, return_hbonds)
+    out = [DSSP_STATES[s] for s in states]
+    return (out, bonds) if return_hbonds else out
+
+
+def dssp_counts(chains: Sequence[np.ndarray], flags: Optional[Sequence[np.ndarray]] = None, device: int = 0) -> np.ndarray:
+    """int [len(chains), 3]: kept hydrogen bonds, maximal runs of 'H' and maximal runs of 'E' of each chain (``dssp``'s
+    labels), in one launch."""
+    return _dssp(chains, flags, device, False)[1].astype(np.int64)
+
+
+def dssp_from_backbones(backbones: Sequence[np.ndarray], device: int = 0, return_hbonds: bool = False):
+    """``dssp(add_oxygens(backbones))``: for NeRF output, where every residue is a glycine and none a proline."""
+    return dssp(add_oxygens(backbones, device=device), device=device, return_hbonds=return_hbonds)
+
+
+def dssp_of_pdb(fname: str, device: int = 0) -> Optional[np.ndarray]:
+    """``dssp`` labels of a PDB file (``None`` for one ``read_backbone`` rejects, or of more than 1024 residues): the file's
+    own O atoms where every residue but the last has one, ``add_oxygens`` otherwise; PRO is flagged as no donor."""
+    bb = read_backbone_atoms(fname)
+    if bb is None or len(bb[0]) > DSSP_MAX_LEN:
+        return None
+    xyz, names = bb
+    if np.isnan(xyz[:-1, 3]).any():
+        xyz = add_oxygens([xyz[:, :3]], device=device)[0]
+    flags = np.array([DSSP_NO_DONOR if n == "PRO" else 0 for n in names], dtype=np.uint8)
+    return dssp([xyz], flags=[flags], device=device)[0]
 
 
 # ---------------------------------------------------------------------------------------------------- alignment

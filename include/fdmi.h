@@ -56,6 +56,7 @@ extern "C" {
 /*    fd_sample_steered, fd_p_sample_step_coef_x0, fd_steer_rewards and fd_steer_resample (steering a few-step run by particle
  *    resampling on device rewards) and the struct fd_steer_params are additive too */
 /*    fd_sample_repeat and fd_tie_repeats (few-step sampling with the angle rows tied across repeat units) are additive too */
+/*    fd_backbone_oxygens and fd_dssp (backbone oxygens and DSSP hydrogen-bond states) are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -678,6 +679,44 @@ int fd_tm_score(int device_id, const double* a, const double* b, const int32_t* 
  * Synchronous; the result does not depend on the other chains of the call. */
 int fd_annotate_sse(int device_id, const double* ca, const int32_t* offsets, const int32_t* lens, int n_chains,
                     int8_t* sse_out /* [sum lens]: 0 c, 1 a, 2 b */, int32_t* counts_out /* [n_chains][2] or NULL */);
+
+/* Longest chain fd_backbone_oxygens and fd_dssp take: C and O of every residue and the per-residue state of the DSSP passes
+ * sit in one workgroup's LDS (54 B per residue). */
+#define FDMI_DSSP_MAX_LEN 1024
+
+/* The carbonyl oxygens of N / CA / C backbones: what the reference's bin/add_oxygen_to_backbone.py adds to a generated backbone,
+ * every chain of a call in one launch, all of it in fp64.  For a residue i that is not its chain's last,
+ * psi = dihedral(N_i, CA_i, C_i, N_{i+1}) and O_i is placed from (N_i, CA_i, C_i) with the CA-C-O angle 2.0992622 rad, the
+ * C=O length 1.2359372 A and the torsion psi + pi: trans to the next N, where a carbonyl oxygen sits.  The reference's script
+ * passes psi itself, which is the next N's own torsion (DESIGN.md 6t has the measurement).
+ *   nca_c       host float64 [n_res][3][3]: N, CA, C of every residue; chain c = residues offsets[c] .. offsets[c] + lens[c] - 1,
+ *               packed back to back like fd_annotate_sse's; 1 <= lens[c] <= FDMI_DSSP_MAX_LEN; finite, |coordinate| <= 1e6
+ *   reference_torsion  != 0: the torsion is psi, the reference script's literal call
+ *   out         float64 [n_res][4][3]: N, CA, C copied, then O; the O of a chain's last residue (it has no psi) is NaN, as the
+ *               reference gives it none
+ * Synchronous; the result does not depend on the other chains of the call. */
+int fd_backbone_oxygens(int device_id, const double* nca_c /* [n_res][3][3] */, const int32_t* offsets, const int32_t* lens,
+                        int n_chains, int reference_torsion, double* out /* [n_res][4][3] */);
+
+/* DSSP states of N / CA / C / O backbones (Kabsch & Sander 1983; DESIGN.md 6t has the exact rules) in fp64: the hydrogen of
+ * residue j >= 1 at N_j + unit(C_{j-1} - O_{j-1}), the electrostatic energy of every C=O(i) -> H-N(j) without a distance
+ * prefilter, per donor the two acceptors of lowest energy below -0.5 kcal/mol, and from those bonds minimal helices (H, G, I),
+ * bridges and ladders (B, E), turns (T) and bends (S).  Not built: beta-bulge linking of ladders and sheet labels.  It is not
+ * pinned to the mkdssp binary (which also keeps a per-acceptor list and rounds energies to three decimals).
+ *   bb          host float64 [n_res][4][3]: N, CA, C, O of every residue, chains packed like fd_backbone_oxygens' (whose output
+ *               this is); 1 <= lens[c] <= FDMI_DSSP_MAX_LEN; finite, |coordinate| <= 1e6, except that the coordinates of an O
+ *               may be NaN: that residue accepts no bond and the next one has no hydrogen
+ *   flags       NULL, or uint8 [n_res]: bit 0 the residue is no donor (proline, or no H), bit 1 it is no acceptor.  A chain's
+ *               first residue is never a donor
+ *   state_out   int8 [n_res]: 0 '-', 1 'H', 2 'B', 3 'E', 4 'G', 5 'I', 6 'T', 7 'S'
+ *   acc_out, energy_out  both NULL, or int32 [n_res][2] and float64 [n_res][2]: per donor the chain-local indices of its kept
+ *               acceptors, lowest energy first (-1 where none), and their energies in kcal/mol (0 where none)
+ *   counts_out  NULL, or int32 [n_chains][3]: kept hydrogen bonds, maximal runs of 'H', maximal runs of 'E' per chain
+ * Synchronous; the result does not depend on the other chains of the call. */
+int fd_dssp(int device_id, const double* bb /* [n_res][4][3]: N, CA, C, O */, const uint8_t* flags /* [n_res] or NULL */,
+            const int32_t* offsets, const int32_t* lens, int n_chains, int8_t* state_out /* [n_res] */,
+            int32_t* acc_out /* [n_res][2] or NULL */, double* energy_out /* [n_res][2] or NULL */,
+            int32_t* counts_out /* [n_chains][3] or NULL */);
 
 /* Longest chain fd_tm_align takes: both traces, the search's state and the 2-bit trace-back matrix of the dynamic
  * programme (n1 x n2 / 4 bytes) sit in one workgroup's LDS. */
