@@ -1,21 +1,18 @@
-// C-ABI host side of libfdmi.so, the part that holds a model: model state, weight packing, workspaces, the launch plan of
-// a timestep, the captured step graph, the profile / debug / option entries and RCCL.  The entry points that run the model
-// (forward, loss, sampling) are api_run.hip, which sees this source through model.h.  The entry points that take a
-// device_id instead of an fd_model live beside them: api_structures.hip (fd_nerf, fd_internal_coords, fd_superpose_rmsd,
-// fd_tm_score, fd_annotate_sse, fd_tm_align) and api_hooks.hip (the fd_test_* hooks); what the four share -- the error
-// string, HIP_TRY, the owner of call-scoped device buffers -- is host_common.h.
+// C-ABI host side of libfdmi.so, the part that holds a model as it runs: the error string, workspaces, the launch plan of
+// a timestep, the step itself, the captured step graph, and the create / destroy / option / profile / debug entries.  The
+// model's weights (fd_set_weight, fd_finalize: packing through weight_pack.h, upload) are api_weights.hip, its RCCL binding
+// api_comm.hip, and the entry points that run the model (forward, loss, sampling) api_run.hip; the four see each other through
+// model.h.  The entry points that take a device_id instead of an fd_model live beside them: api_structures.hip (fd_nerf,
+// fd_internal_coords, fd_superpose_rmsd, fd_tm_score, fd_annotate_sse, fd_tm_align) and api_hooks.hip (the fd_test_* hooks);
+// what all of them share -- the error string, HIP_TRY, the owner of call-scoped device buffers -- is host_common.h.
 // Boundary: include/fdmi.h (each entry point cites the reference function it replaces).
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
-#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/fdmi.h"
@@ -48,310 +45,15 @@ constexpr long long kStampSeqAttn = kStampAttn + 4 * 64 * 8;          // fused a
 constexpr long long kStampFfn = kStampSeqAttn + 4 * 64 * 16 + 16384;  // ffn16.hip's [8][16][16]
 constexpr long long kStampWords = kStampFfn + 8 * 16 * 16;
 
-int dev_alloc(fd_model* m, float** out, size_t n_floats) {
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, n_floats * sizeof(float)));
-  m->allocs.push_back(p);
-  *out = static_cast<float*>(p);
-  return FD_OK;
-}
-
-int upload(fd_model* m, float** out, const float* src, size_t n) {
-  int rc = dev_alloc(m, out, n);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(*out, src, n * sizeof(float), hipMemcpyHostToDevice));
-  return FD_OK;
-}
-
-// W [N][K] fp32 -> [Npad128][K/32][hi x32 | lo x32] fp16 with w*scale = hi + lo (gemm_f16x3.hip).
-// scale = the power of two that puts max|w|*scale in [8192, 16384): every lo of a weight that
-// matters is a normal fp16 and nothing overflows.
-void pack_split_weight(const float* W, int N, int K, std::vector<uint16_t>* out, float* scale, int row_pad = 128) {
-  float mx = 0.f;
-  for (size_t i = 0; i < (size_t)N * K; ++i) mx = std::fmax(mx, std::fabs(W[i]));
-  float s = 1.f;
-  if (mx > 0.f && std::isfinite(mx)) s = std::exp2(std::floor(std::log2(16384.0f / mx)));
-  *scale = s;
-  const int npad = (N + row_pad - 1) / row_pad * row_pad, nk = K / 32;
-  out->assign((size_t)npad * nk * 64, 0);
-  for (int n = 0; n < N; ++n)
-    for (int kt = 0; kt < nk; ++kt) {
-      uint16_t* dst = out->data() + ((size_t)n * nk + kt) * 64;
-      for (int j = 0; j < 32; ++j) {
-        const float xs = W[(size_t)n * K + kt * 32 + j] * s;
-        const _Float16 hi = (_Float16)xs;
-        const _Float16 lo = (_Float16)(xs - (float)hi);
-        memcpy(dst + j, &hi, 2);
-        memcpy(dst + 32 + j, &lo, 2);
-      }
-    }
-}
+size_t kHeadBytes(const fd_config& c) { return (size_t)(c.d_model / c.n_heads) * 4; }  // q / k / v image bytes per position and head
 
 }  // namespace
 
-// Row-image GEMM weights, ordered [384-row tile][k-tile][48 KiB = the workgroup's LDS stage, byte for byte]: the loader copies a
-// k-tile with lane-linear LDS-DMA from CONSECUTIVE cache lines.  The stage is 48 pieces of 8 rows, each piece unit-major:
-// [piece j][position p][row % 8][16 B] with position p holding 16-byte unit p ^ (j & 1) of the row's block (the layout the
-// compute waves' fragment reads are bank-conflict free on; gemm_img.hip uses the same for the activation pieces).
-// Rows padded to whole tiles with zeros.
-void fdmi::pack_weight_tiles(const float* W, int N, int K, std::vector<uint16_t>* out, float* scale) {  // (host_common.h)
-  std::vector<uint16_t> rm;
-  pack_split_weight(W, N, K, &rm, scale, 384);
-  const int npad = (N + 383) / 384 * 384, nk = K / 32;
-  out->assign(rm.size(), 0);
-  for (int n = 0; n < npad; ++n)
-    for (int kt = 0; kt < nk; ++kt) {
-      const int R = n % 384, j = R >> 3, r = R & 7;
-      uint16_t* stage = out->data() + ((size_t)(n / 384) * nk + kt) * 384 * 64;
-      const uint16_t* blk = rm.data() + ((size_t)n * nk + kt) * 64;
-      for (int u = 0; u < 8; ++u) memcpy(stage + (j * 1024 + (((u ^ (j & 1)) * 8 + r) << 4)) / 2, blk + u * 8, 16);
-    }
-}
-namespace {
-
-int upload_split(fd_model* m, SplitW* dst, const float* W, int N, int K, int row_pad = 128) {
-  std::vector<uint16_t> img;
-  if (row_pad == 384) pack_weight_tiles(W, N, K, &img, &dst->scale);
-  else pack_split_weight(W, N, K, &img, &dst->scale, row_pad);
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, img.size() * 2));
-  m->allocs.push_back(p);
-  HIP_TRY(hipMemcpy(p, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  dst->p = p;
-  return FD_OK;
-}
-
-// seq_attn.hip's weights: the q | k | v projection [3 d][d] ordered per head, [head][k-tile][unit 0-7][96 rows: q_h | k_h | v_h][16 B]
-// (a k-tile of a head = one 12 KiB LDS ring stage, byte for byte, unit-major), split at the SAME scale as wqkv_i (one power of two for
-// the whole matrix), so the fused kernel multiplies the very same fp16 hi / lo values as the tile GEMM.
-int upload_seq_attn_weights(fd_model* m, SplitW* dst, const float* W, int d) {
-  std::vector<uint16_t> rm, img;
-  pack_split_weight(W, 3 * d, d, &rm, &dst->scale, 384);
-  const int nk = d / 32, H = d / 32;
-  img.assign((size_t)H * nk * 96 * 64, 0);
-  for (int h = 0; h < H; ++h)
-    for (int kt = 0; kt < nk; ++kt) {
-      uint16_t* stage = img.data() + ((size_t)h * nk + kt) * 96 * 64;
-      for (int r = 0; r < 96; ++r) {
-        const int n = (r / 32) * d + h * 32 + (r % 32);
-        const uint16_t* blk = rm.data() + ((size_t)n * nk + kt) * 64;
-        for (int u = 0; u < 8; ++u) memcpy(stage + ((size_t)u * 96 + r) * 8, blk + u * 8, 16);
-      }
-    }
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, img.size() * 2));
-  m->allocs.push_back(p);
-  HIP_TRY(hipMemcpy(p, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  dst->p = p;
-  return FD_OK;
-}
-
-// seq_attn16.hip's weights: [head][k32 step][tile: q 0, q 1, k 0, k 1, v 0, v 1][unit 0-7][row 0-15][16 B] (a k32 step of a head = 12 KiB,
-// two of them = one LDS ring stage byte for byte; a tile = one v_mfma_f32_16x16x32_f16 operand, unit-major).  Row i of tile j holds
-// head feature 8 (i / 4) + 4 j + (i % 4): with that order the 16 x 16 C/D layout gives every lane eight consecutive features of its
-// token (seq_attn16.hip).  Split at the SAME scale as wqkv_i.
-int upload_seq_attn16_weights(fd_model* m, SplitW* dst, const float* W, int d) {
-  std::vector<uint16_t> rm, img;
-  pack_split_weight(W, 3 * d, d, &rm, &dst->scale, 384);
-  const int nk = d / 32, H = d / 32;
-  img.assign((size_t)H * nk * 96 * 64, 0);
-  for (int h = 0; h < H; ++h)
-    for (int kt = 0; kt < nk; ++kt) {
-      uint16_t* step = img.data() + ((size_t)h * nk + kt) * 96 * 64;
-      for (int t = 0; t < 6; ++t)
-        for (int i = 0; i < 16; ++i) {
-          const int f = 8 * (i >> 2) + 4 * (t & 1) + (i & 3);
-          const int n = (t >> 1) * d + h * 32 + f;
-          const uint16_t* blk = rm.data() + ((size_t)n * nk + kt) * 64;
-          for (int u = 0; u < 8; ++u) memcpy(step + (size_t)t * 1024 + ((size_t)u * 16 + i) * 8, blk + u * 8, 16);
-        }
-    }
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, img.size() * 2));
-  m->allocs.push_back(p);
-  HIP_TRY(hipMemcpy(p, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  dst->p = p;
-  return FD_OK;
-}
-
-// ffn16.hip's weights: intermediate.dense [ff][d] and output.dense [d][ff] as ONE stream in consumption order.  Per group G of 64
-// intermediate features (the first dense runs one group ahead of the second: up(0) | up(1) down(0) | ... | up(ng - 1) down(ng - 2) |
-// down(ng - 1)): d / 32 steps of the first dense (k32 step ks: four tiles, tile t = 2 pair + j, row i = feature
-// 64 G + 32 pair + 8 (i / 4) + 4 j + (i % 4)), then d / 32 steps of the second (pair 0, 1: its 32 features are one k32 step; output
-// tiles T = 0 .. d / 16 - 1 four to a step, tile T = 2 kt + j, row i = output feature 32 kt + 8 (i / 4) + 4 j + (i % 4)).  A tile =
-// [unit 0-7][row 0-15][16 B] (units 0-3: hi of k 8 u .. 8 u + 7, 4-7: lo), a step = 8 KiB, two steps = one LDS ring stage byte for
-// byte.  Each matrix is split at its own power-of-two scale.
-int upload_ffn16_weights(fd_model* m, LayerDev* lw, const float* Wi, const float* Wd, const float* Wo, int d, int ff) {
-  std::vector<uint16_t> ri, rd, img;
-  pack_split_weight(Wi, ff, d, &ri, &lw->wff_i.scale, 128);
-  pack_split_weight(Wd, d, ff, &rd, &lw->wff_scale_dn, 128);
-  const int nkt = d / 32, ng = ff / 64, spg = 2 * nkt, nkd = ff / 32;
-  img.assign((size_t)ng * spg * 4 * 1024, 0);
-  // stream position (in steps) of a group's blocks: up(0) | up(1) down(0) | up(2) down(1) | ... | up(ng - 1) down(ng - 2) | down(ng - 1)
-  auto up_at = [&](int G) { return G == 0 ? 0 : nkt + (G - 1) * spg; };
-  auto down_at = [&](int G) { return G == ng - 1 ? nkt + (ng - 1) * spg : nkt + G * spg + nkt; };
-  auto put = [&](int step, int t, int i, const uint16_t* blk) {
-    uint16_t* tile = img.data() + ((size_t)step * 4 + t) * 1024;
-    for (int u = 0; u < 8; ++u) memcpy(tile + ((size_t)u * 16 + i) * 8, blk + u * 8, 16);
-  };
-  for (int G = 0; G < ng; ++G) {
-    for (int ks = 0; ks < nkt; ++ks)
-      for (int t = 0; t < 4; ++t)
-        for (int i = 0; i < 16; ++i) {
-          const int f = 64 * G + 32 * (t >> 1) + 8 * (i >> 2) + 4 * (t & 1) + (i & 3);
-          put(up_at(G) + ks, t, i, ri.data() + ((size_t)f * nkt + ks) * 64);
-        }
-    for (int pr = 0; pr < 2; ++pr)
-      for (int T = 0; T < 2 * nkt; ++T)
-        for (int i = 0; i < 16; ++i) {
-          const int o = 32 * (T >> 1) + 8 * (i >> 2) + 4 * (T & 1) + (i & 3);
-          put(down_at(G) + pr * (nkt / 2) + T / 4, T % 4, i, rd.data() + ((size_t)o * nkd + 2 * G + pr) * 64);
-        }
-  }
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, img.size() * 2));
-  m->allocs.push_back(p);
-  HIP_TRY(hipMemcpy(p, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  lw->wff_i.p = p;
-  if (Wo) {
-    // ... and with attention.output.dense [d][d] in front (ffn16.hip TAIL): step kt * (d / 64) + q = k32 step kt of the context against
-    // the output tiles 4 q .. 4 q + 3 (rows permuted like the second dense's)
-    std::vector<uint16_t> ro, timg;
-    pack_split_weight(Wo, d, d, &ro, &lw->wtail_i.scale, 128);
-    const int nsa = nkt * nkt / 2;
-    timg.assign((size_t)nsa * 4 * 1024 + img.size(), 0);
-    for (int kt = 0; kt < nkt; ++kt)
-      for (int T = 0; T < 2 * nkt; ++T)
-        for (int i = 0; i < 16; ++i) {
-          const int o = 32 * (T >> 1) + 8 * (i >> 2) + 4 * (T & 1) + (i & 3);
-          uint16_t* tile = timg.data() + ((size_t)(kt * (nkt / 2) + T / 4) * 4 + T % 4) * 1024;
-          const uint16_t* blk = ro.data() + ((size_t)o * nkt + kt) * 64;
-          for (int u = 0; u < 8; ++u) memcpy(tile + ((size_t)u * 16 + i) * 8, blk + u * 8, 16);
-        }
-    memcpy(timg.data() + (size_t)nsa * 4 * 1024, img.data(), img.size() * 2);
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, timg.size() * 2));
-    m->allocs.push_back(q);
-    HIP_TRY(hipMemcpy(q, timg.data(), timg.size() * 2, hipMemcpyHostToDevice));
-    lw->wtail_i.p = q;
-  }
-  return FD_OK;
-}
-
-void free_weights(fd_model* m) {
-  for (void* p : m->allocs) (void)hipFree(p);
-  m->allocs.clear();
-  m->layers.clear();
-  m->finalized = false;
-}
-
-// ---- static scales of the activation images (row-image path).
-// Every image tensor gets the largest power of two s with  bound * s <= 30000 < fp16 max, where `bound` is a
-// guaranteed bound of |x| derived from the weights: a LayerNorm output obeys |y_i| <= max|gamma| sqrt(d) + max|beta|
-// and ||y||_2 <= max|gamma| sqrt(d) + ||beta||_2; a dense output |y W_j + b_j| <= ||y||_2 ||W_j||_2 + |b_j|; GELU and the
-// softmax-weighted average of V do not grow their argument.  Nothing overflows for ANY weights (trained outliers
-// included); elements far below the bound merely lose low bits of `lo` (absolute error bound * 2^-40).
-struct Bound {
-  float linf, l2;
-};
-}  // namespace
-float fdmi::scale_for(float bound) {  // (host_common.h)
-  if (!(bound > 0.f) || !std::isfinite(bound)) return 1.f;
-  float e = std::floor(std::log2(30000.0f / bound));
-  e = e < -40.f ? -40.f : (e > 40.f ? 40.f : e);
-  return std::exp2(e);
-}
-namespace {
-Bound ln_bound(const HostTensor* g, const HostTensor* b, float extra_each = 0.f) {
-  const size_t d = g->data.size();
-  float gm = 0.f, bm = 0.f;
-  double b2 = 0.0;
-  for (size_t i = 0; i < d; ++i) {
-    gm = std::fmax(gm, std::fabs(g->data[i]));
-    bm = std::fmax(bm, std::fabs(b->data[i]));
-    b2 += (double)b->data[i] * b->data[i];
-  }
-  const float sd = std::sqrt((float)d);
-  return Bound{gm * sd + bm + extra_each, gm * sd + (float)std::sqrt(b2) + extra_each * sd};
-}
-}  // namespace
-// bound of a dense layer's outputs (rows [r0, r1) of W [N][K]) for inputs with ||x||_2 <= in_l2
-float fdmi::dense_bound(const float* W, const float* bias, int r0, int r1, int K, float in_l2) {  // (host_common.h)
-  float worst = 0.f;
-  for (int j = r0; j < r1; ++j) {
-    double n2 = 0.0;
-    for (int k = 0; k < K; ++k) n2 += (double)W[(size_t)j * K + k] * W[(size_t)j * K + k];
-    worst = std::fmax(worst, (float)std::sqrt(n2) * in_l2 + std::fabs(bias[j]));
-  }
-  return worst;
-}
-namespace {
-
-// expected shape of a state_dict entry; returns false if the name is not a parameter we consume
-bool expected_shape(const fd_config& c, const std::string& name, std::vector<int64_t>* shp, bool* ignored) {
-  *ignored = false;
-  const int64_t d = c.d_model, F = c.n_features, ff = c.d_ff;
-  auto set = [&](std::initializer_list<int64_t> s) { *shp = s; return true; };
-  if (name == "time_embed.W" || name == "embeddings.position_ids") { *ignored = true; return true; }
-  if (name == "inputs_to_hidden_dim.weight") return set({d, F});
-  if (name == "inputs_to_hidden_dim.bias") return set({d});
-  if (name == "embeddings.LayerNorm.weight" || name == "embeddings.LayerNorm.bias") return set({d});
-  if (name == "embeddings.position_embeddings.weight") return set({c.max_pos, d});
-  if (c.decoder == FD_DEC_MLP) {
-    if (name == "token_decoder.dense1.weight") return set({d, d});
-    if (name == "token_decoder.dense1.bias") return set({d});
-    if (name == "token_decoder.layer_norm.weight" || name == "token_decoder.layer_norm.bias") return set({d});
-    if (name == "token_decoder.dense2.weight") return set({F, d});
-    if (name == "token_decoder.dense2.bias") return set({F});
-  } else {
-    if (name == "token_decoder.weight") return set({F, d});
-    if (name == "token_decoder.bias") return set({F});
-  }
-  const std::string pre = "encoder.layer.";
-  if (name.compare(0, pre.size(), pre) == 0) {
-    size_t dot = name.find('.', pre.size());
-    if (dot == std::string::npos) return false;
-    int li = atoi(name.substr(pre.size(), dot - pre.size()).c_str());
-    if (li < 0 || li >= c.n_layers) return false;
-    const std::string rest = name.substr(dot + 1);
-    for (const char* p : {"attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense"}) {
-      if (rest == std::string(p) + ".weight") return set({d, d});
-      if (rest == std::string(p) + ".bias") return set({d});
-    }
-    if (rest == "attention.self.distance_embedding.weight") return set({2 * (int64_t)c.max_pos - 1, (int64_t)(c.d_model / c.n_heads)});
-    for (const char* p : {"attention.output.LayerNorm", "output.LayerNorm"}) {
-      if (rest == std::string(p) + ".weight" || rest == std::string(p) + ".bias") return set({d});
-    }
-    if (rest == "intermediate.dense.weight") return set({ff, d});
-    if (rest == "intermediate.dense.bias") return set({ff});
-    if (rest == "output.dense.weight") return set({d, ff});
-    if (rest == "output.dense.bias") return set({d});
-  }
-  return false;
-}
-
-const HostTensor* need(fd_model* m, const std::string& name) {
-  auto it = m->host.find(name);
-  if (it == m->host.end()) {
-    fail(FD_E_MISSING, "weight '%s' was never provided (fd_set_weight)", name.c_str());
-    return nullptr;
-  }
-  return &it->second;
-}
-
-void drop_workspaces(fd_model* m) {
+void fdmi::drop_workspaces(fd_model* m) {
   m->ws.release();
   for (Workspace& w : m->cache) w.release();
   m->cache.clear();
 }
-
-size_t kHeadBytes(const fd_config& c) { return (size_t)(c.d_model / c.n_heads) * 4; }  // q / k / v image bytes per position and head
-// The q | k | v projections are stored per 32-column SUB-HEAD (d_model / 32 of them; a head of size 32 nb is nb consecutive
-// sub-heads): head size 32 (every released configuration) runs attention_img.hip, 64 / 96 / 128 the general attention_gen.hip.
-int head_dim(const fd_config& c) { return c.d_model / c.n_heads; }
-int sub_heads(const fd_config& c) { return c.d_model / 32; }
-
-}  // namespace
 
 int fdmi::ensure_ws(fd_model* m, int B, int L) {
   Workspace& w = m->ws;
@@ -1002,95 +704,8 @@ int check_flag(fd_model* m) {
 
 }  // namespace fdmi
 
-// ---- RCCL, bound at run time (dlopen): the library has no link-time dependency on it, and a host process that already
-// carries an RCCL (PyTorch does) shares that instance.  Only what the single gather of SURVEY 8(e) needs.
-namespace {
-struct RcclId {
-  char internal[128];
-};
-struct Rccl {
-  void* lib = nullptr;
-  int (*GetUniqueId)(RcclId*) = nullptr;
-  int (*CommInitRank)(void**, int, RcclId, int) = nullptr;
-  int (*CommDestroy)(void*) = nullptr;
-  int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(int) = nullptr;
-};
-Rccl* rccl() {
-  static Rccl r;
-  static bool tried = false;
-  if (!tried) {
-    tried = true;
-    for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-      r.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-      if (r.lib) break;
-    }
-    if (r.lib) {
-      r.GetUniqueId = reinterpret_cast<int (*)(RcclId*)>(dlsym(r.lib, "ncclGetUniqueId"));
-      r.CommInitRank = reinterpret_cast<int (*)(void**, int, RcclId, int)>(dlsym(r.lib, "ncclCommInitRank"));
-      r.CommDestroy = reinterpret_cast<int (*)(void*)>(dlsym(r.lib, "ncclCommDestroy"));
-      r.AllGather = reinterpret_cast<int (*)(const void*, void*, size_t, int, void*, hipStream_t)>(dlsym(r.lib, "ncclAllGather"));
-      r.GetErrorString = reinterpret_cast<const char* (*)(int)>(dlsym(r.lib, "ncclGetErrorString"));
-      if (!r.GetUniqueId || !r.CommInitRank || !r.CommDestroy || !r.AllGather) r.lib = nullptr;
-    }
-  }
-  return r.lib ? &r : nullptr;
-}
-int rccl_fail(const char* what, int rc) {
-  Rccl* r = rccl();
-  return fail(FD_E_HIP, "%s failed: %s", what, (r && r->GetErrorString) ? r->GetErrorString(rc) : "RCCL error");
-}
-}  // namespace
-
 // ============================================================================ C ABI
 extern "C" {
-
-int fd_comm_unique_id(void* id_out) {
-  if (!id_out) return fail(FD_E_INVALID, "null argument");
-  Rccl* r = rccl();
-  if (!r) return fail(FD_E_UNSUPPORTED, "librccl.so could not be loaded");
-  RcclId id;
-  if (int rc = r->GetUniqueId(&id)) return rccl_fail("ncclGetUniqueId", rc);
-  memcpy(id_out, &id, sizeof id);
-  return FD_OK;
-}
-
-int fd_comm_init(fd_model* m, int rank, int world, const void* unique_id) {
-  if (!m || !unique_id) return fail(FD_E_INVALID, "null argument");
-  if (world < 1 || rank < 0 || rank >= world) return fail(FD_E_INVALID, "rank %d of %d", rank, world);
-  Rccl* r = rccl();
-  if (!r) return fail(FD_E_UNSUPPORTED, "librccl.so could not be loaded");
-  HIP_TRY(hipSetDevice(m->device));
-  if (m->comm) {
-    (void)r->CommDestroy(m->comm);
-    m->comm = nullptr;
-  }
-  RcclId id;
-  memcpy(&id, unique_id, sizeof id);
-  if (int rc = r->CommInitRank(&m->comm, world, id, rank)) return rccl_fail("ncclCommInitRank", rc);
-  m->comm_world = world;
-  m->comm_rank = rank;
-  return FD_OK;
-}
-
-int fd_comm_destroy(fd_model* m) {
-  if (!m) return fail(FD_E_INVALID, "null argument");
-  Rccl* r = rccl();
-  if (m->comm && r) (void)r->CommDestroy(m->comm);
-  m->comm = nullptr;
-  m->comm_world = 0;
-  return FD_OK;
-}
-
-int fd_gather_dev(fd_model* m, const void* local_dev, int64_t n_floats, void* out_dev, void* hip_stream) {
-  if (!m || !local_dev || !out_dev || n_floats < 0) return fail(FD_E_INVALID, "bad argument");
-  if (!m->comm) return fail(FD_E_STATE, "fd_comm_init has not been called");
-  Rccl* r = rccl();
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->stream;
-  if (int rc = r->AllGather(local_dev, out_dev, (size_t)n_floats, /*ncclFloat*/ 7, m->comm, s)) return rccl_fail("ncclAllGather", rc);
-  return FD_OK;
-}
 
 int fd_abi_version(void) { return FDMI_ABI_VERSION; }
 
@@ -1133,162 +748,6 @@ int fd_create(const fd_config* cfg, int device_id, fd_model** out) {
     return fail(FD_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
   }
   *out = m;
-  return FD_OK;
-}
-
-int fd_set_weight(fd_model* m, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-  if (!m || !name || !host_data || (ndim > 0 && !shape)) return fail(FD_E_INVALID, "null argument");
-  std::vector<int64_t> want;
-  bool ignored = false;
-  if (!expected_shape(m->cfg, name, &want, &ignored)) return fail(FD_E_INVALID, "unexpected state_dict entry '%s'", name);
-  if (ignored) return FD_OK;
-  std::vector<int64_t> got(shape, shape + ndim);
-  if (got != want) {
-    std::string a, b;
-    for (auto v : got) a += std::to_string(v) + ",";
-    for (auto v : want) b += std::to_string(v) + ",";
-    return fail(FD_E_INVALID, "'%s': shape [%s] does not match config [%s]", name, a.c_str(), b.c_str());
-  }
-  size_t n = 1;
-  for (auto v : got) n *= (size_t)v;
-  HostTensor& t = m->host[name];
-  t.shape = got;
-  t.data.assign(host_data, host_data + n);
-  m->finalized = false;
-  return FD_OK;
-}
-
-int fd_finalize(fd_model* m, int T, const float* coef, const float* time_table, const uint8_t* is_angle, int precision) {
-  if (!m || !coef || !time_table || !is_angle) return fail(FD_E_INVALID, "null argument");
-  if (T < 1) return fail(FD_E_INVALID, "T=%d", T);
-  if (precision != FD_PREC_F32 && precision != FD_PREC_F16X3) return fail(FD_E_UNSUPPORTED, "precision mode %d", precision);
-  if (precision == FD_PREC_F32 && head_dim(m->cfg) != kHeadDim)
-    return fail(FD_E_UNSUPPORTED, "head size %d: the exact-fp32 attention kernel is built for head size %d; use FD_PREC_F16X3", head_dim(m->cfg), kHeadDim);
-  HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  drop_workspaces(m);
-  free_weights(m);
-  const fd_config& c = m->cfg;
-  const size_t d = c.d_model, F = c.n_features, ff = c.d_ff;
-  // FD_PREC_F16X3 runs on the row-image kernels; the attention-output / FFN-down LayerNorm is fused into the GEMM when a row
-  // fits one 384-column workgroup tile (d_model <= 384: every released configuration), else it is its own launch
-  const bool img = precision == FD_PREC_F16X3;
-  m->img = img;
-#define NEED(var, nm)                         \
-  const HostTensor* var = need(m, nm);        \
-  if (!var) return FD_E_MISSING
-#define UP(dst, t) \
-  if (int rc_ = upload(m, &(dst), (t)->data.data(), (t)->data.size())) return rc_
-  NEED(t_win, "inputs_to_hidden_dim.weight");
-  NEED(t_bin, "inputs_to_hidden_dim.bias");
-  NEED(t_eg, "embeddings.LayerNorm.weight");
-  NEED(t_eb, "embeddings.LayerNorm.bias");
-  UP(m->w_in, t_win);
-  UP(m->b_in, t_bin);
-  UP(m->emb_g, t_eg);
-  UP(m->emb_b, t_eb);
-  // bound of the hidden state entering layer 0: embeddings LayerNorm + time embedding (|sin|, |cos| <= 1)
-  Bound hb = ln_bound(t_eg, t_eb, 1.0f);
-  m->pos_emb = nullptr;
-  if (c.pos_type == FD_POS_ABSOLUTE) {
-    NEED(t_pe, "embeddings.position_embeddings.weight");
-    UP(m->pos_emb, t_pe);
-  }
-  m->layers.resize(c.n_layers);
-  for (int li = 0; li < c.n_layers; ++li) {
-    const std::string p = "encoder.layer." + std::to_string(li) + ".";
-    LayerDev& lw = m->layers[li];
-    NEED(wq, p + "attention.self.query.weight");
-    NEED(wk, p + "attention.self.key.weight");
-    NEED(wv, p + "attention.self.value.weight");
-    NEED(bq, p + "attention.self.query.bias");
-    NEED(bk, p + "attention.self.key.bias");
-    NEED(bv, p + "attention.self.value.bias");
-    std::vector<float> wqkv, bqkv;  // rows: [query | key | value]  => one N = 3d GEMM
-    wqkv.reserve(3 * d * d);
-    for (const HostTensor* t : {wq, wk, wv}) wqkv.insert(wqkv.end(), t->data.begin(), t->data.end());
-    for (const HostTensor* t : {bq, bk, bv}) bqkv.insert(bqkv.end(), t->data.begin(), t->data.end());
-    if (int rc = upload(m, &lw.wqkv, wqkv.data(), wqkv.size())) return rc;
-    if (int rc = upload(m, &lw.bqkv, bqkv.data(), bqkv.size())) return rc;
-    if (img) {
-      if (int rc = upload_split(m, &lw.wqk_i, wqkv.data(), 2 * (int)d, (int)d, 384)) return rc;
-      if (int rc = upload_split(m, &lw.wv_i, wqkv.data() + 2 * d * d, (int)d, (int)d, 384)) return rc;
-      if (sub_heads(c) % 6 == 0)
-        if (int rc = upload_split(m, &lw.wqkv_i, wqkv.data(), 3 * (int)d, (int)d, 384)) return rc;
-      lw.wsa_i = SplitW();
-      if (c.pos_type == FD_POS_RELATIVE_KEY && seq_attn_supported((int)d, c.n_heads, c.max_pos < 128 ? c.max_pos : 128, c.max_pos))
-        if (int rc = upload_seq_attn_weights(m, &lw.wsa_i, wqkv.data(), (int)d)) return rc;
-      lw.wsa16_i = SplitW();
-      if (c.pos_type == FD_POS_RELATIVE_KEY && seq_attn16_supported((int)d, c.n_heads, c.max_pos < 128 ? c.max_pos : 128, c.max_pos))
-        if (int rc = upload_seq_attn16_weights(m, &lw.wsa16_i, wqkv.data(), (int)d)) return rc;
-      lw.bqk = lw.bqkv;
-      lw.bv = lw.bqkv + 2 * d;
-      lw.s_h = scale_for(hb.linf);
-      lw.s_q = scale_for(dense_bound(wqkv.data(), bqkv.data(), 0, (int)d, (int)d, hb.l2));
-      lw.s_k = scale_for(dense_bound(wqkv.data(), bqkv.data(), (int)d, 2 * (int)d, (int)d, hb.l2));
-      lw.s_v = scale_for(dense_bound(wqkv.data(), bqkv.data(), 2 * (int)d, 3 * (int)d, (int)d, hb.l2));  // also bounds ctx
-    }
-    lw.demb = nullptr;
-    if (c.pos_type != FD_POS_ABSOLUTE) {  // relative_key and relative_key_query
-      NEED(de, p + "attention.self.distance_embedding.weight");
-      UP(lw.demb, de);
-      if (precision == FD_PREC_F16X3)
-        if (int rc = upload_split(m, &lw.demb_s, de->data.data(), 2 * c.max_pos - 1, head_dim(c))) return rc;
-    }
-    NEED(wo, p + "attention.output.dense.weight");
-    NEED(bo, p + "attention.output.dense.bias");
-    NEED(g1, p + "attention.output.LayerNorm.weight");
-    NEED(b1, p + "attention.output.LayerNorm.bias");
-    NEED(wi, p + "intermediate.dense.weight");
-    NEED(bi, p + "intermediate.dense.bias");
-    NEED(wd, p + "output.dense.weight");
-    NEED(bd, p + "output.dense.bias");
-    NEED(g2, p + "output.LayerNorm.weight");
-    NEED(b2, p + "output.LayerNorm.bias");
-    UP(lw.wo, wo); UP(lw.bo, bo); UP(lw.ln1g, g1); UP(lw.ln1b, b1);
-    UP(lw.wi, wi); UP(lw.bi, bi); UP(lw.wd, wd); UP(lw.bd, bd); UP(lw.ln2g, g2); UP(lw.ln2b, b2);
-    if (img) {
-      if (int rc = upload_split(m, &lw.wo_i, wo->data.data(), (int)d, (int)d, 384)) return rc;
-      if (int rc = upload_split(m, &lw.wi_i, wi->data.data(), (int)ff, (int)d, 384)) return rc;
-      if (int rc = upload_split(m, &lw.wd_i, wd->data.data(), (int)d, (int)ff, 384)) return rc;
-      lw.wff_i = SplitW();
-      lw.wtail_i = SplitW();
-      if (ffn16_supported((int)d, (int)ff))
-        if (int rc = upload_ffn16_weights(m, &lw, wi->data.data(), wd->data.data(), wo->data.data(), (int)d, (int)ff)) return rc;
-      const Bound ab = ln_bound(g1, b1);
-      lw.s_a = scale_for(ab.linf);
-      lw.s_g = scale_for(dense_bound(wi->data.data(), bi->data.data(), 0, (int)ff, (int)d, ab.l2));  // |gelu(u)| <= |u|
-      hb = ln_bound(g2, b2);  // hidden state entering the next layer
-    }
-  }
-  m->s_hfinal = scale_for(hb.linf);
-  if (c.decoder == FD_DEC_MLP) {
-    NEED(w1, "token_decoder.dense1.weight");
-    NEED(b1, "token_decoder.dense1.bias");
-    NEED(g, "token_decoder.layer_norm.weight");
-    NEED(b, "token_decoder.layer_norm.bias");
-    NEED(w2, "token_decoder.dense2.weight");
-    NEED(b2, "token_decoder.dense2.bias");
-    UP(m->hd_w1, w1); UP(m->hd_b1, b1); UP(m->hd_g, g); UP(m->hd_b, b); UP(m->hd_w2, w2); UP(m->hd_b2, b2);
-    if (img) {
-      if (int rc = upload_split(m, &m->hd_w1_i, w1->data.data(), (int)d, (int)d, 384)) return rc;
-      m->s_hg = scale_for(dense_bound(w1->data.data(), b1->data.data(), 0, (int)d, (int)d, hb.l2));
-    }
-  } else {
-    NEED(w2, "token_decoder.weight");
-    NEED(b2, "token_decoder.bias");
-    UP(m->hd_w2, w2); UP(m->hd_b2, b2);
-  }
-#undef NEED
-#undef UP
-  if (int rc = upload(m, &m->coef, coef, (size_t)4 * T)) return rc;
-  if (int rc = upload(m, &m->time_table, time_table, (size_t)T * d)) return rc;
-  m->angle_mask = 0;
-  for (size_t f = 0; f < F; ++f)
-    if (is_angle[f]) m->angle_mask |= 1u << f;
-  m->T = T;
-  m->precision = precision;
-  m->finalized = true;
   return FD_OK;
 }
 

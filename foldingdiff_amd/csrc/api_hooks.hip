@@ -7,6 +7,7 @@
 
 #include "fdmi_kernels.h"
 #include "host_common.h"
+#include "weight_pack.h"
 
 using namespace fdmi;
 
@@ -42,10 +43,9 @@ int img_gemm_hook(int epilogue, const float* A, const float* W, const float* bia
   HIP_TRY(bufs.zeros(1024, &dtrash));
   const int hd[2] = {M, (int)rows};
   HIP_TRY(bufs.upload(hd, sizeof hd, &ddims));
-  std::vector<uint16_t> img;
-  float wscale = 1.f;
-  pack_weight_tiles(W, N, K, &img, &wscale);
-  HIP_TRY(bufs.upload(img.data(), img.size() * 2, &dWi));
+  const Image wimg = pack_weight_tiles(W, N, K);
+  const float wscale = wimg.scale;
+  HIP_TRY(bufs.upload(wimg.data.data(), wimg.data.size() * 2, &dWi));
   const float a_scale = scale_for(max_abs(A, (size_t)M * K));
   launch_f32_to_img(dA, dAi, rows, K, M, a_scale, nullptr);
   // output bound as fd_finalize derives it: ||row of A||_2 ||row of W||_2 + |bias| (+ residual); LayerNorm: gamma/beta
@@ -249,11 +249,10 @@ int fd_test_gemm_time(int device_id, int precision, int M, int N, int K, int rep
     unsigned char *dAi, *dtrash;
     const unsigned char* dWi;
     const int* ddims;
-    std::vector<uint16_t> img;
-    float wscale = 1.f;
-    pack_weight_tiles(hW.data(), N, K, &img, &wscale);
+    const Image wimg = pack_weight_tiles(hW.data(), N, K);
+    const float wscale = wimg.scale;
     HIP_TRY(bufs.zeros((size_t)rows * K * 4, &dAi));
-    HIP_TRY(bufs.upload(img.data(), img.size() * 2, &dWi));
+    HIP_TRY(bufs.upload(wimg.data.data(), wimg.data.size() * 2, &dWi));
     HIP_TRY(bufs.zeros(1024, &dtrash));
     const int hd[2] = {M, (int)rows};
     HIP_TRY(bufs.upload(hd, sizeof hd, &ddims));

@@ -1,4 +1,5 @@
-// Internal launch interface between the C-ABI host code (api.hip: the model; api_run.hip: the entries that run it;
+// Internal launch interface between the C-ABI host code (api.hip: the model as it runs; api_weights.hip: its weights, packed by
+// weight_pack.h; api_run.hip: the entries that run it;
 // api_structures.hip: fd_nerf and the structure entries; api_hooks.hip: the fd_test_* hooks) and the gfx950 kernels.  Not installed; include/fdmi.h is the
 // public boundary.
 #pragma once
@@ -335,7 +336,7 @@ bool launch_attention_gen(const AttnImgArgs& p, int nb, hipStream_t s);
 struct SeqAttnArgs {
   const unsigned char* himg;   // hidden-state image [rows128][d/32] (grouped, img_common.h)
   unsigned himg_bytes;         // its size (< 4 GiB: 32-bit lane offsets; rows beyond it read as zeros)
-  const unsigned char* wimg;   // weight image [head][k-tile][unit 0-7][96 rows: q_h | k_h | v_h][16 B] at the scale of wqkv_i (api.hip: upload_seq_attn_weights)
+  const unsigned char* wimg;   // weight image [head][k-tile][unit 0-7][96 rows: q_h | k_h | v_h][16 B] at the scale of wqkv_i (weight_pack.h: pack_seq_attn)
   const float* bias;           // [3 d]: q | k | v
   const u32x4_t* demb;         // distance table image [2 maxpos - 1][128 B]
   const int* lens;             // [B] unmasked keys per sequence
@@ -352,12 +353,12 @@ bool seq_attn_supported(int d_model, int n_heads, int L, int maxpos);
 // grid_cap > 0: at most that many workgroups (launch_common.h persistent_grid; option "debug_grid"); *grid_used: the x-grid launched
 bool launch_seq_attn(const SeqAttnArgs& p, hipStream_t s, int grid_cap = 0, int* grid_used = nullptr);   // false: the LDS opt-in or the launch was refused
 // seq_attn16.hip (round 6): the same operation with 16-row waves, two per SIMD (v_mfma_f32_16x16x32_f16); wimg = [head][k32 step][tile]
-// [unit][row][16 B] (api.hip: upload_seq_attn16_weights); any L <= 128, padded or packed rows.  false: the launch failed.
+// [unit][row][16 B] (weight_pack.h: pack_seq_attn16); any L <= 128, padded or packed rows.  false: the launch failed.
 bool seq_attn16_supported(int d_model, int n_heads, int L, int maxpos);
 bool launch_seq_attn16(const SeqAttnArgs& p, hipStream_t s, int grid_cap = 0, int* grid_used = nullptr);
 
 // ffn16.hip (round 6): BertIntermediate + GELU + BertOutput (dense + residual + LayerNorm) of 128 token rows per pass in ONE kernel;
-// the intermediate never reaches HBM.  wimg = ONE stream of 16 KiB stages in consumption order (api.hip: upload_ffn16_weights).
+// the intermediate never reaches HBM.  wimg = ONE stream of 16 KiB stages in consumption order (weight_pack.h: pack_ffn16).
 struct FfnArgs {
   const unsigned char* aimg;   // input image [rows128][d/32] (BertSelfOutput's LayerNorm output): operand AND residual
   unsigned a_bytes;            // its size (rows beyond it read as zeros)

@@ -17,7 +17,7 @@
 //    sequence of 1 KiB pieces of 8 rows, each piece UNIT-major ([position p][row % 8][16 B], p holding unit p ^ (piece & 1)):
 //    eight neighbouring lanes copy the eight rows of one unit, which are one 128-byte line of the grouped activation
 //    image, and the fragment reads (ds_read_b128) are bank-conflict free.  The weight image in HBM is the stage byte for
-//    byte ([384-row tile][k-tile][48 KiB], api.hip: pack_weight_tiles).
+//    byte ([384-row tile][k-tile][48 KiB], weight_pack.h: pack_weight_tiles).
 //  * loader waves issue every piece, paced by counted s_waitcnt vmcnt and a raw s_barrier that leaves the vector-memory
 //    queue alone (one wave sustains ~22 B/clk out of L2, two ~40: scripts/probes/dma_probe.hip).  W ring 2 stages (L2
 //    hits), A ring 3 stages (the HBM stream, two k-tiles ahead), ONE workgroup barrier per k-tile.
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(NTHR) void gemm_img_kernel(GemmImgArgs p) {
   // (g+1) & 1 and A slot (g+2) % 3.  The compute waves execute the same barriers and nothing else of this protocol.
   if (wid >= 8) {
     const int li = wid - 8;  // pieces j = li, li + NL, ...: all of one parity
-    const int vw = lane * 16;  // W: the HBM image of a (tile, k-tile) IS the LDS stage (api.hip: pack_weight_tiles)
+    const int vw = lane * 16;  // W: the HBM image of a (tile, k-tile) IS the LDS stage (weight_pack.h: pack_weight_tiles)
     // A: grouped image [row / 32][k-tile][unit][row % 32][16 B].  A piece = rows 8j..8j+7 x 8 units, read unit-major (eight
     // neighbouring lanes fetch the eight rows of one unit = one 128-byte line) and therefore ALSO unit-major in LDS:
     // [piece j][unit position p][row % 8][16 B], position p holding unit p ^ (j & 1) (bank-conflict-free fragment reads)

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void gemm_ln_rows_kernel(GemmImgArgs p) {
   }
 
   // ---- weights: row R = wn * 96 + 32 jn + l31 of W, k-tile kt, k16 step c: unit 2c + half (hi), 4 + 2c + half (lo) of the weight
-  // image ([384-row tile][k-tile][48 KiB stage], pieces of 8 rows, unit u of row r at ((u ^ (piece & 1)) * 8 + r % 8) * 16: api.hip)
+  // image ([384-row tile][k-tile][48 KiB stage], pieces of 8 rows, unit u of row r at ((u ^ (piece & 1)) * 8 + r % 8) * 16: weight_pack.h)
   struct WT {
     f16x8 h[3][2], l[3][2];
   };

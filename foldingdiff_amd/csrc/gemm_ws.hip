@@ -146,7 +146,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmImgArgs p) {
     }
   }
 
-  // ---- the wave's weights: row R of W (an output column) as A-operand fragments.  Weight image (api.hip: pack_weight_tiles):
+  // ---- the wave's weights: row R of W (an output column) as A-operand fragments.  Weight image (weight_pack.h: pack_weight_tiles):
   // [384-row tile][k-tile][48 KiB stage], a stage = pieces of 8 rows, unit u of row r at ((u ^ (piece & 1)) * 8 + r % 8) * 16
   f16x8 Wh[NKT][2], Wl[NKT][2];
   {

@@ -1,5 +1,6 @@
-// Host-only helpers shared by the four C-ABI sources (api.hip: the model; api_run.hip: the entries that run it;
-// api_structures.hip: the structure entries; api_hooks.hip: the test hooks): the error string, the owner of device buffers
+// Host-only helpers shared by the C-ABI sources (api.hip: the model as it runs; api_weights.hip: its weights; api_comm.hip:
+// its RCCL binding; api_run.hip: the entries that run it; api_structures.hip: the structure entries; api_hooks.hip: the test
+// hooks): the error string, the owner of device buffers
 // that live for one call, the synchronous round trip built on it, and the argument checks of the packed-chain entries.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,11 +25,6 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
     if (e_ != hipSuccess) return ::fdmi::fail(FD_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                                               __FILE__, __LINE__);                                  \
   } while (0)
-
-// api.hip's weight packing and scale rules, as the test hooks use them
-void pack_weight_tiles(const float* W, int N, int K, std::vector<uint16_t>* out, float* scale);
-float scale_for(float bound);
-float dense_bound(const float* W, const float* bias, int r0, int r1, int K, float in_l2);
 
 // Device buffers that live for one call: freed when the owner goes out of scope, on every path.
 class DeviceBufs {

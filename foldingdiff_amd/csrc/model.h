@@ -1,5 +1,6 @@
-// The model behind the C ABI as its two sources see it: api.hip (weights, workspaces, the launch plan of a timestep, the captured
-// graph) defines what is declared here, api_run.hip (the entries that run the model) calls it.  Private to the library.
+// The model behind the C ABI as its sources see it: api.hip (workspaces, the launch plan of a timestep, the step, the captured
+// graph) and api_weights.hip (fd_set_weight, fd_finalize) define what is declared here; api_run.hip (the entries that run the
+// model) and api_comm.hip (the RCCL binding) call it or use fd_model alone.  Private to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -205,7 +206,16 @@ struct StepMode {
   bool ar = false;  // fd_ar_forward / fd_ar_sample (row-image path, with t_seq = the target lengths): the autoregressive baseline's embedding
 };
 
+// The q | k | v projections are stored per 32-column SUB-HEAD (d_model / 32 of them; a head of size 32 nb is nb consecutive
+// sub-heads): head size 32 (every released configuration) runs attention_img.hip, 64 / 96 / 128 the general attention_gen.hip.
+inline int head_dim(const fd_config& c) { return c.d_model / c.n_heads; }
+inline int sub_heads(const fd_config& c) { return c.d_model / 32; }
+
+// ---- defined in api_weights.hip
+void free_weights(fd_model* m);  // frees the device weights; the model is no longer finalized
+
 // ---- defined in api.hip
+void drop_workspaces(fd_model* m);  // frees every workspace (and with it every captured graph)
 int check_shape(fd_model* m, int B, int L, int t);  // the model is finalized and takes this shape and timestep
 // makes the (B, L) workspace current (m->ws), allocating it on first use; ends a sampling run begun earlier
 int ensure_ws(fd_model* m, int B, int L);
