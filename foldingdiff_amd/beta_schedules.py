@@ -3,7 +3,7 @@ Variance schedules and the derived per-timestep tables, computed ONCE on the
 host in float32 with the same torch op order as the reference
 (foldingdiff/beta_schedules.py:20-78) so the values are bit-identical, then
 uploaded to the GPU where the sampling loop indexes them by the device-resident
-step counter (csrc/rowwise.hip ``head_update_kernel``).
+step counter (csrc/p_sample_update.h ``resolve_update`` and csrc/rowwise_img.hip ``head_update_img_kernel``).
 """
 from typing import Dict, Literal, get_args
 

@@ -1,6 +1,7 @@
 // Motif-conditioned sampling ("replacement"): the one device definition of the value a FIXED element of a state
-// takes, shared by the three head + p_sample update kernels (rowwise.hip, rowwise_img.hip) and the kernel that replaces
-// the fixed elements of the start point, so that the statement cannot drift between them.
+// takes, shared by the p_sample update (update_element in p_sample_update.h for the two fp32 kernels, head_update_img_kernel's
+// own copy in rowwise_img.hip) and the kernel that replaces the fixed elements of the start point, so that the statement cannot
+// drift between them.
 //
 // Levels.  A state at level j = 0 .. T has seen j forward-noising steps: the state that enters reverse step t is at level
 // t + 1, the state that step t leaves is at level t.  coef = [2][T + 1]: keep[j] then spread[j], keep[0] = 1,

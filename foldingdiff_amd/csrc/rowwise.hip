@@ -9,12 +9,12 @@
 // A token's d_model row is spread over the 64 lanes (column = lane + 64*j, coalesced
 // 256-byte wave accesses); reductions are xor-shuffle butterflies over the wavefront.
 #include <cstdlib>
+#include <type_traits>
 
 #include "fdmi_kernels.h"
 #include "inpaint_replace.h"
+#include "p_sample_update.h"
 #include "philox_normal.h"
-#include "solver_update.h"
-#include "strided_update.h"
 #include "wrap_pi.h"
 
 namespace fdmi {
@@ -93,17 +93,20 @@ __device__ __forceinline__ void row_layernorm(float (&v)[NJ], int lane, int d, c
 }
 
 // ------------------------------------------------------------------ embed (K1)
-template <int NJ>
+// PER_SEQ (fd_forward_t, fd_denoise_loss): t_src is t_seq[B], one timestep per sequence, and a token of sequence b = tok / L
+// adds time_table[t_seq[b]]; otherwise t_src is the step's t_dev.  A compile-time parameter, so that the single-timestep
+// kernels (every sampling step, the captured graph) hold no trace of the other mode.
+template <int NJ, bool PER_SEQ>
 __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ x, const float* __restrict__ w_in,
                                                     const float* __restrict__ b_in, const float* __restrict__ pos_emb,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     float eps, const float* __restrict__ time_table,
-                                                    const int* __restrict__ t_dev, float* __restrict__ h, int M, int L,
+                                                    const int* __restrict__ t_src, float* __restrict__ h, int M, int L,
                                                     int F, int d) {
   const int lane = threadIdx.x & 63;
   const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (tok >= M) return;
-  const int t = *t_dev;
+  const int t = PER_SEQ ? t_src[tok / L] : *t_src;
   float xin[kMaxFeat];
 #pragma unroll
   for (int f = 0; f < kMaxFeat; ++f) xin[f] = f < F ? x[(size_t)tok * F + f] : 0.f;
@@ -127,12 +130,12 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ x,
   }
 }
 
-template <int NV>
+template <int NV, bool PER_SEQ>
 __global__ __launch_bounds__(256) void embed16_kernel(const float* __restrict__ x, const float* __restrict__ w_in,
                                                       const float* __restrict__ b_in, const float* __restrict__ pos_emb,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       float eps, const float* __restrict__ time_table,
-                                                      const int* __restrict__ t_dev, float* __restrict__ h, int M, int L,
+                                                      const int* __restrict__ t_src, float* __restrict__ h, int M, int L,
                                                       int F) {
   constexpr int d = 64 * NV;
   extern __shared__ __attribute__((aligned(16))) float wT[];  // [F][d]: w_in transposed
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(256) void embed16_kernel(const float* __restrict__ 
     wT[i] = w_in[c * F + f];
   }
   const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int t = *t_dev;
+  [[maybe_unused]] const int t = PER_SEQ ? 0 : *t_src;
   float4 bi[NV], gm[NV], bt[NV], tt[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(256) void embed16_kernel(const float* __restrict__ 
     bi[j] = *reinterpret_cast<const float4*>(b_in + c);
     gm[j] = *reinterpret_cast<const float4*>(gamma + c);
     bt[j] = *reinterpret_cast<const float4*>(beta + c);
-    tt[j] = *reinterpret_cast<const float4*>(time_table + (size_t)t * d + c);
+    if constexpr (!PER_SEQ) tt[j] = *reinterpret_cast<const float4*>(time_table + (size_t)t * d + c);  // the step's row, once
   }
   __syncthreads();
   for (int tg = blockIdx.x; tg * 16 < M; tg += gridDim.x) {
@@ -174,6 +177,11 @@ __global__ __launch_bounds__(256) void embed16_kernel(const float* __restrict__ 
       }
     }
     row16_layernorm<NV>(v, gm, bt, d, eps);
+    if constexpr (PER_SEQ) {
+      const float* trow = time_table + (size_t)t_src[tc / L] * d;  // the sequence's own row of the table
+#pragma unroll
+      for (int j = 0; j < NV; ++j) tt[j] = *reinterpret_cast<const float4*>(trow + 4 * (k + 16 * j));
+    }
     if (tok < M) {
 #pragma unroll
       for (int j = 0; j < NV; ++j)  // time embedding added AFTER the LayerNorm (modelling.py:472)
@@ -181,114 +189,6 @@ __global__ __launch_bounds__(256) void embed16_kernel(const float* __restrict__ 
             make_float4(v[j].x + tt[j].x, v[j].y + tt[j].y, v[j].z + tt[j].z, v[j].w + tt[j].w);
     }
   }
-}
-
-// ---- one timestep per sequence (fd_forward_t, fd_denoise_loss): the siblings of the two kernels above.  t_seq[B] takes
-// t_dev's place and a token of sequence b = tok / L adds time_table[t_seq[b]]; everything else is the kernel above, line
-// for line.  Separate kernels, so that the single-timestep ones (every sampling step, the captured graph) stay as they are.
-template <int NJ>
-__global__ __launch_bounds__(256) void embed_tseq_kernel(const float* __restrict__ x, const float* __restrict__ w_in,
-                                                         const float* __restrict__ b_in, const float* __restrict__ pos_emb,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float eps, const float* __restrict__ time_table,
-                                                         const int* __restrict__ t_seq, float* __restrict__ h, int M, int L,
-                                                         int F, int d){
-  const int lane = threadIdx.x & 63;
-  const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (tok >= M) return;
-  const int t = t_seq[tok / L];
-  float xin[kMaxFeat];
-#pragma unroll
-  for (int f = 0; f < kMaxFeat; ++f) xin[f] = f < F ? x[(size_t)tok * F + f] : 0.f;
-  float v[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
-    float a = 0.f;
-    if (c < d) {
-      a = b_in[c];
-      for (int f = 0; f < F; ++f) a += xin[f] * w_in[c * F + f];
-      if (pos_emb) a += pos_emb[(size_t)(tok % L) * d + c];  // absolute positions only (modelling.py:164-166)
-    }
-    v[j] = a;
-  }
-  row_layernorm<NJ>(v, lane, d, gamma, beta, eps);
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
-    if (c < d) h[(size_t)tok * d + c] = v[j] + time_table[(size_t)t * d + c];  // added AFTER the LayerNorm (:472)
-  }
-}
-
-template <int NV>
-__global__ __launch_bounds__(256) void embed16_tseq_kernel(const float* __restrict__ x, const float* __restrict__ w_in,
-                                                           const float* __restrict__ b_in, const float* __restrict__ pos_emb,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float eps, const float* __restrict__ time_table,
-                                                           const int* __restrict__ t_seq, float* __restrict__ h, int M, int L,
-                                                           int F){
-  constexpr int d = 64 * NV;
-  extern __shared__ __attribute__((aligned(16))) float wT[];  // [F][d]: w_in transposed
-  for (int i = threadIdx.x; i < F * d; i += 256) {
-    const int f = i / d, c = i - f * d;
-    wT[i] = w_in[c * F + f];
-  }
-  const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
-  float4 bi[NV], gm[NV], bt[NV], tt[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = 4 * (k + 16 * j);
-    bi[j] = *reinterpret_cast<const float4*>(b_in + c);
-    gm[j] = *reinterpret_cast<const float4*>(gamma + c);
-    bt[j] = *reinterpret_cast<const float4*>(beta + c);
-  }
-  __syncthreads();
-  for (int tg = blockIdx.x; tg * 16 < M; tg += gridDim.x) {
-    const int tok = tg * 16 + g;
-    const int tc = tok < M ? tok : M - 1;
-    float4 v[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = bi[j];
-    for (int f = 0; f < F; ++f) {
-      const float xf = x[(size_t)tc * F + f];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const float4 w = *reinterpret_cast<const float4*>(wT + f * d + 4 * (k + 16 * j));
-        v[j].x += xf * w.x; v[j].y += xf * w.y; v[j].z += xf * w.z; v[j].w += xf * w.w;
-      }
-    }
-    if (pos_emb) {  // absolute positions only (modelling.py:164-166)
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const float4 pe = *reinterpret_cast<const float4*>(pos_emb + (size_t)(tc % L) * d + 4 * (k + 16 * j));
-        v[j].x += pe.x; v[j].y += pe.y; v[j].z += pe.z; v[j].w += pe.w;
-      }
-    }
-    row16_layernorm<NV>(v, gm, bt, d, eps);
-    const float* trow = time_table + (size_t)t_seq[tc / L] * d;  // the sequence's own row of the table
-#pragma unroll
-    for (int j = 0; j < NV; ++j) tt[j] = *reinterpret_cast<const float4*>(trow + 4 * (k + 16 * j));
-    if (tok < M) {
-#pragma unroll
-      for (int j = 0; j < NV; ++j)  // time embedding added AFTER the LayerNorm (modelling.py:472)
-        *reinterpret_cast<float4*>(h + (size_t)tok * d + 4 * (k + 16 * j)) =
-            make_float4(v[j].x + tt[j].x, v[j].y + tt[j].y, v[j].z + tt[j].z, v[j].w + tt[j].w);
-    }
-  }
-}
-
-template <int NV>
-static void launch_embed16(const float* x, const float* w_in, const float* b_in, const float* pos_emb, const float* gamma,
-                           const float* beta, float eps, const float* time_table, const int* t_dev, const int* t_seq, float* h,
-                           int M, int L, int F, hipStream_t s) {
-  int grid = (M + 15) / 16;
-  if (grid > 2048) grid = 2048;
-  if (t_seq)
-    hipLaunchKernelGGL((embed16_tseq_kernel<NV>), dim3(grid), dim3(256), (size_t)F * 64 * NV * 4, s, x, w_in, b_in, pos_emb,
-                       gamma, beta, eps, time_table, t_seq, h, M, L, F);
-  else
-    hipLaunchKernelGGL((embed16_kernel<NV>), dim3(grid), dim3(256), (size_t)F * 64 * NV * 4, s, x, w_in, b_in, pos_emb, gamma,
-                       beta, eps, time_table, t_dev, h, M, L, F);
 }
 
 // FDMI_ROWWISE16=0 keeps the one-wave-per-token kernels (also the generic path for d % 64 != 0 or d > 512)
@@ -297,32 +197,43 @@ static bool use_row16(int d) {
   return on && d % 64 == 0 && d >= 64 && d <= 512;
 }
 
-void launch_embed(const float* x, const float* w_in, const float* b_in, const float* pos_emb, const float* gamma,
-                  const float* beta, float eps, const float* time_table, const int* t_dev, const int* t_seq, float* h, int B,
-                  int L, int F, int d, hipStream_t s) {
-  const int M = B * L;
+// The one-wave-per-token kernels exist for 1, 3, 6, 12 and 16 columns per lane: fn(integral_constant NJ) of the smallest that holds d
+template <typename Fn>
+static void with_row_nj(int d, Fn&& fn) {
+  const int nj = (d + 63) / 64;
+  if (nj <= 1) fn(std::integral_constant<int, 1>{});
+  else if (nj <= 3) fn(std::integral_constant<int, 3>{});
+  else if (nj <= 6) fn(std::integral_constant<int, 6>{});
+  else if (nj <= 12) fn(std::integral_constant<int, 12>{});
+  else fn(std::integral_constant<int, 16>{});
+}
+
+template <bool PER_SEQ>
+static void launch_embed_as(const float* x, const float* w_in, const float* b_in, const float* pos_emb, const float* gamma,
+                            const float* beta, float eps, const float* time_table, const int* t_src, float* h, int M, int L, int F,
+                            int d, hipStream_t s) {
   if (use_row16(d)) {
-#define FD_E16(NV) case NV: launch_embed16<NV>(x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, t_dev, t_seq, h, M, L, F, s); return;
+    int grid = (M + 15) / 16;
+    if (grid > 2048) grid = 2048;
+#define FD_E16(NV)                                                                                                             \
+  case NV:                                                                                                                     \
+    hipLaunchKernelGGL((embed16_kernel<NV, PER_SEQ>), dim3(grid), dim3(256), (size_t)F * 64 * NV * 4, s, x, w_in, b_in, pos_emb, \
+                       gamma, beta, eps, time_table, t_src, h, M, L, F);                                                       \
+    return;
     switch (d / 64) { FD_E16(1) FD_E16(2) FD_E16(3) FD_E16(4) FD_E16(5) FD_E16(6) FD_E16(7) FD_E16(8) }
 #undef FD_E16
   }
-  const dim3 grid((M + 3) / 4), block(256);
-  const int nj = (d + 63) / 64;
-#define FD_EMBED(NJ)                                                                                                       \
-  do {                                                                                                                     \
-    if (t_seq)                                                                                                             \
-      hipLaunchKernelGGL((embed_tseq_kernel<NJ>), grid, block, 0, s, x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, \
-                         t_seq, h, M, L, F, d);                                                                            \
-    else                                                                                                                   \
-      hipLaunchKernelGGL((embed_kernel<NJ>), grid, block, 0, s, x, w_in, b_in, pos_emb, gamma, beta, eps, time_table,      \
-                         t_dev, h, M, L, F, d);                                                                            \
-  } while (0)
-  if (nj <= 1) FD_EMBED(1);
-  else if (nj <= 3) FD_EMBED(3);
-  else if (nj <= 6) FD_EMBED(6);
-  else if (nj <= 12) FD_EMBED(12);
-  else FD_EMBED(16);
-#undef FD_EMBED
+  with_row_nj(d, [&](auto nj) {
+    hipLaunchKernelGGL((embed_kernel<decltype(nj)::value, PER_SEQ>), dim3((M + 3) / 4), dim3(256), 0, s, x, w_in, b_in, pos_emb, gamma,
+                       beta, eps, time_table, t_src, h, M, L, F, d);
+  });
+}
+
+void launch_embed(const float* x, const float* w_in, const float* b_in, const float* pos_emb, const float* gamma,
+                  const float* beta, float eps, const float* time_table, const int* t_dev, const int* t_seq, float* h, int B,
+                  int L, int F, int d, hipStream_t s) {
+  if (t_seq) launch_embed_as<true>(x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, t_seq, h, B * L, L, F, d, s);
+  else launch_embed_as<false>(x, w_in, b_in, pos_emb, gamma, beta, eps, time_table, t_dev, h, B * L, L, F, d, s);
 }
 
 // ------------------------------------------------------------- standalone LN
@@ -349,15 +260,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 
 void launch_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int d,
                       hipStream_t s) {
-  const dim3 grid((rows + 3) / 4), block(256);
-  const int nj = (d + 63) / 64;
-#define FD_LN(NJ) hipLaunchKernelGGL((layernorm_kernel<NJ>), grid, block, 0, s, x, gamma, beta, eps, y, rows, d)
-  if (nj <= 1) FD_LN(1);
-  else if (nj <= 3) FD_LN(3);
-  else if (nj <= 6) FD_LN(6);
-  else if (nj <= 12) FD_LN(12);
-  else FD_LN(16);
-#undef FD_LN
+  with_row_nj(d, [&](auto nj) {
+    hipLaunchKernelGGL((layernorm_kernel<decltype(nj)::value>), dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma, beta, eps, y, rows, d);
+  });
 }
 
 // ---------------------------------------------------------- Philox4x32-10 (philox_normal.h)
@@ -416,78 +321,7 @@ __global__ __launch_bounds__(256) void head_update_kernel(UpdateArgs a) {
   const size_t o = (size_t)tok * F + lane;
   if (a.eps_out) a.eps_out[o] = mine;
   if (!a.x_out) return;
-  const int t = *a.t_dev;
-  const float* noise = a.noise;
-  float* hist = a.hist;
-  unsigned long long seed = a.seed;
-  long long seq_offset = a.seq_offset;
-  int t_start = a.t_start, hist_every = 1;
-  const float *known = a.known, *known_noise = a.known_noise, *known_coef = a.known_coef;  // (inpaint_replace.h)
-  const unsigned char* fixed = a.fixed;
-  if (a.dyn) {
-    noise = a.dyn->noise; hist = a.dyn->hist; seed = a.dyn->seed; seq_offset = a.dyn->seq_offset; t_start = a.dyn->t_start;
-    hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
-    known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
-  }
-  // strided sampling (fd_sample_strided: the tables of `dyn`; fd_p_sample_step_coef: by value)
-  bool strided = a.strided != 0;
-  float sa = a.sa, sb = a.sb, ss = a.ss;
-  int ord = 0, t_next = -1;
-  // ... of the second-order solver (fd_sample_solver: `dyn`'s cuv and x0_prev; fd_p_sample_step_solver: by value)
-  bool solver = a.x0_out != nullptr && a.strided != 2;  // (strided == 2: a steered visit, which only writes x0 to x0_out)
-  float sc = a.sc, su = a.su, sv = a.sv;
-  const float* x0_prev = a.x0_prev;
-  float* x0_out = a.x0_out;
-  int level = strided ? a.level_out : t, known_row = level;  // what a fixed element leaves at, and its row of known_noise (inpaint_replace.h)
-  if (a.dyn && a.dyn->next_t) {
-    strided = true;
-    t_next = a.dyn->next_t[t]; ord = a.dyn->ord[t];
-    level = t_next + 1; known_row = ord + 1;
-    sa = a.dyn->abs[t]; sb = a.dyn->abs[a.T + t]; ss = a.dyn->abs[2 * a.T + t];
-    if (a.dyn->cuv) {
-      solver = true;
-      sc = a.dyn->cuv[t]; su = a.dyn->cuv[a.T + t]; sv = a.dyn->cuv[2 * a.T + t];
-      x0_prev = x0_out = a.dyn->x0_prev;
-    } else if (a.dyn->uv) {  // a steered run (fd_sample_steered): the visit also writes its x0
-      su = a.dyn->uv[t]; sv = a.dyn->uv[a.T + t];
-      x0_out = a.dyn->x0_steer;
-    }
-  }
-  const float c1 = a.coef[t], bt = a.coef[a.T + t], c3 = a.coef[2 * a.T + t], sg = a.coef[3 * a.T + t];
-  // model_mean = sqrt_recip_alphas_t * (x - betas_t * eps / sqrt_one_minus_alphas_cumprod_t)   (sampling.py:62-67)
-  float xn;
-  if (fixed && fixed[o]) {  // a fixed element leaves step t at level t (a strided visit: where it lands), whatever the model predicted
-    xn = inpaint_value_row(known, known_noise, known_coef, a.T, a.noise_stride, level, known_row, o, seed, seq_offset + tok / a.L, tok % a.L, lane,
-                       (a.angle_mask >> lane) & 1u);
-  } else if (strided && !solver) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
-    xn = strided_mean(sa, a.x[o], sb, mine);
-    if (x0_out) {  // a steered visit: solver_update.h's x0 statement; x' does not depend on it
-      float p0 = strided_mean(su, a.x[o], sv, mine);
-      if ((a.angle_mask >> lane) & 1u) p0 = wrap_pi(p0);
-      x0_out[o] = p0;
-    }
-    if (ss != 0.f) {
-      const float z = noise ? noise[(size_t)ord * a.noise_stride + o]
-                            : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, lane);
-      xn = strided_add_noise(xn, ss, z);
-    }
-    if ((a.angle_mask >> lane) & 1u) xn = wrap_pi(xn);
-  } else if (strided) {  // solver_update.h: the strided mean, corrected by c * wrap(x0 - prev); no draw
-    xn = solver_update(sa, a.x[o], sb, mine, sc, su, sv, x0_prev + o, x0_out + o, (a.angle_mask >> lane) & 1u);
-  } else {
-    xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(bt, mine), c3)));
-    if (t > 0) {  // sampling.py:69-75
-      const float z = noise ? noise[(size_t)t * a.noise_stride + o]
-                            : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, lane);
-      xn = __fadd_rn(xn, __fmul_rn(sg, z));
-    }
-    if ((a.angle_mask >> lane) & 1u) xn = wrap_pi(xn);
-  }
-  a.x_out[o] = xn;
-  const int state = strided ? ord : t_start - t;   // the state's ordinal in the run
-  const bool last = strided ? t_next < 0 : t == 0;
-  if (hist && ((state + 1) % hist_every == 0 || last))  // state j goes to row j / hist_every
-    hist[(size_t)(state / hist_every) * a.M * F + o] = xn;
+  update_element(a, resolve_update(a, *a.t_dev, true), o, mine, tok / a.L, tok % a.L, lane, (size_t)a.M * F);
 }
 
 template <int NV>
@@ -506,46 +340,7 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
     }
   }
   const float b2k = a.b2[k < F ? k : 0];
-  // per-call values (see UpdateDyn)
-  const int t = a.x_out ? *a.t_dev : 0;
-  const float* noise = a.noise;
-  float* hist = a.hist;
-  unsigned long long seed = a.seed;
-  long long seq_offset = a.seq_offset;
-  int t_start = a.t_start, hist_every = 1;
-  const float *known = a.known, *known_noise = a.known_noise, *known_coef = a.known_coef;  // (inpaint_replace.h)
-  const unsigned char* fixed = a.fixed;
-  if (a.dyn) {
-    noise = a.dyn->noise; hist = a.dyn->hist; seed = a.dyn->seed; seq_offset = a.dyn->seq_offset; t_start = a.dyn->t_start;
-    hist_every = a.dyn->hist_every > 1 ? a.dyn->hist_every : 1;
-    known = a.dyn->known; fixed = a.dyn->fixed; known_noise = a.dyn->known_noise; known_coef = a.dyn->known_coef;
-  }
-  // strided sampling (fd_sample_strided: the tables of `dyn`; fd_p_sample_step_coef: by value)
-  bool strided = a.strided != 0;
-  float sa = a.sa, sb = a.sb, ss = a.ss;
-  int ord = 0, t_next = -1;
-  // ... of the second-order solver (fd_sample_solver: `dyn`'s cuv and x0_prev; fd_p_sample_step_solver: by value)
-  bool solver = a.x0_out != nullptr && a.strided != 2;  // (strided == 2: a steered visit, which only writes x0 to x0_out)
-  float sc = a.sc, su = a.su, sv = a.sv;
-  const float* x0_prev = a.x0_prev;
-  float* x0_out = a.x0_out;
-  int level = strided ? a.level_out : t, known_row = level;  // what a fixed element leaves at, and its row of known_noise (inpaint_replace.h)
-  if (a.x_out && a.dyn && a.dyn->next_t) {
-    strided = true;
-    t_next = a.dyn->next_t[t]; ord = a.dyn->ord[t];
-    level = t_next + 1; known_row = ord + 1;
-    sa = a.dyn->abs[t]; sb = a.dyn->abs[a.T + t]; ss = a.dyn->abs[2 * a.T + t];
-    if (a.dyn->cuv) {
-      solver = true;
-      sc = a.dyn->cuv[t]; su = a.dyn->cuv[a.T + t]; sv = a.dyn->cuv[2 * a.T + t];
-      x0_prev = x0_out = a.dyn->x0_prev;
-    } else if (a.dyn->uv) {  // a steered run (fd_sample_steered): the visit also writes its x0
-      su = a.dyn->uv[t]; sv = a.dyn->uv[a.T + t];
-      x0_out = a.dyn->x0_steer;
-    }
-  }
-  float c1 = 0.f, btc = 0.f, c3 = 1.f, sg = 0.f;
-  if (a.x_out) { c1 = a.coef[t]; btc = a.coef[a.T + t]; c3 = a.coef[2 * a.T + t]; sg = a.coef[3 * a.T + t]; }
+  const UpdateVisit m = resolve_update(a, a.x_out ? *a.t_dev : 0, a.x_out != nullptr);  // before the row loop: see p_sample_update.h
   __syncthreads();
   for (int tg = blockIdx.x; tg * 16 < a.M; tg += gridDim.x) {
     const int tok = tg * 16 + g;
@@ -569,42 +364,7 @@ __global__ __launch_bounds__(256) void head_update16_kernel(UpdateArgs a) {
     if (k < F && tok < a.M) {
       const size_t o = (size_t)tok * F + k;
       if (a.eps_out) a.eps_out[o] = mine;
-      if (a.x_out) {
-        // model_mean = sqrt_recip_alphas_t * (x - betas_t * eps / sqrt_one_minus_alphas_cumprod_t)   (sampling.py:62-67)
-        float xn;
-        if (fixed && fixed[o]) {  // a fixed element leaves step t at level t (a strided visit: where it lands), whatever the model predicted
-          xn = inpaint_value_row(known, known_noise, known_coef, a.T, a.noise_stride, level, known_row, o, seed, seq_offset + tok / a.L,
-                             tok % a.L, k, (a.angle_mask >> k) & 1u);
-        } else if (strided && !solver) {  // strided_update.h: x' = a x + b eps (+ s z), rounded once each; z neither read nor drawn where s == 0
-          xn = strided_mean(sa, a.x[o], sb, mine);
-          if (x0_out) {  // a steered visit: solver_update.h's x0 statement; x' does not depend on it
-            float p0 = strided_mean(su, a.x[o], sv, mine);
-            if ((a.angle_mask >> k) & 1u) p0 = wrap_pi(p0);
-            x0_out[o] = p0;
-          }
-          if (ss != 0.f) {
-            const float z = noise ? noise[(size_t)ord * a.noise_stride + o]
-                                  : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, k);
-            xn = strided_add_noise(xn, ss, z);
-          }
-          if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
-        } else if (strided) {  // solver_update.h: the strided mean, corrected by c * wrap(x0 - prev); no draw
-          xn = solver_update(sa, a.x[o], sb, mine, sc, su, sv, x0_prev + o, x0_out + o, (a.angle_mask >> k) & 1u);
-        } else {
-          xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fdiv_rn(__fmul_rn(btc, mine), c3)));
-          if (t > 0) {  // sampling.py:69-75
-            const float z = noise ? noise[(size_t)t * a.noise_stride + o]
-                                  : philox_normal(seed, t, seq_offset + tok / a.L, tok % a.L, k);
-            xn = __fadd_rn(xn, __fmul_rn(sg, z));
-          }
-          if ((a.angle_mask >> k) & 1u) xn = wrap_pi(xn);
-        }
-        a.x_out[o] = xn;
-        const int state = strided ? ord : t_start - t;   // the state's ordinal in the run
-        const bool last = strided ? t_next < 0 : t == 0;
-        if (hist && ((state + 1) % hist_every == 0 || last))  // state j goes to row j / hist_every
-          hist[(size_t)(state / hist_every) * a.M * F + o] = xn;
-      }
+      if (a.x_out) update_element(a, m, o, mine, tok / a.L, tok % a.L, k, (size_t)a.M * F);
     }
   }
 }
@@ -622,15 +382,9 @@ void launch_head_update(const UpdateArgs& a, hipStream_t s) {
     switch (a.d / 64) { FD_H16(1) FD_H16(2) FD_H16(3) FD_H16(4) FD_H16(5) FD_H16(6) FD_H16(7) FD_H16(8) }
 #undef FD_H16
   }
-  const dim3 grid((a.M + 3) / 4), block(256);
-  const int nj = (a.d + 63) / 64;
-#define FD_HU(NJ) hipLaunchKernelGGL((head_update_kernel<NJ>), grid, block, 0, s, a)
-  if (nj <= 1) FD_HU(1);
-  else if (nj <= 3) FD_HU(3);
-  else if (nj <= 6) FD_HU(6);
-  else if (nj <= 12) FD_HU(12);
-  else FD_HU(16);
-#undef FD_HU
+  with_row_nj(a.d, [&](auto nj) {
+    hipLaunchKernelGGL((head_update_kernel<decltype(nj)::value>), dim3((a.M + 3) / 4), dim3(256), 0, s, a);
+  });
 }
 
 // ---- the start point of a motif-conditioned run: its fixed elements at level `level` (inpaint_replace.h)

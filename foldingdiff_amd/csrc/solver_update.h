@@ -1,5 +1,5 @@
-// The update of a visit of the second-order multistep solver (include/fdmi.h), shared by the three update
-// kernels.  With the visit's (a, b, c, u, v):
+// The update of a visit of the second-order multistep solver (include/fdmi.h); its callers are update_element
+// (p_sample_update.h) and head_update_img_kernel (rowwise_img.hip).  With the visit's (a, b, c, u, v):
 //   m  = a x + b eps                                   strided_update.h's mean
 //   x0 = u x + v eps, wrapped where angular            the visit's prediction of the clean state
 //   m  = m + c * wrap(x0 - prev)  where c != 0         prev = the prediction of the visit before; the difference of two angles

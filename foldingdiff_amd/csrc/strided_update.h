@@ -1,4 +1,5 @@
-// The update of a strided (few-step) sampling visit (include/fdmi.h), shared by the three update kernels:
+// The update of a strided (few-step) sampling visit (include/fdmi.h), called by update_element (p_sample_update.h),
+// head_update_img_kernel (rowwise_img.hip) and solver_update.h:
 //   x' = a x + b eps, then + s z where s != 0 -- every product and every sum rounded once.
 // hipcc's default lets a * b + c contract into an FMA, and the __f*_rn functions of the HIP headers are plain operators that
 // are contracted all the same once they are inlined (see angle_stats.hip); so the statement is written with operators, in
