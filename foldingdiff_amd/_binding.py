@@ -53,6 +53,16 @@ class FdSteerParams(C.Structure):
     ]
 
 
+class FdGuideParams(C.Structure):
+    """``fd_guide_params`` of include/fdmi.h."""
+    _fields_ = [
+        ("feat_idx", C.c_int32 * 9),
+        ("has_offset", C.c_int32),
+        ("offset", C.c_float * 16),
+        ("max_norm", C.c_double),
+    ]
+
+
 # every symbol include/fdmi.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -97,6 +107,12 @@ _SIGNATURES = {
     "fd_sample_repeat": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.c_int64, _P, _P]),
     "fd_tie_repeats": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, _P, C.c_uint64, C.c_int, C.c_int64,
                                  _P]),
+    "fd_nerf_vjp": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "fd_restraint_energy": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_guide_step": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_double,
+                                C.c_float, _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P]),
+    "fd_sample_guided": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.c_int64, _P, C.POINTER(FdGuideParams),
+                                   _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fd_sample_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_begin_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_steps_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),

@@ -1,6 +1,6 @@
 // C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
 // single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned, solver, steered,
-// repeat) and their device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry
+// repeat, guided) and their device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry
 // checks its arguments before its first HIP call, and the paragraphs the entries share are written once, below: make the
 // workspace current and upload (open_call), download and synchronise (finish), the one-copy staging of the loss entries
 // (PackedUpload), one reverse step from host arrays (host_step), the owner of a run from host arrays (HostRun: stage, begin,
@@ -809,6 +809,88 @@ int repeat_host_run(fd_model* m, const RunArrays& a, const int32_t* visits, cons
   return r.finish(rc);
 }
 
+// ---- restraint-guided sampling: a strided run whose visits leave wrap(a x + b eps) and their prediction of the
+// clean state -- the tables' row s is zero, as in a repeat run; u | v as in a steered run -- with the guide statement's five
+// launches (steer.hip's shift, nerf.hip, nerf_vjp.hip) behind every visit.  The entry has checked every argument; a.states = K,
+// final state only.  The tables, the restraints and the work buffers die with this frame.
+struct GuidedHostRun {
+  RunArrays arrays;
+  const int32_t* visits;
+  const float* coef;   // [5][K] a | b | s | u | v
+  const float* guide;  // [K]
+  const fd_guide_params* params;
+  RestraintLists rst;
+  double *energy_out, *max_violation_out;
+};
+
+int guided_host_run(fd_model* m, const GuidedHostRun& a) {
+  const RunArrays& h = a.arrays;
+  const int F = m->cfg.n_features, B = h.B, L = h.L, K = (int)h.states;
+  const size_t na = (size_t)B * 3 * L * 3, nb = (size_t)B, Kz = h.states, R = a.rst.count();
+  const fd_guide_params& gp = *a.params;
+  HostRun r(m, h);
+  if (int rc = r.stage()) return rc;
+  const size_t n = r.n;
+  DeviceBufs& bufs = r.bufs;
+  VisitTables tb;
+  if (int rc = stage_tables(m, &bufs, a.visits, K, {a.coef, a.coef + Kz, nullptr, a.coef + 3 * Kz, a.coef + 4 * Kz}, &tb)) return rc;
+  float *d_x0, *d_ang;
+  double *d_coords, *d_gc, *d_G, *d_energy, *d_maxv, *d_gnorm;
+  HIP_TRY(bufs.zeros(n * 4, &d_x0));  // (packed rows: a position beyond a length is never written, and never read)
+  HIP_TRY(bufs.alloc(n * 4, &d_ang));
+  HIP_TRY(bufs.alloc(na * 8, &d_coords));
+  HIP_TRY(bufs.alloc(na * 8, &d_gc));
+  HIP_TRY(bufs.alloc(n * 8, &d_G));
+  HIP_TRY(bufs.alloc(nb * 8, &d_energy));
+  HIP_TRY(bufs.alloc(nb * 8, &d_maxv));
+  HIP_TRY(bufs.alloc(nb * 8, &d_gnorm));
+  Restraints rs{};  // (an empty list: the kernel reads the offsets only)
+  HIP_TRY(bufs.upload(a.rst.offsets, (nb + 1) * 4, &rs.offsets));
+  if (R) {
+    HIP_TRY(bufs.upload(a.rst.i, R * 4, &rs.i));
+    HIP_TRY(bufs.upload(a.rst.j, R * 4, &rs.j));
+    HIP_TRY(bufs.upload(a.rst.d0, R * 8, &rs.d0));
+    HIP_TRY(bufs.upload(a.rst.tol, R * 8, &rs.tol));
+    HIP_TRY(bufs.upload(a.rst.w, R * 8, &rs.w));
+  }
+  const NerfFeatures fx{gp.feat_idx[0], gp.feat_idx[1], gp.feat_idx[2], gp.feat_idx[3], gp.feat_idx[4],
+                        gp.feat_idx[5], gp.feat_idx[6], gp.feat_idx[7], gp.feat_idx[8]};
+  SteerOffset off{};
+  off.has_offset = gp.has_offset ? 1 : 0;
+  for (int f = 0; gp.has_offset && f < F; ++f) off.offset[f] = gp.offset[f];
+
+  if (int rc = r.begin(a.visits[0], K)) return rc;
+  hipStream_t s = m->stream;
+  Workspace& w = m->ws;
+  tb.apply(&m->dyn_host);
+  m->dyn_host.uv = tb.row(3);
+  m->dyn_host.x0_steer = d_x0;
+  auto energy_of = [&](const float* state, double* grad) {  // shift, NeRF and the restraints of a [B][L][F] state in model space
+    launch_steer_shift(state, w.lens, B, L, F, off, m->angle_mask, d_ang, s);
+    launch_nerf(d_ang, w.lens, B, L, F, fx, 0, d_coords, s);
+    launch_restraint_energy(d_coords, w.lens, B, L, rs, d_energy, d_maxv, grad, s);
+  };
+  auto launched = [&]() -> int {
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? fail(FD_E_HIP, "the guide launches: %s", hipGetErrorString(e)) : FD_OK;
+  };
+  int rc = FD_OK;
+  for (int i = 0; !rc && i < K; ++i) {
+    rc = fd_sample_steps_dev(m, 1, nullptr, 0, nullptr);
+    if (rc) break;
+    energy_of(d_x0, d_gc);
+    launch_nerf_vjp(d_coords, w.lens, B, L, F, fx, 0, d_gc, d_G, s);
+    launch_guide_update(w.x, d_G, w.lens, B, L, F, m->angle_mask, a.guide[i], gp.max_norm, a.coef[2 * Kz + i],
+                        r.noise ? r.noise + (size_t)i * r.n : nullptr, h.seed, a.visits[i], h.seq_offset, d_gnorm, s);
+    rc = launched();
+  }
+  if (!rc) {
+    energy_of(w.x, nullptr);  // the final state's
+    rc = launched();
+  }
+  return r.finish(rc, {{a.energy_out, d_energy, nb * 8}, {a.max_violation_out, d_maxv, nb * 8}});
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -1304,6 +1386,25 @@ int fd_sample_repeat(fd_model* m, const float* x_init, const int32_t* lens, int 
   if (int rc = check_lens(lens, B, L)) return rc;
   if (int rc = check_tie(tie, lens, B)) return rc;
   return repeat_host_run(m, {x_init, lens, B, L, (size_t)n_visits, noise, nullptr, seed, seq_offset, out, 0}, visits, coef, tie);
+}
+
+int fd_sample_guided(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                     const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, const float* guide,
+                     const fd_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i, const int32_t* rst_j,
+                     const double* rst_d0, const double* rst_tol, const double* rst_w, float* out, double* energy_out,
+                     double* max_violation_out) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;  // (rows a | b | s too)
+  if (int rc = check_coef_rows(coef, n_visits, 3, 5)) return rc;
+  if (!guide || !params) return fail(FD_E_INVALID, "null argument: guide and params are required");
+  if (!energy_out || !max_violation_out) return fail(FD_E_INVALID, "null argument: energy_out and max_violation_out are required");
+  for (int i = 0; i < n_visits; ++i)
+    if (!std::isfinite(guide[i])) return fail(FD_E_INVALID, "guide[%d] = %g is not finite", i, (double)guide[i]);
+  if (int rc = check_guide_shape(lens, B, L, m->cfg.n_features, params->feat_idx)) return rc;
+  if (int rc = check_guide_scalars(params->max_norm, params->has_offset ? params->offset : nullptr, m->cfg.n_features)) return rc;
+  const RestraintLists rl{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
+  if (int rc = check_restraints(rl, lens)) return rc;
+  return guided_host_run(m, GuidedHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, nullptr, seed, seq_offset, out, 0}, visits, coef,
+                                          guide, params, rl, energy_out, max_violation_out});
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

@@ -1,5 +1,5 @@
 // C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, dssp.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
-// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) and of the steering kernels on their own (steer.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip) and of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
 #include <cstring>
@@ -9,6 +9,21 @@
 #include "host_common.h"
 
 using namespace fdmi;
+
+// the six uploads of a batch's restraints (check_restraints has passed); an empty list uploads one entry per array, never read
+namespace {
+struct RestraintInputs {
+  std::pair<const void*, size_t> offsets, i, j, d0, tol, w;
+};
+RestraintInputs restraint_inputs(const RestraintLists& r) {
+  static const int32_t no_atom = 0;
+  static const double no_value = 0.0;
+  const size_t R = r.count();
+  const auto ints = [&](const int32_t* p) { return std::pair<const void*, size_t>(R ? p : &no_atom, (R ? R : 1) * 4); };
+  const auto doubles = [&](const double* p) { return std::pair<const void*, size_t>(R ? p : &no_value, (R ? R : 1) * 8); };
+  return {{r.offsets, ((size_t)r.n_chains + 1) * 4}, ints(r.i), ints(r.j), doubles(r.d0), doubles(r.tol), doubles(r.w)};
+}
+}  // namespace
 
 extern "C" {
 
@@ -22,6 +37,95 @@ int fd_nerf(int device_id, const float* feats, const int32_t* lens, int B, int L
   return device_roundtrip(device_id, {{feats, (size_t)B * L * F * 4}, {lens, (size_t)B * 4}},
                           {{coords_out, (size_t)B * 3 * L * 3 * 8}},
                           [&](const RoundtripBufs& d) { launch_nerf(d.in(0), d.in(1), B, L, F, fx, center, d.out(0), nullptr); });
+}
+
+int fd_nerf_vjp(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int centered,
+                const double* dcoords, double* dfeats_out) {
+  if (!coords || !lens || !feat_idx || !dcoords || !dfeats_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_guide_shape(lens, B, L, F, feat_idx)) return rc;
+  if (int rc = check_chain_doubles("coords", coords, lens, B, L)) return rc;
+  if (int rc = check_chain_doubles("dcoords", dcoords, lens, B, L)) return rc;
+  const NerfFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5], feat_idx[6], feat_idx[7], feat_idx[8]};
+  const size_t na = (size_t)B * 3 * L * 3, n = (size_t)B * L * F;
+  std::vector<double> grad_host(n);  // the rows at or beyond a length are not the kernel's: dfeats_out keeps what it held there
+  const int rc = device_roundtrip(device_id, {{coords, na * 8}, {dcoords, na * 8}, {lens, (size_t)B * 4}}, {{grad_host.data(), n * 8}},
+                                  [&](const RoundtripBufs& d) { launch_nerf_vjp(d.in(0), d.in(2), B, L, F, fx, centered, d.in(1), d.out(0), nullptr); });
+  if (rc) return rc;
+  for (int b = 0; b < B; ++b)
+    memcpy(dfeats_out + (size_t)b * L * F, grad_host.data() + (size_t)b * L * F, (size_t)lens[b] * F * 8);
+  return FD_OK;
+}
+
+int fd_restraint_energy(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* rst_offsets,
+                        const int32_t* rst_i, const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
+                        double* energy_out, double* max_violation_out, double* dcoords_out) {
+  if (!coords || !lens || !energy_out || !max_violation_out) return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if ((long long)B * L * 9 > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * 9 = %lld coordinates, at most 2^31 - 1", (long long)B * L * 9);
+  if (int rc = check_lens(lens, B, L < kGuideMaxLen ? L : kGuideMaxLen)) return rc;
+  const RestraintLists rl{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
+  if (int rc = check_restraints(rl, lens)) return rc;
+  if (int rc = check_chain_doubles("coords", coords, lens, B, L)) return rc;
+  const RestraintInputs ri = restraint_inputs(rl);
+  const size_t na = (size_t)B * 3 * L * 3, nb = (size_t)B;
+  return device_roundtrip(device_id, {{coords, na * 8}, {lens, nb * 4}, ri.offsets, ri.i, ri.j, ri.d0, ri.tol, ri.w},
+                          {{energy_out, nb * 8}, {max_violation_out, nb * 8}, {dcoords_out, dcoords_out ? na * 8 : 8}},
+                          [&](const RoundtripBufs& d) {
+                            const Restraints rs{d.in(2), d.in(3), d.in(4), d.in(5), d.in(6), d.in(7)};
+                            double* grad = d.out(2);
+                            launch_restraint_energy(d.in(0), d.in(1), B, L, rs, d.out(0), d.out(1), dcoords_out ? grad : nullptr, nullptr);
+                          });
+}
+
+int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                  const float* offset, const uint8_t* is_angle, const int32_t* rst_offsets, const int32_t* rst_i,
+                  const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float c, double max_norm,
+                  float s, const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
+                  double* gnorm_out) {
+  if (!x || !x0 || !lens || !feat_idx || !is_angle || !x_out || !energy_out || !gnorm_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_guide_shape(lens, B, L, F, feat_idx)) return rc;
+  const RestraintLists rl{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
+  if (int rc = check_restraints(rl, lens)) return rc;
+  if (!std::isfinite(c)) return fail(FD_E_INVALID, "c = %g is not finite", (double)c);
+  if (!std::isfinite(s)) return fail(FD_E_INVALID, "s = %g is not finite", (double)s);
+  if (int rc = check_guide_scalars(max_norm, offset, F)) return rc;
+  if (int rc = check_rows_finite("x", x, lens, B, L, F)) return rc;
+  if (int rc = check_rows_finite("x0", x0, lens, B, L, F)) return rc;
+  const NerfFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5], feat_idx[6], feat_idx[7], feat_idx[8]};
+  SteerOffset off{};
+  off.has_offset = offset ? 1 : 0;
+  unsigned angle_mask = 0;
+  for (int f = 0; f < F; ++f) {
+    if (offset) off.offset[f] = offset[f];
+    if (is_angle[f]) angle_mask |= 1u << f;
+  }
+  const RestraintInputs ri = restraint_inputs(rl);
+  const size_t n = (size_t)B * L * F, na = (size_t)B * 3 * L * 3, nb = (size_t)B;
+  const bool draws = s != 0.f && z;  // (the slab is read only then)
+  std::vector<float> state_host(n);  // the rows at or beyond a length are not the kernels': x_out keeps what it held there
+  const int rc = device_roundtrip(
+      device_id, {{x, n * 4}, {x0, n * 4}, {lens, nb * 4}, {draws ? z : x, draws ? n * 4 : 4}, ri.offsets, ri.i, ri.j, ri.d0, ri.tol, ri.w},
+      {{state_host.data(), n * 4}, {nullptr, n * 4}, {nullptr, na * 8}, {nullptr, na * 8}, {nullptr, n * 8}, {energy_out, nb * 8},
+       {nullptr, nb * 8}, {gnorm_out, nb * 8}},
+      [&](const RoundtripBufs& d) -> hipError_t {
+        float *state = d.out(0), *ang = d.out(1);
+        double *coords = d.out(2), *gc = d.out(3), *G = d.out(4);
+        const float *x_dev = d.in(0), *z_dev = d.in(3);
+        const int* lens_dev = d.in(2);
+        const Restraints rs{d.in(4), d.in(5), d.in(6), d.in(7), d.in(8), d.in(9)};
+        if (hipError_t e = hipMemcpyAsync(state, x_dev, n * 4, hipMemcpyDeviceToDevice, nullptr)) return e;
+        launch_steer_shift(d.in(1), lens_dev, B, L, F, off, angle_mask, ang, nullptr);
+        launch_nerf(ang, lens_dev, B, L, F, fx, 0, coords, nullptr);
+        launch_restraint_energy(coords, lens_dev, B, L, rs, d.out(5), d.out(6), gc, nullptr);
+        launch_nerf_vjp(coords, lens_dev, B, L, F, fx, 0, gc, G, nullptr);
+        launch_guide_update(state, G, lens_dev, B, L, F, angle_mask, c, max_norm, s, draws ? z_dev : nullptr, seed, t, seq_offset,
+                            d.out(7), nullptr);
+        return hipSuccess;
+      });
+  if (rc) return rc;
+  for (int b = 0; b < B; ++b)
+    memcpy(x_out + (size_t)b * L * F, state_host.data() + (size_t)b * L * F, (size_t)lens[b] * F * 4);
+  return FD_OK;
 }
 
 int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens, int n_chains,

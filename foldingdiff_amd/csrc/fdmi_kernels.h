@@ -254,6 +254,28 @@ void launch_steer_gather(const float* x, const int* ancestors, float* x_new, int
 void launch_repeat_tie(float* x, const int* lens, const int* tie, int B, int L, int F, unsigned angle_mask, int init, float s,
                        const float* z, unsigned long long seed, int t, long long seq_offset, hipStream_t st);
 
+// ---- the derivative of NeRF and restraint guidance (nerf_vjp.hip; the statements are in its header and in include/fdmi.h).
+// One 256-lane workgroup per chain in all three; lens[b] <= kGuideMaxLen and distinct feature columns, checked by the host.
+constexpr int kGuideMaxLen = 2048;
+// dfeats [B][L][F] fp64 <- the gradient with respect to the NeRF features of a function whose gradient with respect to the
+// coordinates [B][3L][3] (launch_nerf's layout) is dcoords; rows at or beyond lens[b] are not written
+void launch_nerf_vjp(const double* coords, const int* lens, int B, int L, int F, const NerfFeatures& fx, int centered,
+                     const double* dcoords, double* dfeats, hipStream_t s);
+// a batch's distance restraints, packed per chain: chain b owns entries offsets[b] .. offsets[b + 1] - 1
+struct Restraints {
+  const int* offsets;          // [B + 1]
+  const int *i, *j;            // atom indices inside the chain's [0, 3 lens[b])
+  const double *d0, *tol, *w;
+};
+// energy [B], max_violation [B] and, unless null, dcoords [B][3L][3] (atoms at or beyond 3 lens[b]: 0)
+void launch_restraint_energy(const double* coords, const int* lens, int B, int L, const Restraints& r, double* energy,
+                             double* max_violation, double* dcoords, hipStream_t s);
+// the last three lines of the guide statement, in place on x [B][L][F]: gnorm [B] <- |G_b|, x <- x - float32(c k_b G) where
+// c != 0, then launch_repeat_tie's + s z and wrap of an untied element
+void launch_guide_update(float* x, const double* G, const int* lens, int B, int L, int F, unsigned angle_mask, float c,
+                         double max_norm, float s, const float* z, unsigned long long seed, int t, long long seq_offset,
+                         double* gnorm, hipStream_t st);
+
 // *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);
 

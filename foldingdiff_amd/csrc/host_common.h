@@ -1,7 +1,7 @@
 // Host-only helpers shared by the C-ABI sources (api.hip: the model as it runs; api_weights.hip: its weights; api_comm.hip:
 // its RCCL binding; api_run.hip: the entries that run it; api_structures.hip: the structure entries; api_hooks.hip: the test
 // hooks): the error string, the owner of device buffers
-// that live for one call, the synchronous round trip built on it, and the argument checks of the packed-chain entries.
+// that live for one call, the synchronous round trip built on it, and the argument checks of the packed-chain entries and of restraint guidance.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -245,6 +245,73 @@ inline int check_tie(const int32_t* tie, const int32_t* lens, int B) {
       return fail(FD_E_INVALID, "tie[%d] = (%d, %d, %d) ends at row %lld, beyond lens[%d] = %d", b, start, period, units,
                   (long long)start + (long long)period * units, b, lens[b]);
   }
+  return FD_OK;
+}
+
+// ---- restraint guidance (fd_nerf_vjp, fd_restraint_energy, fd_guide_step, fd_sample_guided)
+// lengths the one-workgroup-per-chain kernels take, a feature count the shift kernel takes, fd_nerf's columns with no column
+// named twice (the derivative stores one result per element)
+inline int check_guide_shape(const int32_t* lens, int B, int L, int F, const int32_t* feat_idx) {
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if (F < 3 || F > 16) return fail(FD_E_INVALID, "F=%d outside [3, 16]", F);
+  if ((long long)B * L * F > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * F = %lld elements, at most 2^31 - 1", (long long)B * L * F);
+  if (int rc = check_lens(lens, B, L < 2048 ? L : 2048)) return rc;
+  for (int i = 0; i < 9; ++i) {
+    if (feat_idx[i] >= F || feat_idx[i] < -1 || (i < 3 && feat_idx[i] < 0)) return fail(FD_E_INVALID, "feat_idx[%d]=%d (F=%d)", i, feat_idx[i], F);
+    for (int j = 0; j < i; ++j)
+      if (feat_idx[i] >= 0 && feat_idx[j] == feat_idx[i]) return fail(FD_E_INVALID, "feat_idx[%d]=%d repeats feat_idx[%d]", i, feat_idx[i], j);
+  }
+  return FD_OK;
+}
+
+// [B][3L][3] doubles (fd_nerf's layout), finite on the atoms below 3 lens[b]; `what` names the array
+inline int check_chain_doubles(const char* what, const double* v, const int32_t* lens, int B, int L) {
+  for (int b = 0; b < B; ++b)
+    for (size_t i = (size_t)b * L * 9; i < ((size_t)b * L + lens[b]) * 9; ++i)
+      if (!std::isfinite(v[i])) return fail(FD_E_INVALID, "%s is not finite at chain %d, atom %d", what, b, (int)(i / 3 - (size_t)b * L * 3));
+  return FD_OK;
+}
+
+// [B][L][F] floats, finite on the rows below lens[b]
+inline int check_rows_finite(const char* what, const float* v, const int32_t* lens, int B, int L, int F) {
+  for (int b = 0; b < B; ++b)
+    for (size_t i = (size_t)b * L * F; i < ((size_t)b * L + lens[b]) * F; ++i)
+      if (!std::isfinite(v[i])) return fail(FD_E_INVALID, "%s is not finite at sequence %d, position %d", what, b, (int)(i / F - (size_t)b * L));
+  return FD_OK;
+}
+
+// a batch's packed distance restraints as the host hands them over (check_lens has passed)
+struct RestraintLists {
+  int n_chains;
+  const int32_t *offsets, *i, *j;
+  const double *d0, *tol, *w;
+  size_t count() const { return (size_t)offsets[n_chains]; }  // (once check_restraints has passed)
+};
+inline int check_restraints(const RestraintLists& r, const int32_t* lens) {
+  const int B = r.n_chains;
+  if (!r.offsets) return fail(FD_E_INVALID, "null argument: rst_offsets");
+  if (r.offsets[0] != 0) return fail(FD_E_INVALID, "rst_offsets[0]=%d must be 0", r.offsets[0]);
+  for (int b = 0; b < B; ++b)
+    if (r.offsets[b + 1] < r.offsets[b]) return fail(FD_E_INVALID, "rst_offsets[%d]=%d is below rst_offsets[%d]=%d", b + 1, r.offsets[b + 1], b, r.offsets[b]);
+  if (r.offsets[B] > 0 && (!r.i || !r.j || !r.d0 || !r.tol || !r.w)) return fail(FD_E_INVALID, "null argument: the restraint lists");
+  for (int b = 0; b < B; ++b)
+    for (int k = r.offsets[b]; k < r.offsets[b + 1]; ++k) {
+      const int n = 3 * lens[b];
+      if (r.i[k] < 0 || r.i[k] >= n || r.j[k] < 0 || r.j[k] >= n)
+        return fail(FD_E_INVALID, "restraint %d = atoms (%d, %d) outside chain %d's [0, %d)", k, r.i[k], r.j[k], b, n);
+      if (r.i[k] == r.j[k]) return fail(FD_E_INVALID, "restraint %d names atom %d twice", k, r.i[k]);
+      if (!(r.d0[k] >= 0.0) || !std::isfinite(r.d0[k])) return fail(FD_E_INVALID, "restraint %d: d0=%g must be >= 0 and finite", k, r.d0[k]);
+      if (!(r.tol[k] >= 0.0) || !std::isfinite(r.tol[k])) return fail(FD_E_INVALID, "restraint %d: tol=%g must be >= 0 and finite", k, r.tol[k]);
+      if (!(r.w[k] >= 0.0) || !std::isfinite(r.w[k])) return fail(FD_E_INVALID, "restraint %d: w=%g must be >= 0 and finite", k, r.w[k]);
+    }
+  return FD_OK;
+}
+
+// the guide statement's own scalars and its shift
+inline int check_guide_scalars(double max_norm, const float* offset, int F) {
+  if (!(max_norm > 0.0) || !std::isfinite(max_norm)) return fail(FD_E_INVALID, "max_norm=%g must be > 0 and finite", max_norm);
+  for (int f = 0; offset && f < F; ++f)
+    if (!std::isfinite(offset[f])) return fail(FD_E_INVALID, "offset[%d]=%g must be finite", f, (double)offset[f]);
   return FD_OK;
 }
 

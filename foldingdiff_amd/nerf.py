@@ -65,6 +65,78 @@ def build_backbones(
     return [out[i, : 3 * lens[i]].copy() for i in range(B)]
 
 
+def _vjp_padded(coords: np.ndarray, lens: np.ndarray, dcoords: np.ndarray, F: int, idx: np.ndarray, centered: bool, device: int) -> np.ndarray:
+    """``fd_nerf_vjp`` on padded arrays: float64 ``[B, 3L, 3]`` twice -> float64 ``[B, L, F]`` (rows at or beyond a length 0)."""
+    B, L = coords.shape[0], coords.shape[1] // 3
+    out = np.zeros((B, L, F), dtype=np.float64)
+    ptr = _binding.ptr
+    _binding.check(_binding.load().fd_nerf_vjp(device, ptr(coords), ptr(lens), B, L, F, ptr(idx), 1 if centered else 0, ptr(dcoords), ptr(out)))
+    return out
+
+
+def coords_vjp(
+    coords: Sequence[np.ndarray],
+    dcoords: Sequence[np.ndarray],
+    feature_names: Sequence[str],
+    centered: bool = True,
+    device: int = 0,
+) -> List[np.ndarray]:
+    """The gradient of any function of backbone coordinates with respect to the angles (and bond lengths) NeRF built them
+    from, on the GPU (``fd_nerf_vjp``), from the coordinates alone.
+
+    ``coords``: one ``[3 len_i, 3]`` array per chain, as ``build_backbones`` returns them; ``dcoords``: the function's
+    gradient with respect to them, the same shapes; ``centered``: the coordinates came from ``center_coords=True``.  Returns
+    one ``float64 [len_i, F]`` array per chain in the column order of ``feature_names``: exact (a torsion, an angle or a bond
+    length moves everything behind it as a rigid body), fp64, the same bits on every call.  Columns and rows NeRF does not
+    read (phi of the first residue, the last residue's other angles) are 0."""
+    xs = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in coords]
+    gs = [np.asarray(g, dtype=np.float64).reshape(-1, 3) for g in dcoords]
+    assert len(xs) == len(gs) and len(xs) > 0 and all(x.shape == g.shape and len(x) % 3 == 0 and len(x) > 0 for x, g in zip(xs, gs)), \
+        "coords and dcoords are lists of equally shaped [3 len, 3] arrays"
+    F = len(feature_names)
+    idx = feature_columns(feature_names)
+    B, L = len(xs), max(len(x) for x in xs) // 3
+    lens = np.array([len(x) // 3 for x in xs], dtype=np.int32)
+    xyz, grad = np.zeros((B, 3 * L, 3), dtype=np.float64), np.zeros((B, 3 * L, 3), dtype=np.float64)
+    for i, (x, g) in enumerate(zip(xs, gs)):
+        xyz[i, : len(x)] = x
+        grad[i, : len(g)] = g
+    out = _vjp_padded(xyz, lens, grad, F, idx, centered, device)
+    return [out[i, : lens[i]].copy() for i in range(B)]
+
+
+def build_backbones_torch(angles, lengths: Sequence[int], feature_names: Sequence[str], center_coords: bool = True, device: int = 0):
+    """``build_backbones`` as a differentiable torch function: a float32 ``[B, L, F]`` tensor of angles and the chains'
+    ``lengths`` -> a float64 ``[B, 3L, 3]`` tensor of coordinates (atoms at or beyond ``3 * lengths[b]``: 0).  The forward is
+    ``fd_nerf``, the backward ``fd_nerf_vjp``, so any torch loss on the coordinates back-propagates to the angles; the
+    gradient is ``coords_vjp``'s, cast to the dtype of ``angles``, and 0 on the rows at or beyond a length.  Both passes go
+    through host arrays, whatever device ``angles`` lives on."""
+    import torch
+
+    idx = feature_columns(feature_names)
+    F = len(feature_names)
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+
+    class _Nerf(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, ang):
+            feats = np.ascontiguousarray(ang.detach().cpu().numpy(), dtype=np.float32)
+            assert feats.ndim == 3 and feats.shape[2] == F and feats.shape[0] == len(lens), "angles are [B, L, F], one length per chain"
+            B, L, _ = feats.shape
+            out = np.empty((B, 3 * L, 3), dtype=np.float64)
+            ptr = _binding.ptr
+            _binding.check(_binding.load().fd_nerf(device, ptr(feats), ptr(lens), B, L, F, ptr(idx), 1 if center_coords else 0, ptr(out)))
+            ctx.coords, ctx.dtype = out, ang.dtype
+            return torch.from_numpy(out.copy()).to(ang.device)
+
+        @staticmethod
+        def backward(ctx, grad):
+            g = np.ascontiguousarray(grad.detach().cpu().numpy(), dtype=np.float64)
+            return torch.from_numpy(_vjp_padded(ctx.coords, lens, g, F, idx, center_coords, device)).to(device=grad.device, dtype=ctx.dtype)
+
+    return _Nerf.apply(angles)
+
+
 class NERFBuilder:
     """Single-chain builder with the reference's constructor arguments (bond angles / lengths as floats
     or per-residue arrays); ``cartesian_coords`` / ``centered_cartesian_coords`` run on the GPU."""

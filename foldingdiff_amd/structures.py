@@ -445,6 +445,129 @@ def repeat_rmsd(backbones: Sequence[np.ndarray], start, period, units, device: i
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- distance restraints
+BACKBONE_ATOMS = {"N": 0, "CA": 1, "C": 2}
+
+
+class Restraints:
+    """One chain's distance restraints between backbone atoms (``fd_restraint_energy``): arrays ``i``, ``j``
+    (int32 atom indices ``3 * residue + {0 N, 1 CA, 2 C}``, ``i != j``) and ``d0``, ``tol``, ``w`` (float64, finite, ``>= 0``).
+    A restraint costs ``w * max(0, |d - d0| - tol)^2`` with ``d`` the distance of its two atoms: ``tol = 0`` is harmonic,
+    ``d0 = 0, tol = 8`` is "within 8 Angstrom".  ``a + b`` joins two sets.
+
+    Distances alone do not fix handedness: a structure and its mirror image cost the same.  Restraints among L-amino-acid
+    backbone segments mostly do tell the two apart, because each segment's own internal angles enter the sampler's state and
+    are not mirrored; that is a tendency, not a guarantee."""
+
+    def __init__(self, i, j, d0, tol, w):
+        self.i = np.ascontiguousarray(np.asarray(i, dtype=np.int64).reshape(-1).astype(np.int32))
+        self.j = np.ascontiguousarray(np.asarray(j, dtype=np.int64).reshape(-1).astype(np.int32))
+        n = len(self.i)
+        self.d0, self.tol, self.w = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))) for v in (d0, tol, w))
+        if len(self.j) != n:
+            raise ValueError(f"{n} first atoms, {len(self.j)} second atoms")
+        if n and ((self.i < 0).any() or (self.j < 0).any() or (self.i == self.j).any()):
+            raise ValueError("a restraint names two different atoms, each >= 0")
+        for name, v in (("d0", self.d0), ("tol", self.tol), ("w", self.w)):
+            if not (np.isfinite(v).all() and (v >= 0).all()):
+                raise ValueError(f"{name} must be finite and >= 0")
+
+    def __len__(self) -> int:
+        return len(self.i)
+
+    def __add__(self, other: "Restraints") -> "Restraints":
+        return Restraints(*(np.concatenate([getattr(self, k), getattr(other, k)]) for k in ("i", "j", "d0", "tol", "w")))
+
+    def min_length(self) -> int:
+        """The residues a chain needs for every atom named here to exist."""
+        return 0 if not len(self) else int(max(self.i.max(), self.j.max())) // 3 + 1
+
+
+def contact_restraints(pairs, max_dist: float = 8.0, weight: float = 1.0, atom: str = "CA") -> Restraints:
+    """"These residues are in contact": for every entry ``(i, j)`` or ``(i, j, max_dist)`` of ``pairs`` (residue indices from
+    0) a restraint that costs nothing while the two residues' ``atom`` (``"N"``, ``"CA"`` or ``"C"``) lie within ``max_dist``
+    Angstrom and ``weight * (d - max_dist)^2`` beyond."""
+    if atom not in BACKBONE_ATOMS:
+        raise ValueError(f"atom={atom!r}: expected one of {sorted(BACKBONE_ATOMS)}")
+    rows = [tuple(p) for p in pairs]
+    if any(len(p) not in (2, 3) for p in rows):
+        raise ValueError("every pair is (i, j) or (i, j, max_dist)")
+    if any(int(p[0]) < 0 or int(p[1]) < 0 or int(p[0]) == int(p[1]) for p in rows):
+        raise ValueError("a contact names two different residues, each >= 0")
+    a = BACKBONE_ATOMS[atom]
+    return Restraints([3 * int(p[0]) + a for p in rows], [3 * int(p[1]) + a for p in rows], np.zeros(len(rows)),
+                      np.array([float(p[2]) if len(p) == 3 else float(max_dist) for p in rows], dtype=np.float64), float(weight))
+
+
+def motif_restraints(motif_backbone: np.ndarray, placed_at: Sequence[int], weight: float = 1.0, tol: float = 0.0,
+                     atoms: Sequence[str] = ("CA",)) -> Restraints:
+    """"These residues sit relative to each other as in the motif": every pair among the chosen ``atoms`` of the motif's
+    residues, at the distance it has in ``motif_backbone`` (``[3 m, 3]``, N / CA / C per residue, e.g. the residues picked
+    from ``read_backbone``).  ``placed_at[r]`` is the residue index motif residue ``r`` takes in the new chain; the residues
+    need not be contiguous, so two separate segments are placed relative to each other.  ``m (m - 1) / 2`` restraints per
+    atom pair type; see ``Restraints`` on the mirror image."""
+    xyz = np.asarray(motif_backbone, dtype=np.float64).reshape(-1, 3)
+    placed = [int(p) for p in placed_at]
+    if len(xyz) % 3 or len(xyz) != 3 * len(placed):
+        raise ValueError(f"motif_backbone has {len(xyz)} atoms for {len(placed)} placed residues (3 per residue)")
+    if len(set(placed)) != len(placed) or (placed and min(placed) < 0):
+        raise ValueError("placed_at names distinct residues, each >= 0")
+    unknown = [a for a in atoms if a not in BACKBONE_ATOMS]
+    if unknown or not len(atoms) or len(set(atoms)) != len(atoms):
+        raise ValueError(f"atoms={tuple(atoms)!r}: distinct entries of {sorted(BACKBONE_ATOMS)}")
+    if not np.isfinite(xyz).all():
+        raise ValueError("motif_backbone is not finite")
+    sites = [(r, BACKBONE_ATOMS[a]) for r in range(len(placed)) for a in atoms]
+    i, j, d0 = [], [], []
+    for p, (ra, aa) in enumerate(sites):
+        for rb, ab in sites[p + 1:]:
+            i.append(3 * placed[ra] + aa)
+            j.append(3 * placed[rb] + ab)
+            d0.append(float(np.linalg.norm(xyz[3 * ra + aa] - xyz[3 * rb + ab])))
+    return Restraints(i, j, d0, float(tol), float(weight))
+
+
+def pack_restraints(restraints, lengths: Sequence[int]):
+    """``fd_restraint_energy``'s packed layout for a batch: ``(rst_offsets int32 [B + 1], rst_i, rst_j int32 [R], rst_d0,
+    rst_tol, rst_w float64 [R])`` from one ``Restraints`` per chain (``None``: none), or a single one for every chain.
+    ``ValueError`` for a restraint on an atom beyond its chain."""
+    lengths = [int(l) for l in lengths]
+    per = [restraints] * len(lengths) if restraints is None or isinstance(restraints, Restraints) else list(restraints)
+    if len(per) != len(lengths):
+        raise ValueError(f"{len(per)} restraint sets for {len(lengths)} chains")
+    per = [Restraints([], [], [], [], []) if r is None else r for r in per]
+    for b, (r, n) in enumerate(zip(per, lengths)):
+        if r.min_length() > n:
+            raise ValueError(f"chain {b} has {n} residues, its restraints need {r.min_length()}")
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per])]).astype(np.int32)
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([getattr(r, k) for r in per]).astype(dt))   # noqa: E731
+    return (np.ascontiguousarray(offsets), cat("i", np.int32), cat("j", np.int32), cat("d0", np.float64), cat("tol", np.float64),
+            cat("w", np.float64))
+
+
+def restraint_energy(coords: Sequence[np.ndarray], restraints, device: int = 0, return_gradient: bool = False):
+    """Energy and largest violation of distance restraints on a batch of backbones, in one ``fd_restraint_energy`` call.
+    ``coords``: one ``[3 len_i, 3]`` array per chain (``nerf.build_backbones``); ``restraints``: as for ``pack_restraints``.
+    Returns ``(energy, max_violation)``, float64 ``[B]`` each -- and with ``return_gradient`` a third entry, the list of the
+    energy's gradients with respect to the coordinates (``[3 len_i, 3]``), which ``nerf.coords_vjp`` carries on to the
+    angles.  Each atom's gradient is summed in the order of the list, so the bits do not depend on scheduling."""
+    xs = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in coords]
+    assert xs and all(len(x) % 3 == 0 and len(x) > 0 for x in xs), "coords is a list of [3 len, 3] arrays"
+    lens = np.array([len(x) // 3 for x in xs], dtype=np.int32)
+    packed = pack_restraints(restraints, lens.tolist())
+    B, L = len(xs), int(lens.max())
+    xyz = np.zeros((B, 3 * L, 3), dtype=np.float64)
+    for b, x in enumerate(xs):
+        xyz[b, : len(x)] = x
+    energy, worst = np.empty(B, dtype=np.float64), np.empty(B, dtype=np.float64)
+    grad = np.empty((B, 3 * L, 3), dtype=np.float64) if return_gradient else None
+    _binding.check(_binding.load().fd_restraint_energy(device, ptr(xyz), ptr(lens), B, L, *(ptr(a) for a in packed), ptr(energy), ptr(worst),
+                                                       ptr(grad)))
+    if not return_gradient:
+        return energy, worst
+    return energy, worst, [grad[b, : 3 * lens[b]].copy() for b in range(B)]
+
+
 class RmsdScorer:
     """A ``scorer=`` for ``sampling.get_reconstruction_error``: per item (RMSD of NeRF(reconstruction) to NeRF(truth),
     RMSD of NeRF(reconstruction) to the backbone of the item's PDB file), in Angstrom after optimal superposition --

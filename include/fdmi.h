@@ -57,6 +57,8 @@ extern "C" {
  *    resampling on device rewards) and the struct fd_steer_params are additive too */
 /*    fd_sample_repeat and fd_tie_repeats (few-step sampling with the angle rows tied across repeat units) are additive too */
 /*    fd_backbone_oxygens and fd_dssp (backbone oxygens and DSSP hydrogen-bond states) are additive too */
+/*    fd_nerf_vjp, fd_restraint_energy, fd_guide_step and fd_sample_guided (the derivative of NeRF and restraint-guided few-step
+ *    sampling) and the struct fd_guide_params are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -593,6 +595,104 @@ int fd_sample_repeat(fd_model* m, const float* x_init, const int32_t* lens, int 
  * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), `out` untouched. */
 int fd_tie_repeats(int device_id, const float* x, const int32_t* lens, const int32_t* tie, int B, int L, int F,
                    const uint8_t* is_angle, int init, float s, const float* z, uint64_t seed, int t, int64_t seq_offset, float* out);
+
+/* ---- restraint guidance: the derivative of NeRF, distance restraints between backbone atoms, and a few-step run
+ * that follows every visit with a step down the gradient of the restraint energy of the visit's predicted structure.
+ *
+ * fd_nerf_vjp: the gradient with respect to the NeRF features of any function of the coordinates, from the coordinates alone,
+ * model-free and synchronous like fd_nerf, fp64 throughout.  Per chain of len residues, n = 3 len atoms; atom k >= 3 was
+ * placed from atoms k-3, k-2, k-1, and with i = (k - 3) / 3, j = (k - 3) % 3 its features are
+ *     j = 0 (next N):   torsion psi (row i)        angle CA:C:1N (row i)                          length 0C:1N (row i)
+ *     j = 1 (next CA):  torsion omega (row i)      angle C:1N:1CA (row i)                         length N:CA (row i)
+ *     j = 2 (next C):   torsion phi (row i + 1)    angle N:CA:C (row i: the reference's quirk)    length CA:C (row i)
+ *   g_k  = dcoords[k], with centered != 0 minus the mean of dcoords over the chain's atoms (the derivative of fd_nerf's center = 1)
+ *   q_k  = p_k - p_0: positions relative to the chain's atom 0
+ *   Fs_k = sum_{m >= k} g_m,   Tq_k = sum_{m >= k} q_m x g_m
+ *   with b = q_{k-2}, c = q_{k-1}, d = q_k, u = unit(c - b), r = d - c, M = Tq_k - c x Fs_k:
+ *     d / d torsion = u . M      d / d angle = unit(r x u) . M      d / d length = unit(r) . Fs_k
+ * each to its (row, column); a slot whose feat_idx is -1 receives nothing, every other element of a row below len is 0 (phi of
+ * residue 0, the last residue's psi / omega / angles / lengths, columns that are no NeRF feature), rows at or beyond len are not
+ * written, len == 1: all zero.  A torsion, an angle or a length moves everything behind it as a rigid body, hence the suffix
+ * sums; one workgroup per chain, every sum in an order fixed by the chain's length: two calls give the same bits.
+ *   coords      float64 [B][3L][3] in fd_nerf's layout (host); dcoords the same shape; both finite on the atoms below 3 lens[b]
+ *   lens        int32[B], 1 <= lens[b] <= min(L, 2048)
+ *   feat_idx    int32[9] as in fd_nerf, and no column named twice; 3 <= F <= 16
+ *   dfeats_out  float64 [B][L][F]
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs untouched. */
+int fd_nerf_vjp(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int centered,
+                const double* dcoords, double* dfeats_out);
+
+/* Distance restraints, packed per chain: chain b owns entries rst_offsets[b] .. rst_offsets[b + 1] - 1 of the lists
+ * (rst_offsets[0] == 0, non-decreasing; R = rst_offsets[B] may be 0, the lists are then not read).
+ *   rst_i, rst_j           int32[R] atom indices 3 * residue + {0 N, 1 CA, 2 C} inside the chain's [0, 3 lens[b]), i != j
+ *   rst_d0, rst_tol, rst_w double[R], finite, d0 >= 0, tol >= 0, w >= 0
+ * Per restraint: d = |p_i - p_j|, v = max(0, |d - d0| - tol), E_b += w v^2, and where v > 0 and d > 0
+ * dcoords[i] += 2 w v sign(d - d0) (p_i - p_j) / d, the opposite on j.  tol = 0 is harmonic; d0 = 0, tol = 8 is "within 8 A".
+ * Distances do not tell a structure from its mirror image.
+ *   coords             float64 [B][3L][3] (host), finite on the atoms below 3 lens[b]; lens int32[B] in [1, min(L, 2048)]
+ *   energy_out         double[B]; max_violation_out double[B]: the largest v, 0 without restraints
+ *   dcoords_out        float64 [B][3L][3] (atoms at or beyond 3 lens[b]: 0), or NULL
+ * No floating-point atomics: each atom belongs to a lane that walks the chain's list and sums the terms on its atom in list
+ * order; the energy is summed in an order fixed by the list's length.  Two calls give the same bits.
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs untouched. */
+int fd_restraint_energy(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* rst_offsets,
+                        const int32_t* rst_i, const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
+                        double* energy_out, double* max_violation_out, double* dcoords_out);
+
+/* The guide statement.  After a visit, x is the state it left and x0 its prediction of the clean state:
+ *     ang    = the shift statement of fd_sample_steered on x0
+ *     coords = fd_nerf(ang, center = 0)
+ *     E, gc  = the restraint statement on coords
+ *     G      = fd_nerf_vjp(coords, gc, centered = 0)                                    [B][L][F] fp64
+ *     n_b    = sqrt(sum of G^2 over the rows below lens[b]), in a fixed order;   k_b = n_b > max_norm ? max_norm / n_b : 1
+ *     x     <- x - float32((double(c) * k_b) * G)   only where c != 0 (c == 0 leaves x's bits alone, whatever G holds)
+ *     x     <- x + s z  where s != 0;   x <- wrap(x) where angular
+ * the last line being fd_tie_repeats' with units == 1: same draw position, same Philox word, same roundings.
+ *
+ * fd_guide_step: the statement on host arrays, model-free and synchronous like fd_nerf.
+ *   x, x0      float32 [B][L][F] (host), finite on the rows below lens[b]; lens int32[B] in [1, min(L, 2048)]
+ *   feat_idx   int32[9] as in fd_nerf_vjp; 3 <= F <= 16
+ *   offset     float32[F] finite, or NULL: x0 is taken as it is; is_angle uint8[F]: the features to wrap
+ *   rst_*      as in fd_restraint_energy
+ *   c, s       finite; max_norm > 0
+ *   z          float32 [B][L][F], or NULL: Philox with (seed, t, seq_offset); neither is looked at where s == 0
+ *   x_out      float32 [B][L][F]: the rows below lens[b]; the others keep what they held
+ *   energy_out double[B]: E of x0's structure; gnorm_out double[B]: n_b
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs untouched. */
+int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                  const float* offset, const uint8_t* is_angle, const int32_t* rst_offsets, const int32_t* rst_i,
+                  const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float c, double max_norm,
+                  float s, const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
+                  double* gnorm_out);
+
+/* fd_sample_guided is fd_sample_strided (final state only) whose visits write their prediction of the clean state as
+ * fd_sample_steered's do, run their update without its draw as fd_sample_repeat's do -- wrap(a x + b eps) -- and are each
+ * followed by the guide statement with c = guide[i], s = coef[2][i], t = visits[i] and row i of `noise`: five launches (shift,
+ * NeRF, restraints, derivative, update) between two replays of the plain sampler's captured step graph, which is not captured
+ * again; nothing is asked of the host between the upload and the download.
+ *   visits, noise, seed, seq_offset, x_init, lens   as in fd_sample_strided
+ *   coef              float32 [5][K] rows a | b | s | u | v, all finite (host), as in fd_sample_steered
+ *   guide             float32 [K], finite, zeros allowed
+ *   params            feat_idx as in fd_nerf_vjp, the offset of the shift, max_norm > 0
+ *   rst_*             as in fd_restraint_energy
+ *   out               [B][L][F] the final state
+ *   energy_out, max_violation_out   double[B]: the restraint statement on the FINAL state, shifted in the same way
+ * Everything fd_sample_strided rejects, a NULL or non-finite u / v / guide, a NULL params or output, a restraint outside its
+ * chain or with i == j, a negative or non-finite d0 / tol / w, max_norm <= 0 or not finite, a non-finite offset, a length above
+ * 2048, fewer than 3 or more than 16 features, a bad feat_idx: FD_E_INVALID before any device call, `out` untouched.  Options
+ * "use_graph" and "varlen" and both precisions as in fd_sample_strided; a later fd_sample* is unaffected.  Single device, final
+ * state only; not offered with motif conditioning, the second-order solver, steering or ties. */
+typedef struct fd_guide_params {
+  int32_t feat_idx[9];
+  int32_t has_offset;
+  float offset[16];    /* the first F are read, and only where has_offset != 0 */
+  double max_norm;
+} fd_guide_params;
+int fd_sample_guided(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                     const float* coef, const float* noise, uint64_t seed, int64_t seq_offset, const float* guide,
+                     const fd_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i, const int32_t* rst_j,
+                     const double* rst_d0, const double* rst_tol, const double* rst_w, float* out, double* energy_out,
+                     double* max_violation_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
