@@ -20,6 +20,10 @@ reference's ``bin/sample.py`` (same flags, same files):
                     (structures.count_clashes on the coordinates as written: what bin/vdw_clashes.py gives on the files;
                     without --clashes the output tree is unchanged)
 
+    with --relax N: relaxed_angles/generated_{i}.csv.gz, relaxed_pdb/generated_{i}.pdb and relax_report.json: the sampled
+                    backbones after N iterations of the torsion-space relaxer (structures.relax: backbone clashes removed by a
+                    descent on the angles; no force field); without --relax the output tree is unchanged
+
 The secondary structures are annotated on the device (structures.count_secondary_structures: P-SEA, in place of
 biotite's annotate_sse) from the coordinates of the backbones just written, without reading the files back.  The step
 is opt-in: the reference runs it unless --nopsea is given, here it runs only with --psea, and without --psea the
@@ -88,6 +92,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="label the sampled backbones with DSSP states from their backbone hydrogen bonds (on the device) into dssp.json")
     parser.add_argument("--clashes", action="store_true",
                         help="count the van der Waals clashes of the sampled backbones (on the device) into clash_counts.json")
+    parser.add_argument("--relax", type=int, default=None, metavar="N",
+                        help="relax the sampled backbones in torsion space for N iterations (on the device: backbone clashes are pushed apart "
+                             "by a descent on phi / psi / omega; no force field) into relaxed_angles/, relaxed_pdb/ and relax_report.json")
     parser.add_argument("--num_steps", type=int, default=None,
                         help="sample in this many network evaluations on a strided schedule with the DDIM update (default: every timestep, "
                              "the reference's ancestral loop); the run's arguments then go to sampling_args.json")
@@ -211,6 +218,10 @@ def main(argv=None) -> None:
             counts = structures.count_clashes([coords_as_written(xyz).astype("float32") for _, xyz in kept], device=device_index)
             with open(outdir / "clash_counts.json", "w") as sink:
                 json.dump({name: int(c) for (name, _), c in zip(kept, counts)}, sink, indent=4)
+        if args.relax is not None:
+            device_index = torch.device(args.device).index or 0
+            structures.relax_to_folder(sampled_dfs, [f"generated_{i}" for i in range(len(sampled_dfs))], str(outdir), device=device_index,
+                                       n_iter=args.relax)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

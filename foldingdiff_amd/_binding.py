@@ -63,6 +63,23 @@ class FdGuideParams(C.Structure):
     ]
 
 
+class FdRelaxParams(C.Structure):
+    """``fd_relax_params`` of include/fdmi.h."""
+    _fields_ = [
+        ("feat_idx", C.c_int32 * 9),
+        ("is_angle", C.c_uint8 * 16),
+        ("move", C.c_uint8 * 16),
+        ("clash_alpha", C.c_double),
+        ("clash_margin", C.c_double),
+        ("w_clash", C.c_double),
+        ("w_tether", C.c_double),
+        ("step0", C.c_double),
+        ("grow", C.c_double),
+        ("shrink", C.c_double),
+        ("max_step", C.c_double),
+    ]
+
+
 # every symbol include/fdmi.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -113,6 +130,11 @@ _SIGNATURES = {
                                 C.c_float, _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P]),
     "fd_sample_guided": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.c_int64, _P, C.POINTER(FdGuideParams),
                                    _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_nerf_scan": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "fd_relax_energy": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(FdRelaxParams), _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                  _P]),
+    "fd_relax": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(FdRelaxParams), _P, _P, _P, _P, _P, _P, _P, C.c_int, _P,
+                           _P, _P, _P, _P]),
     "fd_sample_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_begin_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, _P, C.c_int, _P]),
     "fd_sample_steps_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),

@@ -1,5 +1,5 @@
 // C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, dssp.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
-// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip) and of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip), of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip) and of the torsion-space relaxer (nerf_scan.hip, relax.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
 #include <cstring>
@@ -126,6 +126,149 @@ int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t*
   for (int b = 0; b < B; ++b)
     memcpy(x_out + (size_t)b * L * F, state_host.data() + (size_t)b * L * F, (size_t)lens[b] * F * 4);
   return FD_OK;
+}
+
+int fd_nerf_scan(int device_id, const float* feats, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int center,
+                 double* coords_out) {
+  if (!feats || !lens || !feat_idx || !coords_out) return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1 || F < 3) return fail(FD_E_INVALID, "B=%d L=%d F=%d: B, L >= 1 and F >= 3", B, L, F);
+  if ((long long)B * L * 9 > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * 9 = %lld coordinates, at most 2^31 - 1", (long long)B * L * 9);
+  for (int i = 0; i < 9; ++i)
+    if (feat_idx[i] >= F || (i < 3 && feat_idx[i] < 0)) return fail(FD_E_INVALID, "feat_idx[%d]=%d (F=%d)", i, feat_idx[i], F);
+  if (int rc = check_lens(lens, B, L < kGuideMaxLen ? L : kGuideMaxLen)) return rc;
+  const NerfFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5], feat_idx[6], feat_idx[7], feat_idx[8]};
+  return device_roundtrip(device_id, {{feats, (size_t)B * L * F * 4}, {lens, (size_t)B * 4}}, {{coords_out, (size_t)B * 3 * L * 3 * 8}},
+                          [&](const RoundtripBufs& d) { launch_nerf_scan(d.in(0), d.in(1), B, L, F, fx, center, d.out(0), nullptr); });
+}
+
+// fd_relax_energy (n_iter == 0, descent == false) and fd_relax: the checks, the uploads, 1 + n_iter evaluations, the downloads
+static int relax_run(int device_id, const float* feats, const float* anchor, const int32_t* lens, int B, int L, int F,
+                     const fd_relax_params* params, const uint8_t* fixed, const RestraintLists& rl, int n_iter, double* step_io,
+                     float* feats_out, double* energy_out, double* gnorm_out, double* dfeats_out, double* trace_out,
+                     int32_t* accepted_out) {
+  if (!feats || !lens || !params || !energy_out) return fail(FD_E_INVALID, "null argument");
+  if (int rc = check_guide_shape(lens, B, L, F, params->feat_idx)) return rc;
+  if (int rc = check_restraints(rl, lens)) return rc;
+  const fd_relax_params& p = *params;
+  unsigned angle_mask = 0, move_mask = 0;
+  for (int f = 0; f < F; ++f) {
+    if (p.is_angle[f]) angle_mask |= 1u << f;
+    if (!p.move[f]) continue;
+    move_mask |= 1u << f;
+    bool named = false;
+    for (int i = 0; i < 9; ++i) named |= p.feat_idx[i] == f;
+    if (!named) return fail(FD_E_INVALID, "move[%d] is set, but column %d is no NeRF feature of feat_idx", f, f);
+  }
+  const struct { const char* name; double v; } weights[] = {{"clash_alpha", p.clash_alpha}, {"clash_margin", p.clash_margin},
+                                                            {"w_clash", p.w_clash}, {"w_tether", p.w_tether}};
+  for (const auto& w : weights)
+    if (!(w.v >= 0.0) || !std::isfinite(w.v)) return fail(FD_E_INVALID, "%s=%g must be >= 0 and finite", w.name, w.v);
+  if (!(p.step0 > 0.0) || !std::isfinite(p.step0)) return fail(FD_E_INVALID, "step0=%g must be > 0 and finite", p.step0);
+  if (!(p.grow >= 1.0) || !std::isfinite(p.grow)) return fail(FD_E_INVALID, "grow=%g must be >= 1 and finite", p.grow);
+  if (!(p.shrink > 0.0 && p.shrink < 1.0)) return fail(FD_E_INVALID, "shrink=%g outside (0, 1)", p.shrink);
+  if (!(p.max_step > 0.0) || !std::isfinite(p.max_step)) return fail(FD_E_INVALID, "max_step=%g must be > 0 and finite", p.max_step);
+  if (n_iter < 0) return fail(FD_E_INVALID, "n_iter=%d must be >= 0", n_iter);
+  if ((long long)(n_iter + 1LL) * B > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "(n_iter + 1) * B = %lld trace entries, at most 2^31 - 1", (n_iter + 1LL) * B);
+  for (int b = 0; step_io && b < B; ++b)
+    if (!(step_io[b] > 0.0) || !std::isfinite(step_io[b])) return fail(FD_E_INVALID, "step_io[%d]=%g must be > 0 and finite", b, step_io[b]);
+  if (int rc = check_rows_finite("feats", feats, lens, B, L, F)) return rc;
+  if (anchor)
+    if (int rc = check_rows_finite("anchor", anchor, lens, B, L, F)) return rc;
+
+  const NerfFeatures fx{p.feat_idx[0], p.feat_idx[1], p.feat_idx[2], p.feat_idx[3], p.feat_idx[4], p.feat_idx[5], p.feat_idx[6], p.feat_idx[7], p.feat_idx[8]};
+  const RestraintInputs ri = restraint_inputs(rl);
+  const size_t n = (size_t)B * L * F, na = (size_t)B * 3 * L * 3, nb = (size_t)B;
+  std::vector<RelaxState> state_host(nb);
+  for (size_t b = 0; b < nb; ++b) {
+    state_host[b] = RelaxState{};
+    state_host[b].h = step_io ? step_io[b] : p.step0;
+  }
+  HIP_TRY(hipSetDevice(device_id));
+  DeviceBufs bufs;
+  RelaxStep a{};
+  int* lens_dev;
+  int *rst_offsets, *rst_i, *rst_j;
+  double *rst_d0, *rst_tol, *rst_w, *coords, *gc, *e_clash, *e_rst, *max_violation;
+  HIP_TRY(bufs.upload(feats, n * 4, &a.xt));  // the first trial is the input
+  HIP_TRY(bufs.upload(anchor ? anchor : feats, n * 4, &a.anchor));
+  HIP_TRY(bufs.upload(lens, nb * 4, &lens_dev));
+  if (fixed) HIP_TRY(bufs.upload(fixed, nb * L, &a.fixed));
+  HIP_TRY(bufs.upload(ri.offsets.first, ri.offsets.second, &rst_offsets));
+  HIP_TRY(bufs.upload(ri.i.first, ri.i.second, &rst_i));
+  HIP_TRY(bufs.upload(ri.j.first, ri.j.second, &rst_j));
+  HIP_TRY(bufs.upload(ri.d0.first, ri.d0.second, &rst_d0));
+  HIP_TRY(bufs.upload(ri.tol.first, ri.tol.second, &rst_tol));
+  HIP_TRY(bufs.upload(ri.w.first, ri.w.second, &rst_w));
+  HIP_TRY(bufs.upload(state_host.data(), nb * sizeof(RelaxState), &a.state));
+  HIP_TRY(bufs.zeros(n * 4, &a.x));
+  HIP_TRY(bufs.alloc(n * 8, &a.Gt));
+  HIP_TRY(bufs.zeros(n * 8, &a.G));
+  HIP_TRY(bufs.alloc(na * 8, &coords));
+  HIP_TRY(bufs.alloc(na * 8, &gc));
+  HIP_TRY(bufs.alloc(nb * 8, &e_clash));
+  HIP_TRY(bufs.alloc(nb * 8, &e_rst));
+  HIP_TRY(bufs.alloc(nb * 8, &max_violation));
+  if (trace_out) HIP_TRY(bufs.alloc((size_t)(n_iter + 1) * nb * 8, &a.trace));
+  a.lens = lens_dev;
+  a.e_clash = e_clash;
+  a.e_rst = e_rst;
+  a.L = L;
+  a.F = F;
+  a.angle_mask = angle_mask;
+  a.move_mask = move_mask;
+  a.w_tether = p.w_tether;
+  a.grow = p.grow;
+  a.shrink = p.shrink;
+  a.max_step = p.max_step;
+  const Restraints rs{rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
+  for (int it = 0; it <= n_iter; ++it) {
+    launch_nerf_scan(a.xt, lens_dev, B, L, F, fx, 0, coords, nullptr);
+    launch_restraint_energy(coords, lens_dev, B, L, rs, e_rst, max_violation, gc, nullptr);
+    launch_soft_clash(coords, lens_dev, B, L, p.clash_alpha, p.clash_margin, p.w_clash, e_clash, gc, nullptr);
+    launch_nerf_vjp(coords, lens_dev, B, L, F, fx, 0, gc, a.Gt, nullptr);
+    a.it = it;
+    a.last = it == n_iter;
+    launch_relax_step(a, B, nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<float> x_host(feats_out ? n : 0);
+  std::vector<double> grad_host(dfeats_out ? n : 0);
+  if (feats_out) HIP_TRY(hipMemcpy(x_host.data(), a.x, n * 4, hipMemcpyDeviceToHost));
+  if (dfeats_out) HIP_TRY(hipMemcpy(grad_host.data(), a.G, n * 8, hipMemcpyDeviceToHost));
+  std::vector<double> trace_host(trace_out ? (size_t)(n_iter + 1) * nb : 0);
+  if (trace_out) HIP_TRY(hipMemcpy(trace_host.data(), a.trace, trace_host.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(state_host.data(), a.state, nb * sizeof(RelaxState), hipMemcpyDeviceToHost));
+  // every download has succeeded: only now are the outputs written (the rows at or beyond a length keep what they held)
+  for (int b = 0; b < B; ++b) {
+    const size_t o = (size_t)b * L * F, rows = (size_t)lens[b] * F;
+    if (feats_out) memcpy(feats_out + o, x_host.data() + o, rows * 4);
+    if (dfeats_out) memcpy(dfeats_out + o, grad_host.data() + o, rows * 8);
+    for (int k = 0; k < 3; ++k) energy_out[3 * b + k] = state_host[b].e[k];
+    if (gnorm_out) gnorm_out[b] = state_host[b].gnorm;
+    if (step_io) step_io[b] = state_host[b].h;
+    if (accepted_out) accepted_out[b] = state_host[b].accepted;
+  }
+  if (trace_out) memcpy(trace_out, trace_host.data(), trace_host.size() * 8);
+  return FD_OK;
+}
+
+int fd_relax_energy(int device_id, const float* feats, const float* anchor, const int32_t* lens, int B, int L, int F,
+                    const fd_relax_params* params, const uint8_t* fixed, const int32_t* rst_offsets, const int32_t* rst_i,
+                    const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, double* energy_out,
+                    double* gnorm_out, double* dfeats_out) {
+  if (!gnorm_out) return fail(FD_E_INVALID, "null argument");
+  return relax_run(device_id, feats, anchor, lens, B, L, F, params, fixed, RestraintLists{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w},
+                   0, nullptr, nullptr, energy_out, gnorm_out, dfeats_out, nullptr, nullptr);
+}
+
+int fd_relax(int device_id, const float* feats, const float* anchor, const int32_t* lens, int B, int L, int F,
+             const fd_relax_params* params, const uint8_t* fixed, const int32_t* rst_offsets, const int32_t* rst_i,
+             const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, int n_iter, double* step_io,
+             float* feats_out, double* energy_out, double* trace_out, int32_t* accepted_out) {
+  if (!feats_out || !accepted_out) return fail(FD_E_INVALID, "null argument");
+  return relax_run(device_id, feats, anchor, lens, B, L, F, params, fixed, RestraintLists{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w},
+                   n_iter, step_io, feats_out, energy_out, nullptr, nullptr, trace_out, accepted_out);
 }
 
 int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens, int n_chains,

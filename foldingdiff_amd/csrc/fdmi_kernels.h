@@ -276,6 +276,41 @@ void launch_guide_update(float* x, const double* G, const int* lens, int B, int 
                          double max_norm, float s, const float* z, unsigned long long seed, int t, long long seq_offset,
                          double* gnorm, hipStream_t st);
 
+// ---- relaxing backbones in torsion space (nerf_scan.hip, relax.hip; the statements are in their headers and in include/fdmi.h).
+// One 256-lane workgroup per chain in all three; lens[b] <= kGuideMaxLen, checked by the host.
+// launch_nerf's statement up to the last bits (the frame is composed along the chain, not recomputed from three positions)
+void launch_nerf_scan(const float* feats, const int* lens, int B, int L, int F, const NerfFeatures& fx, int center,
+                      double* out /* [B][3L][3] */, hipStream_t s);
+// energy [B] <- w sum v^2 of the soft clash term on coords [B][3L][3]; its gradient is ADDED to dcoords [B][3L][3], which holds
+// launch_restraint_energy's (atoms at or beyond 3 lens[b] are left alone)
+void launch_soft_clash(const double* coords, const int* lens, int B, int L, double alpha, double margin, double w, double* energy,
+                       double* dcoords, hipStream_t s);
+// what the descent keeps of a chain between two launches
+struct RelaxState {
+  double e[3];                 // clash | restraint | tether of the chain's state
+  double e_total, gnorm, h;
+  int accepted, pad;
+};
+// one launch of relax_step_kernel: closes the evaluation of the trial xt (Gt: launch_nerf_vjp's output, rewritten in place with the
+// tether's gradient added and what may not move zeroed), then it == 0: the trial becomes the state; it > 0: it does where its
+// energy is not above the state's, and h grows or shrinks; !last: xt <- the next trial.  trace [.][B] or null.
+struct RelaxStep {
+  float* xt;                   // [B][L][F]
+  double* Gt;                  // [B][L][F]
+  const float* anchor;         // [B][L][F]
+  const int* lens;
+  const unsigned char* fixed;  // [B][L] or null
+  const double *e_clash, *e_rst;  // [B] of the trial
+  float* x;                    // [B][L][F] the state
+  double* G;                   // [B][L][F] its gradient
+  RelaxState* state;           // [B]
+  double* trace;
+  int L, F, it, last;
+  unsigned angle_mask, move_mask;
+  double w_tether, grow, shrink, max_step;
+};
+void launch_relax_step(const RelaxStep& a, int B, hipStream_t s);
+
 // *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);
 

@@ -23,12 +23,9 @@ __device__ __forceinline__ float cos32(float v) { return (float)cos((double)v); 
 // length that is a FEATURE) is a float32 array element, a python-float length is "weak" (stays float32
 // against a float32 operand), but a DEFAULT bond angle is a python float whose cos / sin are float64 and
 // pull the products to float64.
-__device__ __forceinline__ D3 place(D3 a, D3 b, D3 c, bool angle_is_feature, float angle_f, double angle_default,
-                                    bool length_is_feature, float length_f, double length_default, float torsion) {
-  const D3 ab = sub(b, a);
-  const D3 bc = unit(sub(c, b));
-  const D3 n = unit(cross(ab, bc));
-  const D3 nbc = cross(n, bc);
+// the displacement of the new atom in the frame [bc | nbc | n] of the three atoms before it
+__device__ __forceinline__ D3 place_local(bool angle_is_feature, float angle_f, double angle_default, bool length_is_feature,
+                                          float length_f, double length_default, float torsion) {
   const float bl = length_is_feature ? length_f : (float)length_default;
   const float blc = bl * cos32(torsion), bls = bl * sin32(torsion);        // float32 in every case
   double d0, d1, d2;
@@ -43,6 +40,17 @@ __device__ __forceinline__ D3 place(D3 a, D3 b, D3 c, bool angle_is_feature, flo
     d1 = (double)blc * sa;
     d2 = (double)bls * sa;
   }
+  return {d0, d1, d2};
+}
+
+__device__ __forceinline__ D3 place(D3 a, D3 b, D3 c, bool angle_is_feature, float angle_f, double angle_default,
+                                    bool length_is_feature, float length_f, double length_default, float torsion) {
+  const D3 ab = sub(b, a);
+  const D3 bc = unit(sub(c, b));
+  const D3 n = unit(cross(ab, bc));
+  const D3 nbc = cross(n, bc);
+  const D3 d = place_local(angle_is_feature, angle_f, angle_default, length_is_feature, length_f, length_default, torsion);
+  const double d0 = d.x, d1 = d.y, d2 = d.z;
   // m = [bc | nbc | n] (columns);  d = m . (d0, d1, d2) + c
   return {bc.x * d0 + nbc.x * d1 + n.x * d2 + c.x, bc.y * d0 + nbc.y * d1 + n.y * d2 + c.y,
           bc.z * d0 + nbc.z * d1 + n.z * d2 + c.z};

@@ -42,13 +42,21 @@ def build_backbones(
     feature_names: Sequence[str],
     center_coords: bool = True,
     device: int = 0,
+    method: str = "serial",
 ) -> List[np.ndarray]:
     """Coordinates for a batch of sampled backbones.
 
     ``angles``: ``[B, L, F]`` array or a list of ``[len_i, F]`` arrays (e.g. ``[s[-1] for s in sample(...)]``);
     ``feature_names``: the F column names (``dset.feature_names["angles"]``).  Returns one
     ``float64 [3 * len_i, 3]`` array per chain (N, CA, C per residue), centred like
-    ``NERFBuilder.centered_cartesian_coords`` unless ``center_coords=False``."""
+    ``NERFBuilder.centered_cartesian_coords`` unless ``center_coords=False``.
+
+    ``method``: ``"serial"`` is ``fd_nerf``, one lane per chain, bit for bit the reference's arithmetic; ``"scan"`` is
+    ``fd_nerf_scan``, one workgroup per chain (chains of at most 2048 residues), which composes the frames along the chain
+    instead of recomputing each from three positions and so differs from ``"serial"`` in the last bits (within 1e-9 of the
+    chain's extent)."""
+    if method not in ("serial", "scan"):
+        raise ValueError(f"method={method!r}: 'serial' or 'scan'")
     chains = [np.asarray(a, dtype=np.float32) for a in (angles if not isinstance(angles, np.ndarray) or angles.ndim != 3 else list(angles))]
     F = len(feature_names)
     assert all(c.ndim == 2 and c.shape[1] == F for c in chains), "each chain must be [len, F]"
@@ -61,7 +69,8 @@ def build_backbones(
         lens[i] = len(c)
     out = np.empty((B, 3 * L, 3), dtype=np.float64)
     ptr = _binding.ptr
-    _binding.check(_binding.load().fd_nerf(device, ptr(feats), ptr(lens), B, L, F, ptr(idx), 1 if center_coords else 0, ptr(out)))
+    entry = _binding.load().fd_nerf if method == "serial" else _binding.load().fd_nerf_scan
+    _binding.check(entry(device, ptr(feats), ptr(lens), B, L, F, ptr(idx), 1 if center_coords else 0, ptr(out)))
     return [out[i, : 3 * lens[i]].copy() for i in range(B)]
 
 

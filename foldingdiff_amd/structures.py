@@ -45,12 +45,13 @@ PDB parser rules (``read_backbone``; the reference relies on biotite 0.34's ``PD
 7. a residue without one of N / CA / C rejects the file (``None``, with a debug log line).  This project's choice:
    it stands in for biotite's ``BadStructureError``, whose exact trigger is not pinned here.
 """
+import ctypes as C
 import glob
 import gzip
 import json
 import logging
 import os
-from typing import Callable, List, Optional, Sequence, Tuple, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import pandas as pd
@@ -566,6 +567,179 @@ def restraint_energy(coords: Sequence[np.ndarray], restraints, device: int = 0, 
     if not return_gradient:
         return energy, worst
     return energy, worst, [grad[b, : 3 * lens[b]].copy() for b in range(B)]
+
+
+# ---------------------------------------------------------------------------------------------------- relaxation in torsion space
+class RelaxResult(NamedTuple):
+    """What ``relax`` returns: per chain the relaxed angles (float32 ``[len_i, F]``), and arrays over the chains: the energy
+    terms clash | restraint | tether before and after (float64 ``[B, 3]``), the accepted steps, the clashing atoms before and
+    after (``count_clashes`` on ``build_backbones(method="scan")``), the largest change of a moved angle in radians, the step
+    sizes to continue from, and with ``return_trace`` the total energy after every iteration (``[n_iter + 1, B]``)."""
+    angles: List[np.ndarray]
+    energy_before: np.ndarray
+    energy_after: np.ndarray
+    accepted: np.ndarray
+    clashes_before: np.ndarray
+    clashes_after: np.ndarray
+    max_change: np.ndarray
+    step: np.ndarray
+    trace: Optional[np.ndarray]
+
+
+def _relax_inputs(angles, lengths, feature_names, restraints, fixed, anchor, move, alpha, margin, clash_weight, tether, step0, grow,
+                  shrink, max_step):
+    """The padded arrays and the ``fd_relax_params`` both relax entries take; argument errors the library would also refuse
+    are left to it (its message names the argument)."""
+    F = len(feature_names)
+    if isinstance(angles, np.ndarray) and angles.ndim == 3:
+        if lengths is None:
+            raise ValueError("a padded [B, L, F] array needs lengths")
+        chains = [np.asarray(a[: int(n)], dtype=np.float32) for a, n in zip(angles, lengths)]
+    else:
+        chains = [np.asarray(a, dtype=np.float32) for a in angles]
+        if lengths is not None:
+            chains = [c[: int(n)] for c, n in zip(chains, lengths)]
+    if not chains or any(c.ndim != 2 or c.shape[1] != F or len(c) == 0 for c in chains):
+        raise ValueError(f"each chain must be [len >= 1, {F}]")
+    idx = nerf.feature_columns(feature_names)
+    unknown = [m for m in move if m not in feature_names]
+    if unknown:
+        raise ValueError(f"move={tuple(move)!r}: {unknown} are not among the features {list(feature_names)}")
+    B, L = len(chains), max(len(c) for c in chains)
+    lens = np.array([len(c) for c in chains], dtype=np.int32)
+    feats = np.zeros((B, L, F), dtype=np.float32)
+    for b, c in enumerate(chains):
+        feats[b, : len(c)] = c
+    anc = None
+    if anchor is not None:
+        anc = np.zeros((B, L, F), dtype=np.float32)
+        rows = list(anchor) if not (isinstance(anchor, np.ndarray) and anchor.ndim == 3) else [a[: n] for a, n in zip(anchor, lens)]
+        if len(rows) != B or any(np.shape(a) != c.shape for a, c in zip(rows, chains)):
+            raise ValueError("anchor: one array per chain, shaped like its angles")
+        for b, a in enumerate(rows):
+            anc[b, : lens[b]] = a
+    fix = None
+    if fixed is not None:
+        if len(fixed) != B:
+            raise ValueError(f"fixed: {len(fixed)} entries for {B} chains")
+        fix = np.zeros((B, L), dtype=np.uint8)
+        for b, f in enumerate(fixed):
+            if f is None:
+                continue
+            f = np.asarray(f)
+            if f.dtype == bool:
+                if len(f) != lens[b]:
+                    raise ValueError(f"fixed[{b}]: a boolean array has one entry per residue ({lens[b]})")
+                fix[b, : lens[b]] = f
+            elif f.size:
+                if f.min() < 0 or f.max() >= lens[b]:
+                    raise ValueError(f"fixed[{b}]: residues outside [0, {lens[b]})")
+                fix[b, f.astype(np.int64)] = 1
+    prm = _binding.FdRelaxParams()
+    for k in range(9):
+        prm.feat_idx[k] = int(idx[k])
+    for f, name in enumerate(feature_names[:16]):
+        prm.is_angle[f] = 0 if ":" in name and name.count(":") == 1 else 1   # one ':' names a bond length, as in the PDB writers
+        prm.move[f] = 1 if name in move else 0
+    prm.clash_alpha, prm.clash_margin, prm.w_clash, prm.w_tether = float(alpha), float(margin), float(clash_weight), float(tether)
+    prm.step0, prm.grow, prm.shrink, prm.max_step = float(step0), float(grow), float(shrink), float(max_step)
+    return chains, feats, anc, lens, fix, prm, pack_restraints(restraints, lens.tolist())
+
+
+def relax_energy(angles, lengths, feature_names: Sequence[str], restraints=None, fixed=None, anchor=None,
+                 move: Sequence[str] = ("phi", "psi", "omega"), alpha: float = 0.63, margin: float = 0.15, clash_weight: float = 1.0,
+                 tether: float = 0.0, device: int = 0):
+    """The energy ``relax`` descends and its gradient with respect to the angles, in one ``fd_relax_energy`` call: float64
+    ``[B, 3]`` (clash | restraint | tether), the gradient norms ``[B]`` and one float64 ``[len_i, F]`` gradient per chain, zero
+    where a column is not in ``move`` or a row is ``fixed``.  Arguments as for ``relax``; ``anchor``: the angles the tether
+    pulls towards (default: the input, so the tether costs nothing)."""
+    chains, feats, anc, lens, fix, prm, packed = _relax_inputs(angles, lengths, feature_names, restraints, fixed, anchor, move, alpha, margin,
+                                                               clash_weight, tether, 0.01, 1.2, 0.5, 0.5)
+    B, L, F = feats.shape
+    energy, gnorm, grad = np.empty((B, 3)), np.empty(B), np.zeros((B, L, F))
+    _binding.check(_binding.load().fd_relax_energy(device, ptr(feats), ptr(anc), ptr(lens), B, L, F, C.byref(prm), ptr(fix),
+                                                   *(ptr(a) for a in packed), ptr(energy), ptr(gnorm), ptr(grad)))
+    return energy, gnorm, [grad[b, : lens[b]].copy() for b in range(B)]
+
+
+def relax(angles, lengths, feature_names: Sequence[str], restraints=None, fixed=None, n_iter: int = 200,
+          move: Sequence[str] = ("phi", "psi", "omega"), alpha: float = 0.63, margin: float = 0.15, clash_weight: float = 1.0,
+          tether: float = 0.0, step0: float = 0.01, grow: float = 1.2, shrink: float = 0.5, max_step: float = 0.5, device: int = 0,
+          return_trace: bool = False) -> RelaxResult:
+    """Relax finished backbones in torsion space on the device (``fd_relax``): ``n_iter`` steps of a descent
+    with an adaptive step on  clash + restraints + tether, whose energy never rises.  The clash term is ``count_clashes``'
+    rule made soft -- a pair closer than ``alpha (r_a + r_b) + margin`` costs ``clash_weight`` times the squared shortfall --
+    so a chain whose clash energy reaches 0 has no clashing atom at ``alpha``.
+
+    ``angles``: a list of ``[len_i, F]`` arrays, or a padded ``[B, L, F]`` array with ``lengths``; ``feature_names`` as for
+    ``nerf.build_backbones``.  ``restraints``: as for ``pack_restraints`` (a ``Restraints`` per chain, one for all, or None).
+    ``fixed``: per chain a boolean array over its residues or a list of residue indices whose angles keep their bits.
+    ``move``: the columns that may change; ``tether``: the weight of the squared distance to the input angles.  ``step0``,
+    ``grow``, ``shrink``, ``max_step``: a step starts at ``step0``, grows by ``grow`` when it lowered the energy, shrinks by
+    ``shrink`` when it did not (the state then stays), and never moves the angles by more than ``max_step`` radians in norm.
+
+    This is not a force field: backbone-only repulsion in torsion space removes clashes and keeps restraints, nothing more;
+    whether relaxed backbones are more designable is unmeasured."""
+    n_iter = int(n_iter)
+    if n_iter < 0:
+        raise ValueError(f"n_iter={n_iter} must be >= 0")
+    chains, feats, anc, lens, fix, prm, packed = _relax_inputs(angles, lengths, feature_names, restraints, fixed, None, move, alpha, margin,
+                                                               clash_weight, tether, step0, grow, shrink, max_step)
+    B, L, F = feats.shape
+    lib = _binding.load()
+    rst = [ptr(a) for a in packed]
+    before, gnorm = np.empty((B, 3)), np.empty(B)
+    _binding.check(lib.fd_relax_energy(device, ptr(feats), None, ptr(lens), B, L, F, C.byref(prm), ptr(fix), *rst, ptr(before), ptr(gnorm), None))
+    out, after, accepted = feats.copy(), np.empty((B, 3)), np.zeros(B, dtype=np.int32)
+    step = np.full(B, float(step0))
+    trace = np.empty((max(n_iter, 0) + 1, B)) if return_trace else None
+    _binding.check(lib.fd_relax(device, ptr(feats), None, ptr(lens), B, L, F, C.byref(prm), ptr(fix), *rst, n_iter, ptr(step), ptr(out),
+                                ptr(after), ptr(trace), ptr(accepted)))
+    relaxed = [out[b, : lens[b]].copy() for b in range(B)]
+    clashes = count_clashes(nerf.build_backbones(chains + relaxed, feature_names, center_coords=False, device=device, method="scan"),
+                            alpha=alpha, device=device)
+    change = np.zeros(B)
+    for b, (c, r) in enumerate(zip(chains, relaxed)):
+        d = r.astype(np.float64) - c.astype(np.float64)
+        ang = np.array([bool(prm.is_angle[f]) for f in range(F)])
+        d[:, ang] = d[:, ang] - 2.0 * np.pi * np.floor((d[:, ang] + np.pi) / (2.0 * np.pi))
+        change[b] = np.abs(d).max()
+    return RelaxResult(relaxed, before, after, accepted.astype(np.int64), clashes[:B], clashes[B:], change, step, trace)
+
+
+def relax_to_folder(angle_frames: Sequence[pd.DataFrame], names: Sequence[str], outdir: str, device: int = 0, **relax_args) -> dict:
+    """``relax`` on the chains of ``angle_frames`` (DataFrames whose columns are the feature names; chains that share their
+    columns go through one call) and its outputs in ``outdir``: ``relaxed_angles/{name}.csv.gz``, ``relaxed_pdb/{name}.pdb``
+    and ``relax_report.json`` -- per chain the clashing atoms and the energy terms (clash | restraint | tether) before and
+    after, the accepted steps and the largest angle change in radians.  Returns the report."""
+    from .angles_and_coords import _write_chains
+    names = [str(n) for n in names]
+    if len(names) != len(angle_frames) or len(set(names)) != len(names):
+        raise ValueError("one distinct name per chain")
+    os.makedirs(os.path.join(outdir, "relaxed_angles"), exist_ok=True)
+    groups = {}
+    for i, df in enumerate(angle_frames):
+        groups.setdefault(tuple(str(c) for c in df.columns), []).append(i)
+    relaxed: List[Optional[pd.DataFrame]] = [None] * len(names)
+    rows = {}
+    for cols, members in groups.items():
+        res = relax([np.nan_to_num(np.asarray(angle_frames[i].values, dtype=np.float32), nan=0.0) for i in members], None, list(cols),
+                    device=device, **relax_args)
+        for k, i in enumerate(members):
+            relaxed[i] = pd.DataFrame(res.angles[k], columns=list(cols))
+            rows[names[i]] = {"clashes_before": int(res.clashes_before[k]), "clashes_after": int(res.clashes_after[k]),
+                              "energy_before": [float(v) for v in res.energy_before[k]], "energy_after": [float(v) for v in res.energy_after[k]],
+                              "accepted": int(res.accepted[k]), "max_angle_change": float(res.max_change[k])}
+    for name, df in zip(names, relaxed):
+        df.to_csv(os.path.join(outdir, "relaxed_angles", f"{name}.csv.gz"))
+    pdb_dir = os.path.join(outdir, "relaxed_pdb")
+    os.makedirs(pdb_dir, exist_ok=True)
+    _write_chains([os.path.join(pdb_dir, f"{name}.pdb") for name in names], relaxed, None, None, True, device)
+    report = {"args": {k: (list(v) if isinstance(v, tuple) else v) for k, v in relax_args.items()},
+              "energy_terms": ["clash", "restraint", "tether"], "chains": {n: rows[n] for n in names}}
+    with open(os.path.join(outdir, "relax_report.json"), "w") as sink:
+        json.dump(report, sink, indent=4)
+    return report
 
 
 class RmsdScorer:

@@ -59,6 +59,8 @@ extern "C" {
 /*    fd_backbone_oxygens and fd_dssp (backbone oxygens and DSSP hydrogen-bond states) are additive too */
 /*    fd_nerf_vjp, fd_restraint_energy, fd_guide_step and fd_sample_guided (the derivative of NeRF and restraint-guided few-step
  *    sampling) and the struct fd_guide_params are additive too */
+/*    fd_nerf_scan, fd_relax_energy and fd_relax (relaxing backbones in torsion space) and the struct fd_relax_params are additive
+ *    too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -693,6 +695,87 @@ int fd_sample_guided(fd_model* m, const float* x_init, const int32_t* lens, int 
                      const fd_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i, const int32_t* rst_j,
                      const double* rst_d0, const double* rst_tol, const double* rst_w, float* out, double* energy_out,
                      double* max_violation_out);
+
+/* ---- relaxing backbones in torsion space: a model-free descent on a finished backbone's angles that removes
+ * backbone clashes, honours distance restraints and may be tethered to where it started.  Backbone-only repulsion in torsion
+ * space is no force field; whether relaxed backbones are more designable is unmeasured.
+ *
+ * fd_nerf_scan: fd_nerf with one workgroup per chain -- the same arguments, layout, `center`, padding zeros and feat_idx, with
+ * 1 <= lens[b] <= min(L, 2048).  The displacement (d0, d1, d2) of atom k >= 3 in the frame of the three atoms before it is
+ * exactly fd_nerf's (the same float32 cos / sin products, the same float64 default-angle path); fd_nerf recomputes that frame
+ * [bc | nbc | n] from three positions, here it is carried: with u = unit(d), m = unit(e_x x u), M_k = [u | m x u | m],
+ *     p_k = R_{k-1} d_k + p_{k-1},   R_k = R_{k-1} M_k,   (R_2, p_2) = fd_nerf's frame of the three seed atoms and the seed C,
+ * and since (R, p) o (M, d) = (R M, R d + p) is associative a chain is a prefix scan over rigid transforms, in a tree whose shape
+ * depends on the chain's length alone: two calls give the same bits, and a chain's bits do not depend on the batch it is in.
+ * Not bit-equal to fd_nerf: per chain max |scan - fd_nerf| <= 1e-9 x the chain's largest |p_k - p_0| (measured: DESIGN.md 6x).
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), the output untouched. */
+int fd_nerf_scan(int device_id, const float* feats, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int center,
+                 double* coords_out);
+
+/* The relax energy of a batch of angle rows x (float32 [B][L][F]) and its gradient in angle space:
+ *     coords = fd_nerf_scan(x, center = 0)                                  fp64, never rounded to float32
+ *     E_clash, gc: atoms 3 i + {0 N, 1 CA, 2 C}, r = 1.55 for N and 1.7 for CA and C; over the pairs a < b with b - a >= 2:
+ *         t_ab = clash_alpha (r_a + r_b) + clash_margin (an fp64 product and sum),  v = max(0, t_ab - d(a, b)),
+ *         E_clash = w_clash sum v^2;  on atom a  -2 w_clash v (p_a - p_b) / d where v > 0 and d > 0, the opposite on b
+ *         (fd_backbone_clashes' rule made soft); an atom's gradient is summed in index order of the partner
+ *     E_rst, gc += the restraint statement of fd_restraint_energy (R = 0 is allowed)
+ *     G = fd_nerf_vjp(coords, gc, centered = 0)
+ *     tether: delta = x - anchor in fp64, and where is_angle[f] delta - 2 pi floor((delta + pi) / (2 pi));
+ *         E_tether = w_tether sum delta^2 over the rows below lens[b] and the columns with move[f];  G += 2 w_tether delta
+ *     G = 0 where !move[f] or fixed[b][l]
+ *     gnorm_b = sqrt(sum G^2) over the rows below lens[b], in a fixed order
+ * No floating-point atomics anywhere; two calls give the same bits.
+ *   feats        float32 [B][L][F] (host), finite on the rows below lens[b]; lens int32[B] in [1, min(L, 2048)]; 3 <= F <= 16
+ *   anchor       the same shape and finite in the same rows, or NULL: the input itself (E_tether = 0, no gradient)
+ *   params       feat_idx as in fd_nerf_vjp; is_angle / move: the first F are read; move[f] != 0 only where f is one of
+ *                feat_idx's columns; clash_alpha, clash_margin, w_clash, w_tether finite and >= 0; the four step numbers are
+ *                fd_relax's and are checked here as there
+ *   fixed        uint8 [B][L] or NULL: rows that do not move
+ *   rst_*        as in fd_restraint_energy
+ *   energy_out   double[B][3] clash | restraint | tether;  gnorm_out double[B]
+ *   dfeats_out   double[B][L][F] or NULL; rows at or beyond lens[b] are not written
+ * With clash_margin >= 1e-3, E_clash == 0 implies that fd_backbone_clashes on the float32-rounded coordinates returns 0 at the
+ * same alpha: rounding to float32 moves a distance by about 1e-5 A.
+ * A bad call (the list is under fd_relax): FD_E_INVALID before any device call, the word in fd_last_error(), outputs untouched. */
+typedef struct fd_relax_params {
+  int32_t feat_idx[9];
+  uint8_t is_angle[16], move[16];
+  double clash_alpha, clash_margin, w_clash, w_tether;
+  double step0, grow, shrink, max_step;
+} fd_relax_params;
+int fd_relax_energy(int device_id, const float* feats, const float* anchor, const int32_t* lens, int B, int L, int F,
+                    const fd_relax_params* params, const uint8_t* fixed, const int32_t* rst_offsets, const int32_t* rst_i,
+                    const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, double* energy_out,
+                    double* gnorm_out, double* dfeats_out);
+
+/* fd_relax: n_iter steps of a descent with an adaptive step on that energy, per chain, chains independent; E is the sum of the
+ * three terms, (E, G, n) = fd_relax_energy's energies, gradient and norm:
+ *     x = feats;  (E, G, n) of x;  h = step_io ? step_io[b] : step0;  trace[0] = E
+ *     for it = 1 .. n_iter:
+ *         s  = (h n > max_step) ? max_step / n : h
+ *         x' = x - float32(s G), then wrapped as the samplers wrap where is_angle[f] -- where G != 0; an element with G == 0
+ *              (immovable columns, fixed rows, phi of residue 0 ...) keeps its bits, as do the rows at or beyond lens[b]
+ *         (E', G', n') of x'
+ *         if E' <= E (false for NaN):  x, E, G, n = x', E', G', n';  h *= grow;  accepted += 1
+ *         else:                        h *= shrink
+ *         trace[it] = E
+ *     feats_out = x;  energy_out = the three terms of x;  step_io[b] = h
+ * anchor == NULL tethers to `feats`.  Nothing is asked of the host between the upload and the download: h, E, the decision and
+ * the trial buffers live on the device; five launches per iteration (scan, restraints, clash, derivative, step).
+ * fd_relax(n_iter = N) equals N calls with n_iter = 1 chained through feats_out, step_io and the same non-NULL anchor, bit for
+ * bit, and energy_out equals fd_relax_energy(feats_out) with that anchor bit for bit.
+ *   n_iter        >= 0; 0 returns the input and its energy
+ *   step_io       double[B], each finite and > 0, or NULL
+ *   feats_out     float32 [B][L][F]: the rows below lens[b]; the others keep what they held
+ *   energy_out    double[B][3];  trace_out double[n_iter + 1][B] or NULL;  accepted_out int32[B]
+ * Everything fd_guide_step rejects for shapes, lengths, feat_idx and restraints, a move column that is no NeRF feature of
+ * feat_idx, a non-finite or negative weight, alpha or margin, step0 <= 0, grow < 1, shrink outside (0, 1), max_step <= 0,
+ * a step_io entry that is not finite and > 0, n_iter < 0, non-finite feats or anchor on the rows below a length, a NULL params
+ * or output: FD_E_INVALID before any device call, the word in fd_last_error(), outputs untouched. */
+int fd_relax(int device_id, const float* feats, const float* anchor, const int32_t* lens, int B, int L, int F,
+             const fd_relax_params* params, const uint8_t* fixed, const int32_t* rst_offsets, const int32_t* rst_i,
+             const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, int n_iter, double* step_io,
+             float* feats_out, double* energy_out, double* trace_out, int32_t* accepted_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
