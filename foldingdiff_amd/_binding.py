@@ -125,6 +125,7 @@ _SIGNATURES = {
     "fd_tie_repeats": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, _P, C.c_uint64, C.c_int, C.c_int64,
                                  _P]),
     "fd_nerf_vjp": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "fd_nerf_vjp_feats": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "fd_restraint_energy": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fd_guide_step": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_double,
                                 C.c_float, _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P]),

@@ -879,7 +879,7 @@ int guided_host_run(fd_model* m, const GuidedHostRun& a) {
     rc = fd_sample_steps_dev(m, 1, nullptr, 0, nullptr);
     if (rc) break;
     energy_of(d_x0, d_gc);
-    launch_nerf_vjp(d_coords, w.lens, B, L, F, fx, 0, d_gc, d_G, s);
+    launch_nerf_vjp(d_coords, w.lens, B, L, F, fx, 0, d_gc, d_ang, d_G, s);
     launch_guide_update(w.x, d_G, w.lens, B, L, F, m->angle_mask, a.guide[i], gp.max_norm, a.coef[2 * Kz + i],
                         r.noise ? r.noise + (size_t)i * r.n : nullptr, h.seed, a.visits[i], h.seq_offset, d_gnorm, s);
     rc = launched();

@@ -39,21 +39,37 @@ int fd_nerf(int device_id, const float* feats, const int32_t* lens, int B, int L
                           [&](const RoundtripBufs& d) { launch_nerf(d.in(0), d.in(1), B, L, F, fx, center, d.out(0), nullptr); });
 }
 
-int fd_nerf_vjp(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int centered,
-                const double* dcoords, double* dfeats_out) {
-  if (!coords || !lens || !feat_idx || !dcoords || !dfeats_out) return fail(FD_E_INVALID, "null argument");
+// fd_nerf_vjp (feats == nullptr: every sign +1) and fd_nerf_vjp_feats
+static int nerf_vjp_run(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                        int centered, const double* dcoords, const float* feats, bool with_feats, double* dfeats_out) {
+  if (!coords || !lens || !feat_idx || !dcoords || !dfeats_out || (with_feats && !feats)) return fail(FD_E_INVALID, "null argument");
   if (int rc = check_guide_shape(lens, B, L, F, feat_idx)) return rc;
   if (int rc = check_chain_doubles("coords", coords, lens, B, L)) return rc;
   if (int rc = check_chain_doubles("dcoords", dcoords, lens, B, L)) return rc;
+  if (with_feats)
+    if (int rc = check_rows_finite("feats", feats, lens, B, L, F)) return rc;
   const NerfFeatures fx{feat_idx[0], feat_idx[1], feat_idx[2], feat_idx[3], feat_idx[4], feat_idx[5], feat_idx[6], feat_idx[7], feat_idx[8]};
   const size_t na = (size_t)B * 3 * L * 3, n = (size_t)B * L * F;
   std::vector<double> grad_host(n);  // the rows at or beyond a length are not the kernel's: dfeats_out keeps what it held there
-  const int rc = device_roundtrip(device_id, {{coords, na * 8}, {dcoords, na * 8}, {lens, (size_t)B * 4}}, {{grad_host.data(), n * 8}},
-                                  [&](const RoundtripBufs& d) { launch_nerf_vjp(d.in(0), d.in(2), B, L, F, fx, centered, d.in(1), d.out(0), nullptr); });
+  const int rc = device_roundtrip(device_id, {{coords, na * 8}, {dcoords, na * 8}, {lens, (size_t)B * 4}, {with_feats ? (const void*)feats : (const void*)coords, with_feats ? n * 4 : 4}},
+                                  {{grad_host.data(), n * 8}}, [&](const RoundtripBufs& d) {
+                                    const float* rows = d.in(3);
+                                    launch_nerf_vjp(d.in(0), d.in(2), B, L, F, fx, centered, d.in(1), with_feats ? rows : nullptr, d.out(0), nullptr);
+                                  });
   if (rc) return rc;
   for (int b = 0; b < B; ++b)
     memcpy(dfeats_out + (size_t)b * L * F, grad_host.data() + (size_t)b * L * F, (size_t)lens[b] * F * 8);
   return FD_OK;
+}
+
+int fd_nerf_vjp(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int centered,
+                const double* dcoords, double* dfeats_out) {
+  return nerf_vjp_run(device_id, coords, lens, B, L, F, feat_idx, centered, dcoords, nullptr, false, dfeats_out);
+}
+
+int fd_nerf_vjp_feats(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                      int centered, const double* dcoords, const float* feats, double* dfeats_out) {
+  return nerf_vjp_run(device_id, coords, lens, B, L, F, feat_idx, centered, dcoords, feats, true, dfeats_out);
 }
 
 int fd_restraint_energy(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* rst_offsets,
@@ -117,7 +133,7 @@ int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t*
         launch_steer_shift(d.in(1), lens_dev, B, L, F, off, angle_mask, ang, nullptr);
         launch_nerf(ang, lens_dev, B, L, F, fx, 0, coords, nullptr);
         launch_restraint_energy(coords, lens_dev, B, L, rs, d.out(5), d.out(6), gc, nullptr);
-        launch_nerf_vjp(coords, lens_dev, B, L, F, fx, 0, gc, G, nullptr);
+        launch_nerf_vjp(coords, lens_dev, B, L, F, fx, 0, gc, ang, G, nullptr);
         launch_guide_update(state, G, lens_dev, B, L, F, angle_mask, c, max_norm, s, draws ? z_dev : nullptr, seed, t, seq_offset,
                             d.out(7), nullptr);
         return hipSuccess;
@@ -225,7 +241,7 @@ static int relax_run(int device_id, const float* feats, const float* anchor, con
     launch_nerf_scan(a.xt, lens_dev, B, L, F, fx, 0, coords, nullptr);
     launch_restraint_energy(coords, lens_dev, B, L, rs, e_rst, max_violation, gc, nullptr);
     launch_soft_clash(coords, lens_dev, B, L, p.clash_alpha, p.clash_margin, p.w_clash, e_clash, gc, nullptr);
-    launch_nerf_vjp(coords, lens_dev, B, L, F, fx, 0, gc, a.Gt, nullptr);
+    launch_nerf_vjp(coords, lens_dev, B, L, F, fx, 0, gc, a.xt, a.Gt, nullptr);
     a.it = it;
     a.last = it == n_iter;
     launch_relax_step(a, B, nullptr);

@@ -258,9 +258,11 @@ void launch_repeat_tie(float* x, const int* lens, const int* tie, int B, int L, 
 // One 256-lane workgroup per chain in all three; lens[b] <= kGuideMaxLen and distinct feature columns, checked by the host.
 constexpr int kGuideMaxLen = 2048;
 // dfeats [B][L][F] fp64 <- the gradient with respect to the NeRF features of a function whose gradient with respect to the
-// coordinates [B][3L][3] (launch_nerf's layout) is dcoords; rows at or beyond lens[b] are not written
+// coordinates [B][3L][3] (launch_nerf's layout) is dcoords; rows at or beyond lens[b] are not written.  feats [B][L][F]: the
+// float32 rows the forward built the coordinates from, which give the angle and length slots their signs (sign(sin(angle))
+// sign(length) and sign(length); the sign of zero and of a default is +1), or null: every sign +1
 void launch_nerf_vjp(const double* coords, const int* lens, int B, int L, int F, const NerfFeatures& fx, int centered,
-                     const double* dcoords, double* dfeats, hipStream_t s);
+                     const double* dcoords, const float* feats, double* dfeats, hipStream_t s);
 // a batch's distance restraints, packed per chain: chain b owns entries offsets[b] .. offsets[b + 1] - 1
 struct Restraints {
   const int* offsets;          // [B + 1]

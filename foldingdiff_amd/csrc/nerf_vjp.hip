@@ -8,6 +8,11 @@
 //     sum_{m >= k} g_m . (axis x (q_m - c)) = axis . (Tq_k - c x Fs_k),     Fs_k = sum_{m >= k} g_m,  Tq_k = sum_{m >= k} q_m x g_m
 // for a rotation and unit(r) . Fs_k for the translation: two suffix sums along the chain and three dot products per atom.
 // Positions are relative to atom 0 (q_m = p_m - p_0), which keeps the cancellation in Tq - c x Fs small.
+// The coordinates do not decide the sense of the last two: r = bl (-cos(angle) u + sin(angle) w), so unit(r x u) is the angle's
+// axis times sign(bl sin(angle)) and unit(r) the bond's direction times sign(bl) -- (angle, torsion) and (-angle, torsion + pi)
+// build the same chain.  With `feats`, the float32 rows the forward read (row i for every angle and length of atom 3 i + 3 + j),
+// the angle's slot is multiplied by sign(sin((double)angle)) sign(bl) and the length's by sign(bl); the sign of zero and of a
+// default counts as +1.  feats == nullptr: every sign +1 (fd_nerf_vjp), right where sin(angle) > 0 and bl > 0.
 // Lane t owns atoms [t * per, (t + 1) * per), per = ceil(n / 256): pass 1 sums its own g and q x g (last atom first), a wave
 // suffix scan (64-lane shuffles of the fp64 halves, a fixed doubling tree) and four wave totals in LDS give the sum over the
 // lanes behind it, pass 2 walks the same atoms again, last first, with the running suffix.  No per-atom array of suffix sums;
@@ -88,13 +93,15 @@ struct VjpColumns {
 
 __global__ __launch_bounds__(kThreads) void nerf_vjp_kernel(const double* __restrict__ coords, const int* __restrict__ lens, int L,
                                                             int F, VjpColumns col, int centered,
-                                                            const double* __restrict__ dcoords, double* __restrict__ dfeats) {
+                                                            const double* __restrict__ dcoords, const float* __restrict__ feats,
+                                                            double* __restrict__ dfeats) {
   __shared__ double slot[kWaves];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int len = lens[b], n = 3 * len;
   const double* p = coords + (size_t)b * 3 * L * 3;
   const double* g = dcoords + (size_t)b * 3 * L * 3;
   double* out = dfeats + (size_t)b * L * F;
+  const float* rows = feats ? feats + (size_t)b * L * F : nullptr;
   for (int e = tid; e < len * F; e += kThreads) out[e] = 0.0;
   const int per = (n + kThreads - 1) / kThreads;
   const int k0 = min(n, tid * per), k1 = min(n, k0 + per);
@@ -130,8 +137,16 @@ __global__ __launch_bounds__(kThreads) void nerf_vjp_kernel(const double* __rest
     const int ca = j == 0 ? col.ang[0] : j == 1 ? col.ang[1] : col.ang[2];
     const int cl = j == 0 ? col.len[0] : j == 1 ? col.len[1] : col.len[2];
     out[(size_t)(i + (j == 2)) * F + ct] = dot(u, M);  // (phi belongs to the residue the C atom is in)
-    if (ca >= 0) out[(size_t)i * F + ca] = dot(unit(cross(r, u)), M);
-    if (cl >= 0) out[(size_t)i * F + cl] = dot(unit(r), Fs);
+    const bool flip_l = rows && cl >= 0 && rows[(size_t)i * F + cl] < 0.f;
+    const bool flip_a = flip_l != (rows && ca >= 0 && sin((double)rows[(size_t)i * F + ca]) < 0.0);
+    if (ca >= 0) {
+      const double da = dot(unit(cross(r, u)), M);
+      out[(size_t)i * F + ca] = flip_a ? -da : da;
+    }
+    if (cl >= 0) {
+      const double dl = dot(unit(r), Fs);
+      out[(size_t)i * F + cl] = flip_l ? -dl : dl;
+    }
   }
 }
 
@@ -226,11 +241,11 @@ __global__ __launch_bounds__(kThreads) void guide_update_kernel(float* __restric
 }  // namespace
 
 void launch_nerf_vjp(const double* coords, const int* lens, int B, int L, int F, const NerfFeatures& fx, int centered,
-                     const double* dcoords, double* dfeats, hipStream_t s) {
+                     const double* dcoords, const float* feats, double* dfeats, hipStream_t s) {
   // atom 3 i + 3 (next N): psi, CA:C:1N, 0C:1N;  3 i + 4 (next CA): omega, C:1N:1CA, N:CA;  3 i + 5 (next C): phi of i + 1,
   // N:CA:C at index i (the reference's quirk, nerf.hip), CA:C
   const VjpColumns col{{fx.psi, fx.omega, fx.phi}, {fx.ang_ca_c_n, fx.ang_c_n_ca, fx.ang_n_ca_c}, {fx.len_c_n, fx.len_n_ca, fx.len_ca_c}};
-  hipLaunchKernelGGL(nerf_vjp_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, coords, lens, L, F, col, centered ? 1 : 0, dcoords, dfeats);
+  hipLaunchKernelGGL(nerf_vjp_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, coords, lens, L, F, col, centered ? 1 : 0, dcoords, feats, dfeats);
 }
 
 void launch_restraint_energy(const double* coords, const int* lens, int B, int L, const Restraints& r, double* energy,

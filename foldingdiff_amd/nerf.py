@@ -74,12 +74,19 @@ def build_backbones(
     return [out[i, : 3 * lens[i]].copy() for i in range(B)]
 
 
-def _vjp_padded(coords: np.ndarray, lens: np.ndarray, dcoords: np.ndarray, F: int, idx: np.ndarray, centered: bool, device: int) -> np.ndarray:
-    """``fd_nerf_vjp`` on padded arrays: float64 ``[B, 3L, 3]`` twice -> float64 ``[B, L, F]`` (rows at or beyond a length 0)."""
+def _vjp_padded(coords: np.ndarray, lens: np.ndarray, dcoords: np.ndarray, F: int, idx: np.ndarray, centered: bool, device: int,
+                feats: Optional[np.ndarray] = None) -> np.ndarray:
+    """``fd_nerf_vjp`` -- with ``feats`` (float32 ``[B, L, F]``) ``fd_nerf_vjp_feats`` -- on padded arrays: float64
+    ``[B, 3L, 3]`` twice -> float64 ``[B, L, F]`` (rows at or beyond a length 0)."""
     B, L = coords.shape[0], coords.shape[1] // 3
     out = np.zeros((B, L, F), dtype=np.float64)
     ptr = _binding.ptr
-    _binding.check(_binding.load().fd_nerf_vjp(device, ptr(coords), ptr(lens), B, L, F, ptr(idx), 1 if centered else 0, ptr(dcoords), ptr(out)))
+    lib = _binding.load()
+    if feats is None:
+        _binding.check(lib.fd_nerf_vjp(device, ptr(coords), ptr(lens), B, L, F, ptr(idx), 1 if centered else 0, ptr(dcoords), ptr(out)))
+    else:
+        assert feats.dtype == np.float32 and feats.shape == (B, L, F) and feats.flags.c_contiguous
+        _binding.check(lib.fd_nerf_vjp_feats(device, ptr(coords), ptr(lens), B, L, F, ptr(idx), 1 if centered else 0, ptr(dcoords), ptr(feats), ptr(out)))
     return out
 
 
@@ -89,13 +96,19 @@ def coords_vjp(
     feature_names: Sequence[str],
     centered: bool = True,
     device: int = 0,
+    angles: Optional[Sequence[np.ndarray]] = None,
 ) -> List[np.ndarray]:
     """The gradient of any function of backbone coordinates with respect to the angles (and bond lengths) NeRF built them
-    from, on the GPU (``fd_nerf_vjp``), from the coordinates alone.
+    from, on the GPU.
+
+    ``angles``: the ``[len_i, F]`` rows ``build_backbones`` was given (``fd_nerf_vjp_feats``): exact wherever the forward is
+    finite.  Without them (``fd_nerf_vjp``, from the coordinates alone) the result is exact only where every bond-angle feature
+    has ``sin > 0`` and every bond-length feature is ``> 0``, as a backbone's are; elsewhere the bond-angle and bond-length
+    entries come out with the wrong sign, because ``(angle, torsion)`` and ``(-angle, torsion + pi)`` build the same chain.
 
     ``coords``: one ``[3 len_i, 3]`` array per chain, as ``build_backbones`` returns them; ``dcoords``: the function's
     gradient with respect to them, the same shapes; ``centered``: the coordinates came from ``center_coords=True``.  Returns
-    one ``float64 [len_i, F]`` array per chain in the column order of ``feature_names``: exact (a torsion, an angle or a bond
+    one ``float64 [len_i, F]`` array per chain in the column order of ``feature_names`` (a torsion, an angle or a bond
     length moves everything behind it as a rigid body), fp64, the same bits on every call.  Columns and rows NeRF does not
     read (phi of the first residue, the last residue's other angles) are 0."""
     xs = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in coords]
@@ -110,15 +123,23 @@ def coords_vjp(
     for i, (x, g) in enumerate(zip(xs, gs)):
         xyz[i, : len(x)] = x
         grad[i, : len(g)] = g
-    out = _vjp_padded(xyz, lens, grad, F, idx, centered, device)
+    feats = None
+    if angles is not None:
+        rows = [np.asarray(a, dtype=np.float32) for a in angles]
+        assert len(rows) == B and all(r.shape == (n, F) for r, n in zip(rows, lens)), "angles: one [len, F] array per chain"
+        feats = np.zeros((B, L, F), dtype=np.float32)
+        for i, r in enumerate(rows):
+            feats[i, : len(r)] = r
+    out = _vjp_padded(xyz, lens, grad, F, idx, centered, device, feats)
     return [out[i, : lens[i]].copy() for i in range(B)]
 
 
 def build_backbones_torch(angles, lengths: Sequence[int], feature_names: Sequence[str], center_coords: bool = True, device: int = 0):
     """``build_backbones`` as a differentiable torch function: a float32 ``[B, L, F]`` tensor of angles and the chains'
     ``lengths`` -> a float64 ``[B, 3L, 3]`` tensor of coordinates (atoms at or beyond ``3 * lengths[b]``: 0).  The forward is
-    ``fd_nerf``, the backward ``fd_nerf_vjp``, so any torch loss on the coordinates back-propagates to the angles; the
-    gradient is ``coords_vjp``'s, cast to the dtype of ``angles``, and 0 on the rows at or beyond a length.  Both passes go
+    ``fd_nerf``, the backward ``fd_nerf_vjp_feats`` on the float32 rows the forward was given, so any torch loss on the
+    coordinates back-propagates to the angles, bond angles and lengths of either sign included; the gradient is
+    ``coords_vjp``'s with ``angles``, cast to the dtype of ``angles``, and 0 on the rows at or beyond a length.  Both passes go
     through host arrays, whatever device ``angles`` lives on."""
     import torch
 
@@ -135,13 +156,13 @@ def build_backbones_torch(angles, lengths: Sequence[int], feature_names: Sequenc
             out = np.empty((B, 3 * L, 3), dtype=np.float64)
             ptr = _binding.ptr
             _binding.check(_binding.load().fd_nerf(device, ptr(feats), ptr(lens), B, L, F, ptr(idx), 1 if center_coords else 0, ptr(out)))
-            ctx.coords, ctx.dtype = out, ang.dtype
+            ctx.coords, ctx.feats, ctx.dtype = out, feats.copy(), ang.dtype
             return torch.from_numpy(out.copy()).to(ang.device)
 
         @staticmethod
         def backward(ctx, grad):
             g = np.ascontiguousarray(grad.detach().cpu().numpy(), dtype=np.float64)
-            return torch.from_numpy(_vjp_padded(ctx.coords, lens, g, F, idx, center_coords, device)).to(device=grad.device, dtype=ctx.dtype)
+            return torch.from_numpy(_vjp_padded(ctx.coords, lens, g, F, idx, center_coords, device, ctx.feats)).to(device=grad.device, dtype=ctx.dtype)
 
     return _Nerf.apply(angles)
 

@@ -1598,7 +1598,7 @@ def guide(model, dset, lengths: Sequence[int], restraints, num_steps: Optional[i
           feature_key: str = "angles"):
     """Sample one backbone per entry of ``lengths`` while steering it toward distance restraints between backbone atoms
     (``fd_sample_guided``): after every visit of the strided sampler the predicted clean angles are built into a
-    backbone on the device, the restraint energy's gradient is carried back to the angles exactly (``fd_nerf_vjp``), and the
+    backbone on the device, the restraint energy's gradient is carried back to the angles exactly (``fd_nerf_vjp_feats``, on the rows NeRF read), and the
     state takes a clipped step down it before the visit's noise is added.
 
     ``restraints``: one ``structures.Restraints`` per length (``None``: none), or a single one for every backbone --

@@ -61,6 +61,7 @@ extern "C" {
  *    sampling) and the struct fd_guide_params are additive too */
 /*    fd_nerf_scan, fd_relax_energy and fd_relax (relaxing backbones in torsion space) and the struct fd_relax_params are additive
  *    too */
+/*    fd_nerf_vjp_feats (the derivative of NeRF with the signs of the features the forward read) is additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -601,8 +602,10 @@ int fd_tie_repeats(int device_id, const float* x, const int32_t* lens, const int
 /* ---- restraint guidance: the derivative of NeRF, distance restraints between backbone atoms, and a few-step run
  * that follows every visit with a step down the gradient of the restraint energy of the visit's predicted structure.
  *
- * fd_nerf_vjp: the gradient with respect to the NeRF features of any function of the coordinates, from the coordinates alone,
- * model-free and synchronous like fd_nerf, fp64 throughout.  Per chain of len residues, n = 3 len atoms; atom k >= 3 was
+ * fd_nerf_vjp_feats: the gradient with respect to the NeRF features of any function of the coordinates, from the coordinates and
+ * the float32 feature rows fd_nerf built them from, model-free and synchronous like fd_nerf, fp64 throughout.  fd_nerf_vjp: the
+ * same from the coordinates alone, with every sign below taken as +1 -- right on the rows where every bond-angle feature has
+ * sin(angle) > 0 and every bond-length feature is > 0 (a backbone's own), wrong in sign elsewhere: use fd_nerf_vjp_feats there.  Per chain of len residues, n = 3 len atoms; atom k >= 3 was
  * placed from atoms k-3, k-2, k-1, and with i = (k - 3) / 3, j = (k - 3) % 3 its features are
  *     j = 0 (next N):   torsion psi (row i)        angle CA:C:1N (row i)                          length 0C:1N (row i)
  *     j = 1 (next CA):  torsion omega (row i)      angle C:1N:1CA (row i)                         length N:CA (row i)
@@ -611,7 +614,12 @@ int fd_tie_repeats(int device_id, const float* x, const int32_t* lens, const int
  *   q_k  = p_k - p_0: positions relative to the chain's atom 0
  *   Fs_k = sum_{m >= k} g_m,   Tq_k = sum_{m >= k} q_m x g_m
  *   with b = q_{k-2}, c = q_{k-1}, d = q_k, u = unit(c - b), r = d - c, M = Tq_k - c x Fs_k:
- *     d / d torsion = u . M      d / d angle = unit(r x u) . M      d / d length = unit(r) . Fs_k
+ *     d / d torsion = u . M      d / d angle = sa unit(r x u) . M      d / d length = sl unit(r) . Fs_k
+ *   sl = sign(length feature),  sa = sign(sin((double)angle feature)) sl, each feature read from row i as float32, the row the
+ *   forward read it from; the sign of zero is +1, and so is the sign of a slot whose feat_idx is -1 (the defaults are positive).
+ *   The coordinates cannot decide these signs: with r = bl (-cos(angle) u + sin(angle) w), unit(r x u) is the angle's rotation
+ *   axis times sign(bl sin(angle)) and unit(r) the bond's direction times sign(bl); (angle, torsion) and (-angle, torsion + pi)
+ *   build the same chain.  sin(angle) == 0 or length == 0 is outside the domain: fd_nerf's next frame is not finite there.
  * each to its (row, column); a slot whose feat_idx is -1 receives nothing, every other element of a row below len is 0 (phi of
  * residue 0, the last residue's psi / omega / angles / lengths, columns that are no NeRF feature), rows at or beyond len are not
  * written, len == 1: all zero.  A torsion, an angle or a length moves everything behind it as a rigid body, hence the suffix
@@ -619,10 +627,14 @@ int fd_tie_repeats(int device_id, const float* x, const int32_t* lens, const int
  *   coords      float64 [B][3L][3] in fd_nerf's layout (host); dcoords the same shape; both finite on the atoms below 3 lens[b]
  *   lens        int32[B], 1 <= lens[b] <= min(L, 2048)
  *   feat_idx    int32[9] as in fd_nerf, and no column named twice; 3 <= F <= 16
+ *   feats       (fd_nerf_vjp_feats) float32 [B][L][F], the array fd_nerf was given; finite on the rows below lens[b]
  *   dfeats_out  float64 [B][L][F]
+ * Where every sign is +1 fd_nerf_vjp_feats returns fd_nerf_vjp's bits.
  * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs untouched. */
 int fd_nerf_vjp(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int centered,
                 const double* dcoords, double* dfeats_out);
+int fd_nerf_vjp_feats(int device_id, const double* coords, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
+                      int centered, const double* dcoords, const float* feats, double* dfeats_out);
 
 /* Distance restraints, packed per chain: chain b owns entries rst_offsets[b] .. rst_offsets[b + 1] - 1 of the lists
  * (rst_offsets[0] == 0, non-decreasing; R = rst_offsets[B] may be 0, the lists are then not read).
@@ -645,7 +657,7 @@ int fd_restraint_energy(int device_id, const double* coords, const int32_t* lens
  *     ang    = the shift statement of fd_sample_steered on x0
  *     coords = fd_nerf(ang, center = 0)
  *     E, gc  = the restraint statement on coords
- *     G      = fd_nerf_vjp(coords, gc, centered = 0)                                    [B][L][F] fp64
+ *     G      = fd_nerf_vjp_feats(coords, gc, centered = 0, feats = ang)                 [B][L][F] fp64
  *     n_b    = sqrt(sum of G^2 over the rows below lens[b]), in a fixed order;   k_b = n_b > max_norm ? max_norm / n_b : 1
  *     x     <- x - float32((double(c) * k_b) * G)   only where c != 0 (c == 0 leaves x's bits alone, whatever G holds)
  *     x     <- x + s z  where s != 0;   x <- wrap(x) where angular
@@ -670,7 +682,7 @@ int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t*
 /* fd_sample_guided is fd_sample_strided (final state only) whose visits write their prediction of the clean state as
  * fd_sample_steered's do, run their update without its draw as fd_sample_repeat's do -- wrap(a x + b eps) -- and are each
  * followed by the guide statement with c = guide[i], s = coef[2][i], t = visits[i] and row i of `noise`: five launches (shift,
- * NeRF, restraints, derivative, update) between two replays of the plain sampler's captured step graph, which is not captured
+ * NeRF, restraints, derivative -- fd_nerf_vjp_feats' on the shifted rows, whose bond angles may lie anywhere on the circle --, update) between two replays of the plain sampler's captured step graph, which is not captured
  * again; nothing is asked of the host between the upload and the download.
  *   visits, noise, seed, seq_offset, x_init, lens   as in fd_sample_strided
  *   coef              float32 [5][K] rows a | b | s | u | v, all finite (host), as in fd_sample_steered
@@ -719,7 +731,7 @@ int fd_nerf_scan(int device_id, const float* feats, const int32_t* lens, int B, 
  *         E_clash = w_clash sum v^2;  on atom a  -2 w_clash v (p_a - p_b) / d where v > 0 and d > 0, the opposite on b
  *         (fd_backbone_clashes' rule made soft); an atom's gradient is summed in index order of the partner
  *     E_rst, gc += the restraint statement of fd_restraint_energy (R = 0 is allowed)
- *     G = fd_nerf_vjp(coords, gc, centered = 0)
+ *     G = fd_nerf_vjp_feats(coords, gc, centered = 0, feats = x)
  *     tether: delta = x - anchor in fp64, and where is_angle[f] delta - 2 pi floor((delta + pi) / (2 pi));
  *         E_tether = w_tether sum delta^2 over the rows below lens[b] and the columns with move[f];  G += 2 w_tether delta
  *     G = 0 where !move[f] or fixed[b][l]

@@ -99,9 +99,10 @@ def wrap64(v):
     return v - 2.0 * np.pi * np.floor((v + np.pi) / (2.0 * np.pi))
 
 
-def relax_energy(x, anchor, prm: Params, fixed=None, rst=None, coords=None, build=nerf_scan):
+def relax_energy(x, anchor, prm: Params, fixed=None, rst=None, coords=None, build=nerf_scan, signs=True):
     """One chain, float32 [len, F] -> (energies [3], G [len, F], gnorm, coords).  ``coords``: evaluate on these (the device's
-    own) instead of building them; ``rst``: an (i, j, d0, tol, w) tuple or None; ``anchor`` None: the input itself."""
+    own) instead of building them; ``rst``: an (i, j, d0, tol, w) tuple or None; ``anchor`` None: the input itself; ``signs``
+    False: the derivative without the rows (every sign +1: right for sin(angle) > 0 and lengths > 0 only)."""
     x = np.asarray(x, dtype=np.float32)
     n, F = x.shape
     idx = np.asarray(prm.feat_idx)
@@ -110,7 +111,7 @@ def relax_energy(x, anchor, prm: Params, fixed=None, rst=None, coords=None, buil
     e_clash, gc = clash_energy(coords, prm.alpha, prm.margin, prm.w_clash)
     e_rst, _, g_rst = gr.restraint_energy(coords, rst if rst is not None else ([], [], [], [], []))
     gc = gc + g_rst
-    G = gr.nerf_vjp(coords, gc, idx, F, False)
+    G = gr.nerf_vjp(coords, gc, idx, F, False, x if signs else None)
     move = np.asarray(prm.move, dtype=bool)[:F]
     ang = np.asarray(prm.is_angle, dtype=bool)[:F]
     delta = x.astype(np.float64) - np.asarray(x if anchor is None else anchor, dtype=np.float32).astype(np.float64)
@@ -133,17 +134,17 @@ def trial(x, G, gnorm, h, prm: Params) -> np.ndarray:
     return np.where(G != 0, moved, x)
 
 
-def relax(x, anchor, prm: Params, n_iter: int, fixed=None, rst=None, h: Optional[float] = None):
+def relax(x, anchor, prm: Params, n_iter: int, fixed=None, rst=None, h: Optional[float] = None, signs=True):
     """One chain: the descent statement -> (x, energies [3], trace [n_iter + 1], accepted, h).  ``anchor`` None: the input."""
     x = np.asarray(x, dtype=np.float32).copy()
     anchor = x.copy() if anchor is None else np.asarray(anchor, dtype=np.float32)
     h = prm.step0 if h is None else float(h)
-    E3, G, gn, _ = relax_energy(x, anchor, prm, fixed, rst)
+    E3, G, gn, _ = relax_energy(x, anchor, prm, fixed, rst, signs=signs)
     E = (E3[0] + E3[1]) + E3[2]
     trace, accepted = [E], 0
     for _ in range(n_iter):
         xt = trial(x, G, gn, h, prm)
-        E3t, Gt, gnt, _ = relax_energy(xt, anchor, prm, fixed, rst)
+        E3t, Gt, gnt, _ = relax_energy(xt, anchor, prm, fixed, rst, signs=signs)
         Et = (E3t[0] + E3t[1]) + E3t[2]
         if Et <= E:
             x, E3, E, G, gn = xt, E3t, Et, Gt, gnt

@@ -23,7 +23,99 @@ def random_features(rng, n, F) -> np.ndarray:
     return np.stack(cols[:F], axis=1).astype(np.float32)
 
 
+SIN_FLOOR = 0.02
+DOMAIN_MODES = ("signs", "negative", "backbone")
+
+
+def domain_features(rng, n, F, mode="signs") -> np.ndarray:
+    """float32 [n, F] over the whole domain of the NeRF forward, in the column order of NAMES9.  Torsions uniform on the circle.
+    ``mode`` "signs": each bond angle uniform in [asin(SIN_FLOOR), pi - asin(SIN_FLOOR)] (both sides of pi / 2) times a random
+    sign, each length as random_features' times a random sign; "negative": the same magnitudes, every bond angle negative,
+    lengths positive; "backbone": random_features.  sin(angle) == 0 and length == 0 stay out: behind such an atom the forward
+    itself is not finite (the next frame's cross product vanishes)."""
+    if mode == "backbone":
+        return random_features(rng, n, F)
+    assert mode in DOMAIN_MODES, mode
+    lo = np.arcsin(SIN_FLOOR)
+    sign = (lambda: rng.choice([-1.0, 1.0], n)) if mode == "signs" else (lambda: -np.ones(n))
+    cols = [rng.uniform(-np.pi, np.pi, n) for _ in range(3)]
+    cols += [rng.uniform(lo, np.pi - lo, n) * sign() for _ in range(3)]
+    cols += [(m + 0.03 * rng.standard_normal(n)) * (rng.choice([-1.0, 1.0], n) if mode == "signs" else 1.0) for m in (1.33, 1.46, 1.52)]
+    return np.stack(cols[:F], axis=1).astype(np.float32)
+
+
+def reparametrise(x, rows) -> np.ndarray:
+    """float32 [n, F >= 6] in the column order of NAMES9 with the three bond angles of ``rows`` negated and the torsion each
+    one shares an atom with moved by pi and wrapped: the same chain up to the float32 rounding of the torsion.  tau (N:CA:C
+    of row i) places the C atom with phi of row i + 1; CA:C:1N goes with psi and C:1N:1CA with omega of the same row.  The last
+    row's angles are negated all the same (NeRF does not read them)."""
+    x = np.array(x, dtype=np.float32)
+    n = len(x)
+    wrap = lambda v: (v - 2.0 * np.pi * np.floor((v + np.pi) / (2.0 * np.pi))).astype(np.float32)   # noqa: E731
+    for i in np.nonzero(np.asarray(rows, dtype=bool))[0]:
+        for ca, ct in ((3, 0), (4, 1), (5, 2)):
+            up = 1 if ca == 3 else 0
+            x[i, ca] = -x[i, ca]
+            if i + up < n:
+                x[i + up, ct] = wrap(np.float64(x[i + up, ct]) + np.pi)
+    return x
+
+
 # ---------------------------------------------------------------------------------- 1. the formula against autograd
+@pytest.mark.parametrize("F", [3, 6, 9])
+@pytest.mark.parametrize("centered", [0, 1])
+@pytest.mark.parametrize("n", [2, 3, 7, 40, 128, 600])
+def test_vjp_formula_agrees_with_autograd_on_the_whole_domain(F, centered, n):
+    """domain_features (bond angles of either sign on both sides of pi / 2, |sin| >= 0.02, lengths of either sign), 2 to 600
+    residues: the statement with the forward's rows is within 1e-12 of autograd's largest entry on the float64 restatement's
+    own coordinates and within 1e-5 on ref_nerf.build's (float32 products inside); the gates of the backbone-like test below.
+    Without the rows (every sign +1) the statement is wrong by about the largest entry itself wherever a sign is negative.
+
+    Measured: on ref_nerf.build's coordinates at most 9.3e-7; on the restatement's own at most 3.9e-14 up to 128 residues and
+    7.5e-14 at 600.  (With the restatement's frames recomputed from positions, as ref_nerf.place does, one 600-residue case
+    stood at 1.55e-12 -- autograd's own rounding, 1.6e-12 from a long-double evaluation; tests/guide_reference.py carries the
+    frame instead and its autograd is within 1.0e-14 of that evaluation.)"""
+    idx = IDX[F]
+    for m, mode in enumerate(DOMAIN_MODES if n <= 128 else DOMAIN_MODES[:1]):
+        rng = np.random.default_rng(100000 * m + 1000 * F + 10 * n + centered)
+        ang = domain_features(rng, n, F, mode)
+        g = rng.standard_normal((3 * n, 3))
+        xyz64, want = gr.autograd_vjp(ang, idx, g, bool(centered))
+        xyz32 = gr.build_ref(ang, idx)
+        if centered:
+            xyz32 = xyz32 - xyz32.mean(axis=0)
+        scale = np.abs(want).max()
+        on_ref = np.abs(gr.nerf_vjp(xyz32, g, idx, F, centered, ang) - want).max() / scale
+        on_own = np.abs(gr.nerf_vjp(xyz64, g, idx, F, centered, ang) - want).max() / scale
+        unsigned = np.abs(gr.nerf_vjp(xyz64, g, idx, F, centered) - want).max() / scale
+        print(f"F={F} centered={centered} len={n} {mode}: {on_ref:.2e} on ref_nerf's coordinates, {on_own:.2e} on the restatement's, "
+              f"{unsigned:.2e} without the rows")
+        assert on_ref <= 1e-5 and on_own <= 1e-12
+        assert (want[0, 0] == 0) and (want[-1, 1:] == 0).all()
+        if F > 3 and mode != "backbone" and n >= 7:
+            assert unsigned > 0.1                                       # (the inputs do tell the two statements apart)
+
+
+def test_reparametrised_rows_build_the_same_chain_and_flip_the_angle_gradient():
+    """(angle, torsion) -> (-angle, wrap(torsion + pi)) on a random half of the rows moves no atom by more than 1e-4 A (the
+    float32 rounding of the torsion) and negates the angle entries of the gradient exactly in those rows."""
+    rng = np.random.default_rng(77)
+    n = 24
+    ang = random_features(rng, n, 6)
+    rows = rng.random(n) < 0.5
+    assert rows[:-1].any() and not rows[:-1].all()
+    flipped = reparametrise(ang, rows)
+    assert (flipped[rows, 3:] < 0).all() and (flipped[~rows, 3:] > 0).all()
+    g = rng.standard_normal((3 * n, 3))
+    xyz, xyz_f = gr.build_ref(ang, IDX[6]), gr.build_ref(flipped, IDX[6])
+    assert np.abs(xyz - xyz_f).max() <= 1e-4
+    G, Gf = gr.nerf_vjp(xyz, g, IDX[6], 6, 0, ang), gr.nerf_vjp(xyz_f, g, IDX[6], 6, 0, flipped)
+    sign = np.where(rows, -1.0, 1.0)[:, None]
+    big = np.abs(G[:, 3:]) > 1e-3 * np.abs(G).max()
+    assert big.sum() > n and (np.abs(Gf[:, 3:] - sign * G[:, 3:])[big] <= 1e-4 * np.abs(G[:, 3:])[big]).all()
+    assert (np.abs(Gf[:, :3] - G[:, :3]) <= 1e-4 * np.abs(G).max()).all()   # the torsions' entries stay
+
+
 @pytest.mark.parametrize("F", [3, 6, 9])
 @pytest.mark.parametrize("centered", [0, 1])
 def test_vjp_formula_agrees_with_autograd(F, centered):
@@ -155,6 +247,45 @@ def test_model_free_entries_reject_bad_arguments_before_touching_a_device(lib):
                      (dict(x=nan_x), b"x is not finite at sequence 0, position 3"), (dict(x0=nan_x), b"x0 is not finite")] + shape_cases + rst_cases:
         expect(word, *step(**kw))
     assert checked == (7 + 9) + (6 + 15) + (14 + 9 + 15)
+
+
+def test_nerf_vjp_feats_is_additive_and_rejects_what_fd_nerf_vjp_rejects(lib):
+    """The ABI stays at 7; fd_nerf_vjp_feats has fd_nerf_vjp's rejections plus a null or non-finite `feats` on the rows below a
+    length.  No valid call is made."""
+    import os
+    import re
+    from conftest import REPO
+    from foldingdiff_amd import _binding
+    header = open(os.path.join(REPO, "include", "fdmi.h")).read()
+    assert "#define FDMI_ABI_VERSION 7" in header and lib.fd_abi_version() == 7 and _binding.ABI_VERSION == 7
+    assert hasattr(lib, "fd_nerf_vjp_feats") and re.search(r"\bint fd_nerf_vjp_feats\(", header) and re.search(r"\bint fd_nerf_vjp\(", header)
+    P = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)   # noqa: E731
+    i32 = lambda *v: np.array(v, np.int32)                              # noqa: E731
+    B, L, F = 2, 6, 6
+    lens, idx = i32(4, 6), IDX[6]
+    rng = np.random.default_rng(1)
+    xyz = rng.standard_normal((B, 3 * L, 3))
+    rows = rng.standard_normal((B, L, F)).astype(np.float32)
+    nan_xyz, inf_g, nan_rows, pad_nan = xyz.copy(), xyz.copy(), rows.copy(), rows.copy()
+    nan_xyz[1, 17, 2], inf_g[0, 11, 0], nan_rows[0, 3, 4] = np.nan, np.inf, np.nan
+    pad_nan[0, 4:] = np.nan                                               # beyond chain 0's length: not looked at
+
+    def call(coords=xyz, lens=lens, B=B, F=F, idx=idx, g=xyz, feats=rows, out="default"):
+        out = np.full((2, L, 16), -7.0) if isinstance(out, str) else out
+        return out, lib.fd_nerf_vjp_feats(0, P(coords), P(lens), B, L, F, P(idx), 1, P(g), P(feats), P(out))
+
+    cases = [(dict(coords=None), b"null"), (dict(lens=None), b"null"), (dict(idx=None), b"null"), (dict(g=None), b"null"), (dict(feats=None), b"null"),
+             (dict(out=None), b"null"), (dict(coords=nan_xyz), b"coords is not finite at chain 1, atom 17"),
+             (dict(g=inf_g), b"dcoords is not finite at chain 0, atom 11"), (dict(feats=nan_rows), b"feats is not finite at sequence 0, position 3"),
+             (dict(lens=i32(4, 0)), b"lens[1]=0"), (dict(lens=i32(7, 6)), b"outside [1, 6]"), (dict(B=0), b"B=0"), (dict(F=2), b"F=2 outside [3, 16]"),
+             (dict(F=17), b"F=17 outside [3, 16]"), (dict(idx=i32(0, 1, 6, 3, 4, 5, -1, -1, -1)), b"feat_idx[2]=6"),
+             (dict(idx=i32(0, 1, 2, 3, 3, 5, -1, -1, -1)), b"feat_idx[4]=3 repeats")]
+    for kw, word in cases:
+        out, rc = call(**kw)
+        msg = lib.fd_last_error()
+        assert rc == -1 and msg and word in msg, (word, rc, msg)
+        assert out is None or (out == -7).all(), word
+    assert call(feats=pad_nan, lens=i32(4, 0))[1] == -1 and b"lens" in lib.fd_last_error()   # (a length error, not the padding's NaN)
 
 
 # ---------------------------------------------------------------------------------- 3. the coefficients

@@ -4,6 +4,7 @@ tests/guide_reference.py and the existing entries composed on the host: bits are
 bound derived at its test.
 """
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -17,8 +18,9 @@ import guide_reference as gr
 from conftest import REPO
 from foldingdiff_amd import _binding, beta_schedules, datasets, nerf, sampling, structures
 from oracle import ref_model, ref_sampling
+import relax_reference as rx
 from test_gpu_parity import PRECISIONS, _inputs, _pair, _write_model_dir
-from test_guide import IDX, descent_case, random_features
+from test_guide import IDX, NAMES9, descent_case, domain_features, random_features, reparametrise
 from test_repeat_gpu import LENS4, LENS5, L_R, T_R, _repeat, _tie
 from test_steer_gpu import MODEL_D, NAMES, OFFSET, VISIT_SETS, _step_x0
 from test_strided_gpu import ANG, F, SENTINEL, _bits, _strided, _valid
@@ -54,6 +56,16 @@ def _vjp(coords, lens, idx, Fx, centered, g):
     out = np.full((B, L, Fx), SENTINEL, dtype=np.float64)
     rc = _binding.load().fd_nerf_vjp(0, P(np.ascontiguousarray(coords)), P(ls), B, L, Fx, P(np.ascontiguousarray(idx, dtype=np.int32)), int(centered),
                                      P(np.ascontiguousarray(g)), P(out))
+    return rc, out
+
+
+def _vjp_feats(coords, lens, idx, Fx, centered, g, feats):
+    """fd_nerf_vjp_feats -> (rc, dfeats); `dfeats` starts at the sentinel."""
+    B, L = coords.shape[0], coords.shape[1] // 3
+    ls = np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+    out = np.full((B, L, Fx), SENTINEL, dtype=np.float64)
+    rc = _binding.load().fd_nerf_vjp_feats(0, P(np.ascontiguousarray(coords)), P(ls), B, L, Fx, P(np.ascontiguousarray(idx, dtype=np.int32)),
+                                           int(centered), P(np.ascontiguousarray(g)), P(np.ascontiguousarray(feats, dtype=np.float32)), P(out))
     return rc, out
 
 
@@ -178,6 +190,180 @@ def test_vjp_on_chains_with_more_atoms_than_lanes(gpu, n, Fx):
         print(f"len={n} F={Fx} centered={centered}: {worst:.2e} of the chain's largest entry")
 
 
+# ---------------------------------------------------------------------------------- 5b. the whole domain of the forward
+DOMAIN_BATCHES = (((1, 2, 3, 7, 12, 12), ("signs", "negative", "backbone", "signs", "negative", "signs")), ((86,), ("signs",)), ((100,), ("negative",)),
+                  ((600,), ("signs",)))
+
+
+@functools.lru_cache(maxsize=None)
+def _domain_case(Fx, centered, batches=DOMAIN_BATCHES):
+    """Chains of tests/test_guide.py's domain_features (bond angles and lengths of either sign), the coordinates of the float64
+    torch restatement on them and autograd's gradient of a random weighting of those coordinates.  Computed once per (F,
+    centered) and left unchanged: a list of dicts feats [B, L, F], lens, g [B, 3L, 3], xyz64 [B, 3L, 3], want [B, L, F]."""
+    out = []
+    for k, (lens, modes) in enumerate(batches):
+        rng = np.random.default_rng(9000 + 100 * Fx + 10 * k + centered)
+        B, L = len(lens), max(lens)
+        feats = np.full((B, L, Fx), SENTINEL, dtype=np.float32)
+        g, xyz64, want = rng.standard_normal((B, 3 * L, 3)), np.zeros((B, 3 * L, 3)), np.zeros((B, L, Fx))
+        for b, (n, mode) in enumerate(zip(lens, modes)):
+            feats[b, :n] = domain_features(rng, n, Fx, mode)
+            xyz64[b, : 3 * n], want[b, :n] = gr.autograd_vjp(feats[b, :n], IDX[Fx], g[b, : 3 * n], bool(centered))
+        out.append(dict(feats=feats, lens=lens, g=g, xyz64=xyz64, want=want))
+    return out
+
+
+def _check_against_autograd(case, coords, Fx, centered, gate):
+    """fd_nerf_vjp_feats on `coords` against the case's autograd gradient, per chain within `gate` of its largest entry."""
+    lens = case["lens"]
+    rc, got = _vjp_feats(coords, lens, IDX[Fx], Fx, centered, case["g"], case["feats"])
+    assert rc == 0, _err()
+    worst = 0.0
+    for b, n in enumerate(lens):
+        assert (got[b, n:] == SENTINEL).all()
+        want = case["want"][b, :n]
+        if n == 1:
+            assert (got[b, :1] == 0).all() and (want == 0).all()
+            continue
+        rel = np.abs(got[b, :n] - want).max() / np.abs(want).max()
+        worst = max(worst, rel)
+        assert rel <= gate, (lens, b, n, rel)
+        assert (got[b, :n][want == 0] == 0).all()
+    return worst, got
+
+
+@pytest.mark.parametrize("Fx", [3, 6, 9])
+@pytest.mark.parametrize("centered", [0, 1])
+def test_vjp_feats_against_autograd_on_the_restatements_coordinates(gpu, Fx, centered):
+    """The device is given the float64 restatement's coordinates and the rows they were built from; gate 2e-9 of the chain's
+    largest entry: the 1e-9 derived for device against statement (test_vjp_equals_the_statement_on_fd_nerf_coordinates) plus the
+    statement's 1e-12 against autograd.  Lengths 1 .. 12 in one ragged batch, 86 (258 atoms: more than one per lane), 100, 600."""
+    worst = 0.0
+    for case in _domain_case(Fx, centered):
+        w, got = _check_against_autograd(case, case["xyz64"], Fx, centered, 2e-9)
+        worst = max(worst, w)
+        rc, again = _vjp_feats(case["xyz64"], case["lens"], IDX[Fx], Fx, centered, case["g"], case["feats"])
+        assert rc == 0 and np.array_equal(_f64bits(again), _f64bits(got))                # two calls, the same bits
+    print(f"F={Fx} centered={centered}: largest distance to autograd {worst:.2e} of the chain's largest entry")
+
+
+def test_vjp_feats_against_autograd_at_2048_residues(gpu):
+    """Every lane owns 24 atoms and every wave boundary carries.  The same gate."""
+    case = _domain_case(6, 1, (((2048,), ("signs",)),))[0]
+    worst, _ = _check_against_autograd(case, case["xyz64"], 6, 1, 2e-9)
+    print(f"len=2048: {worst:.2e} of the chain's largest entry")
+
+
+@pytest.mark.parametrize("Fx", [3, 6, 9])
+@pytest.mark.parametrize("centered", [0, 1])
+def test_vjp_feats_against_autograd_end_to_end(gpu, Fx, centered):
+    """fd_nerf's own coordinates (float32 cos / sin products inside), then fd_nerf_vjp_feats: within 1e-5 of autograd's largest
+    entry through the float64 restatement -- the statement alone stays within 2.1e-6 at 600 residues (tests/test_guide.py), the
+    device adds the last bit of float32 sin and cos."""
+    worst = 0.0
+    for case in _domain_case(Fx, centered):
+        coords = _nerf(case["feats"], case["lens"], IDX[Fx], centered)
+        worst = max(worst, _check_against_autograd(case, coords, Fx, centered, 1e-5)[0])
+    print(f"F={Fx} centered={centered}: largest distance to autograd {worst:.2e} of the chain's largest entry")
+
+
+def _scan(feats, lens, idx, center):
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    B, L, Fx = feats.shape
+    out = np.empty((B, 3 * L, 3))
+    rc = _binding.load().fd_nerf_scan(0, P(feats), P(np.ascontiguousarray(np.asarray(lens, dtype=np.int32))), B, L, Fx,
+                                      P(np.ascontiguousarray(idx, dtype=np.int32)), int(center), P(out))
+    assert rc == 0, _err()
+    return out
+
+
+@pytest.mark.parametrize("Fx", [3, 6, 9])
+def test_forward_against_the_oracle_and_scan_against_serial_on_the_whole_domain(gpu, Fx):
+    """fd_nerf against oracle/ref_nerf.build on the same rows.  Per chain d_ref = max |float64 restatement - ref_nerf.build| is
+    how far rounding the float32 products alone moves that chain; the device differs from the oracle by last bits of the same
+    float32 quantities, so the gate is 4 d_ref and the measured ratio is printed.  fd_nerf_scan against fd_nerf:
+    the header's 1e-9 of the chain's extent.  Both centred and not; two calls give the same bits; a chain gives the same bits
+    alone and inside the batch."""
+    worst_ratio, worst_scan = 0.0, 0.0
+    for centered in (0, 1):
+        for case in _domain_case(Fx, centered):
+            feats, lens = case["feats"], case["lens"]
+            serial, scan = _nerf(feats, lens, IDX[Fx], centered), _scan(feats, lens, IDX[Fx], centered)
+            assert np.array_equal(_f64bits(serial), _f64bits(_nerf(feats, lens, IDX[Fx], centered)))
+            assert np.array_equal(_f64bits(scan), _f64bits(_scan(feats, lens, IDX[Fx], centered)))
+            for b, n in enumerate(lens):
+                ref = gr.build_ref(feats[b, :n], IDX[Fx])
+                gate = rx.scan_gate(ref)
+                if centered:
+                    ref = ref - ref.mean(axis=0)
+                d_ref = np.abs(case["xyz64"][b, : 3 * n] - ref).max()
+                err = np.abs(serial[b, : 3 * n] - ref).max()
+                if d_ref > 0:
+                    worst_ratio = max(worst_ratio, err / d_ref)
+                assert err <= 4 * d_ref, (Fx, centered, n, err, d_ref)
+                err_scan = np.abs(scan[b, : 3 * n] - serial[b, : 3 * n]).max()
+                worst_scan = max(worst_scan, err_scan / gate * 1e-9)
+                assert err_scan <= gate, (Fx, centered, n, err_scan, gate)
+                assert (serial[b, 3 * n:] == 0).all() and (scan[b, 3 * n:] == 0).all()
+            if len(lens) > 1:                                                           # the 12-residue chain at index 4, alone
+                alone = feats[4:5].copy()
+                assert np.array_equal(_f64bits(_nerf(alone, [12], IDX[Fx], centered)[0]), _f64bits(serial[4]))
+                assert np.array_equal(_f64bits(_scan(alone, [12], IDX[Fx], centered)[0]), _f64bits(scan[4]))
+                args = (IDX[Fx], Fx, centered, case["g"][4:5], alone)
+                rc, one = _vjp_feats(serial[4:5], [12], *args)
+                rc2, batch = _vjp_feats(serial, lens, IDX[Fx], Fx, centered, case["g"], feats)
+                assert rc == 0 and rc2 == 0 and np.array_equal(_f64bits(one[0]), _f64bits(batch[4]))
+    print(f"F={Fx}: |fd_nerf - ref_nerf.build| is at most {worst_ratio:.3f} d_ref; fd_nerf_scan within {worst_scan:.2e} of the chain's extent of fd_nerf")
+
+
+@pytest.mark.parametrize("Fx", [6, 9])
+def test_vjp_feats_returns_fd_nerf_vjp_bits_where_every_sign_is_positive(gpu, Fx):
+    """random_features chains (sin(angle) > 0, lengths > 0): the new entry and fd_nerf_vjp agree bit for bit; on domain_features
+    they differ in sign exactly where the statement says and nowhere in magnitude."""
+    lens = [1, 2, 3, 7, 12, 86]
+    rng = np.random.default_rng(70 + Fx)
+    feats = np.zeros((len(lens), 86, Fx), dtype=np.float32)
+    for b, n in enumerate(lens):
+        feats[b, :n] = random_features(rng, n, Fx)
+    for centered in (0, 1):
+        coords = _nerf(feats, lens, IDX[Fx], centered)
+        g = rng.standard_normal(coords.shape)
+        rc, plain = _vjp(coords, lens, IDX[Fx], Fx, centered, g)
+        rc2, signed = _vjp_feats(coords, lens, IDX[Fx], Fx, centered, g, feats)
+        assert rc == 0 and rc2 == 0 and np.array_equal(_f64bits(plain), _f64bits(signed))
+    case = _domain_case(Fx, 0)[1]                                                       # 86 residues, signs of either kind
+    n = case["lens"][0]
+    rc, plain = _vjp(case["xyz64"], [n], IDX[Fx], Fx, 0, case["g"])
+    rc2, signed = _vjp_feats(case["xyz64"], [n], IDX[Fx], Fx, 0, case["g"], case["feats"])
+    assert rc == 0 and rc2 == 0 and np.array_equal(_f64bits(np.abs(plain)), _f64bits(np.abs(signed)))
+    f = case["feats"][0]
+    sl = np.where(f[:, 6:9] < 0, -1.0, 1.0) if Fx == 9 else np.ones((n, 3))
+    sa = np.where(np.sin(f[:, 3:6].astype(np.float64)) < 0, -1.0, 1.0) * sl[:, [2, 0, 1]]   # columns 3, 4, 5 go with lengths 8, 6, 7
+    want = plain[0].copy()
+    want[:, 3:6] *= sa
+    if Fx == 9:
+        want[:, 6:9] *= sl
+    assert np.array_equal(_f64bits(want + 0.0), _f64bits(signed[0] + 0.0)) and (sa < 0).sum() > n
+
+
+def test_python_gradients_on_the_whole_domain(gpu):
+    """nerf.coords_vjp with `angles` and build_backbones_torch's backward on chains with bond angles and lengths of either sign:
+    both are fd_nerf_vjp_feats' (within 1e-5 of autograd through the float64 restatement, the end-to-end gate)."""
+    case = _domain_case(9, 1)[0]
+    lens, feats = case["lens"], case["feats"]
+    rows = [feats[b, :n] for b, n in enumerate(lens)]
+    coords = nerf.build_backbones(rows, NAMES9, center_coords=True)
+    got = nerf.coords_vjp(coords, [case["g"][b, : 3 * n] for b, n in enumerate(lens)], NAMES9, centered=True, angles=rows)
+    ang = torch.tensor(feats, requires_grad=True)
+    xyz = nerf.build_backbones_torch(ang, lens, NAMES9, center_coords=True)
+    (xyz * torch.from_numpy(case["g"])).sum().backward()
+    for b, n in enumerate(lens):
+        want = case["want"][b, :n]
+        scale = max(np.abs(want).max(), 1e-300)
+        assert np.abs(got[b] - want).max() <= 1e-5 * scale, (b, n)
+        assert np.array_equal(_bits(ang.grad.numpy()[b, :n]), _bits(got[b].astype(np.float32))) and (ang.grad.numpy()[b, n:] == 0).all()
+
+
 # ---------------------------------------------------------------------------------- 6. the torch path
 def test_torch_backward_is_coords_vjp_and_agrees_with_autograd(gpu):
     lens, L = [12, 7, 2], 12
@@ -282,6 +468,64 @@ def test_guide_step_equals_the_statement(gpu):
         assert (clip < 1).any() and (clip == 1).any()
         rc, plain, _, _ = _guide_step(x, x0, LENS5, packed, 0.0, s=s, z=z, offset=OFFSET, is_angle=is_angle)
         assert rc == 0 and np.abs(got - plain)[ok].max() > 1e-3                         # ... and the step was taken
+
+
+def _device_G(x0, lens, per, packed):
+    """The G of the guide statement from the device's own entries: the shift on the host (one rounding, tests/guide_reference.py),
+    fd_nerf, fd_restraint_energy's gradient, fd_nerf_vjp_feats on the shifted rows."""
+    ang = np.zeros_like(x0)
+    for b, n in enumerate(lens):
+        ang[b, :n] = gr.shift(x0[b, :n], OFFSET, ANG)
+    coords = _nerf(ang, lens, IDX[6], 0)
+    rc, _, _, gc = _energy(coords, lens, packed)
+    assert rc == 0, _err()
+    rc, G = _vjp_feats(coords, lens, IDX[6], F, 0, gc, ang)
+    assert rc == 0, _err()
+    return ang, coords, G
+
+
+def test_guide_step_where_half_of_the_bond_angles_are_negative(gpu):
+    """_step_case with a random half of the rows of the shifted x0 re-parametrised as (-angle, wrap(torsion + pi)): the same
+    structures to about 1e-5 A, so the same energies and the same step on the torsions, but the bond-angle entries of G change
+    sign exactly in those rows (|dG| <= 1e-4 |G| on entries above 1e-3 of the chain's largest).  fd_guide_step against the
+    statement with the gates of test_guide_step_equals_the_statement: 2e-6 on x_out, 1e-9 on gnorm and energy.  A derivative
+    from the coordinates alone pushes those bond angles up the gradient."""
+    x, x0, per, packed = _step_case()
+    ok = _valid(LENS5, L_R)
+    rng = np.random.default_rng(35)
+    x0_neg, flipped = x0.copy(), np.zeros((5, L_R), dtype=bool)
+    for b, n in enumerate(LENS5):
+        flipped[b, :n] = rng.random(n) < 0.5
+        target = reparametrise(gr.shift(x0[b, :n], OFFSET, ANG), flipped[b, :n])
+        x0_neg[b, :n] = ref_sampling.wrap(torch.from_numpy(target - OFFSET)).numpy()
+    ang, coords, G = _device_G(x0, LENS5, per, packed)
+    ang_neg, coords_neg, G_neg = _device_G(x0_neg, LENS5, per, packed)
+    below = ok[:, :, 0]
+    share = (ang_neg[below][:, 3:] < 0).mean()
+    moved = np.abs(coords_neg - coords).max()
+    print(f"{share:.2f} of the bond angles negative; re-parametrising moves the atoms by at most {moved:.2e} A")
+    assert 0.3 < share < 0.7 and (ang[below][:, 3:] > 0).all() and moved <= 1e-4
+    compared = 0
+    for b, n in enumerate(LENS5):
+        big = np.abs(G[b, :n]) > 1e-3 * np.abs(G[b, :n]).max()
+        sign = np.ones((n, F))
+        sign[flipped[b, :n], 3:] = -1.0
+        assert (np.abs(G_neg[b, :n] - sign * G[b, :n])[big] <= 1e-4 * np.abs(G[b, :n])[big]).all(), b
+        compared += int(big[flipped[b, :n], 3:].sum())
+    assert compared >= 30
+    z = np.random.default_rng(34).standard_normal((5, L_R, F)).astype(np.float32)
+    for is_angle, c, s in ((ANG, 0.05, 0.0), (MIXED, 0.05, 0.3), (ANG, -0.2, 0.3)):
+        rc, got, e, gn = _guide_step(x, x0_neg, LENS5, packed, c, max_norm=1.0, s=s, z=z, offset=OFFSET, is_angle=is_angle)
+        assert rc == 0, _err()
+        want, we, wn, clip = gr.guide_step(x, x0_neg, LENS5, IDX[6], OFFSET, is_angle, per, c, 1.0, s=s, z=z, build=_fd_nerf_builder)
+        isang = np.asarray(is_angle, dtype=bool)
+        dist = np.where(isang, ref_sampling.circ_dist(got, want), np.abs(got.astype(np.float64) - want))[ok]
+        print(f"c={c} s={s}: max distance {dist.max():.2e}; energy rel {np.abs(e / we - 1).max():.2e}; gnorm rel {np.abs(gn / wn - 1).max():.2e}")
+        assert dist.max() <= 2e-6 and (got[~ok] == SENTINEL).all()
+        assert np.abs(e / we - 1).max() <= 1e-9 and np.abs(gn / wn - 1).max() <= 1e-9
+        # ... and the statement without the rows is somewhere else: the test tells the two derivatives apart
+        unsigned, *_ = gr.guide_step(x, x0_neg, LENS5, IDX[6], OFFSET, is_angle, per, c, 1.0, s=s, z=z, build=_fd_nerf_builder, signs=False)
+        assert np.where(isang, ref_sampling.circ_dist(got, unsigned), np.abs(got.astype(np.float64) - unsigned))[ok].max() > 1e-3
 
 
 # ---------------------------------------------------------------------------------- 9. descent on the device

@@ -15,6 +15,7 @@ import relax_reference as rx
 from conftest import REPO
 from foldingdiff_amd import _binding
 from foldingdiff_amd import build as fbuild
+from test_guide import DOMAIN_MODES, domain_features, reparametrise
 
 IDX = {3: np.array([0, 1, 2, -1, -1, -1, -1, -1, -1], np.int32), 6: np.array([0, 1, 2, 3, 4, 5, -1, -1, -1], np.int32),
        9: np.arange(9, dtype=np.int32)}
@@ -93,6 +94,60 @@ def test_energy_gradient_agrees_with_autograd(F):
     e0, g0, _, _ = rx.relax_energy(x, None, prm, fixed, rst)
     e1, g1, _, _ = rx.relax_energy(x, None, prm._replace(w_tether=0.0), fixed, rst)
     assert e0[2] == 0 and np.array_equal(g0, g1)
+
+
+@pytest.mark.parametrize("F", [3, 6, 9])
+def test_energy_gradient_agrees_with_autograd_on_the_whole_domain(F):
+    """The same check on tests/test_guide.py's domain_features: bond angles of either sign on both sides of pi / 2, lengths of
+    either sign.  The same gates.  (Not every term need be active here: chains with obtuse and acute angles do not always clash.)"""
+    for n in (2, 3, 7, 40):
+        for m, mode in enumerate(DOMAIN_MODES):
+            x, anchor, rst, prm, fixed = energy_case(n, F, 100 * F + n)
+            rng = np.random.default_rng(7000 * m + 100 * F + n)
+            x = domain_features(rng, n, F, mode)
+            anchor = (x + 0.05 * rng.standard_normal(x.shape)).astype(np.float32)
+            xyz64, e_want, g_want = autograd_energy(x, anchor, rst, prm, fixed, F)
+            scale = np.abs(g_want).max()
+            e_ref, g_ref, _, _ = rx.relax_energy(x, anchor, prm, fixed, rst, coords=gr.build_ref(x, IDX[F]))
+            e_own, g_own, gn_own, _ = rx.relax_energy(x, anchor, prm, fixed, rst, coords=xyz64)
+            _, g_unsigned, _, _ = rx.relax_energy(x, anchor, prm, fixed, rst, coords=xyz64, signs=False)
+            on_ref, on_own = np.abs(g_ref - g_want).max() / scale, np.abs(g_own - g_want).max() / scale
+            unsigned = np.abs(g_unsigned - g_want).max() / scale
+            print(f"F={F} len={n} {mode}: {on_ref:.2e} on ref_nerf's coordinates, {on_own:.2e} on the restatement's, {unsigned:.2e} without "
+                  f"the rows; E = {e_want}")
+            assert e_want[1] > 0 and e_want[2] > 0
+            assert on_ref <= 1e-5 and on_own <= 1e-12
+            assert np.allclose(e_own, e_want, rtol=1e-12, atol=0) and gn_own == np.sqrt((g_own * g_own).sum())
+            if F > 3 and mode != "backbone" and n >= 7:
+                assert unsigned > 0.1
+
+
+NEGATED_CHAINS = ((7, 0), (12, 1), (40, 2), (86, 3))     # (residues, seed)
+NEGATED_ITERS = 10
+
+
+def negated_angle_case(n, seed):
+    """energy_case's restraints on a backbone-like chain of six features whose every bond angle is negated and its torsion
+    moved by pi (the same chain): only the three bond-angle columns move, restraints only (w_clash = 0), no tether."""
+    x = reparametrise(random_features(np.random.default_rng(seed), n, 6), np.ones(n, dtype=bool))
+    last = 3 * n - 1
+    rst = ([0, 1], [last, last - 1], [1.0, 30.0], [0.1, 0.5], [RST_W, 1.0])
+    prm = rx.Params(IDX[6], [True] * 6, [False] * 3 + [True] * 3, w_clash=0.0, w_tether=0.0)
+    return x, rst, prm
+
+
+@pytest.mark.parametrize("n,seed", NEGATED_CHAINS)
+def test_only_the_signed_gradient_descends_on_negated_bond_angles(n, seed):
+    """The chains of tests/test_relax_gpu.py's descent on negated bond angles: within 10 iterations the statement accepts at
+    least one step and ends below its start; with every sign taken as +1 (the derivative from the coordinates alone) the
+    bond-angle gradient points uphill, every trial rises and nothing is accepted."""
+    x, rst, prm = negated_angle_case(n, seed)
+    assert (x[:, 3:] < 0).all()
+    _, _, trace, accepted, _ = rx.relax(x, None, prm, NEGATED_ITERS, rst=rst)
+    _, _, trace_u, accepted_u, h_u = rx.relax(x, None, prm, NEGATED_ITERS, rst=rst, signs=False)
+    print(f"{n} residues (seed {seed}): E {trace[0]:.4f} -> {trace[-1]:.4f}, {accepted} accepted; without the signs {accepted_u} accepted")
+    assert accepted >= 1 and trace[-1] < trace[0]
+    assert accepted_u == 0 and trace_u[-1] == trace_u[0] and h_u == prm.step0 * prm.shrink ** NEGATED_ITERS
 
 
 # ---------------------------------------------------------------------------------- 2. the scan against the oracle

@@ -13,7 +13,7 @@ import pytest
 import relax_reference as rx
 from conftest import GOLDEN, REPO
 from foldingdiff_amd import _binding, nerf, structures
-from test_relax import IDX, random_features
+from test_relax import IDX, NEGATED_CHAINS, NEGATED_ITERS, negated_angle_case, random_features
 
 pytestmark = pytest.mark.gpu
 
@@ -258,6 +258,30 @@ def test_fixed_rows_and_immovable_columns_keep_their_bits_and_a_tether_holds_bac
     for b, n in enumerate(lens):
         assert np.array_equal(bits(same[b, :n]), bits(feats[b, :n]))
     assert (acc0 == 0).all() and np.array_equal(bits(e_same), bits(hook(feats, lens, prm)[0])) and np.array_equal(bits(tr0[0]), bits(descent["run"][2][0]))
+
+
+def test_descent_on_negated_bond_angles_needs_the_signed_derivative(gpu):
+    """Backbone-like chains of 7, 12, 40 and 86 residues with every bond angle negated and its torsion moved by pi (the same
+    chains), restraints only, only the three bond-angle columns free, 10 iterations: every chain accepts at least one step and
+    ends below its start.  With the bond-angle gradient negated -- the derivative from the coordinates alone -- every trial
+    rises and nothing is accepted: tests/test_relax.py shows on the CPU that the statement accepts 7, 7, 4 and 2 steps on these
+    seeds and the unsigned one none.  The hook's gradient agrees with the statement on the device's coordinates within 1e-9 of
+    the chain's largest entry, zero in the torsion columns."""
+    cases = [negated_angle_case(n, seed) for n, seed in NEGATED_CHAINS]
+    prm = cases[0][2]
+    feats, lens = pad([c[0] for c in cases], fill=55.0)
+    rst = [c[1] for c in cases]
+    e, gn, G = hook(feats, lens, prm, rst=rst)
+    coords = build("fd_nerf_scan", feats, lens, IDX[6], 0)
+    for b, n in enumerate(lens):
+        e_want, g_want, gn_want, _ = rx.relax_energy(cases[b][0], None, prm, None, rst[b], coords=coords[b, : 3 * n])
+        assert np.abs(G[b, :n] - g_want).max() <= 1e-9 * np.abs(g_want).max() and abs(gn[b] - gn_want) <= 1e-9 * gn_want
+        assert (G[b, :n, :3] == 0).all() and (G[b, : n - 1, 3:] != 0).all() and e[b, 0] == 0 and e[b, 2] == 0 and e[b, 1] > 0
+    out, e_out, trace, acc, _ = relax(feats, lens, prm, NEGATED_ITERS, rst=rst)
+    print(f"E {trace[0].round(3).tolist()} -> {trace[-1].round(3).tolist()}; accepted {acc.tolist()}")
+    assert (acc >= 1).all() and (trace[-1] < trace[0]).all() and (np.diff(trace, axis=0) <= 0).all()
+    for b, n in enumerate(lens):
+        assert np.array_equal(bits(out[b, :n, :3]), bits(feats[b, :n, :3])) and (out[b, n:] == -7).all()
 
 
 # ---------------------------------------------------------------------------------- 4. end to end
