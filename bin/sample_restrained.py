@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """
-Sample backbones toward distance restraints (sampling.guide): residue pairs that should be in contact
+Sample backbones toward distance restraints (sampling.guide; with ``--hold_motif`` sampling.scaffold_segments, 6y): residue pairs that should be in contact
 (``--contacts``), and / or the residues of a motif, which need not be contiguous, that should sit relative to each other as
 they do in a PDB file (``--motif_pdb --motif_residues --placed_at``).  After every visit of the few-step sampler the predicted
 backbone is built on the device and the state takes a clipped step down the gradient of the restraint energy.  The model and
@@ -19,6 +19,12 @@ output arguments are bin/sample.py's:
 structure from its mirror image, so a low energy with a high RMSD is possible.  A restraint that does not fit ``--length``, or
 a length beyond the model's padded length, is a usage error before the model is loaded or anything is written.  The model
 must be a local directory, as for bin/sample.py.  Single device.
+
+``--hold_motif`` (needs ``--motif_pdb``): every range of ``--motif_residues`` is HELD by replacement -- its angle rows are fixed
+to the file's, so its backbone is reproduced exactly -- and the restraints are kept between residues of different ranges only,
+which places the ranges relative to each other.  ``--clash_weight W`` adds the relaxer's soft clash term, weighted by W, to the
+energy whose gradient is followed; the report then also holds ``clash_energy``.  Without these two flags the script does what
+it did before them.
 """
 import argparse
 import json
@@ -45,6 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--motif_pdb", type=str, default=None, help="PDB file the motif's residues are taken from")
     parser.add_argument("--motif_residues", type=str, default=None, help="residues of the file by position, e.g. 3-9,20-27")
     parser.add_argument("--placed_at", type=str, default=None, help="per range, the index its first residue takes, e.g. 10,40")
+    parser.add_argument("--hold_motif", action="store_true",
+                        help="hold every range of --motif_residues by replacement and restrain across ranges only")
+    parser.add_argument("--clash_weight", type=float, default=None, help="weight of the soft clash term inside the guided run")
     parser.add_argument("--scale", type=float, default=1.0, help="guidance scale; 0 is the unguided sampler")
     parser.add_argument("--max_norm", type=float, default=1.0, help="clip of a backbone's gradient norm")
     parser.add_argument("--guide_from", type=int, default=None, help="guide only the visits at or below this timestep (default: all)")
@@ -90,6 +99,10 @@ def main(argv=None) -> None:
     motif_args = (args.motif_pdb, args.motif_residues, args.placed_at)
     if any(a is not None for a in motif_args) and any(a is None for a in motif_args):
         parser.error("--motif_pdb, --motif_residues and --placed_at go together")
+    if args.hold_motif and args.motif_pdb is None:
+        parser.error("--hold_motif holds the ranges of a motif: give --motif_pdb, --motif_residues and --placed_at")
+    if args.clash_weight is not None and not args.clash_weight >= 0:
+        parser.error(f"--clash_weight {args.clash_weight} must be >= 0")
     if args.contacts is None and args.motif_pdb is None:
         parser.error("nothing to aim at: give --contacts and / or a motif")
     outdir = Path(args.outdir)
@@ -104,7 +117,7 @@ def main(argv=None) -> None:
 
     from foldingdiff_amd import structures
 
-    restraints, motif_ca, placed = None, None, None
+    restraints, motif_ca, placed, segments, file_xyz = None, None, None, None, None
     try:
         if args.contacts is not None:
             restraints = structures.contact_restraints(read_contacts(args.contacts), weight=args.weight)
@@ -123,8 +136,16 @@ def main(argv=None) -> None:
                 raise ValueError(f"{args.motif_pdb} has {len(xyz)} residues, --motif_residues asks for residue {max(picked)}")
             motif = xyz[picked].reshape(-1, 3)
             motif_ca = xyz[picked, 1]
-            m = structures.motif_restraints(motif, placed, weight=args.weight)
+            if args.hold_motif:   # (the ranges of the file are the segments; sampling.scaffold_segments repeats these checks)
+                segments = [(rng[0], rng[-1] + 1, s) for rng, s in zip(ranges, starts)]
+                file_xyz = xyz.reshape(-1, 3)
+                m = structures.segment_restraints(file_xyz, segments, weight=args.weight)
+            else:
+                m = structures.motif_restraints(motif, placed, weight=args.weight)
+            contacts = restraints
             restraints = m if restraints is None else restraints + m
+            if max(placed) >= args.length:
+                raise ValueError(f"the motif is placed up to residue {max(placed)}, --length is {args.length}")
         if restraints.min_length() > args.length:
             raise ValueError(f"the restraints need {restraints.min_length()} residues, --length is {args.length}")
     except ValueError as e:
@@ -146,9 +167,26 @@ def main(argv=None) -> None:
     device = torch.device(args.device)
     model = modelling.BertForDiffusionBase.from_dir(args.model, copy_to=str(outdir / "model_snapshot")).to(device)
     torch.manual_seed(args.seed)
-    sampled, info = sampling.guide(model, train_dset, [args.length] * args.num, restraints, num_steps=args.num_steps, eta=args.eta,
-                                   scale=args.scale, max_norm=args.max_norm, guide_from=args.guide_from, batch_size=args.batchsize)
     names = train_dset.feature_names["angles"]
+    guide_args = dict(num_steps=args.num_steps, eta=args.eta, scale=args.scale, max_norm=args.max_norm, guide_from=args.guide_from,
+                      batch_size=args.batchsize)
+    lengths = [args.length] * args.num
+    if args.hold_motif:
+        feats = structures.featurize([args.motif_pdb], distances=[n for n in names if n.count(":") == 1],
+                                     angles=[n for n in names if n.count(":") != 1], device=device.index or 0)[0]
+        if feats is None:
+            raise AssertionError(f"{args.motif_pdb}: no usable backbone")
+        motif_angles = feats[list(names)].values.astype(np.float32)
+        if not np.isfinite(motif_angles[picked]).all():
+            raise AssertionError(f"--motif_residues of {args.motif_pdb} hold an undefined angle (a chain end?)")
+        sampled, info = sampling.scaffold_segments(model, train_dset, motif_angles, file_xyz, segments, lengths, restraints=contacts,
+                                                   restraint_weight=args.weight, clash_weight=args.clash_weight or 0.0, **guide_args)
+    elif args.clash_weight is not None:   # guidance with the clash term and nothing held
+        free = [np.full((args.length, len(names)), np.nan, dtype=np.float32)] * args.num
+        sampled, info = sampling.guide_inpaint(model, train_dset, free, [np.zeros(args.length, dtype=bool)] * args.num, restraints,
+                                               clash_weight=args.clash_weight, **guide_args)
+    else:
+        sampled, info = sampling.guide(model, train_dset, lengths, restraints, **guide_args)
     sampled_dfs = [pd.DataFrame(s, columns=names) for s in sampled]
     sampled_angles_folder = outdir / "sampled_angles"
     os.makedirs(sampled_angles_folder, exist_ok=True)
@@ -161,6 +199,8 @@ def main(argv=None) -> None:
     report = {"settings": vars(args), "length": args.length, "n_restraints": len(restraints),
               "energy": {os.path.basename(pdb_files[i]): float(info["energy"][i]) for i in kept},
               "max_violation": {os.path.basename(pdb_files[i]): float(info["max_violation"][i]) for i in kept}}
+    if "clash_energy" in info:
+        report["clash_energy"] = {os.path.basename(pdb_files[i]): float(info["clash_energy"][i]) for i in kept}
     if motif_ca is not None:
         ca_rows = [3 * p + 1 for p in placed]
         rmsd = structures.superposed_rmsd([coords[i][ca_rows] for i in kept], [motif_ca] * len(kept), device=device.index or 0)

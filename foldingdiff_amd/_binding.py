@@ -63,6 +63,19 @@ class FdGuideParams(C.Structure):
     ]
 
 
+class FdScaffoldGuideParams(C.Structure):
+    """``fd_scaffold_guide_params`` of include/fdmi.h."""
+    _fields_ = [
+        ("feat_idx", C.c_int32 * 9),
+        ("has_offset", C.c_int32),
+        ("offset", C.c_float * 16),
+        ("max_norm", C.c_double),
+        ("clash_alpha", C.c_double),
+        ("clash_margin", C.c_double),
+        ("w_clash", C.c_double),
+    ]
+
+
 class FdRelaxParams(C.Structure):
     """``fd_relax_params`` of include/fdmi.h."""
     _fields_ = [
@@ -131,6 +144,10 @@ _SIGNATURES = {
                                 C.c_float, _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P]),
     "fd_sample_guided": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.c_int64, _P, C.POINTER(FdGuideParams),
                                    _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_scaffold_guide_step": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(FdScaffoldGuideParams), _P, _P, _P,
+                                         _P, _P, _P, C.c_float, C.c_float, _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
+    "fd_sample_guided_inpaint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int64, _P,
+                                           C.POINTER(FdScaffoldGuideParams), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fd_nerf_scan": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "fd_relax_energy": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(FdRelaxParams), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                   _P]),

@@ -1,6 +1,6 @@
 // C-ABI host side of libfdmi.so, the entries that run a model: the forwards, the denoising losses, the autoregressive sampler,
 // single reverse steps, the sampling runs (plain, motif-conditioned, resampled, strided, strided and conditioned, solver, steered,
-// repeat, guided) and their device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry
+// repeat, guided, guided and conditioned) and their device-buffer pieces.  Host code around api.hip's workspace, launch plan and step (model.h) only: every entry
 // checks its arguments before its first HIP call, and the paragraphs the entries share are written once, below: make the
 // workspace current and upload (open_call), download and synchronise (finish), the one-copy staging of the loss entries
 // (PackedUpload), one reverse step from host arrays (host_step), the owner of a run from host arrays (HostRun: stage, begin,
@@ -891,6 +891,95 @@ int guided_host_run(fd_model* m, const GuidedHostRun& a) {
   return r.finish(rc, {{a.energy_out, d_energy, nb * 8}, {a.max_violation_out, d_maxv, nb * 8}});
 }
 
+// ---- restraint guidance with replacement: guided_host_run with strided_host_run's conditioning in the same
+// per-run values -- a visit's fixed elements take update_element's fixed branch, its free ones leave wrap(a x + b eps) and
+// their x0 -- and the scaffold-guide statement's launches (guide_scaffold.hip) behind every visit.  The entry has checked every
+// argument; a.states = K, final state only.  The tables, the restraints and the work buffers die with this frame.
+struct ScaffoldGuidedHostRun {
+  RunArrays arrays;  // known_noise row 0: the start point, row i + 1: the state visit i leaves
+  const int32_t* visits;
+  const float* coef;   // [5][K] a | b | s | u | v
+  const float* guide;  // [K]
+  InpaintHost cond;
+  const fd_scaffold_guide_params* params;
+  RestraintLists rst;
+  double *energy_out, *max_violation_out;  // [B][2], [B]
+};
+
+int scaffold_guided_host_run(fd_model* m, const ScaffoldGuidedHostRun& a) {
+  const RunArrays& h = a.arrays;
+  const int F = m->cfg.n_features, B = h.B, L = h.L, K = (int)h.states;
+  const size_t na = (size_t)B * 3 * L * 3, nb = (size_t)B, Kz = h.states, R = a.rst.count();
+  const fd_scaffold_guide_params& gp = *a.params;
+  HostRun r(m, h);
+  if (int rc = r.stage()) return rc;
+  const size_t n = r.n;
+  DeviceBufs& bufs = r.bufs;
+  VisitTables tb;
+  if (int rc = stage_tables(m, &bufs, a.visits, K, {a.coef, a.coef + Kz, nullptr, a.coef + 3 * Kz, a.coef + 4 * Kz}, &tb)) return rc;
+  float* d_x0;
+  double *d_G, *d_gnorm;
+  ScaffoldWork wk{};
+  HIP_TRY(bufs.zeros(n * 4, &d_x0));  // (a fixed element and a position beyond a length are never written, and never read)
+  HIP_TRY(bufs.alloc(n * 4, &wk.ang));
+  HIP_TRY(bufs.alloc(na * 8, &wk.coords));
+  HIP_TRY(bufs.alloc(na * 8, &wk.gc));
+  HIP_TRY(bufs.alloc(n * 8, &d_G));
+  HIP_TRY(bufs.alloc(nb * 8, &wk.e_rst));
+  HIP_TRY(bufs.alloc(nb * 8, &wk.max_violation));
+  HIP_TRY(bufs.zeros(nb * 8, &wk.e_clash));  // (stays 0 where there is no clash term)
+  HIP_TRY(bufs.alloc(nb * 8, &d_gnorm));
+  Restraints rs{};  // (an empty list: the kernel reads the offsets only)
+  HIP_TRY(bufs.upload(a.rst.offsets, (nb + 1) * 4, &rs.offsets));
+  if (R) {
+    HIP_TRY(bufs.upload(a.rst.i, R * 4, &rs.i));
+    HIP_TRY(bufs.upload(a.rst.j, R * 4, &rs.j));
+    HIP_TRY(bufs.upload(a.rst.d0, R * 8, &rs.d0));
+    HIP_TRY(bufs.upload(a.rst.tol, R * 8, &rs.tol));
+    HIP_TRY(bufs.upload(a.rst.w, R * 8, &rs.w));
+  }
+  const NerfFeatures fx{gp.feat_idx[0], gp.feat_idx[1], gp.feat_idx[2], gp.feat_idx[3], gp.feat_idx[4],
+                        gp.feat_idx[5], gp.feat_idx[6], gp.feat_idx[7], gp.feat_idx[8]};
+  SteerOffset off{};
+  off.has_offset = gp.has_offset ? 1 : 0;
+  for (int f = 0; gp.has_offset && f < F; ++f) off.offset[f] = gp.offset[f];
+  const SoftClash clash{gp.clash_alpha, gp.clash_margin, gp.w_clash};
+
+  if (int rc = r.begin(a.visits[0], K)) return rc;
+  hipStream_t s = m->stream;
+  Workspace& w = m->ws;
+  tb.apply(&m->dyn_host);
+  m->dyn_host.uv = tb.row(3);
+  m->dyn_host.x0_steer = d_x0;
+  InpaintDev ip;  // the start point enters visit 0, so it is at level visits[0] + 1; its draws are row 0
+  int rc = begin_conditioning(m, s, a.cond, h, a.visits[0] + 1, r.known_noise, r.known_noise, &ip);
+  auto launched = [&]() -> int {
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? fail(FD_E_HIP, "the scaffold-guide launches: %s", hipGetErrorString(e)) : FD_OK;
+  };
+  for (int i = 0; !rc && i < K; ++i) {
+    rc = fd_sample_steps_dev(m, 1, nullptr, 0, nullptr);
+    if (rc) break;
+    launch_scaffold_energy(d_x0, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, wk, d_G, s);
+    launch_scaffold_update(w.x, d_G, ip.fixed, w.lens, B, L, F, m->angle_mask, a.guide[i], gp.max_norm, a.coef[2 * Kz + i],
+                           r.noise ? r.noise + (size_t)i * r.n : nullptr, h.seed, a.visits[i], h.seq_offset, d_gnorm, s);
+    rc = launched();
+  }
+  if (!rc) {  // the final state's: its fixed elements hold known's bits, so p is the state itself
+    launch_scaffold_energy(w.x, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, wk, nullptr, s);
+    rc = launched();
+  }
+  std::vector<double> e_rst(nb), e_clash(nb), maxv(nb);
+  rc = r.finish(rc, {{e_rst.data(), wk.e_rst, nb * 8}, {e_clash.data(), wk.e_clash, nb * 8}, {maxv.data(), wk.max_violation, nb * 8}});
+  if (rc && rc != FD_E_NONFINITE) return rc;  // (a run that answers FD_E_NONFINITE has written its outputs, as every family's)
+  for (size_t b = 0; b < nb; ++b) {
+    a.energy_out[2 * b] = e_rst[b];
+    a.energy_out[2 * b + 1] = e_clash[b];
+    a.max_violation_out[b] = maxv[b];
+  }
+  return rc;
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -1405,6 +1494,28 @@ int fd_sample_guided(fd_model* m, const float* x_init, const int32_t* lens, int 
   if (int rc = check_restraints(rl, lens)) return rc;
   return guided_host_run(m, GuidedHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, nullptr, seed, seq_offset, out, 0}, visits, coef,
                                           guide, params, rl, energy_out, max_violation_out});
+}
+
+int fd_sample_guided_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                             const float* coef, const float* noise, const float* known, const uint8_t* fixed, const float* known_coef,
+                             const float* known_noise, uint64_t seed, int64_t seq_offset, const float* guide,
+                             const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                             const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float* out,
+                             double* energy_out, double* max_violation_out) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;  // (rows a | b | s too)
+  if (int rc = check_coef_rows(coef, n_visits, 3, 5)) return rc;
+  if (!guide || !params) return fail(FD_E_INVALID, "null argument: guide and params are required");
+  if (!energy_out || !max_violation_out) return fail(FD_E_INVALID, "null argument: energy_out and max_violation_out are required");
+  for (int i = 0; i < n_visits; ++i)
+    if (!std::isfinite(guide[i])) return fail(FD_E_INVALID, "guide[%d] = %g is not finite", i, (double)guide[i]);
+  if (int rc = check_guide_shape(lens, B, L, m->cfg.n_features, params->feat_idx)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  if (int rc = check_scaffold_guide(*params, known, fixed, lens, B, L, m->cfg.n_features)) return rc;
+  const RestraintLists rl{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
+  if (int rc = check_restraints(rl, lens)) return rc;
+  return scaffold_guided_host_run(m, ScaffoldGuidedHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, known_noise, seed, seq_offset, out, 0},
+                                                           visits, coef, guide, {known, fixed, known_coef}, params, rl, energy_out,
+                                                           max_violation_out});
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

@@ -1,5 +1,5 @@
 // C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, dssp.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
-// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip), of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip) and of the torsion-space relaxer (nerf_scan.hip, relax.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip), of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip), of the torsion-space relaxer (nerf_scan.hip, relax.hip) and of the scaffold-guide step (guide_scaffold.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
 #include <cstring>
@@ -141,6 +141,94 @@ int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t*
   if (rc) return rc;
   for (int b = 0; b < B; ++b)
     memcpy(x_out + (size_t)b * L * F, state_host.data() + (size_t)b * L * F, (size_t)lens[b] * F * 4);
+  return FD_OK;
+}
+
+int fd_scaffold_guide_step(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                           const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                           const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                           const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float c, float s,
+                           const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
+                           double* max_violation_out, double* gnorm_out, double* dfeats_out) {
+  if (!x || !x0 || !lens || !is_angle || !params || !x_out || !energy_out || !max_violation_out || !gnorm_out)
+    return fail(FD_E_INVALID, "null argument");
+  if (!known) return fail(FD_E_INVALID, "known is null");
+  if (!fixed) return fail(FD_E_INVALID, "fixed is null");
+  if (int rc = check_guide_shape(lens, B, L, F, params->feat_idx)) return rc;
+  const RestraintLists rl{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
+  if (int rc = check_restraints(rl, lens)) return rc;
+  if (!std::isfinite(c)) return fail(FD_E_INVALID, "c = %g is not finite", (double)c);
+  if (!std::isfinite(s)) return fail(FD_E_INVALID, "s = %g is not finite", (double)s);
+  if (int rc = check_scaffold_guide(*params, known, fixed, lens, B, L, F)) return rc;
+  if (int rc = check_rows_finite("x", x, lens, B, L, F)) return rc;
+  for (int b = 0; b < B; ++b)  // (x0 is not read where fixed)
+    for (size_t o = (size_t)b * L * F; o < ((size_t)b * L + lens[b]) * F; ++o)
+      if (!fixed[o] && !std::isfinite(x0[o]))
+        return fail(FD_E_INVALID, "x0 is not finite at a free element: sequence %d, position %d", b, (int)(o / F - (size_t)b * L));
+  const fd_scaffold_guide_params& p = *params;
+  const NerfFeatures fx{p.feat_idx[0], p.feat_idx[1], p.feat_idx[2], p.feat_idx[3], p.feat_idx[4], p.feat_idx[5], p.feat_idx[6], p.feat_idx[7], p.feat_idx[8]};
+  SteerOffset off{};
+  off.has_offset = p.has_offset ? 1 : 0;
+  unsigned angle_mask = 0;
+  for (int f = 0; f < F; ++f) {
+    if (p.has_offset) off.offset[f] = p.offset[f];
+    if (is_angle[f]) angle_mask |= 1u << f;
+  }
+  const SoftClash clash{p.clash_alpha, p.clash_margin, p.w_clash};
+  const RestraintInputs ri = restraint_inputs(rl);
+  const size_t n = (size_t)B * L * F, na = (size_t)B * 3 * L * 3, nb = (size_t)B;
+  const bool draws = s != 0.f && z;  // (the slab is read only then)
+  HIP_TRY(hipSetDevice(device_id));
+  DeviceBufs bufs;
+  float* state;
+  const float *x0_dev, *known_dev, *z_dev = nullptr;
+  const unsigned char* fixed_dev;
+  const int* lens_dev;
+  Restraints rs{};
+  ScaffoldWork wk{};
+  double *G, *gnorm;
+  HIP_TRY(bufs.upload(x, n * 4, &state));
+  HIP_TRY(bufs.upload(x0, n * 4, &x0_dev));
+  HIP_TRY(bufs.upload(known, n * 4, &known_dev));
+  HIP_TRY(bufs.upload(fixed, n, &fixed_dev));
+  HIP_TRY(bufs.upload(lens, nb * 4, &lens_dev));
+  if (draws) HIP_TRY(bufs.upload(z, n * 4, &z_dev));
+  HIP_TRY(bufs.upload(ri.offsets.first, ri.offsets.second, &rs.offsets));
+  HIP_TRY(bufs.upload(ri.i.first, ri.i.second, &rs.i));
+  HIP_TRY(bufs.upload(ri.j.first, ri.j.second, &rs.j));
+  HIP_TRY(bufs.upload(ri.d0.first, ri.d0.second, &rs.d0));
+  HIP_TRY(bufs.upload(ri.tol.first, ri.tol.second, &rs.tol));
+  HIP_TRY(bufs.upload(ri.w.first, ri.w.second, &rs.w));
+  HIP_TRY(bufs.alloc(n * 4, &wk.ang));
+  HIP_TRY(bufs.alloc(na * 8, &wk.coords));
+  HIP_TRY(bufs.alloc(na * 8, &wk.gc));
+  HIP_TRY(bufs.alloc(nb * 8, &wk.e_rst));
+  HIP_TRY(bufs.alloc(nb * 8, &wk.max_violation));
+  HIP_TRY(bufs.zeros(nb * 8, &wk.e_clash));  // (stays 0 where there is no clash term)
+  HIP_TRY(bufs.alloc(n * 8, &G));
+  HIP_TRY(bufs.alloc(nb * 8, &gnorm));
+  launch_scaffold_energy(x0_dev, known_dev, fixed_dev, lens_dev, B, L, F, off, angle_mask, fx, rs, clash, wk, G, nullptr);
+  launch_scaffold_update(state, G, fixed_dev, lens_dev, B, L, F, angle_mask, c, p.max_norm, s, z_dev, seed, t, seq_offset, gnorm, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<float> state_host(n);
+  std::vector<double> grad_host(dfeats_out ? n : 0), e_rst(nb), e_clash(nb), maxv(nb), norm(nb);
+  HIP_TRY(hipMemcpy(state_host.data(), state, n * 4, hipMemcpyDeviceToHost));
+  if (dfeats_out) HIP_TRY(hipMemcpy(grad_host.data(), G, n * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(e_rst.data(), wk.e_rst, nb * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(e_clash.data(), wk.e_clash, nb * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(maxv.data(), wk.max_violation, nb * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(norm.data(), gnorm, nb * 8, hipMemcpyDeviceToHost));
+  // every download has succeeded: only now are the outputs written (the rows at or beyond a length keep what they held)
+  for (int b = 0; b < B; ++b) {
+    const size_t o = (size_t)b * L * F, rows = (size_t)lens[b] * F;
+    memcpy(x_out + o, state_host.data() + o, rows * 4);
+    if (dfeats_out) memcpy(dfeats_out + o, grad_host.data() + o, rows * 8);
+    energy_out[2 * b] = e_rst[b];
+    energy_out[2 * b + 1] = e_clash[b];
+    max_violation_out[b] = maxv[b];
+    gnorm_out[b] = norm[b];
+  }
   return FD_OK;
 }
 

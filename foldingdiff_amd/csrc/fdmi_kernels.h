@@ -313,6 +313,29 @@ struct RelaxStep {
 };
 void launch_relax_step(const RelaxStep& a, int B, hipStream_t s);
 
+// ---- restraint guidance combined with replacement (guide_scaffold.hip; the statement is in its header and in include/fdmi.h).
+// One 256-lane workgroup per chain; known / fixed [B][L][F] (fixed: bytes), lens[b] <= kGuideMaxLen, checked by the host.
+// ang [B][L][F] <- launch_steer_shift's statement on p = fixed ? known : x0 (x0 is not read where fixed); 0 at or beyond a length
+void launch_scaffold_shift(const float* x0, const float* known, const unsigned char* fixed, const int* lens, int B, int L, int F,
+                           const SteerOffset& off, unsigned angle_mask, float* ang, hipStream_t s);
+// launch_guide_update with a mask: G <- 0 where fixed (in place), gnorm [B] <- |G_b|, and only the free elements move and draw
+void launch_scaffold_update(float* x, double* G, const unsigned char* fixed, const int* lens, int B, int L, int F, unsigned angle_mask,
+                            float c, double max_norm, float s, const float* z, unsigned long long seed, int t, long long seq_offset,
+                            double* gnorm, hipStream_t st);
+struct SoftClash {
+  double alpha, margin, w;     // launch_soft_clash's; w == 0: no clash launch, alpha and margin unread
+};
+struct ScaffoldWork {
+  float* ang;                  // [B][L][F] the shifted rows the structure is built from
+  double *coords, *gc;         // [B][3L][3] the structure and the energy's gradient on it
+  double *e_rst, *max_violation, *e_clash;  // [B]; e_clash is written only where clash.w > 0
+};
+// the statement up to G: shift, launch_nerf_scan, launch_restraint_energy, launch_soft_clash (clash.w > 0) and, unless G is null,
+// launch_nerf_vjp on the shifted rows -> G [B][L][F], unmasked
+void launch_scaffold_energy(const float* x0, const float* known, const unsigned char* fixed, const int* lens, int B, int L, int F,
+                            const SteerOffset& off, unsigned angle_mask, const NerfFeatures& fx, const Restraints& rs,
+                            const SoftClash& clash, const ScaffoldWork& wk, double* G, hipStream_t s);
+
 // *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);
 

@@ -315,4 +315,23 @@ inline int check_guide_scalars(double max_norm, const float* offset, int F) {
   return FD_OK;
 }
 
+// what fd_scaffold_guide_step and fd_sample_guided_inpaint ask beyond fd_guide_step's checks (check_lens has passed; known and
+// fixed are not null): the statement's scalars, nothing fixed at or beyond a length, known finite where fixed
+inline int check_scaffold_guide(const fd_scaffold_guide_params& p, const float* known, const uint8_t* fixed, const int32_t* lens,
+                                int B, int L, int F) {
+  if (int rc = check_guide_scalars(p.max_norm, p.has_offset ? p.offset : nullptr, F)) return rc;
+  const struct { const char* name; double v; } clash[] = {{"clash_alpha", p.clash_alpha}, {"clash_margin", p.clash_margin}, {"w_clash", p.w_clash}};
+  for (const auto& w : clash)
+    if (!(w.v >= 0.0) || !std::isfinite(w.v)) return fail(FD_E_INVALID, "%s=%g must be >= 0 and finite", w.name, w.v);
+  for (int b = 0; b < B; ++b)
+    for (int l = 0; l < L; ++l)
+      for (int f = 0; f < F; ++f) {
+        const size_t o = ((size_t)b * L + l) * F + f;
+        if (!fixed[o]) continue;
+        if (l >= lens[b]) return fail(FD_E_INVALID, "fixed element beyond a length: sequence %d position %d feature %d, lens[%d] = %d", b, l, f, b, lens[b]);
+        if (!std::isfinite(known[o])) return fail(FD_E_INVALID, "known is not finite at a fixed element: sequence %d position %d feature %d", b, l, f);
+      }
+  return FD_OK;
+}
+
 }  // namespace fdmi

@@ -25,17 +25,16 @@
 //
 // guide_update_kernel.  |G_b| over the rows below the length (lane-strided squares, the fixed tree), the clip factor, then per
 // element x - float32(c k G) where c != 0 and repeat_tie.hip's + s z and wrap of an untied element, with the same draw.
+#include "block_sum.h"
 #include "fdmi_kernels.h"
-#include "philox_normal.h"
-#include "strided_update.h"
-#include "wrap_pi.h"
+#include "guide_element.h"
 
 namespace fdmi {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kChainThreads;
+constexpr int kWaves = kChainWaves;
 
 struct V3 {
   double x, y, z;
@@ -50,28 +49,7 @@ __device__ __forceinline__ V3 unit(V3 a) {
 }
 __device__ __forceinline__ V3 load3(const double* p, int k) { return {p[3 * k], p[3 * k + 1], p[3 * k + 2]}; }
 
-// lane i of a wave ends with v_i + v_{i+1} + ... + v_63, by a doubling tree whose shape does not depend on the data
-__device__ __forceinline__ double wave_suffix(double v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_down(v, d, 64);
-    if (lane + d < 64) v += o;
-  }
-  return v;
-}
-
-// the sum of v over the workgroup, the same bits in every lane; `slot` holds kWaves doubles and is free again on return
-__device__ __forceinline__ double block_sum(double v, double* slot) {
-  const double s = wave_suffix(v);
-  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = s;
-  __syncthreads();
-  double total = slot[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) total += slot[w];
-  __syncthreads();
-  return total;
-}
+// (wave_suffix and block_sum, the workgroup's sum in every lane: block_sum.h)
 
 // the sum of v over the lanes BEHIND this one (exclusive suffix over the workgroup)
 __device__ __forceinline__ double block_suffix_excl(double v, double* slot) {
@@ -208,11 +186,6 @@ __global__ __launch_bounds__(kThreads) void restraint_kernel(const double* __res
   }
 }
 
-__device__ __forceinline__ float guide_sub(float x, float step) {
-#pragma clang fp contract(off)
-  return x - step;
-}
-
 __global__ __launch_bounds__(kThreads) void guide_update_kernel(float* __restrict__ x, const double* __restrict__ G,
                                                                 const int* __restrict__ lens, int L, int F, unsigned angle_mask,
                                                                 float c, double max_norm, float s, const float* __restrict__ z,
@@ -230,11 +203,7 @@ __global__ __launch_bounds__(kThreads) void guide_update_kernel(float* __restric
   for (int e = tid; e < ne; e += kThreads) {
     const size_t o = base + e;
     const int l = e / F, f = e % F;
-    float m = x[o];
-    if (c != 0.f) m = guide_sub(m, (float)(ck * G[o]));
-    if (s != 0.f) m = strided_add_noise(m, s, z ? z[o] : philox_normal(seed, t, seq_offset + b, l, f));
-    if ((angle_mask >> f) & 1u) m = wrap_pi(m);
-    x[o] = m;
+    x[o] = guide_move(x[o], c, ck, G[o], s, z, o, seed, t, seq_offset + b, l, f, angle_mask);
   }
 }
 

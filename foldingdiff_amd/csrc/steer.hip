@@ -10,16 +10,12 @@
 // two operands commute, the weights of a group by one thread in index order.  No floating-point atomics, no scratch of the
 // kernels' own; two launches on the same input give the same bits.
 #include "fdmi_kernels.h"
+#include "guide_element.h"
 #include "wrap_pi.h"
 
 namespace fdmi {
 
 namespace {
-
-__device__ __forceinline__ float shift_add(float v, float off) {
-#pragma clang fp contract(off)
-  return v + off;
-}
 
 __global__ __launch_bounds__(256) void steer_shift_kernel(const float* __restrict__ x0, const int* __restrict__ lens, long long n,
                                                           int L, int F, SteerOffset off, unsigned angle_mask,
@@ -29,13 +25,7 @@ __global__ __launch_bounds__(256) void steer_shift_kernel(const float* __restric
     const long long tok = i / F;
     const int l = (int)(tok % L), b = (int)(tok / L);
     float v = 0.f;
-    if (l < lens[b]) {
-      v = x0[i];
-      if (off.has_offset) {
-        v = shift_add(v, off.offset[f]);
-        if ((angle_mask >> f) & 1u) v = wrap_pi(v);
-      }
-    }
+    if (l < lens[b]) v = steer_shift_value(x0[i], off, angle_mask, f);
     ang[i] = v;
   }
 }

@@ -1139,6 +1139,29 @@ def _model_space(vals: np.ndarray, offset: Optional[np.ndarray], angular: np.nda
     return v.astype(np.float32)
 
 
+def _known_fixed(known: Sequence[np.ndarray], fixed: Sequence[np.ndarray], F: int, pad: int, offset: Optional[np.ndarray],
+                 angular: np.ndarray) -> Tuple[List[np.ndarray], List[np.ndarray], List[int]]:
+    """The conditioning of ``inpaint`` and ``guide_inpaint`` per item: the known values in model space (float32 ``[len, F]``,
+    0 where nothing is fixed), the mask per element (uint8 ``[len, F]``; a ``[len]`` mask fixes whole rows) and the lengths."""
+    ks, fs, lengths = [], [], []
+    for i in range(len(known)):
+        k = np.asarray(known[i])
+        assert k.ndim == 2 and k.shape[1] == F, f"known[{i}] is {k.shape}, expected [len, {F}]"
+        if not 1 <= len(k) <= pad:
+            raise ValueError(f"known[{i}] has {len(k)} residues, the dataset pads to {pad}")
+        fx = np.asarray(fixed[i]).astype(bool)
+        if fx.ndim == 1:
+            fx = np.repeat(fx[:, None], F, axis=1)
+        assert fx.shape == k.shape, f"fixed[{i}] is {fx.shape}, known[{i}] is {k.shape}"
+        if not np.isfinite(k[fx]).all():
+            raise ValueError(f"known[{i}] is not finite at a fixed element")
+        v = _model_space(np.where(fx, k, 0.0), offset, angular)
+        ks.append(np.where(fx, v, np.float32(0.0)).astype(np.float32))
+        fs.append(fx.astype(np.uint8))
+        lengths.append(len(k))
+    return ks, fs, lengths
+
+
 @torch.no_grad()
 def inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.ndarray], batch_size: int = 512,
             t_start: Optional[int] = None, final_only: bool = True, feature_key: str = "angles",
@@ -1194,23 +1217,7 @@ def inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.ndarray
         grid_coef = ddim_coefficients(dset.alpha_beta_terms["betas"], grid, eta)
     offset = _mean_offset(dset)
     angular = np.asarray(dset.feature_is_angular[feature_key], dtype=bool)
-    pad = dset.pad
-    ks, fs, lengths = [], [], []
-    for i in range(n):
-        k = np.asarray(known[i])
-        assert k.ndim == 2 and k.shape[1] == F, f"known[{i}] is {k.shape}, expected [len, {F}]"
-        if not 1 <= len(k) <= pad:
-            raise ValueError(f"known[{i}] has {len(k)} residues, the dataset pads to {pad}")
-        fx = np.asarray(fixed[i]).astype(bool)
-        if fx.ndim == 1:
-            fx = np.repeat(fx[:, None], F, axis=1)
-        assert fx.shape == k.shape, f"fixed[{i}] is {fx.shape}, known[{i}] is {k.shape}"
-        if not np.isfinite(k[fx]).all():
-            raise ValueError(f"known[{i}] is not finite at a fixed element")
-        v = _model_space(np.where(fx, k, 0.0), offset, angular)
-        ks.append(np.where(fx, v, np.float32(0.0)).astype(np.float32))
-        fs.append(fx.astype(np.uint8))
-        lengths.append(len(k))
+    ks, fs, lengths = _known_fixed(known, fixed, F, dset.pad, offset, angular)
     betas = dset.alpha_beta_terms["betas"]
     h = model.prepare(betas, dset.feature_is_angular[feature_key])
     coef = inpaint_levels(betas)
@@ -1613,7 +1620,7 @@ def guide(model, dset, lengths: Sequence[int], restraints, num_steps: Optional[i
     ``sample``'s final states, and ``info`` with ``energy`` and ``max_violation`` (float64 ``[n]``: the restraint energy and
     the largest violation in Angstrom of each returned backbone), ``visits`` and ``guide``.  ``ValueError``, before any device
     call, for a restraint on a residue beyond its backbone and a setting out of range.  Single device; not combined with
-    motif replacement, the second-order solver, steering or ties.  Guidance follows a gradient through NeRF only: the
+    the second-order solver, steering or ties; with motif replacement: ``guide_inpaint``.  Guidance follows a gradient through NeRF only: the
     network's Jacobian is left out, and how ``scale`` trades restraint satisfaction against sample quality depends on the
     trained model."""
     from . import structures
@@ -1661,6 +1668,163 @@ def guide(model, dset, lengths: Sequence[int], restraints, num_steps: Optional[i
             energies.append(energy)
             worsts.append(worst)
     return samples, {"energy": np.concatenate(energies), "max_violation": np.concatenate(worsts), "visits": visits, "guide": guide_tab}
+
+
+def scaffold_guide_params(feature_names: Sequence[str], offset: Optional[np.ndarray], max_norm: float, clash_weight: float = 0.0,
+                          clash_alpha: float = 0.63, clash_margin: float = 0.15) -> "_binding.FdScaffoldGuideParams":
+    """``fd_scaffold_guide_params`` from Python values: ``guide_params``' fields and the soft clash term's."""
+    g = guide_params(feature_names, offset, max_norm)
+    p = _binding.FdScaffoldGuideParams()
+    p.feat_idx[:] = list(g.feat_idx)
+    p.has_offset = g.has_offset
+    p.offset[:] = list(g.offset)
+    p.max_norm = g.max_norm
+    p.clash_alpha, p.clash_margin, p.w_clash = float(clash_alpha), float(clash_margin), float(clash_weight)
+    return p
+
+
+def _run_fd_sample_guided_inpaint(h, x0: np.ndarray, lens: np.ndarray, visits: np.ndarray, coef: np.ndarray, known: np.ndarray,
+                                  fixed: np.ndarray, known_coef: np.ndarray, seed: int, guide_tab: np.ndarray, params, packed,
+                                  out: np.ndarray, energy: np.ndarray, worst: np.ndarray) -> None:
+    """The one call into libfdmi.so that runs a guided, conditioned schedule on a host batch (fd_sample_guided_inpaint).
+    Philox for every noise stream."""
+    B, L, _ = x0.shape
+    _binding.check(_binding.load().fd_sample_guided_inpaint(
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, _binding.ptr(visits), len(visits), _binding.ptr(coef), None, _binding.ptr(known),
+        _binding.ptr(fixed), _binding.ptr(known_coef), None, C.c_uint64(seed), C.c_int64(0), _binding.ptr(guide_tab), C.byref(params),
+        *(_binding.ptr(a) for a in packed), _binding.ptr(out), _binding.ptr(energy), _binding.ptr(worst)))
+
+
+@torch.no_grad()
+def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.ndarray], restraints, num_steps: Optional[int] = None,
+                  eta: float = 1.0, scale: float = 1.0, max_norm: float = 1.0, guide_from: Optional[int] = None,
+                  clash_weight: float = 0.0, clash_alpha: float = 0.63, clash_margin: float = 0.15, batch_size: int = 512,
+                  seed: Optional[int] = None, feature_key: str = "angles"):
+    """Restraint guidance combined with replacement (``fd_sample_guided_inpaint``): one backbone per item whose
+    elements marked in ``fixed[i]`` are held to ``known[i]`` as in ``inpaint``, while the rest is steered toward distance
+    restraints as in ``guide``.  The structure a visit is scored on carries the held elements exactly -- their known values,
+    whatever the network predicted there -- and the gradient moves the free elements only.  This is what a motif of several
+    separate segments needs: replacement reproduces each segment's backbone, the restraints place the segments relative to
+    each other (``scaffold_segments``).
+
+    ``known`` / ``fixed``: as in ``inpaint`` -- ``[len_i, F]`` data-space angles, NaN allowed where nothing is fixed, and a
+    bool mask per row or per element; the dataset's mean offset is subtracted.  ``restraints``, ``num_steps``, ``eta``,
+    ``scale``, ``max_norm``, ``guide_from``, ``seed``: as in ``guide``.  ``clash_weight > 0`` adds ``structures.relax``' soft
+    clash term (``clash_alpha``, ``clash_margin``: its defaults) to the energy whose gradient is followed: pulling two held
+    segments together is where chains get pushed through themselves.
+
+    Returns ``(samples, info)`` as ``guide`` does, ``info`` with ``clash_energy`` (float64 ``[n]``, 0 without a clash term)
+    beside ``energy`` and ``max_violation``.  ``ValueError``, before any device call, for what ``inpaint`` and ``guide``
+    reject and a negative or non-finite clash setting.  Single device, final states only; not combined with resampling
+    schedules, the second-order solver, steering or ties.  Distances do not tell a scaffold from its mirror image, and how
+    often one comes out mirrored -- like designability -- is unmeasured: there are no trained weights here."""
+    from . import structures
+    _check_few_step(None, "uniform", num_steps, eta)
+    n = len(known)
+    assert len(fixed) == n, f"{n} known arrays, {len(fixed)} masks"
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size={batch_size} must be positive")
+    if not (max_norm > 0 and np.isfinite(max_norm)):
+        raise ValueError(f"max_norm={max_norm} must be positive and finite")
+    for name, v in (("clash_weight", clash_weight), ("clash_alpha", clash_alpha), ("clash_margin", clash_margin)):
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"{name}={v} must be finite and >= 0")
+    F = model.n_inputs
+    offset = _mean_offset(dset)
+    angular = np.asarray(dset.feature_is_angular[feature_key], dtype=bool)
+    ks, fs, lengths = _known_fixed(known, fixed, F, min(dset.pad, 2048), offset, angular)
+    if not lengths:
+        raise ValueError("known is empty")
+    structures.pack_restraints(restraints, lengths)   # (its checks, before anything is drawn)
+    per_chain = [restraints] * n if restraints is None or isinstance(restraints, structures.Restraints) else list(restraints)
+    T = dset.timesteps
+    betas = dset.alpha_beta_terms["betas"]
+    visits = _few_step_visits(betas, T if num_steps is None else int(num_steps), None, "uniform", -3.0)
+    coef = steer_coefficients(betas, visits, eta)
+    guide_tab = guidance_coefficients(betas, visits, coef, scale, guide_from)
+    known_coef = inpaint_levels(betas)
+    params = scaffold_guide_params(list(dset.feature_names[feature_key]), offset, max_norm, clash_weight, clash_alpha, clash_margin)
+    h = model.prepare(betas, dset.feature_is_angular[feature_key])
+    on_gpu = _on_device(model, "_run_fd_sample_guided_inpaint")
+    samples: List[np.ndarray] = []
+    energies, clashes, worsts = [], [], []
+    with contextlib.ExitStack() as stack:
+        if seed is not None:
+            stack.enter_context(torch.random.fork_rng(devices=[]))
+            torch.manual_seed(int(seed))
+        for lo in range(0, n, int(batch_size)):
+            these = lengths[lo: lo + int(batch_size)]
+            B, L = len(these), max(these)
+            x0 = _start_noise(dset, B, L, F)
+            kb = np.zeros((B, L, F), dtype=np.float32)
+            fb = np.zeros((B, L, F), dtype=np.uint8)
+            for i, l in enumerate(these):
+                kb[i, :l] = ks[lo + i]
+                fb[i, :l] = fs[lo + i]
+            philox_seed = _draw_philox_seed()
+            out = np.empty((B, L, F), dtype=np.float32)
+            energy, worst = np.empty((B, 2), dtype=np.float64), np.empty(B, dtype=np.float64)
+            packed = structures.pack_restraints(per_chain[lo: lo + B], these)
+            with _packed_batch(model, these, on_gpu):   # positions beyond an item's length are cut away below, as in sample()
+                _run_fd_sample_guided_inpaint(h, x0, _lens_array(these, B, L), visits, coef, kb, fb, known_coef, philox_seed, guide_tab,
+                                              params, packed, out, energy, worst)
+            samples.extend(s[0] for s in _shift_trim(model, torch.from_numpy(out[None]), these, offset, angular))
+            energies.append(energy[:, 0].copy())
+            clashes.append(energy[:, 1].copy())
+            worsts.append(worst)
+    return samples, {"energy": np.concatenate(energies), "clash_energy": np.concatenate(clashes),
+                     "max_violation": np.concatenate(worsts), "visits": visits, "guide": guide_tab}
+
+
+_run_fd_sample_guided_inpaint_default = _run_fd_sample_guided_inpaint
+
+
+def scaffold_segments(model, dset, motif_angles: np.ndarray, motif_backbone: np.ndarray, segments: Sequence[Tuple[int, int, int]],
+                      total_lengths: Sequence[int], pin_lead_angle: bool = True, feature_key: str = "angles",
+                      restraints=None, restraint_weight: float = 1.0, restraint_tol: float = 0.0,
+                      restraint_atoms: Sequence[str] = ("CA",), **kwargs):
+    """Scaffold a discontiguous motif: one backbone of each of ``total_lengths`` in which every segment
+    ``(motif_start, motif_stop, placed_at)`` of ``segments`` holds rows ``motif_start .. motif_stop - 1`` of ``motif_angles``
+    (``[m, F]`` data-space angles, what ``structures.featurize`` returns) at residues ``placed_at ..`` by replacement, and the
+    segments are steered to their mutual placement in ``motif_backbone`` (``[3 m, 3]``, N / CA / C per residue of the same
+    structure) by ``structures.segment_restraints`` (``restraint_weight``, ``restraint_tol``, ``restraint_atoms``), to which
+    ``restraints`` (one ``structures.Restraints``, e.g. contacts) is added.  The same
+    segments go into every chain.  ``pin_lead_angle``: ``scaffold``'s rule at the front of every segment that does not start
+    at residue 0 -- ``tau`` of the row before it is fixed to ``tau`` of the motif row before the segment (NeRF reads the N-CA-C
+    angle inside the segment's first residue from there), or, for a segment that starts at motif residue 0, to the segment's
+    own first ``tau`` as ``structures.motif_backbone`` does.  ``kwargs`` go to ``guide_inpaint``.
+
+    ``ValueError`` for overlapping segments, a segment outside the motif or outside one of the chains.  Returns
+    ``guide_inpaint``'s ``(samples, info)``; see there on mirror images."""
+    from . import structures
+    motif_angles = np.asarray(motif_angles, dtype=np.float32)
+    assert motif_angles.ndim == 2 and motif_angles.shape[1] == model.n_inputs, f"motif_angles is {motif_angles.shape}, expected [m, {model.n_inputs}]"
+    m, F = motif_angles.shape
+    total_lengths = [int(l) for l in total_lengths]
+    rst = structures.segment_restraints(motif_backbone, segments, weight=restraint_weight, tol=restraint_tol, atoms=restraint_atoms)
+    if restraints is not None:
+        rst = rst + restraints
+    segs = [tuple(int(v) for v in seg) for seg in segments]   # (segment_restraints has checked them against the motif and each other)
+    if 3 * m != len(np.asarray(motif_backbone).reshape(-1, 3)):
+        raise ValueError(f"motif_angles has {m} residues, motif_backbone {len(np.asarray(motif_backbone).reshape(-1, 3)) // 3}")
+    names = list(dset.feature_names[feature_key])
+    tau = names.index("tau") if pin_lead_angle and "tau" in names else -1
+    known, fixed = [], []
+    for l in total_lengths:
+        k = np.full((l, F), np.nan, dtype=np.float32)
+        f = np.zeros((l, F), dtype=bool)
+        for lo, hi, at in segs:
+            if at + hi - lo > l:
+                raise ValueError(f"segment [{lo}, {hi}) placed at {at} does not fit a chain of {l}")
+            k[at: at + hi - lo] = motif_angles[lo:hi]
+            f[at: at + hi - lo] = True
+        for lo, hi, at in segs:   # (behind the rows: a lead element never overwrites a held row)
+            if tau >= 0 and at >= 1 and not f[at - 1, tau]:
+                k[at - 1, tau] = motif_angles[lo - 1 if lo >= 1 else lo, tau]
+                f[at - 1, tau] = True
+        known.append(k)
+        fixed.append(f)
+    return guide_inpaint(model, dset, known, fixed, rst, feature_key=feature_key, **kwargs)
 
 
 def sample_simple(model_dir: str, n: int = 10, sweep_lengths: Tuple[int, int] = (50, 128)):

@@ -528,6 +528,40 @@ def motif_restraints(motif_backbone: np.ndarray, placed_at: Sequence[int], weigh
     return Restraints(i, j, d0, float(tol), float(weight))
 
 
+def segment_restraints(motif_backbone: np.ndarray, segments: Sequence[Tuple[int, int, int]], weight: float = 1.0, tol: float = 0.0,
+                       atoms: Sequence[str] = ("CA",)) -> Restraints:
+    """"These segments sit relative to each other as in the motif" (``sampling.scaffold_segments``): a
+    discontiguous motif is a list of ``segments`` ``(motif_start, motif_stop, placed_at)`` -- residues ``motif_start ..
+    motif_stop - 1`` of ``motif_backbone`` (``[3 m, 3]``, N / CA / C per residue) take the residues ``placed_at ..`` of the new
+    chain.  Returns ``motif_restraints``' restraints, in its order and with its distances bit for bit, for the atom pairs whose
+    two residues lie in DIFFERENT segments only: a segment's own geometry is held exactly by replacement, and pairs inside it
+    would only add stiffness.  ``ValueError`` for a segment that is empty or outside the motif, segments that share a motif
+    residue or a placed residue, and everything ``motif_restraints`` rejects; see ``Restraints`` on the mirror image."""
+    xyz = np.asarray(motif_backbone, dtype=np.float64).reshape(-1, 3)
+    if len(xyz) % 3:
+        raise ValueError(f"motif_backbone has {len(xyz)} atoms (3 per residue)")
+    m = len(xyz) // 3
+    rows, placed, owner = [], [], []
+    for k, seg in enumerate(segments):
+        if len(seg) != 3:
+            raise ValueError("every segment is (motif_start, motif_stop, placed_at)")
+        lo, hi, at = (int(v) for v in seg)
+        if not 0 <= lo < hi <= m:
+            raise ValueError(f"segment {k} = motif residues [{lo}, {hi}) is empty or outside the motif's {m} residues")
+        if at < 0:
+            raise ValueError(f"segment {k} is placed at residue {at}")
+        rows.extend(range(lo, hi))
+        placed.extend(range(at, at + hi - lo))
+        owner.extend([k] * (hi - lo))
+    if len(set(rows)) != len(rows):
+        raise ValueError("two segments share a motif residue")
+    sub = xyz.reshape(m, 3, 3)[rows].reshape(-1, 3) if rows else xyz[:0]
+    every = motif_restraints(sub, placed, weight=weight, tol=tol, atoms=atoms)   # (its checks: distinct placed residues, the atoms)
+    seg_of = {p: k for p, k in zip(placed, owner)}
+    keep = np.array([seg_of[int(i) // 3] != seg_of[int(j) // 3] for i, j in zip(every.i, every.j)], dtype=bool)
+    return Restraints(every.i[keep], every.j[keep], every.d0[keep], every.tol[keep], every.w[keep])
+
+
 def pack_restraints(restraints, lengths: Sequence[int]):
     """``fd_restraint_energy``'s packed layout for a batch: ``(rst_offsets int32 [B + 1], rst_i, rst_j int32 [R], rst_d0,
     rst_tol, rst_w float64 [R])`` from one ``Restraints`` per chain (``None``: none), or a single one for every chain.

@@ -695,7 +695,7 @@ int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t*
  * chain or with i == j, a negative or non-finite d0 / tol / w, max_norm <= 0 or not finite, a non-finite offset, a length above
  * 2048, fewer than 3 or more than 16 features, a bad feat_idx: FD_E_INVALID before any device call, `out` untouched.  Options
  * "use_graph" and "varlen" and both precisions as in fd_sample_strided; a later fd_sample* is unaffected.  Single device, final
- * state only; not offered with motif conditioning, the second-order solver, steering or ties. */
+ * state only; not offered with the second-order solver, steering or ties; with motif conditioning: fd_sample_guided_inpaint. */
 typedef struct fd_guide_params {
   int32_t feat_idx[9];
   int32_t has_offset;
@@ -788,6 +788,79 @@ int fd_relax(int device_id, const float* feats, const float* anchor, const int32
              const fd_relax_params* params, const uint8_t* fixed, const int32_t* rst_offsets, const int32_t* rst_i,
              const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, int n_iter, double* step_io,
              float* feats_out, double* energy_out, double* trace_out, int32_t* accepted_out);
+
+/* ---- restraint guidance combined with replacement: discontiguous motifs.  Replacement (fd_sample_inpaint)
+ * holds chosen elements of the angle rows, so a held run of residues reproduces that segment's backbone exactly, but says nothing
+ * about where two held segments sit relative to each other; distance restraints (fd_sample_guided) place them.  Distances do
+ * not tell a structure from its mirror image, and whether such scaffolds are designable is unmeasured.
+ *
+ * The scaffold-guide statement, per element o = (b, l, f) of [B][L][F].  After a visit, x is the state it left and x0 its
+ * prediction of the clean state; fixed is uint8 [B][L][F], known float32 [B][L][F] in model space as for fd_sample_inpaint:
+ *     p[o]   = fixed[o] ? known[o] : x0[o]        (a held element's clean value is KNOWN; x0[o] is never read where fixed[o])
+ *     ang    = the shift statement of fd_sample_steered on p
+ *     coords = fd_nerf_scan(ang, center = 0)
+ *     E_rst, max_violation, gc = the restraint statement of fd_restraint_energy on coords
+ *     E_clash, gc +=             fd_relax_energy's soft clash statement (clash_alpha, clash_margin, w_clash), only where w_clash > 0
+ *     G      = fd_nerf_vjp_feats(coords, gc, centered = 0, feats = ang)                 [B][L][F] fp64
+ *     G[o]   = 0 where fixed[o]
+ *     n_b    = sqrt(sum of G^2 over the rows below lens[b]), in fd_guide_step's fixed order;  k_b = n_b > max_norm ? max_norm / n_b : 1
+ *     free element:   x <- x - float32((double(c) * k_b) * G) only where c != 0;  x <- x + s z where s != 0;  x <- wrap(x) where
+ *                     angular -- fd_guide_step's three lines: same draw position, same Philox word, same roundings
+ *     fixed element:  keeps its bits; neither reads nor draws a z
+ * The restraints are evaluated before the clashes, fd_relax_energy's order: with w_tether = 0 and every NeRF column movable,
+ * fd_relax_energy's dfeats_out on the same ang is the unmasked G bit for bit.  No floating-point atomics; two calls give the
+ * same bits.  With fixed all zero and w_clash = 0 the statement is fd_guide_step's with fd_nerf_scan in place of fd_nerf.
+ *
+ * fd_scaffold_guide_step: the statement on host arrays, model-free and synchronous like fd_guide_step.
+ *   x            float32 [B][L][F] (host), finite on the rows below lens[b]; lens int32[B] in [1, min(L, 2048)]; 3 <= F <= 16
+ *   x0           the same shape, finite on the free elements of those rows
+ *   known, fixed never NULL; known finite where fixed (not read elsewhere: NaN is allowed there); nothing fixed at or beyond lens[b]
+ *   is_angle     uint8[F]: the features to wrap
+ *   params       feat_idx as in fd_nerf_vjp, the offset of the shift, max_norm > 0 and finite; clash_alpha, clash_margin and
+ *                w_clash finite and >= 0 (w_clash == 0: no clash term)
+ *   rst_*        as in fd_restraint_energy;  c, s finite
+ *   z            float32 [B][L][F], or NULL: Philox with (seed, t, seq_offset); neither is looked at where s == 0
+ *   x_out        float32 [B][L][F]: the rows below lens[b]; the others keep what they held
+ *   energy_out   double[B][2] restraint | clash of p's structure (clash: 0 where w_clash == 0); max_violation_out, gnorm_out double[B]
+ *   dfeats_out   double[B][L][F] the masked G on the rows below lens[b], or NULL
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs untouched. */
+typedef struct fd_scaffold_guide_params {
+  int32_t feat_idx[9];
+  int32_t has_offset;
+  float offset[16];                           /* the first F are read, and only where has_offset != 0 */
+  double max_norm;                            /* > 0 */
+  double clash_alpha, clash_margin, w_clash;  /* finite, >= 0; w_clash == 0: no clash term, alpha and margin unread */
+} fd_scaffold_guide_params;
+int fd_scaffold_guide_step(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                           const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                           const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                           const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float c, float s,
+                           const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
+                           double* max_violation_out, double* gnorm_out, double* dfeats_out);
+
+/* fd_sample_guided_inpaint is fd_sample_guided with fd_sample_strided_inpaint's conditioning, final state only.  The start
+ * point's fixed elements are replaced at level visits[0] + 1 (known_noise row 0).  Visit i is a replay of the plain sampler's
+ * captured step graph, which is not captured again: a fixed element leaves it at the level the visit lands on, next_t + 1, from
+ * row i + 1 of known_noise or the Philox draw fd_sample_strided_inpaint takes; a free element leaves as wrap(a x + b eps) with
+ * x0 = wrap(u x + v eps).  The scaffold-guide statement follows with c = guide[i], s = coef[2][i], t = visits[i] and row i of
+ * `noise`: six launches (shift, scan, restraints, clashes, derivative, update; five where w_clash == 0), all one workgroup per
+ * chain.  Behind the last visit the fixed elements hold known's bits.  Nothing is asked of the host between the upload and the
+ * download.
+ *   visits, coef, noise, seed, seq_offset, guide, rst_*   as in fd_sample_guided
+ *   known, fixed, known_coef, known_noise                 as in fd_sample_strided_inpaint (known_noise [K + 1][B][L][F] or NULL)
+ *   params            as in fd_scaffold_guide_step
+ *   out               [B][L][F] the final state
+ *   energy_out        double[B][2] restraint | clash and max_violation_out double[B]: the statement's energies with p = the FINAL state
+ * Everything fd_sample_guided and fd_sample_strided_inpaint reject, a NULL known or fixed, a non-finite known[o] where fixed[o]
+ * (where nothing is fixed known is not read), a negative or non-finite clash_alpha, clash_margin or w_clash: FD_E_INVALID before
+ * any device call, outputs untouched.  Options "use_graph" and "varlen" and both precisions as in fd_sample_guided; a later
+ * fd_sample* of any family is unaffected.  Single device; not offered with jumps, the second-order solver, steering or ties. */
+int fd_sample_guided_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                             const float* coef, const float* noise, const float* known, const uint8_t* fixed, const float* known_coef,
+                             const float* known_noise, uint64_t seed, int64_t seq_offset, const float* guide,
+                             const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                             const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float* out,
+                             double* energy_out, double* max_violation_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
