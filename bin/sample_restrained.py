@@ -25,6 +25,14 @@ to the file's, so its backbone is reproduced exactly -- and the restraints are k
 which places the ranges relative to each other.  ``--clash_weight W`` adds the relaxer's soft clash term, weighted by W, to the
 energy whose gradient is followed; the report then also holds ``clash_energy``.  Without these two flags the script does what
 it did before them.
+
+``--placement {distances,template,both}`` (needs a motif) chooses what places the motif's residues: ``distances``
+is the behaviour above; ``template`` replaces the motif's distance restraints by a superposition restraint -- the N, CA and C
+atoms of the placed residues are fitted to the file's by a proper rotation, weighted by ``--template_weight W``, which a mirror
+image cannot satisfy --; ``both`` uses the two together.  Without ``--hold_motif`` nothing is held and the run is
+``sampling.guide_inpaint`` with nothing fixed.  The report then also holds ``template_energy``, ``template_rmsd`` and
+``template_mirror_rmsd`` (the fit of the template reflected in z: below ``template_rmsd`` means the wrong hand came out).
+Without the flag the script does what it did before it.
 """
 import argparse
 import json
@@ -54,6 +62,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--hold_motif", action="store_true",
                         help="hold every range of --motif_residues by replacement and restrain across ranges only")
     parser.add_argument("--clash_weight", type=float, default=None, help="weight of the soft clash term inside the guided run")
+    parser.add_argument("--placement", type=str, default=None, choices=("distances", "template", "both"),
+                        help="what places the motif: its pair distances (default), a superposition restraint, or both")
+    parser.add_argument("--template_weight", type=float, default=1.0, help="weight of every atom of the superposition restraint")
     parser.add_argument("--scale", type=float, default=1.0, help="guidance scale; 0 is the unguided sampler")
     parser.add_argument("--max_norm", type=float, default=1.0, help="clip of a backbone's gradient norm")
     parser.add_argument("--guide_from", type=int, default=None, help="guide only the visits at or below this timestep (default: all)")
@@ -103,6 +114,11 @@ def main(argv=None) -> None:
         parser.error("--hold_motif holds the ranges of a motif: give --motif_pdb, --motif_residues and --placed_at")
     if args.clash_weight is not None and not args.clash_weight >= 0:
         parser.error(f"--clash_weight {args.clash_weight} must be >= 0")
+    with_template = args.placement in ("template", "both")
+    if with_template and args.motif_pdb is None:
+        parser.error(f"--placement {args.placement} places a motif: give --motif_pdb, --motif_residues and --placed_at")
+    if not (args.template_weight > 0 and args.template_weight < float("inf")):
+        parser.error(f"--template_weight {args.template_weight} must be > 0 and finite")
     if args.contacts is None and args.motif_pdb is None:
         parser.error("nothing to aim at: give --contacts and / or a motif")
     outdir = Path(args.outdir)
@@ -117,7 +133,7 @@ def main(argv=None) -> None:
 
     from foldingdiff_amd import structures
 
-    restraints, motif_ca, placed, segments, file_xyz = None, None, None, None, None
+    restraints, motif_ca, placed, segments, file_xyz, template = None, None, None, None, None, None
     try:
         if args.contacts is not None:
             restraints = structures.contact_restraints(read_contacts(args.contacts), weight=args.weight)
@@ -143,10 +159,14 @@ def main(argv=None) -> None:
             else:
                 m = structures.motif_restraints(motif, placed, weight=args.weight)
             contacts = restraints
-            restraints = m if restraints is None else restraints + m
+            if args.placement != "template":
+                restraints = m if restraints is None else restraints + m
+            if with_template:
+                template = structures.motif_template(xyz.reshape(-1, 3), [(rng[0], rng[-1] + 1, s) for rng, s in zip(ranges, starts)],
+                                                     weight=args.template_weight)
             if max(placed) >= args.length:
                 raise ValueError(f"the motif is placed up to residue {max(placed)}, --length is {args.length}")
-        if restraints.min_length() > args.length:
+        if restraints is not None and restraints.min_length() > args.length:
             raise ValueError(f"the restraints need {restraints.min_length()} residues, --length is {args.length}")
     except ValueError as e:
         parser.error(str(e))
@@ -180,11 +200,14 @@ def main(argv=None) -> None:
         if not np.isfinite(motif_angles[picked]).all():
             raise AssertionError(f"--motif_residues of {args.motif_pdb} hold an undefined angle (a chain end?)")
         sampled, info = sampling.scaffold_segments(model, train_dset, motif_angles, file_xyz, segments, lengths, restraints=contacts,
-                                                   restraint_weight=args.weight, clash_weight=args.clash_weight or 0.0, **guide_args)
-    elif args.clash_weight is not None:   # guidance with the clash term and nothing held
+                                                   restraint_weight=args.weight, clash_weight=args.clash_weight or 0.0,
+                                                   **(dict(placement=args.placement, template_weight=args.template_weight) if with_template else {}),
+                                                   **guide_args)
+    elif args.clash_weight is not None or with_template:   # guidance with the clash term or a template and nothing held
         free = [np.full((args.length, len(names)), np.nan, dtype=np.float32)] * args.num
         sampled, info = sampling.guide_inpaint(model, train_dset, free, [np.zeros(args.length, dtype=bool)] * args.num, restraints,
-                                               clash_weight=args.clash_weight, **guide_args)
+                                               clash_weight=args.clash_weight or 0.0, **(dict(templates=template) if with_template else {}),
+                                               **guide_args)
     else:
         sampled, info = sampling.guide(model, train_dset, lengths, restraints, **guide_args)
     sampled_dfs = [pd.DataFrame(s, columns=names) for s in sampled]
@@ -196,11 +219,16 @@ def main(argv=None) -> None:
     coords = []
     pdb_files = write_preds_pdb_folder(sampled_dfs, str(outdir / "sampled_pdb"), device=device.index or 0, coords_out=coords)
     kept = [i for i, (f, xyz) in enumerate(zip(pdb_files, coords)) if f and xyz is not None]
-    report = {"settings": vars(args), "length": args.length, "n_restraints": len(restraints),
+    report = {"settings": vars(args), "length": args.length, "n_restraints": 0 if restraints is None else len(restraints),
               "energy": {os.path.basename(pdb_files[i]): float(info["energy"][i]) for i in kept},
               "max_violation": {os.path.basename(pdb_files[i]): float(info["max_violation"][i]) for i in kept}}
     if "clash_energy" in info:
         report["clash_energy"] = {os.path.basename(pdb_files[i]): float(info["clash_energy"][i]) for i in kept}
+    if with_template:
+        for key in ("template_energy", "template_rmsd"):
+            report[key] = {os.path.basename(pdb_files[i]): float(info[key][i]) for i in kept}
+        _, mirrored = structures.template_energy([coords[i] for i in kept], template, device=device.index or 0, mirror=True)
+        report["template_mirror_rmsd"] = {os.path.basename(pdb_files[i]): float(r) for i, r in zip(kept, mirrored)}
     if motif_ca is not None:
         ca_rows = [3 * p + 1 for p in placed]
         rmsd = structures.superposed_rmsd([coords[i][ca_rows] for i in kept], [motif_ca] * len(kept), device=device.index or 0)

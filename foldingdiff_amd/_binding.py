@@ -148,6 +148,12 @@ _SIGNATURES = {
                                          _P, _P, _P, C.c_float, C.c_float, _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "fd_sample_guided_inpaint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int64, _P,
                                            C.POINTER(FdScaffoldGuideParams), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_template_energy": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_scaffold_guide_step_tpl": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(FdScaffoldGuideParams), _P, _P,
+                                             _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P,
+                                             _P, _P, _P]),
+    "fd_sample_guided_inpaint_tpl": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int64, _P,
+                                               C.POINTER(FdScaffoldGuideParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fd_nerf_scan": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "fd_relax_energy": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(FdRelaxParams), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                   _P]),

@@ -894,7 +894,8 @@ int guided_host_run(fd_model* m, const GuidedHostRun& a) {
 // ---- restraint guidance with replacement: guided_host_run with strided_host_run's conditioning in the same
 // per-run values -- a visit's fixed elements take update_element's fixed branch, its free ones leave wrap(a x + b eps) and
 // their x0 -- and the scaffold-guide statement's launches (guide_scaffold.hip) behind every visit.  The entry has checked every
-// argument; a.states = K, final state only.  The tables, the restraints and the work buffers die with this frame.
+// argument; a.states = K, final state only.  The tables, the restraints and the work buffers die with this frame.  With a
+// template (fd_sample_guided_inpaint_tpl) the statement has one more launch, template_fit.hip's.
 struct ScaffoldGuidedHostRun {
   RunArrays arrays;  // known_noise row 0: the start point, row i + 1: the state visit i leaves
   const int32_t* visits;
@@ -903,7 +904,9 @@ struct ScaffoldGuidedHostRun {
   InpaintHost cond;
   const fd_scaffold_guide_params* params;
   RestraintLists rst;
-  double *energy_out, *max_violation_out;  // [B][2], [B]
+  TemplateLists tpl;   // none, or a chain's entries
+  int n_energies;      // 2: restraint | clash (fd_sample_guided_inpaint); 3: | template, and tpl_rmsd_out
+  double *energy_out, *max_violation_out, *tpl_rmsd_out;  // [B][n_energies], [B], [B]
 };
 
 int scaffold_guided_host_run(fd_model* m, const ScaffoldGuidedHostRun& a) {
@@ -928,7 +931,17 @@ int scaffold_guided_host_run(fd_model* m, const ScaffoldGuidedHostRun& a) {
   HIP_TRY(bufs.alloc(nb * 8, &wk.e_rst));
   HIP_TRY(bufs.alloc(nb * 8, &wk.max_violation));
   HIP_TRY(bufs.zeros(nb * 8, &wk.e_clash));  // (stays 0 where there is no clash term)
+  HIP_TRY(bufs.zeros(nb * 8, &wk.e_tpl));    // (and these where no chain has a template entry: that launch is skipped)
+  HIP_TRY(bufs.zeros(nb * 8, &wk.rmsd_tpl));
   HIP_TRY(bufs.alloc(nb * 8, &d_gnorm));
+  TemplateFit tf{};
+  const TemplateFit* fit = a.tpl.count() ? &tf : nullptr;
+  if (fit) {
+    HIP_TRY(bufs.upload(a.tpl.offsets, (nb + 1) * 4, &tf.offsets));
+    HIP_TRY(bufs.upload(a.tpl.atom, a.tpl.count() * 4, &tf.atom));
+    HIP_TRY(bufs.upload(a.tpl.xyz, a.tpl.count() * 24, &tf.xyz));
+    HIP_TRY(bufs.upload(a.tpl.w, a.tpl.count() * 8, &tf.w));
+  }
   Restraints rs{};  // (an empty list: the kernel reads the offsets only)
   HIP_TRY(bufs.upload(a.rst.offsets, (nb + 1) * 4, &rs.offsets));
   if (R) {
@@ -960,21 +973,27 @@ int scaffold_guided_host_run(fd_model* m, const ScaffoldGuidedHostRun& a) {
   for (int i = 0; !rc && i < K; ++i) {
     rc = fd_sample_steps_dev(m, 1, nullptr, 0, nullptr);
     if (rc) break;
-    launch_scaffold_energy(d_x0, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, wk, d_G, s);
+    launch_scaffold_energy(d_x0, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, fit, wk, d_G, s);
     launch_scaffold_update(w.x, d_G, ip.fixed, w.lens, B, L, F, m->angle_mask, a.guide[i], gp.max_norm, a.coef[2 * Kz + i],
                            r.noise ? r.noise + (size_t)i * r.n : nullptr, h.seed, a.visits[i], h.seq_offset, d_gnorm, s);
     rc = launched();
   }
   if (!rc) {  // the final state's: its fixed elements hold known's bits, so p is the state itself
-    launch_scaffold_energy(w.x, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, wk, nullptr, s);
+    launch_scaffold_energy(w.x, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, fit, wk, nullptr, s);
     rc = launched();
   }
-  std::vector<double> e_rst(nb), e_clash(nb), maxv(nb);
-  rc = r.finish(rc, {{e_rst.data(), wk.e_rst, nb * 8}, {e_clash.data(), wk.e_clash, nb * 8}, {maxv.data(), wk.max_violation, nb * 8}});
+  std::vector<double> e_rst(nb), e_clash(nb), maxv(nb), e_tpl(nb), rmsd_tpl(nb);
+  rc = r.finish(rc, {{e_rst.data(), wk.e_rst, nb * 8}, {e_clash.data(), wk.e_clash, nb * 8}, {maxv.data(), wk.max_violation, nb * 8},
+                     {e_tpl.data(), wk.e_tpl, nb * 8}, {rmsd_tpl.data(), wk.rmsd_tpl, nb * 8}});
   if (rc && rc != FD_E_NONFINITE) return rc;  // (a run that answers FD_E_NONFINITE has written its outputs, as every family's)
+  const size_t ne = (size_t)a.n_energies;
   for (size_t b = 0; b < nb; ++b) {
-    a.energy_out[2 * b] = e_rst[b];
-    a.energy_out[2 * b + 1] = e_clash[b];
+    a.energy_out[ne * b] = e_rst[b];
+    a.energy_out[ne * b + 1] = e_clash[b];
+    if (ne == 3) {
+      a.energy_out[3 * b + 2] = e_tpl[b];
+      a.tpl_rmsd_out[b] = rmsd_tpl[b];
+    }
     a.max_violation_out[b] = maxv[b];
   }
   return rc;
@@ -1496,26 +1515,54 @@ int fd_sample_guided(fd_model* m, const float* x_init, const int32_t* lens, int 
                                           guide, params, rl, energy_out, max_violation_out});
 }
 
+}  // extern "C"
+
+// fd_sample_guided_inpaint (n_energies == 2, no template) and fd_sample_guided_inpaint_tpl (3): the checks, then the run
+static int guided_inpaint_entry(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
+                                const float* coef, const float* noise, const float* known, const uint8_t* fixed, const float* known_coef,
+                                const float* known_noise, uint64_t seed, int64_t seq_offset, const float* guide,
+                                const fd_scaffold_guide_params* params, const RestraintLists& rl, const TemplateLists& tl, int n_energies,
+                                float* out, double* energy_out, double* max_violation_out, double* tpl_rmsd_out) {
+  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;  // (rows a | b | s too)
+  if (int rc = check_coef_rows(coef, n_visits, 3, 5)) return rc;
+  if (!guide || !params) return fail(FD_E_INVALID, "null argument: guide and params are required");
+  if (!energy_out || !max_violation_out) return fail(FD_E_INVALID, "null argument: energy_out and max_violation_out are required");
+  if (n_energies == 3 && !tpl_rmsd_out) return fail(FD_E_INVALID, "null argument: tpl_rmsd_out is required");
+  for (int i = 0; i < n_visits; ++i)
+    if (!std::isfinite(guide[i])) return fail(FD_E_INVALID, "guide[%d] = %g is not finite", i, (double)guide[i]);
+  if (int rc = check_guide_shape(lens, B, L, m->cfg.n_features, params->feat_idx)) return rc;
+  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
+  if (int rc = check_scaffold_guide(*params, known, fixed, lens, B, L, m->cfg.n_features)) return rc;
+  if (int rc = check_restraints(rl, lens)) return rc;
+  if (int rc = check_template(tl, lens)) return rc;
+  return scaffold_guided_host_run(m, ScaffoldGuidedHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, known_noise, seed, seq_offset, out, 0},
+                                                           visits, coef, guide, {known, fixed, known_coef}, params, rl, tl, n_energies,
+                                                           energy_out, max_violation_out, tpl_rmsd_out});
+}
+
+extern "C" {
+
 int fd_sample_guided_inpaint(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits, int n_visits,
                              const float* coef, const float* noise, const float* known, const uint8_t* fixed, const float* known_coef,
                              const float* known_noise, uint64_t seed, int64_t seq_offset, const float* guide,
                              const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
                              const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float* out,
                              double* energy_out, double* max_violation_out) {
-  if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;  // (rows a | b | s too)
-  if (int rc = check_coef_rows(coef, n_visits, 3, 5)) return rc;
-  if (!guide || !params) return fail(FD_E_INVALID, "null argument: guide and params are required");
-  if (!energy_out || !max_violation_out) return fail(FD_E_INVALID, "null argument: energy_out and max_violation_out are required");
-  for (int i = 0; i < n_visits; ++i)
-    if (!std::isfinite(guide[i])) return fail(FD_E_INVALID, "guide[%d] = %g is not finite", i, (double)guide[i]);
-  if (int rc = check_guide_shape(lens, B, L, m->cfg.n_features, params->feat_idx)) return rc;
-  if (int rc = check_inpaint(known, fixed, known_coef, lens, B, L, m->cfg.n_features)) return rc;
-  if (int rc = check_scaffold_guide(*params, known, fixed, lens, B, L, m->cfg.n_features)) return rc;
-  const RestraintLists rl{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
-  if (int rc = check_restraints(rl, lens)) return rc;
-  return scaffold_guided_host_run(m, ScaffoldGuidedHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, known_noise, seed, seq_offset, out, 0},
-                                                           visits, coef, guide, {known, fixed, known_coef}, params, rl, energy_out,
-                                                           max_violation_out});
+  return guided_inpaint_entry(m, x_init, lens, B, L, visits, n_visits, coef, noise, known, fixed, known_coef, known_noise, seed, seq_offset,
+                              guide, params, RestraintLists{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w},
+                              TemplateLists{B, nullptr, nullptr, nullptr, nullptr}, 2, out, energy_out, max_violation_out, nullptr);
+}
+
+int fd_sample_guided_inpaint_tpl(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits,
+                                 int n_visits, const float* coef, const float* noise, const float* known, const uint8_t* fixed,
+                                 const float* known_coef, const float* known_noise, uint64_t seed, int64_t seq_offset,
+                                 const float* guide, const fd_scaffold_guide_params* params, const int32_t* rst_offsets,
+                                 const int32_t* rst_i, const int32_t* rst_j, const double* rst_d0, const double* rst_tol,
+                                 const double* rst_w, const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz,
+                                 const double* tpl_w, float* out, double* energy_out, double* max_violation_out, double* tpl_rmsd_out) {
+  return guided_inpaint_entry(m, x_init, lens, B, L, visits, n_visits, coef, noise, known, fixed, known_coef, known_noise, seed, seq_offset,
+                              guide, params, RestraintLists{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w},
+                              TemplateLists{B, tpl_offsets, tpl_atom, tpl_xyz, tpl_w}, 3, out, energy_out, max_violation_out, tpl_rmsd_out);
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

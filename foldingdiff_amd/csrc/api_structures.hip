@@ -1,5 +1,5 @@
 // C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, dssp.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
-// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip), of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip), of the torsion-space relaxer (nerf_scan.hip, relax.hip) and of the scaffold-guide step (guide_scaffold.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip), of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip), of the torsion-space relaxer (nerf_scan.hip, relax.hip) of the scaffold-guide step (guide_scaffold.hip) and of the superposition restraints (template_fit.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
 #include <cstring>
@@ -22,6 +22,23 @@ RestraintInputs restraint_inputs(const RestraintLists& r) {
   const auto ints = [&](const int32_t* p) { return std::pair<const void*, size_t>(R ? p : &no_atom, (R ? R : 1) * 4); };
   const auto doubles = [&](const double* p) { return std::pair<const void*, size_t>(R ? p : &no_value, (R ? R : 1) * 8); };
   return {{r.offsets, ((size_t)r.n_chains + 1) * 4}, ints(r.i), ints(r.j), doubles(r.d0), doubles(r.tol), doubles(r.w)};
+}
+// the four uploads of a batch's templates (check_template has passed); none: B + 1 zero offsets; no entry: one per array, never read
+struct TemplateInputs {
+  std::vector<int32_t> no_offsets;
+  std::pair<const void*, size_t> offsets, atom, xyz, w;
+};
+TemplateInputs template_inputs(const TemplateLists& t) {
+  static const int32_t no_atom = 0;
+  static const double no_value[3] = {0.0, 0.0, 0.0};
+  TemplateInputs r;
+  const size_t n = t.count(), nb = (size_t)t.n_chains + 1;
+  if (t.none()) r.no_offsets.assign(nb, 0);
+  r.offsets = {t.none() ? r.no_offsets.data() : t.offsets, nb * 4};
+  r.atom = {n ? (const void*)t.atom : &no_atom, (n ? n : 1) * 4};
+  r.xyz = {n ? (const void*)t.xyz : no_value, (n ? n : 1) * 24};
+  r.w = {n ? (const void*)t.w : no_value, (n ? n : 1) * 8};
+  return r;
 }
 }  // namespace
 
@@ -93,6 +110,30 @@ int fd_restraint_energy(int device_id, const double* coords, const int32_t* lens
                           });
 }
 
+int fd_template_energy(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* tpl_offsets,
+                       const int32_t* tpl_atom, const double* tpl_xyz, const double* tpl_w, double* energy_out, double* rmsd_out,
+                       double* transform_out, double* dcoords_out) {
+  if (!coords || !lens || !energy_out || !rmsd_out) return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if ((long long)B * L * 9 > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * 9 = %lld coordinates, at most 2^31 - 1", (long long)B * L * 9);
+  if (int rc = check_lens(lens, B, L < kGuideMaxLen ? L : kGuideMaxLen)) return rc;
+  const TemplateLists tl{B, tpl_offsets, tpl_atom, tpl_xyz, tpl_w};
+  if (int rc = check_template(tl, lens)) return rc;
+  if (int rc = check_chain_doubles("coords", coords, lens, B, L)) return rc;
+  const TemplateInputs ti = template_inputs(tl);
+  const size_t na = (size_t)B * 3 * L * 3, nb = (size_t)B;
+  return device_roundtrip(device_id, {{coords, na * 8}, ti.offsets, ti.atom, ti.xyz, ti.w},
+                          {{energy_out, nb * 8}, {rmsd_out, nb * 8}, {transform_out, transform_out ? nb * 96 : 8}, {dcoords_out, dcoords_out ? na * 8 : 8}},
+                          [&](const RoundtripBufs& d) -> hipError_t {
+                            const TemplateFit tf{d.in(1), d.in(2), d.in(3), d.in(4)};
+                            double *T = d.out(2), *grad = d.out(3);
+                            if (dcoords_out)  // (the launch adds: the atoms it does not name stay 0)
+                              if (hipError_t e = hipMemsetAsync(grad, 0, na * 8, nullptr)) return e;
+                            launch_template_energy(d.in(0), B, L, tf, d.out(0), d.out(1), transform_out ? T : nullptr, dcoords_out ? grad : nullptr, nullptr);
+                            return hipSuccess;
+                          });
+}
+
 int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx,
                   const float* offset, const uint8_t* is_angle, const int32_t* rst_offsets, const int32_t* rst_i,
                   const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float c, double max_norm,
@@ -144,19 +185,25 @@ int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t*
   return FD_OK;
 }
 
-int fd_scaffold_guide_step(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
-                           const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
-                           const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
-                           const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float c, float s,
-                           const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
-                           double* max_violation_out, double* gnorm_out, double* dfeats_out) {
-  if (!x || !x0 || !lens || !is_angle || !params || !x_out || !energy_out || !max_violation_out || !gnorm_out)
+}  // extern "C"
+
+// fd_scaffold_guide_step (energy_out [B][2], tpl_rmsd_out == nullptr, no template) and fd_scaffold_guide_step_tpl ([B][3])
+static int scaffold_guide_step_run(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                                   const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                                   const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                                   const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
+                                   const TemplateLists& tl, int n_energies, float c, float s, const float* z, uint64_t seed, int t,
+                                   int64_t seq_offset, float* x_out, double* energy_out, double* max_violation_out, double* gnorm_out,
+                                   double* dfeats_out, double* tpl_rmsd_out) {
+  if (!x || !x0 || !lens || !is_angle || !params || !x_out || !energy_out || !max_violation_out || !gnorm_out ||
+      (n_energies == 3 && !tpl_rmsd_out))
     return fail(FD_E_INVALID, "null argument");
   if (!known) return fail(FD_E_INVALID, "known is null");
   if (!fixed) return fail(FD_E_INVALID, "fixed is null");
   if (int rc = check_guide_shape(lens, B, L, F, params->feat_idx)) return rc;
   const RestraintLists rl{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w};
   if (int rc = check_restraints(rl, lens)) return rc;
+  if (int rc = check_template(tl, lens)) return rc;
   if (!std::isfinite(c)) return fail(FD_E_INVALID, "c = %g is not finite", (double)c);
   if (!std::isfinite(s)) return fail(FD_E_INVALID, "s = %g is not finite", (double)s);
   if (int rc = check_scaffold_guide(*params, known, fixed, lens, B, L, F)) return rc;
@@ -205,14 +252,26 @@ int fd_scaffold_guide_step(int device_id, const float* x, const float* x0, const
   HIP_TRY(bufs.alloc(nb * 8, &wk.e_rst));
   HIP_TRY(bufs.alloc(nb * 8, &wk.max_violation));
   HIP_TRY(bufs.zeros(nb * 8, &wk.e_clash));  // (stays 0 where there is no clash term)
+  HIP_TRY(bufs.zeros(nb * 8, &wk.e_tpl));    // (and these where no chain has a template entry)
+  HIP_TRY(bufs.zeros(nb * 8, &wk.rmsd_tpl));
   HIP_TRY(bufs.alloc(n * 8, &G));
   HIP_TRY(bufs.alloc(nb * 8, &gnorm));
-  launch_scaffold_energy(x0_dev, known_dev, fixed_dev, lens_dev, B, L, F, off, angle_mask, fx, rs, clash, wk, G, nullptr);
+  TemplateFit tf{};
+  const bool fit = tl.count() > 0;
+  if (fit) {
+    HIP_TRY(bufs.upload(tl.offsets, (nb + 1) * 4, &tf.offsets));
+    HIP_TRY(bufs.upload(tl.atom, tl.count() * 4, &tf.atom));
+    HIP_TRY(bufs.upload(tl.xyz, tl.count() * 24, &tf.xyz));
+    HIP_TRY(bufs.upload(tl.w, tl.count() * 8, &tf.w));
+  }
+  launch_scaffold_energy(x0_dev, known_dev, fixed_dev, lens_dev, B, L, F, off, angle_mask, fx, rs, clash, fit ? &tf : nullptr, wk, G, nullptr);
   launch_scaffold_update(state, G, fixed_dev, lens_dev, B, L, F, angle_mask, c, p.max_norm, s, z_dev, seed, t, seq_offset, gnorm, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   std::vector<float> state_host(n);
-  std::vector<double> grad_host(dfeats_out ? n : 0), e_rst(nb), e_clash(nb), maxv(nb), norm(nb);
+  std::vector<double> grad_host(dfeats_out ? n : 0), e_rst(nb), e_clash(nb), maxv(nb), norm(nb), e_tpl(nb), rmsd_tpl(nb);
+  HIP_TRY(hipMemcpy(e_tpl.data(), wk.e_tpl, nb * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rmsd_tpl.data(), wk.rmsd_tpl, nb * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(state_host.data(), state, n * 4, hipMemcpyDeviceToHost));
   if (dfeats_out) HIP_TRY(hipMemcpy(grad_host.data(), G, n * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(e_rst.data(), wk.e_rst, nb * 8, hipMemcpyDeviceToHost));
@@ -224,12 +283,41 @@ int fd_scaffold_guide_step(int device_id, const float* x, const float* x0, const
     const size_t o = (size_t)b * L * F, rows = (size_t)lens[b] * F;
     memcpy(x_out + o, state_host.data() + o, rows * 4);
     if (dfeats_out) memcpy(dfeats_out + o, grad_host.data() + o, rows * 8);
-    energy_out[2 * b] = e_rst[b];
-    energy_out[2 * b + 1] = e_clash[b];
+    energy_out[n_energies * b] = e_rst[b];
+    energy_out[n_energies * b + 1] = e_clash[b];
+    if (n_energies == 3) {
+      energy_out[3 * b + 2] = e_tpl[b];
+      tpl_rmsd_out[b] = rmsd_tpl[b];
+    }
     max_violation_out[b] = maxv[b];
     gnorm_out[b] = norm[b];
   }
   return FD_OK;
+}
+
+extern "C" {
+
+int fd_scaffold_guide_step(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                           const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                           const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                           const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float c, float s,
+                           const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
+                           double* max_violation_out, double* gnorm_out, double* dfeats_out) {
+  return scaffold_guide_step_run(device_id, x, x0, known, fixed, lens, B, L, F, is_angle, params, rst_offsets, rst_i, rst_j, rst_d0, rst_tol,
+                                 rst_w, TemplateLists{B, nullptr, nullptr, nullptr, nullptr}, 2, c, s, z, seed, t, seq_offset, x_out,
+                                 energy_out, max_violation_out, gnorm_out, dfeats_out, nullptr);
+}
+
+int fd_scaffold_guide_step_tpl(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                               const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                               const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                               const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
+                               const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz, const double* tpl_w, float c,
+                               float s, const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
+                               double* max_violation_out, double* gnorm_out, double* dfeats_out, double* tpl_rmsd_out) {
+  return scaffold_guide_step_run(device_id, x, x0, known, fixed, lens, B, L, F, is_angle, params, rst_offsets, rst_i, rst_j, rst_d0, rst_tol,
+                                 rst_w, TemplateLists{B, tpl_offsets, tpl_atom, tpl_xyz, tpl_w}, 3, c, s, z, seed, t, seq_offset, x_out,
+                                 energy_out, max_violation_out, gnorm_out, dfeats_out, tpl_rmsd_out);
 }
 
 int fd_nerf_scan(int device_id, const float* feats, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int center,

@@ -325,16 +325,30 @@ void launch_scaffold_update(float* x, double* G, const unsigned char* fixed, con
 struct SoftClash {
   double alpha, margin, w;     // launch_soft_clash's; w == 0: no clash launch, alpha and margin unread
 };
+// ---- superposition restraints (template_fit.hip; the statement is in its header and in include/fdmi.h).  A batch's templates,
+// packed per chain: chain b owns entries offsets[b] .. offsets[b + 1] - 1, its atoms strictly increasing inside [0, 3 lens[b])
+struct TemplateFit {
+  const int* offsets;          // [B + 1]
+  const int* atom;             // [n]
+  const double* xyz;           // [n][3] the targets
+  const double* w;             // [n] > 0
+};
+// energy [B], rmsd [B] and, unless null, transform [B][12] (R row-major, then t); unless dcoords is null the gradient is ADDED to
+// dcoords [B][3L][3] on the named atoms, which holds the terms launched before (a chain without entries: 0, 0, the identity)
+void launch_template_energy(const double* coords, int B, int L, const TemplateFit& t, double* energy, double* rmsd,
+                            double* transform, double* dcoords, hipStream_t s);
+
 struct ScaffoldWork {
   float* ang;                  // [B][L][F] the shifted rows the structure is built from
   double *coords, *gc;         // [B][3L][3] the structure and the energy's gradient on it
   double *e_rst, *max_violation, *e_clash;  // [B]; e_clash is written only where clash.w > 0
+  double *e_tpl, *rmsd_tpl;    // [B]; written only where there is a template
 };
-// the statement up to G: shift, launch_nerf_scan, launch_restraint_energy, launch_soft_clash (clash.w > 0) and, unless G is null,
-// launch_nerf_vjp on the shifted rows -> G [B][L][F], unmasked
+// the statement up to G: shift, launch_nerf_scan, launch_restraint_energy, launch_soft_clash (clash.w > 0),
+// launch_template_energy (tpl not null) and, unless G is null, launch_nerf_vjp on the shifted rows -> G [B][L][F], unmasked
 void launch_scaffold_energy(const float* x0, const float* known, const unsigned char* fixed, const int* lens, int B, int L, int F,
                             const SteerOffset& off, unsigned angle_mask, const NerfFeatures& fx, const Restraints& rs,
-                            const SoftClash& clash, const ScaffoldWork& wk, double* G, hipStream_t s);
+                            const SoftClash& clash, const TemplateFit* tpl, const ScaffoldWork& wk, double* G, hipStream_t s);
 
 // *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);

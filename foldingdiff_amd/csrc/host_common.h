@@ -334,4 +334,34 @@ inline int check_scaffold_guide(const fd_scaffold_guide_params& p, const float* 
   return FD_OK;
 }
 
+// ---- superposition restraints (fd_template_energy, fd_scaffold_guide_step_tpl, fd_sample_guided_inpaint_tpl)
+// a batch's packed templates as the host hands them over (check_lens has passed); all four null: no template
+struct TemplateLists {
+  int n_chains;
+  const int32_t *offsets, *atom;
+  const double *xyz, *w;
+  bool none() const { return !offsets; }
+  size_t count() const { return none() ? 0 : (size_t)offsets[n_chains]; }  // (once check_template has passed)
+};
+inline int check_template(const TemplateLists& t, const int32_t* lens) {
+  const int B = t.n_chains;
+  const int given = (t.offsets ? 1 : 0) + (t.atom ? 1 : 0) + (t.xyz ? 1 : 0) + (t.w ? 1 : 0);
+  if (given == 0) return FD_OK;
+  if (given != 4) return fail(FD_E_INVALID, "null argument: tpl_offsets, tpl_atom, tpl_xyz and tpl_w are given together or not at all");
+  if (t.offsets[0] != 0) return fail(FD_E_INVALID, "tpl_offsets[0]=%d must be 0", t.offsets[0]);
+  for (int b = 0; b < B; ++b)
+    if (t.offsets[b + 1] < t.offsets[b]) return fail(FD_E_INVALID, "tpl_offsets[%d]=%d is below tpl_offsets[%d]=%d", b + 1, t.offsets[b + 1], b, t.offsets[b]);
+  for (int b = 0; b < B; ++b)
+    for (int k = t.offsets[b]; k < t.offsets[b + 1]; ++k) {
+      const int n = 3 * lens[b];
+      if (t.atom[k] < 0 || t.atom[k] >= n) return fail(FD_E_INVALID, "template entry %d = atom %d outside chain %d's [0, %d)", k, t.atom[k], b, n);
+      if (k > t.offsets[b] && t.atom[k] <= t.atom[k - 1])
+        return fail(FD_E_INVALID, "template entry %d = atom %d after atom %d: a chain's atoms are strictly increasing", k, t.atom[k], t.atom[k - 1]);
+      if (!(t.w[k] > 0.0) || !std::isfinite(t.w[k])) return fail(FD_E_INVALID, "template entry %d: w=%g must be > 0 and finite", k, t.w[k]);
+      for (int d = 0; d < 3; ++d)
+        if (!std::isfinite(t.xyz[(size_t)k * 3 + d])) return fail(FD_E_INVALID, "template entry %d: target coordinate %d is not finite", k, d);
+    }
+  return FD_OK;
+}
+
 }  // namespace fdmi

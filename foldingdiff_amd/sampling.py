@@ -1695,11 +1695,23 @@ def _run_fd_sample_guided_inpaint(h, x0: np.ndarray, lens: np.ndarray, visits: n
         *(_binding.ptr(a) for a in packed), _binding.ptr(out), _binding.ptr(energy), _binding.ptr(worst)))
 
 
+def _run_fd_sample_guided_inpaint_tpl(h, x0: np.ndarray, lens: np.ndarray, visits: np.ndarray, coef: np.ndarray, known: np.ndarray,
+                                      fixed: np.ndarray, known_coef: np.ndarray, seed: int, guide_tab: np.ndarray, params, packed,
+                                      tpl_packed, out: np.ndarray, energy: np.ndarray, worst: np.ndarray, tpl_rmsd: np.ndarray) -> None:
+    """The same with superposition restraints (fd_sample_guided_inpaint_tpl): ``energy`` is ``[B, 3]``."""
+    B, L, _ = x0.shape
+    _binding.check(_binding.load().fd_sample_guided_inpaint_tpl(
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, _binding.ptr(visits), len(visits), _binding.ptr(coef), None, _binding.ptr(known),
+        _binding.ptr(fixed), _binding.ptr(known_coef), None, C.c_uint64(seed), C.c_int64(0), _binding.ptr(guide_tab), C.byref(params),
+        *(_binding.ptr(a) for a in packed), *(_binding.ptr(a) for a in tpl_packed), _binding.ptr(out), _binding.ptr(energy),
+        _binding.ptr(worst), _binding.ptr(tpl_rmsd)))
+
+
 @torch.no_grad()
 def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.ndarray], restraints, num_steps: Optional[int] = None,
                   eta: float = 1.0, scale: float = 1.0, max_norm: float = 1.0, guide_from: Optional[int] = None,
                   clash_weight: float = 0.0, clash_alpha: float = 0.63, clash_margin: float = 0.15, batch_size: int = 512,
-                  seed: Optional[int] = None, feature_key: str = "angles"):
+                  seed: Optional[int] = None, feature_key: str = "angles", templates=None):
     """Restraint guidance combined with replacement (``fd_sample_guided_inpaint``): one backbone per item whose
     elements marked in ``fixed[i]`` are held to ``known[i]`` as in ``inpaint``, while the rest is steered toward distance
     restraints as in ``guide``.  The structure a visit is scored on carries the held elements exactly -- their known values,
@@ -1716,8 +1728,14 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
     Returns ``(samples, info)`` as ``guide`` does, ``info`` with ``clash_energy`` (float64 ``[n]``, 0 without a clash term)
     beside ``energy`` and ``max_violation``.  ``ValueError``, before any device call, for what ``inpaint`` and ``guide``
     reject and a negative or non-finite clash setting.  Single device, final states only; not combined with resampling
-    schedules, the second-order solver, steering or ties.  Distances do not tell a scaffold from its mirror image, and how
-    often one comes out mirrored -- like designability -- is unmeasured: there are no trained weights here."""
+    schedules, the second-order solver, steering or ties.  Distances do not tell a scaffold from its mirror image.
+
+    ``templates`` (one ``structures.Template`` per item, ``None`` entries allowed, or a single one for all) adds
+    the superposition term to the energy that is followed -- the squared deviation of the named atoms from the template after
+    the optimal fit by a proper rotation, which a mirror image cannot satisfy (``fd_sample_guided_inpaint_tpl``); ``info`` then
+    also holds ``template_energy`` and ``template_rmsd`` (float64 ``[n]``) of the final states.  Without ``templates`` the call
+    is the one made before the term existed.  How often a scaffold comes out in the wrong hand with a trained model -- like
+    designability -- is unmeasured: there are no trained weights here."""
     from . import structures
     _check_few_step(None, "uniform", num_steps, eta)
     n = len(known)
@@ -1737,6 +1755,9 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
         raise ValueError("known is empty")
     structures.pack_restraints(restraints, lengths)   # (its checks, before anything is drawn)
     per_chain = [restraints] * n if restraints is None or isinstance(restraints, structures.Restraints) else list(restraints)
+    if templates is not None:
+        structures.pack_templates(templates, lengths)
+        tpl_per_chain = [templates] * n if isinstance(templates, structures.Template) else list(templates)
     T = dset.timesteps
     betas = dset.alpha_beta_terms["betas"]
     visits = _few_step_visits(betas, T if num_steps is None else int(num_steps), None, "uniform", -3.0)
@@ -1747,7 +1768,7 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
     h = model.prepare(betas, dset.feature_is_angular[feature_key])
     on_gpu = _on_device(model, "_run_fd_sample_guided_inpaint")
     samples: List[np.ndarray] = []
-    energies, clashes, worsts = [], [], []
+    energies, clashes, worsts, tpl_energies, tpl_rmsds = [], [], [], [], []
     with contextlib.ExitStack() as stack:
         if seed is not None:
             stack.enter_context(torch.random.fork_rng(devices=[]))
@@ -1763,17 +1784,28 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
                 fb[i, :l] = fs[lo + i]
             philox_seed = _draw_philox_seed()
             out = np.empty((B, L, F), dtype=np.float32)
-            energy, worst = np.empty((B, 2), dtype=np.float64), np.empty(B, dtype=np.float64)
+            energy, worst = np.empty((B, 2 if templates is None else 3), dtype=np.float64), np.empty(B, dtype=np.float64)
             packed = structures.pack_restraints(per_chain[lo: lo + B], these)
             with _packed_batch(model, these, on_gpu):   # positions beyond an item's length are cut away below, as in sample()
-                _run_fd_sample_guided_inpaint(h, x0, _lens_array(these, B, L), visits, coef, kb, fb, known_coef, philox_seed, guide_tab,
-                                              params, packed, out, energy, worst)
+                if templates is None:
+                    _run_fd_sample_guided_inpaint(h, x0, _lens_array(these, B, L), visits, coef, kb, fb, known_coef, philox_seed, guide_tab,
+                                                  params, packed, out, energy, worst)
+                else:
+                    tpl_rmsd = np.empty(B, dtype=np.float64)
+                    _run_fd_sample_guided_inpaint_tpl(h, x0, _lens_array(these, B, L), visits, coef, kb, fb, known_coef, philox_seed,
+                                                      guide_tab, params, packed, structures.pack_templates(tpl_per_chain[lo: lo + B], these),
+                                                      out, energy, worst, tpl_rmsd)
+                    tpl_energies.append(energy[:, 2].copy())
+                    tpl_rmsds.append(tpl_rmsd)
             samples.extend(s[0] for s in _shift_trim(model, torch.from_numpy(out[None]), these, offset, angular))
             energies.append(energy[:, 0].copy())
             clashes.append(energy[:, 1].copy())
             worsts.append(worst)
-    return samples, {"energy": np.concatenate(energies), "clash_energy": np.concatenate(clashes),
-                     "max_violation": np.concatenate(worsts), "visits": visits, "guide": guide_tab}
+    info = {"energy": np.concatenate(energies), "clash_energy": np.concatenate(clashes), "max_violation": np.concatenate(worsts),
+            "visits": visits, "guide": guide_tab}
+    if templates is not None:
+        info["template_energy"], info["template_rmsd"] = np.concatenate(tpl_energies), np.concatenate(tpl_rmsds)
+    return samples, info
 
 
 _run_fd_sample_guided_inpaint_default = _run_fd_sample_guided_inpaint
@@ -1782,7 +1814,8 @@ _run_fd_sample_guided_inpaint_default = _run_fd_sample_guided_inpaint
 def scaffold_segments(model, dset, motif_angles: np.ndarray, motif_backbone: np.ndarray, segments: Sequence[Tuple[int, int, int]],
                       total_lengths: Sequence[int], pin_lead_angle: bool = True, feature_key: str = "angles",
                       restraints=None, restraint_weight: float = 1.0, restraint_tol: float = 0.0,
-                      restraint_atoms: Sequence[str] = ("CA",), **kwargs):
+                      restraint_atoms: Sequence[str] = ("CA",), placement: str = "distances", template_weight: float = 1.0,
+                      template_atoms: Sequence[str] = ("N", "CA", "C"), **kwargs):
     """Scaffold a discontiguous motif: one backbone of each of ``total_lengths`` in which every segment
     ``(motif_start, motif_stop, placed_at)`` of ``segments`` holds rows ``motif_start .. motif_stop - 1`` of ``motif_angles``
     (``[m, F]`` data-space angles, what ``structures.featurize`` returns) at residues ``placed_at ..`` by replacement, and the
@@ -1794,16 +1827,28 @@ def scaffold_segments(model, dset, motif_angles: np.ndarray, motif_backbone: np.
     angle inside the segment's first residue from there), or, for a segment that starts at motif residue 0, to the segment's
     own first ``tau`` as ``structures.motif_backbone`` does.  ``kwargs`` go to ``guide_inpaint``.
 
+    ``placement`` chooses what places the segments: ``"distances"`` (the default, as above: a mirror-image placement costs
+    nothing), ``"template"`` -- ``structures.motif_template`` over ``template_atoms`` of every held residue with weight
+    ``template_weight``, fitted by a proper rotation, which fixes the hand too; ``restraints`` is still added,
+    the segment distances are not -- or ``"both"``.  With a template ``info`` also holds ``template_energy`` and
+    ``template_rmsd``.
+
     ``ValueError`` for overlapping segments, a segment outside the motif or outside one of the chains.  Returns
-    ``guide_inpaint``'s ``(samples, info)``; see there on mirror images."""
+    ``guide_inpaint``'s ``(samples, info)``; ``structures.template_energy(..., mirror=True)`` measures which hand came out."""
     from . import structures
     motif_angles = np.asarray(motif_angles, dtype=np.float32)
     assert motif_angles.ndim == 2 and motif_angles.shape[1] == model.n_inputs, f"motif_angles is {motif_angles.shape}, expected [m, {model.n_inputs}]"
     m, F = motif_angles.shape
     total_lengths = [int(l) for l in total_lengths]
+    if placement not in ("distances", "template", "both"):
+        raise ValueError(f"placement={placement!r}: expected 'distances', 'template' or 'both'")
     rst = structures.segment_restraints(motif_backbone, segments, weight=restraint_weight, tol=restraint_tol, atoms=restraint_atoms)
-    if restraints is not None:
+    if placement == "template":   # (the call above has still checked the segments)
+        rst = restraints
+    elif restraints is not None:
         rst = rst + restraints
+    if placement != "distances":
+        kwargs = dict(kwargs, templates=structures.motif_template(motif_backbone, segments, atoms=template_atoms, weight=template_weight))
     segs = [tuple(int(v) for v in seg) for seg in segments]   # (segment_restraints has checked them against the motif and each other)
     if 3 * m != len(np.asarray(motif_backbone).reshape(-1, 3)):
         raise ValueError(f"motif_angles has {m} residues, motif_backbone {len(np.asarray(motif_backbone).reshape(-1, 3)) // 3}")

@@ -458,7 +458,7 @@ class Restraints:
 
     Distances alone do not fix handedness: a structure and its mirror image cost the same.  Restraints among L-amino-acid
     backbone segments mostly do tell the two apart, because each segment's own internal angles enter the sampler's state and
-    are not mirrored; that is a tendency, not a guarantee."""
+    are not mirrored; that is a tendency, not a guarantee.  ``Template`` is the term that does fix it."""
 
     def __init__(self, i, j, d0, tol, w):
         self.i = np.ascontiguousarray(np.asarray(i, dtype=np.int64).reshape(-1).astype(np.int32))
@@ -601,6 +601,132 @@ def restraint_energy(coords: Sequence[np.ndarray], restraints, device: int = 0, 
     if not return_gradient:
         return energy, worst
     return energy, worst, [grad[b, : 3 * lens[b]].copy() for b in range(B)]
+
+
+# ---------------------------------------------------------------------------------------------------- superposition restraints
+class Template:
+    """One chain's superposition restraint (``fd_template_energy``): ``atoms`` (int32 atom indices ``3 * residue
+    + {0 N, 1 CA, 2 C}``, strictly increasing), ``xyz`` (float64 ``[n, 3]``, the position each should take in the template's
+    own frame) and ``w`` (float64, finite, ``> 0``).  The chain costs ``sum w |r|^2`` with ``r`` the residuals after the optimal
+    superposition of the template on the named atoms by a PROPER rotation and a translation: unlike distances
+    (``Restraints``), this tells a structure from its mirror image.  Entries are kept sorted by atom."""
+
+    def __init__(self, atoms, xyz, w=1.0):
+        atoms = np.asarray(atoms, dtype=np.int64).reshape(-1)
+        xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+        n = len(atoms)
+        if len(xyz) != n:
+            raise ValueError(f"{n} atoms, {len(xyz)} target positions")
+        w = np.broadcast_to(np.asarray(w, dtype=np.float64), (n,))
+        order = np.argsort(atoms, kind="stable")
+        self.atoms = np.ascontiguousarray(atoms[order].astype(np.int32))
+        self.xyz = np.ascontiguousarray(xyz[order])
+        self.w = np.ascontiguousarray(w[order])
+        if n and (self.atoms[0] < 0 or (np.diff(self.atoms) <= 0).any()):
+            raise ValueError("a template names distinct atoms, each >= 0")
+        if not np.isfinite(self.xyz).all():
+            raise ValueError("xyz must be finite")
+        if not (np.isfinite(self.w).all() and (self.w > 0).all()):
+            raise ValueError("w must be finite and > 0")
+
+    def __len__(self) -> int:
+        return len(self.atoms)
+
+    def min_length(self) -> int:
+        """The residues a chain needs for every atom named here to exist."""
+        return 0 if not len(self) else int(self.atoms[-1]) // 3 + 1
+
+    def mirrored(self) -> "Template":
+        """The same template reflected in z: what the mirror image of a fitting structure fits."""
+        return Template(self.atoms, self.xyz * np.array([1.0, 1.0, -1.0]), self.w)
+
+
+def motif_template(motif_backbone: np.ndarray, segments: Sequence[Tuple[int, int, int]], atoms: Sequence[str] = ("N", "CA", "C"),
+                   weight: float = 1.0) -> Template:
+    """"These segments sit in space as in the motif, in the motif's hand": ``segment_restraints``' ``segments``
+    ``(motif_start, motif_stop, placed_at)`` -- residues ``motif_start .. motif_stop - 1`` of ``motif_backbone`` (``[3 m, 3]``,
+    N / CA / C per residue) take the residues ``placed_at ..`` of the new chain -- as one ``Template`` over the chosen ``atoms``
+    of every segment residue, with the motif's own coordinates as targets.  ``ValueError`` for what ``segment_restraints``
+    rejects."""
+    xyz = np.asarray(motif_backbone, dtype=np.float64).reshape(-1, 3)
+    if len(xyz) % 3:
+        raise ValueError(f"motif_backbone has {len(xyz)} atoms (3 per residue)")
+    m = len(xyz) // 3
+    unknown = [a for a in atoms if a not in BACKBONE_ATOMS]
+    if unknown or not len(atoms) or len(set(atoms)) != len(atoms):
+        raise ValueError(f"atoms={tuple(atoms)!r}: distinct entries of {sorted(BACKBONE_ATOMS)}")
+    if not np.isfinite(xyz).all():
+        raise ValueError("motif_backbone is not finite")
+    rows, placed = [], []
+    for k, seg in enumerate(segments):
+        if len(seg) != 3:
+            raise ValueError("every segment is (motif_start, motif_stop, placed_at)")
+        lo, hi, at = (int(v) for v in seg)
+        if not 0 <= lo < hi <= m:
+            raise ValueError(f"segment {k} = motif residues [{lo}, {hi}) is empty or outside the motif's {m} residues")
+        if at < 0:
+            raise ValueError(f"segment {k} is placed at residue {at}")
+        rows.extend(range(lo, hi))
+        placed.extend(range(at, at + hi - lo))
+    if len(set(rows)) != len(rows):
+        raise ValueError("two segments share a motif residue")
+    if len(set(placed)) != len(placed):
+        raise ValueError("two segments share a placed residue")
+    which = sorted(BACKBONE_ATOMS[a] for a in atoms)
+    return Template([3 * p + a for p in placed for a in which], [xyz[3 * r + a] for r in rows for a in which] or np.zeros((0, 3)),
+                    float(weight))
+
+
+def pack_templates(templates, lengths: Sequence[int]):
+    """``fd_template_energy``'s packed layout for a batch: ``(tpl_offsets int32 [B + 1], tpl_atom int32 [n], tpl_xyz float64
+    [n, 3], tpl_w float64 [n])`` from one ``Template`` per chain (``None``: none), or a single one for every chain.
+    ``ValueError`` for a template on an atom beyond its chain."""
+    lengths = [int(l) for l in lengths]
+    per = [templates] * len(lengths) if templates is None or isinstance(templates, Template) else list(templates)
+    if len(per) != len(lengths):
+        raise ValueError(f"{len(per)} templates for {len(lengths)} chains")
+    per = [Template([], np.zeros((0, 3))) if t is None else t for t in per]
+    for b, (t, n) in enumerate(zip(per, lengths)):
+        if t.min_length() > n:
+            raise ValueError(f"chain {b} has {n} residues, its template needs {t.min_length()}")
+    offsets = np.concatenate([[0], np.cumsum([len(t) for t in per])]).astype(np.int32)
+    return (np.ascontiguousarray(offsets), np.ascontiguousarray(np.concatenate([t.atoms for t in per]).astype(np.int32)),
+            np.ascontiguousarray(np.concatenate([t.xyz for t in per]).astype(np.float64).reshape(-1, 3)),
+            np.ascontiguousarray(np.concatenate([t.w for t in per]).astype(np.float64)))
+
+
+def template_energy(coords: Sequence[np.ndarray], templates, device: int = 0, return_gradient: bool = False,
+                    return_transform: bool = False, mirror: bool = False):
+    """Energy and RMSD of superposition restraints on a batch of backbones, in one ``fd_template_energy`` call.  ``coords``:
+    one ``[3 len_i, 3]`` array per chain; ``templates``: as for ``pack_templates``.  Returns ``(energy, rmsd)``, float64 ``[B]``
+    each (``rmsd``: the weighted RMSD of the named atoms after the optimal proper fit, 0 without entries); with
+    ``return_gradient`` the list of the energy's gradients with respect to the coordinates (``[3 len_i, 3]``, zero on atoms
+    not named) follows, and with ``return_transform`` the fits ``(R [B, 3, 3], t [B, 3])`` with ``R m + t`` the template laid
+    on the chain.  ``mirror=True`` fits the template reflected in z instead: comparing ``rmsd`` with the ``rmsd`` of
+    ``mirror=True`` says which hand a placement has, which no distance can."""
+    xs = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in coords]
+    assert xs and all(len(x) % 3 == 0 and len(x) > 0 for x in xs), "coords is a list of [3 len, 3] arrays"
+    lens = np.array([len(x) // 3 for x in xs], dtype=np.int32)
+    if mirror:
+        one = templates is None or isinstance(templates, Template)
+        flip = lambda t: None if t is None else t.mirrored()   # noqa: E731
+        templates = flip(templates) if one else [flip(t) for t in templates]
+    packed = pack_templates(templates, lens.tolist())
+    B, L = len(xs), int(lens.max())
+    xyz = np.zeros((B, 3 * L, 3), dtype=np.float64)
+    for b, x in enumerate(xs):
+        xyz[b, : len(x)] = x
+    energy, rmsd = np.empty(B, dtype=np.float64), np.empty(B, dtype=np.float64)
+    grad = np.empty((B, 3 * L, 3), dtype=np.float64) if return_gradient else None
+    fit = np.empty((B, 12), dtype=np.float64) if return_transform else None
+    _binding.check(_binding.load().fd_template_energy(device, ptr(xyz), ptr(lens), B, L, *(ptr(a) for a in packed), ptr(energy), ptr(rmsd),
+                                                      ptr(fit), ptr(grad)))
+    result = [energy, rmsd]
+    if return_gradient:
+        result.append([grad[b, : 3 * lens[b]].copy() for b in range(B)])
+    if return_transform:
+        result.append((fit[:, :9].reshape(B, 3, 3).copy(), fit[:, 9:].copy()))
+    return tuple(result)
 
 
 # ---------------------------------------------------------------------------------------------------- relaxation in torsion space

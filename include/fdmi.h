@@ -642,7 +642,7 @@ int fd_nerf_vjp_feats(int device_id, const double* coords, const int32_t* lens, 
  *   rst_d0, rst_tol, rst_w double[R], finite, d0 >= 0, tol >= 0, w >= 0
  * Per restraint: d = |p_i - p_j|, v = max(0, |d - d0| - tol), E_b += w v^2, and where v > 0 and d > 0
  * dcoords[i] += 2 w v sign(d - d0) (p_i - p_j) / d, the opposite on j.  tol = 0 is harmonic; d0 = 0, tol = 8 is "within 8 A".
- * Distances do not tell a structure from its mirror image.
+ * Distances do not tell a structure from its mirror image; fd_template_energy's term does.
  *   coords             float64 [B][3L][3] (host), finite on the atoms below 3 lens[b]; lens int32[B] in [1, min(L, 2048)]
  *   energy_out         double[B]; max_violation_out double[B]: the largest v, 0 without restraints
  *   dcoords_out        float64 [B][3L][3] (atoms at or beyond 3 lens[b]: 0), or NULL
@@ -792,7 +792,8 @@ int fd_relax(int device_id, const float* feats, const float* anchor, const int32
 /* ---- restraint guidance combined with replacement: discontiguous motifs.  Replacement (fd_sample_inpaint)
  * holds chosen elements of the angle rows, so a held run of residues reproduces that segment's backbone exactly, but says nothing
  * about where two held segments sit relative to each other; distance restraints (fd_sample_guided) place them.  Distances do
- * not tell a structure from its mirror image, and whether such scaffolds are designable is unmeasured.
+ * not tell a structure from its mirror image -- the superposition term below (fd_sample_guided_inpaint_tpl) does -- and whether
+ * such scaffolds are designable is unmeasured.
  *
  * The scaffold-guide statement, per element o = (b, l, f) of [B][L][F].  After a visit, x is the state it left and x0 its
  * prediction of the clean state; fixed is uint8 [B][L][F], known float32 [B][L][F] in model space as for fd_sample_inpaint:
@@ -861,6 +862,80 @@ int fd_sample_guided_inpaint(fd_model* m, const float* x_init, const int32_t* le
                              const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
                              const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w, float* out,
                              double* energy_out, double* max_violation_out);
+
+/* ---- superposition restraints: place chosen atoms in 3D, handedness included.  The squared deviation of chosen
+ * atoms from a template after the optimal superposition by a PROPER rotation: a mirror image cannot be superposed, so it costs
+ * energy, which no set of distances can make it do.
+ *
+ * The template statement.  Chain b's entries are k = tpl_offsets[b] .. tpl_offsets[b + 1] - 1: an atom index a_k inside the chain's
+ * [0, 3 lens[b]) (3 * residue + {0 N, 1 CA, 2 C}), strictly increasing within the chain, a target m_k and a weight w_k > 0.
+ *     W   = sum w_k;   cp = sum w_k p[a_k] / W;   cm = sum w_k m_k / W
+ *     M[i][j] = sum w_k (m_k - cm)_i (p[a_k] - cp)_j        centred: a second pass over the entries, so that a template far from
+ *                                                           the origin loses nothing
+ *     R   = the proper rotation that maximises trace(R^T M) -- R (m - cm) ~ p - cp --, by Horn's quaternion method in fp64
+ *     r_k = (p[a_k] - cp) - R (m_k - cm)                    explicit residuals
+ *     E_tpl = sum w_k |r_k|^2;   rmsd = sqrt(E_tpl / W);   dE/dp[a_k] = 2 w_k r_k
+ *     transform: R (row-major), t = cp - R cm               (R m + t superposes the template on the chain)
+ * The gradient is exact by the envelope theorem: R is optimal, so E does not change to first order with R, and sum w_k r_k = 0,
+ * so the centroid adds nothing.  E and rmsd come from the explicit residuals, never from the eigenvalue: at a perfect fit the
+ * eigenvalue form cancels.  A chain with no entries has E = 0 and rmsd = 0, the identity transform, and receives no gradient.
+ * One or two entries, or collinear targets, are allowed: the optimal R is then not unique, but every optimal R gives the same
+ * residuals (transform_out then holds one of them).  OUTSIDE THE DOMAIN: where the two largest eigenvalues of Horn's 4x4 matrix
+ * coincide with non-collinear points the optimal rotation jumps and the energy is not differentiable; that is a set of measure
+ * zero (a structure as close to the template's mirror image as to the template), and what is returned there is one of the
+ * optimal fits.  One template per chain.
+ * No floating-point atomics: one 256-lane workgroup per chain, three lane-strided passes over the entries, every sum in an order
+ * fixed by (entry count, lane); each named atom is written by the one lane that owns its entry.  Two calls give the same bits,
+ * and a chain's bits do not depend on the batch it is in.
+ *
+ * fd_template_energy: the statement on host arrays, model-free and synchronous like fd_restraint_energy.
+ *   coords         float64 [B][3L][3] (host), finite on the atoms below 3 lens[b]; lens int32[B] in [1, min(L, 2048)]
+ *   tpl_offsets    int32[B + 1], tpl_offsets[0] == 0, non-decreasing; n = tpl_offsets[B] may be 0
+ *   tpl_atom       int32[n];  tpl_xyz double[n][3], finite;  tpl_w double[n], finite and > 0
+ *                  (all four NULL: no template anywhere; some but not all NULL is an error)
+ *   energy_out, rmsd_out   double[B]
+ *   transform_out  double[B][12] R row-major then t, or NULL
+ *   dcoords_out    float64 [B][3L][3], or NULL: written everywhere, 0 on the atoms that are not named
+ * A bad call -- non-monotone offsets or tpl_offsets[0] != 0, an atom outside [0, 3 lens[b]) or atoms not strictly increasing
+ * within a chain, a weight that is not finite or <= 0, a non-finite target, some but not all of the four arrays NULL, and what
+ * fd_restraint_energy rejects for coords and lens: FD_E_INVALID before any device call, the offending word in fd_last_error(),
+ * outputs untouched. */
+int fd_template_energy(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* tpl_offsets,
+                       const int32_t* tpl_atom, const double* tpl_xyz, const double* tpl_w, double* energy_out, double* rmsd_out,
+                       double* transform_out, double* dcoords_out);
+
+/* fd_scaffold_guide_step_tpl: fd_scaffold_guide_step whose statement gains one line after the clash line,
+ *     E_tpl, rmsd, gc += the template statement on coords        (that launch is skipped when no chain has an entry)
+ * with fd_scaffold_guide_step's arguments and meaning otherwise.
+ *   tpl_*          as in fd_template_energy; all four NULL: no template, and every output fd_scaffold_guide_step shares equals
+ *                  that entry's bit for bit
+ *   energy_out     double[B][3] restraint | clash | template of p's structure;  tpl_rmsd_out double[B] (0 without entries)
+ * Everything fd_scaffold_guide_step and fd_template_energy reject, a NULL tpl_rmsd_out: FD_E_INVALID before any device call,
+ * outputs untouched. */
+int fd_scaffold_guide_step_tpl(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                               const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                               const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                               const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
+                               const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz, const double* tpl_w, float c,
+                               float s, const float* z, uint64_t seed, int t, int64_t seq_offset, float* x_out, double* energy_out,
+                               double* max_violation_out, double* gnorm_out, double* dfeats_out, double* tpl_rmsd_out);
+
+/* fd_sample_guided_inpaint_tpl: fd_sample_guided_inpaint whose visits are followed by fd_scaffold_guide_step_tpl's statement:
+ * seven launches per visit at most (shift, scan, restraints, clashes, template, derivative, update).  The plain sampler's
+ * captured step graph is not captured again.
+ *   tpl_*          as in fd_scaffold_guide_step_tpl; all four NULL: out, the two energies and max_violation_out are
+ *                  fd_sample_guided_inpaint's bit for bit
+ *   energy_out     double[B][3] restraint | clash | template and tpl_rmsd_out double[B]: the statement with p = the FINAL state
+ * Everything fd_sample_guided_inpaint and fd_template_energy reject, a NULL tpl_rmsd_out: FD_E_INVALID before any device call,
+ * outputs untouched.  Not offered in fd_relax, fd_sample_guided or fd_guide_step, nor with jumps, the second-order solver,
+ * steering or ties; single device. */
+int fd_sample_guided_inpaint_tpl(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits,
+                                 int n_visits, const float* coef, const float* noise, const float* known, const uint8_t* fixed,
+                                 const float* known_coef, const float* known_noise, uint64_t seed, int64_t seq_offset,
+                                 const float* guide, const fd_scaffold_guide_params* params, const int32_t* rst_offsets,
+                                 const int32_t* rst_i, const int32_t* rst_j, const double* rst_d0, const double* rst_tol,
+                                 const double* rst_w, const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz,
+                                 const double* tpl_w, float* out, double* energy_out, double* max_violation_out, double* tpl_rmsd_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
