@@ -93,6 +93,27 @@ class FdRelaxParams(C.Structure):
     ]
 
 
+class FdSymmetryParams(C.Structure):
+    """``fd_symmetry_params`` of include/fdmi.h."""
+    _fields_ = [
+        ("clash_alpha", C.c_double),
+        ("clash_margin", C.c_double),
+        ("w_clash", C.c_double),
+        ("w_contact", C.c_double),
+        ("d_on", C.c_double),
+        ("d_off", C.c_double),
+        ("w_radial", C.c_double),
+        ("r_max", C.c_double),
+        ("lever", C.c_double),
+        ("max_shift", C.c_double),
+        ("step0", C.c_double),
+        ("grow", C.c_double),
+        ("shrink", C.c_double),
+        ("pose_iters", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 # every symbol include/fdmi.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -154,6 +175,14 @@ _SIGNATURES = {
                                              _P, _P, _P]),
     "fd_sample_guided_inpaint_tpl": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int64, _P,
                                                C.POINTER(FdScaffoldGuideParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_symmetry_energy": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(FdSymmetryParams), _P, _P, _P, _P]),
+    "fd_symmetry_dock": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(FdSymmetryParams), C.c_int, _P, _P, _P, _P, _P, _P]),
+    "fd_scaffold_guide_step_sym": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(FdScaffoldGuideParams), _P, _P,
+                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(FdSymmetryParams), _P, C.c_float, C.c_float,
+                                             _P, C.c_uint64, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_sample_guided_inpaint_sym": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int64, _P,
+                                               C.POINTER(FdScaffoldGuideParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               C.POINTER(FdSymmetryParams), _P, _P, _P, _P, _P, _P, _P]),
     "fd_nerf_scan": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "fd_relax_energy": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(FdRelaxParams), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                   _P]),

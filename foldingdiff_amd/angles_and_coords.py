@@ -95,12 +95,39 @@ def write_backbone_with_o_pdb(coords4: np.ndarray, out_fname: str) -> str:
     return out_fname
 
 
-def read_pdb_backbone(fname: str) -> np.ndarray:
-    """[3N, 3] coordinates of the ATOM records of a backbone PDB (fixed columns 31-54)."""
+def write_assembly_pdb(chains, out_fname: str) -> str:
+    """Write several backbones (each 3N coordinates, N, CA, C per residue: ``structures.cyclic_assembly``) as ONE PDB file in
+    ``write_coords_to_pdb``'s ATOM line layout: chain IDs A, B, ... (at most 26), atom serials running on through the file,
+    residues numbered from 1 in every chain, and a TER record behind each chain.  Returns ``out_fname``."""
+    chains = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in chains]
+    assert 1 <= len(chains) <= 26, f"Expected 1 to 26 chains, got {len(chains)}"
+    lines = []
+    serial = 0
+    for k, coords in enumerate(chains):
+        assert len(coords) % 3 == 0 and len(coords), f"Expected 3N coords, got {len(coords)}"
+        chain_id = chr(ord("A") + k)
+        for j, (x, y, z) in enumerate(coords):
+            name, element = _ATOMS[j % 3]
+            atom_field = f" {name:<3}" if len(name) < 4 else name
+            lines.append(
+                f"ATOM  {((serial % 99999) + 1):>5d} {atom_field} GLY {chain_id}{((j // 3) % 9999 + 1):>4d}    "
+                f"{x:>8.3f}{y:>8.3f}{z:>8.3f}{1.0:>6.2f}{5.0:>6.2f}          {element:>2}  ")
+            serial += 1
+        lines.append(f"TER   {((serial % 99999) + 1):>5d}      GLY {chain_id}{((len(coords) // 3 - 1) % 9999 + 1):>4d}")
+        serial += 1
+    lines.append("END")
+    with open(out_fname, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return out_fname
+
+
+def read_pdb_backbone(fname: str, chain: Optional[str] = None) -> np.ndarray:
+    """[3N, 3] coordinates of the ATOM records of a backbone PDB (fixed columns 31-54); ``chain``: only that chain ID's
+    (column 22)."""
     out = []
     with open(fname) as fh:
         for line in fh:
-            if line.startswith("ATOM"):
+            if line.startswith("ATOM") and (chain is None or line[21] == chain):
                 out.append([float(line[30:38]), float(line[38:46]), float(line[46:54])])
     return np.asarray(out, dtype=np.float64)
 

@@ -23,7 +23,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "_lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfdmi.so")
 SOURCES = ["api.hip", "api_weights.hip", "api_comm.hip", "api_run.hip", "api_structures.hip", "api_hooks.hip", "gemm_f32.hip", "gemm_img.hip", "gemm_ws.hip", "gemm_ln_rows.hip", "attention_f32.hip", "attention_img.hip", "attention_gen.hip", "seq_attn.hip", "seq_attn16.hip", "ffn16.hip", "rowwise.hip",
-           "rowwise_img.hip", "inpaint_jump.hip", "loss.hip", "loss_variants.hip", "nerf.hip", "internal_coords.hip", "tm_score.hip", "psea.hip", "dssp.hip", "tm_align.hip", "tm_align_starts.hip", "clash_lddt.hip", "angle_stats.hip", "steer.hip", "repeat_tie.hip", "nerf_vjp.hip", "nerf_scan.hip", "relax.hip", "guide_scaffold.hip", "template_fit.hip"]
+           "rowwise_img.hip", "inpaint_jump.hip", "loss.hip", "loss_variants.hip", "nerf.hip", "internal_coords.hip", "tm_score.hip", "psea.hip", "dssp.hip", "tm_align.hip", "tm_align_starts.hip", "clash_lddt.hip", "angle_stats.hip", "steer.hip", "repeat_tie.hip", "nerf_vjp.hip", "nerf_scan.hip", "relax.hip", "guide_scaffold.hip", "template_fit.hip", "symmetry.hip"]
 HEADERS = [os.path.join(CSRC, "fdmi_kernels.h"), os.path.join(CSRC, "img_common.h"), os.path.join(CSRC, "horn_fit.h"),
            os.path.join(CSRC, "launch_common.h"), os.path.join(CSRC, "host_common.h"), os.path.join(CSRC, "model.h"), os.path.join(CSRC, "weight_pack.h"), os.path.join(CSRC, "tm_search.h"), os.path.join(CSRC, "tm_align_common.h"), os.path.join(CSRC, "wrap_pi.h"), os.path.join(CSRC, "nerf_place.h"), os.path.join(CSRC, "smooth_l1_term.h"), os.path.join(CSRC, "philox_normal.h"), os.path.join(CSRC, "inpaint_replace.h"), os.path.join(CSRC, "strided_update.h"), os.path.join(CSRC, "solver_update.h"), os.path.join(CSRC, "p_sample_update.h"), os.path.join(CSRC, "block_sum.h"), os.path.join(CSRC, "guide_element.h"), os.path.join(os.path.dirname(PKG_DIR), "include", "fdmi.h")]
 ARCH = "gfx950"

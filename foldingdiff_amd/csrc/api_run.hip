@@ -19,6 +19,7 @@
 #include "fdmi_kernels.h"
 #include "host_common.h"
 #include "model.h"
+#include "symmetry_host.h"
 
 using namespace fdmi;
 
@@ -896,6 +897,8 @@ int guided_host_run(fd_model* m, const GuidedHostRun& a) {
 // their x0 -- and the scaffold-guide statement's launches (guide_scaffold.hip) behind every visit.  The entry has checked every
 // argument; a.states = K, final state only.  The tables, the restraints and the work buffers die with this frame.  With a
 // template (fd_sample_guided_inpaint_tpl) the statement has one more launch, template_fit.hip's.
+// With symmetry orders (fd_sample_guided_inpaint_sym) launch_symmetry_guide's launches follow the template's, and
+// the pose, its step size and the placed atoms stay on the device from visit to visit.
 struct ScaffoldGuidedHostRun {
   RunArrays arrays;  // known_noise row 0: the start point, row i + 1: the state visit i leaves
   const int32_t* visits;
@@ -907,6 +910,13 @@ struct ScaffoldGuidedHostRun {
   TemplateLists tpl;   // none, or a chain's entries
   int n_energies;      // 2: restraint | clash (fd_sample_guided_inpaint); 3: | template, and tpl_rmsd_out
   double *energy_out, *max_violation_out, *tpl_rmsd_out;  // [B][n_energies], [B], [B]
+  // cyclic symmetry (fd_sample_guided_inpaint_sym); sym_order null: none, and the rest is not looked at
+  const int32_t* sym_order;
+  const double* sym_pose0;  // [B][12]
+  const fd_symmetry_params* sym_params;
+  double* sym_energy_out;   // [B][3]
+  int32_t* sym_contacts_out;
+  double* sym_pose_out;     // [B][12]
 };
 
 int scaffold_guided_host_run(fd_model* m, const ScaffoldGuidedHostRun& a) {
@@ -957,6 +967,14 @@ int scaffold_guided_host_run(fd_model* m, const ScaffoldGuidedHostRun& a) {
   off.has_offset = gp.has_offset ? 1 : 0;
   for (int f = 0; gp.has_offset && f < F; ++f) off.offset[f] = gp.offset[f];
   const SoftClash clash{gp.clash_alpha, gp.clash_margin, gp.w_clash};
+  // the symmetry lines: the pose, h and the placed atoms are carried on the device from visit to visit (the first visit takes
+  // sym_pose0 as it is, every later one fits onto where the visit before placed the chain)
+  bool symmetric = false;
+  for (int b = 0; a.sym_order && b < B; ++b) symmetric |= a.sym_order[b] >= 2;
+  SymGuide sg{};
+  if (symmetric)
+    if (int rc = stage_symmetry_guide(&bufs, a.sym_order, a.sym_pose0, nullptr, *a.sym_params, h.lens, r.lens, wk.coords, B, L, nullptr, true, &sg))
+      return rc;
 
   if (int rc = r.begin(a.visits[0], K)) return rc;
   hipStream_t s = m->stream;
@@ -973,20 +991,32 @@ int scaffold_guided_host_run(fd_model* m, const ScaffoldGuidedHostRun& a) {
   for (int i = 0; !rc && i < K; ++i) {
     rc = fd_sample_steps_dev(m, 1, nullptr, 0, nullptr);
     if (rc) break;
-    launch_scaffold_energy(d_x0, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, fit, wk, d_G, s);
+    launch_scaffold_energy(d_x0, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, fit, wk, d_G, s,
+                           symmetric ? &sg : nullptr);
+    sg.fit.xyz = sg.placed_packed;  // (from the second visit on)
     launch_scaffold_update(w.x, d_G, ip.fixed, w.lens, B, L, F, m->angle_mask, a.guide[i], gp.max_norm, a.coef[2 * Kz + i],
                            r.noise ? r.noise + (size_t)i * r.n : nullptr, h.seed, a.visits[i], h.seq_offset, d_gnorm, s);
     rc = launched();
   }
   if (!rc) {  // the final state's: its fixed elements hold known's bits, so p is the state itself
-    launch_scaffold_energy(w.x, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, fit, wk, nullptr, s);
+    launch_scaffold_energy(w.x, ip.known, ip.fixed, w.lens, B, L, F, off, m->angle_mask, fx, rs, clash, fit, wk, nullptr, s,
+                           symmetric ? &sg : nullptr);
     rc = launched();
   }
-  std::vector<double> e_rst(nb), e_clash(nb), maxv(nb), e_tpl(nb), rmsd_tpl(nb);
+  std::vector<double> e_rst(nb), e_clash(nb), maxv(nb), e_tpl(nb), rmsd_tpl(nb), e_sym(symmetric ? nb * 3 : 0);
+  std::vector<int32_t> c_sym(symmetric ? nb : 0);
+  std::vector<SymState> st_sym(symmetric ? nb : 0);
+  const auto opt = [&](void* host) { return symmetric ? host : nullptr; };  // (a null host pointer: not downloaded)
   rc = r.finish(rc, {{e_rst.data(), wk.e_rst, nb * 8}, {e_clash.data(), wk.e_clash, nb * 8}, {maxv.data(), wk.max_violation, nb * 8},
-                     {e_tpl.data(), wk.e_tpl, nb * 8}, {rmsd_tpl.data(), wk.rmsd_tpl, nb * 8}});
+                     {e_tpl.data(), wk.e_tpl, nb * 8}, {rmsd_tpl.data(), wk.rmsd_tpl, nb * 8}, {opt(e_sym.data()), sg.energy, nb * 24},
+                     {opt(c_sym.data()), sg.contacts, nb * 4}, {opt(st_sym.data()), sg.dock.state, nb * sizeof(SymState)}});
   if (rc && rc != FD_E_NONFINITE) return rc;  // (a run that answers FD_E_NONFINITE has written its outputs, as every family's)
   const size_t ne = (size_t)a.n_energies;
+  for (size_t b = 0; a.sym_order && b < nb; ++b) {
+    for (int k = 0; k < 3; ++k) a.sym_energy_out[3 * b + k] = symmetric ? e_sym[3 * b + k] : 0.0;
+    a.sym_contacts_out[b] = symmetric ? c_sym[b] : 0;
+    memcpy(a.sym_pose_out + 12 * b, symmetric ? st_sym[b].pose : a.sym_pose0 + 12 * b, 96);
+  }
   for (size_t b = 0; b < nb; ++b) {
     a.energy_out[ne * b] = e_rst[b];
     a.energy_out[ne * b + 1] = e_clash[b];
@@ -1522,7 +1552,10 @@ static int guided_inpaint_entry(fd_model* m, const float* x_init, const int32_t*
                                 const float* coef, const float* noise, const float* known, const uint8_t* fixed, const float* known_coef,
                                 const float* known_noise, uint64_t seed, int64_t seq_offset, const float* guide,
                                 const fd_scaffold_guide_params* params, const RestraintLists& rl, const TemplateLists& tl, int n_energies,
-                                float* out, double* energy_out, double* max_violation_out, double* tpl_rmsd_out) {
+                                float* out, double* energy_out, double* max_violation_out, double* tpl_rmsd_out,
+                                const int32_t* sym_order = nullptr, const double* sym_pose0 = nullptr,
+                                const fd_symmetry_params* sym_params = nullptr, double* sym_energy_out = nullptr,
+                                int32_t* sym_contacts_out = nullptr, double* sym_pose_out = nullptr) {
   if (int rc = check_strided_call(m, x_init, lens, out, B, L, visits, n_visits, coef, 0)) return rc;  // (rows a | b | s too)
   if (int rc = check_coef_rows(coef, n_visits, 3, 5)) return rc;
   if (!guide || !params) return fail(FD_E_INVALID, "null argument: guide and params are required");
@@ -1535,9 +1568,15 @@ static int guided_inpaint_entry(fd_model* m, const float* x_init, const int32_t*
   if (int rc = check_scaffold_guide(*params, known, fixed, lens, B, L, m->cfg.n_features)) return rc;
   if (int rc = check_restraints(rl, lens)) return rc;
   if (int rc = check_template(tl, lens)) return rc;
+  if (sym_order) {
+    if (!sym_pose0 || !sym_params || !sym_energy_out || !sym_contacts_out || !sym_pose_out)
+      return fail(FD_E_INVALID, "null argument: the symmetry arrays");
+    if (int rc = check_symmetry(*sym_params, sym_order, sym_pose0, B)) return rc;
+  }
   return scaffold_guided_host_run(m, ScaffoldGuidedHostRun{{x_init, lens, B, L, (size_t)n_visits, noise, known_noise, seed, seq_offset, out, 0},
                                                            visits, coef, guide, {known, fixed, known_coef}, params, rl, tl, n_energies,
-                                                           energy_out, max_violation_out, tpl_rmsd_out});
+                                                           energy_out, max_violation_out, tpl_rmsd_out, sym_order, sym_pose0, sym_params,
+                                                           sym_energy_out, sym_contacts_out, sym_pose_out});
 }
 
 extern "C" {
@@ -1563,6 +1602,21 @@ int fd_sample_guided_inpaint_tpl(fd_model* m, const float* x_init, const int32_t
   return guided_inpaint_entry(m, x_init, lens, B, L, visits, n_visits, coef, noise, known, fixed, known_coef, known_noise, seed, seq_offset,
                               guide, params, RestraintLists{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w},
                               TemplateLists{B, tpl_offsets, tpl_atom, tpl_xyz, tpl_w}, 3, out, energy_out, max_violation_out, tpl_rmsd_out);
+}
+
+int fd_sample_guided_inpaint_sym(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits,
+                                 int n_visits, const float* coef, const float* noise, const float* known, const uint8_t* fixed,
+                                 const float* known_coef, const float* known_noise, uint64_t seed, int64_t seq_offset,
+                                 const float* guide, const fd_scaffold_guide_params* params, const int32_t* rst_offsets,
+                                 const int32_t* rst_i, const int32_t* rst_j, const double* rst_d0, const double* rst_tol,
+                                 const double* rst_w, const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz,
+                                 const double* tpl_w, const int32_t* sym_order, const double* sym_pose0,
+                                 const fd_symmetry_params* sym_params, float* out, double* energy_out, double* max_violation_out,
+                                 double* tpl_rmsd_out, double* sym_energy_out, int32_t* sym_contacts_out, double* sym_pose_out) {
+  return guided_inpaint_entry(m, x_init, lens, B, L, visits, n_visits, coef, noise, known, fixed, known_coef, known_noise, seed, seq_offset,
+                              guide, params, RestraintLists{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w},
+                              TemplateLists{B, tpl_offsets, tpl_atom, tpl_xyz, tpl_w}, 3, out, energy_out, max_violation_out, tpl_rmsd_out,
+                              sym_order, sym_pose0, sym_params, sym_energy_out, sym_contacts_out, sym_pose_out);
 }
 
 int fd_philox_normal_dev(fd_model* m, uint64_t seed, int t, int64_t seq_offset, int B, int L, void* out_dev,

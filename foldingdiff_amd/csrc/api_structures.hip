@@ -1,12 +1,14 @@
 // C-ABI entry points of the structure kernels (nerf.hip, internal_coords.hip, tm_score.hip, psea.hip, dssp.hip, tm_align.hip, tm_align_starts.hip, clash_lddt.hip), of
-// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip), of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip), of the torsion-space relaxer (nerf_scan.hip, relax.hip) of the scaffold-guide step (guide_scaffold.hip) and of the superposition restraints (template_fit.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
+// the loss arithmetic on its own (loss.hip, loss_variants.hip), of the angle histograms (angle_stats.hip) of the steering kernels on their own (steer.hip), of the NeRF derivative, the restraints and the guide step (nerf_vjp.hip), of the torsion-space relaxer (nerf_scan.hip, relax.hip) of the scaffold-guide step (guide_scaffold.hip) of the superposition restraints (template_fit.hip) and of the cyclic-symmetry statements (symmetry.hip).  None of them sees a model: each takes a device_id, checks its arguments on the host, and makes one synchronous
 // round trip (host_common.h).  Boundary: include/fdmi.h.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
 #include "fdmi_kernels.h"
 #include "host_common.h"
+#include "symmetry_host.h"
 
 using namespace fdmi;
 
@@ -187,14 +189,28 @@ int fd_guide_step(int device_id, const float* x, const float* x0, const int32_t*
 
 }  // extern "C"
 
-// fd_scaffold_guide_step (energy_out [B][2], tpl_rmsd_out == nullptr, no template) and fd_scaffold_guide_step_tpl ([B][3])
+// fd_scaffold_guide_step_sym's own arguments; order == nullptr: no symmetry, and nothing else is looked at
+namespace {
+struct SymStepArgs {
+  const int32_t* order;
+  const double *pose_in, *placed_in;
+  const fd_symmetry_params* params;
+  double* step_io;
+  double* energy_out;
+  int32_t* contacts_out;
+  double *pose_out, *placed_out;
+};
+}  // namespace
+
+// fd_scaffold_guide_step (energy_out [B][2], tpl_rmsd_out == nullptr, no template), fd_scaffold_guide_step_tpl ([B][3]) and
+// fd_scaffold_guide_step_sym (sym != nullptr)
 static int scaffold_guide_step_run(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
                                    const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
                                    const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
                                    const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
                                    const TemplateLists& tl, int n_energies, float c, float s, const float* z, uint64_t seed, int t,
                                    int64_t seq_offset, float* x_out, double* energy_out, double* max_violation_out, double* gnorm_out,
-                                   double* dfeats_out, double* tpl_rmsd_out) {
+                                   double* dfeats_out, double* tpl_rmsd_out, const SymStepArgs* sym = nullptr) {
   if (!x || !x0 || !lens || !is_angle || !params || !x_out || !energy_out || !max_violation_out || !gnorm_out ||
       (n_energies == 3 && !tpl_rmsd_out))
     return fail(FD_E_INVALID, "null argument");
@@ -208,6 +224,18 @@ static int scaffold_guide_step_run(int device_id, const float* x, const float* x
   if (!std::isfinite(s)) return fail(FD_E_INVALID, "s = %g is not finite", (double)s);
   if (int rc = check_scaffold_guide(*params, known, fixed, lens, B, L, F)) return rc;
   if (int rc = check_rows_finite("x", x, lens, B, L, F)) return rc;
+  bool symmetric = false;  // a chain has an order above 1: only then do the symmetry launches run
+  if (sym && sym->order) {
+    if (!sym->pose_in || !sym->params || !sym->energy_out || !sym->contacts_out || !sym->pose_out || !sym->placed_out)
+      return fail(FD_E_INVALID, "null argument: the symmetry arrays");
+    if (int rc = check_symmetry(*sym->params, sym->order, sym->pose_in, B)) return rc;
+    for (int b = 0; sym->step_io && b < B; ++b)
+      if (!(sym->step_io[b] > 0.0) || !std::isfinite(sym->step_io[b]))
+        return fail(FD_E_INVALID, "sym_step_io[%d]=%g must be > 0 and finite", b, sym->step_io[b]);
+    if (sym->placed_in)
+      if (int rc = check_chain_doubles("sym_placed_in", sym->placed_in, lens, B, L)) return rc;
+    for (int b = 0; b < B; ++b) symmetric |= sym->order[b] >= 2;
+  }
   for (int b = 0; b < B; ++b)  // (x0 is not read where fixed)
     for (size_t o = (size_t)b * L * F; o < ((size_t)b * L + lens[b]) * F; ++o)
       if (!fixed[o] && !std::isfinite(x0[o]))
@@ -264,7 +292,16 @@ static int scaffold_guide_step_run(int device_id, const float* x, const float* x
     HIP_TRY(bufs.upload(tl.xyz, tl.count() * 24, &tf.xyz));
     HIP_TRY(bufs.upload(tl.w, tl.count() * 8, &tf.w));
   }
-  launch_scaffold_energy(x0_dev, known_dev, fixed_dev, lens_dev, B, L, F, off, angle_mask, fx, rs, clash, fit ? &tf : nullptr, wk, G, nullptr);
+  SymGuide sg{};
+  std::vector<SymState> sym_host(symmetric ? nb : 0);
+  if (symmetric) {
+    if (int rc = stage_symmetry_guide(&bufs, sym->order, sym->pose_in, sym->step_io, *sym->params, lens, lens_dev, wk.coords, B, L,
+                                      sym->placed_in, false, &sg))
+      return rc;
+    HIP_TRY(bufs.zeros(na * 8, &sg.placed));
+  }
+  launch_scaffold_energy(x0_dev, known_dev, fixed_dev, lens_dev, B, L, F, off, angle_mask, fx, rs, clash, fit ? &tf : nullptr, wk, G, nullptr,
+                         symmetric ? &sg : nullptr);
   launch_scaffold_update(state, G, fixed_dev, lens_dev, B, L, F, angle_mask, c, p.max_norm, s, z_dev, seed, t, seq_offset, gnorm, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
@@ -278,7 +315,24 @@ static int scaffold_guide_step_run(int device_id, const float* x, const float* x
   HIP_TRY(hipMemcpy(e_clash.data(), wk.e_clash, nb * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(maxv.data(), wk.max_violation, nb * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(norm.data(), gnorm, nb * 8, hipMemcpyDeviceToHost));
+  std::vector<double> sym_e(symmetric ? nb * 3 : 0), sym_placed(symmetric ? na : 0);
+  std::vector<int32_t> sym_c(symmetric ? nb : 0);
+  if (symmetric) {
+    HIP_TRY(hipMemcpy(sym_host.data(), sg.dock.state, nb * sizeof(SymState), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sym_e.data(), sg.energy, nb * 24, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sym_c.data(), sg.contacts, nb * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sym_placed.data(), sg.placed, na * 8, hipMemcpyDeviceToHost));
+  }
   // every download has succeeded: only now are the outputs written (the rows at or beyond a length keep what they held)
+  for (int b = 0; sym && sym->order && b < B; ++b) {
+    for (int k = 0; k < 3; ++k) sym->energy_out[3 * b + k] = symmetric ? sym_e[3 * (size_t)b + k] : 0.0;
+    sym->contacts_out[b] = symmetric ? sym_c[b] : 0;
+    memcpy(sym->pose_out + 12 * (size_t)b, symmetric ? sym_host[b].pose : sym->pose_in + 12 * (size_t)b, 96);
+    if (symmetric) {
+      memcpy(sym->placed_out + (size_t)b * 3 * L * 3, sym_placed.data() + (size_t)b * 3 * L * 3, (size_t)lens[b] * 72);
+      if (sym->step_io) sym->step_io[b] = sym_host[b].h;
+    }
+  }
   for (int b = 0; b < B; ++b) {
     const size_t o = (size_t)b * L * F, rows = (size_t)lens[b] * F;
     memcpy(x_out + o, state_host.data() + o, rows * 4);
@@ -318,6 +372,22 @@ int fd_scaffold_guide_step_tpl(int device_id, const float* x, const float* x0, c
   return scaffold_guide_step_run(device_id, x, x0, known, fixed, lens, B, L, F, is_angle, params, rst_offsets, rst_i, rst_j, rst_d0, rst_tol,
                                  rst_w, TemplateLists{B, tpl_offsets, tpl_atom, tpl_xyz, tpl_w}, 3, c, s, z, seed, t, seq_offset, x_out,
                                  energy_out, max_violation_out, gnorm_out, dfeats_out, tpl_rmsd_out);
+}
+
+int fd_scaffold_guide_step_sym(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                               const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                               const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                               const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
+                               const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz, const double* tpl_w,
+                               const int32_t* sym_order, const double* sym_pose_in, const double* sym_placed_in,
+                               const fd_symmetry_params* sym_params, double* sym_step_io, float c, float s, const float* z, uint64_t seed,
+                               int t, int64_t seq_offset, float* x_out, double* energy_out, double* max_violation_out, double* gnorm_out,
+                               double* dfeats_out, double* tpl_rmsd_out, double* sym_energy_out, int32_t* sym_contacts_out,
+                               double* sym_pose_out, double* sym_placed_out) {
+  const SymStepArgs sym{sym_order, sym_pose_in, sym_placed_in, sym_params, sym_step_io, sym_energy_out, sym_contacts_out, sym_pose_out, sym_placed_out};
+  return scaffold_guide_step_run(device_id, x, x0, known, fixed, lens, B, L, F, is_angle, params, rst_offsets, rst_i, rst_j, rst_d0, rst_tol,
+                                 rst_w, TemplateLists{B, tpl_offsets, tpl_atom, tpl_xyz, tpl_w}, 3, c, s, z, seed, t, seq_offset, x_out,
+                                 energy_out, max_violation_out, gnorm_out, dfeats_out, tpl_rmsd_out, &sym);
 }
 
 int fd_nerf_scan(int device_id, const float* feats, const int32_t* lens, int B, int L, int F, const int32_t* feat_idx, int center,
@@ -461,6 +531,109 @@ int fd_relax(int device_id, const float* feats, const float* anchor, const int32
   if (!feats_out || !accepted_out) return fail(FD_E_INVALID, "null argument");
   return relax_run(device_id, feats, anchor, lens, B, L, F, params, fixed, RestraintLists{B, rst_offsets, rst_i, rst_j, rst_d0, rst_tol, rst_w},
                    n_iter, step_io, feats_out, energy_out, nullptr, nullptr, trace_out, accepted_out);
+}
+
+}  // extern "C"
+
+// fd_symmetry_energy (descent == false: one evaluation of `pose`) and fd_symmetry_dock: the checks, the uploads, 1 + n_iter
+// evaluations of two launches each, the downloads
+static int symmetry_run(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* order, const double* pose,
+                        const fd_symmetry_params* params, bool descent, int n_iter, double* step_io, double* pose_out, double* energy_out,
+                        int32_t* contacts_out, double* wrench_out, double* dcoords_out, double* trace_out, int32_t* accepted_out) {
+  if (!coords || !lens || !order || !pose || !params || !energy_out || !contacts_out) return fail(FD_E_INVALID, "null argument");
+  if (B < 1 || L < 1) return fail(FD_E_INVALID, "B=%d L=%d must be positive", B, L);
+  if ((long long)B * L * 9 > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "B * L * 9 = %lld coordinates, at most 2^31 - 1", (long long)B * L * 9);
+  if (int rc = check_lens(lens, B, L < kGuideMaxLen ? L : kGuideMaxLen)) return rc;
+  if (int rc = check_symmetry(*params, order, pose, B)) return rc;
+  if (n_iter < 0) return fail(FD_E_INVALID, "n_iter=%d must be >= 0", n_iter);
+  if ((n_iter + 1LL) * B > 0x7fffffffLL) return fail(FD_E_UNSUPPORTED, "(n_iter + 1) * B = %lld trace entries, at most 2^31 - 1", (n_iter + 1LL) * B);
+  for (int b = 0; step_io && b < B; ++b)
+    if (!(step_io[b] > 0.0) || !std::isfinite(step_io[b])) return fail(FD_E_INVALID, "step_io[%d]=%g must be > 0 and finite", b, step_io[b]);
+  if (int rc = check_chain_doubles("coords", coords, lens, B, L)) return rc;
+  const fd_symmetry_params& p = *params;
+  const size_t na = (size_t)B * 3 * L * 3, nb = (size_t)B;
+  std::vector<SymState> state_host(nb);
+  for (size_t b = 0; b < nb; ++b) {
+    state_host[b] = SymState{};
+    memcpy(state_host[b].pose, pose + b * 12, 96);
+    memcpy(state_host[b].trial, pose + b * 12, 96);  // the first trial is the input
+    state_host[b].h = step_io ? step_io[b] : p.step0;
+  }
+  std::vector<double> rot_host((size_t)(kSymMaxOrder + 1) * 24);
+  symmetry_rotations(rot_host.data());
+  HIP_TRY(hipSetDevice(device_id));
+  DeviceBufs bufs;
+  SymPair sp{};
+  SymDock sd{};
+  double *e_trial, *wrench_trial, *grad = nullptr;
+  int* contacts_trial;
+  HIP_TRY(bufs.upload(coords, na * 8, &sp.coords));
+  HIP_TRY(bufs.upload(lens, nb * 4, &sp.lens));
+  HIP_TRY(bufs.upload(order, nb * 4, &sp.order));
+  HIP_TRY(bufs.upload(rot_host.data(), rot_host.size() * 8, &sp.rot));
+  HIP_TRY(bufs.upload(state_host.data(), nb * sizeof(SymState), &sd.state));
+  HIP_TRY(bufs.alloc(nb * 24, &e_trial));
+  HIP_TRY(bufs.alloc(nb * 4, &contacts_trial));
+  HIP_TRY(bufs.alloc(nb * 48, &wrench_trial));
+  if (dcoords_out) HIP_TRY(bufs.zeros(na * 8, &grad));  // (the launch adds: the chains with order 1 stay 0)
+  if (trace_out) HIP_TRY(bufs.alloc((size_t)(n_iter + 1) * nb * 8, &sd.trace));
+  sp.pose = reinterpret_cast<const double*>(sd.state) + offsetof(SymState, trial) / 8;
+  sp.pose_stride = (int)(sizeof(SymState) / 8);
+  sp.energy = e_trial;
+  sp.contacts = contacts_trial;
+  sp.wrench = wrench_trial;
+  sp.dcoords = grad;
+  sp.L = L;
+  sp.clash_alpha = p.clash_alpha; sp.clash_margin = p.clash_margin; sp.w_clash = p.w_clash; sp.w_contact = p.w_contact;
+  sp.d_on = p.d_on; sp.d_off = p.d_off; sp.w_radial = p.w_radial; sp.r_max = p.r_max;
+  sd.order = sp.order;
+  sd.e_trial = e_trial;
+  sd.contacts_trial = contacts_trial;
+  sd.wrench_trial = wrench_trial;
+  sd.B = B;
+  sd.lever = p.lever; sd.max_shift = p.max_shift; sd.grow = p.grow; sd.shrink = p.shrink;
+  for (int it = 0; it <= n_iter; ++it) {
+    launch_symmetry_pair(sp, B, nullptr);
+    sd.it = it;
+    sd.last = it == n_iter;
+    launch_symmetry_pose(sd, nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<double> grad_host(dcoords_out ? na : 0), trace_host(trace_out ? (size_t)(n_iter + 1) * nb : 0);
+  if (dcoords_out) HIP_TRY(hipMemcpy(grad_host.data(), grad, na * 8, hipMemcpyDeviceToHost));
+  if (trace_out) HIP_TRY(hipMemcpy(trace_host.data(), sd.trace, trace_host.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(state_host.data(), sd.state, nb * sizeof(SymState), hipMemcpyDeviceToHost));
+  // every download has succeeded: only now are the outputs written
+  for (size_t b = 0; b < nb; ++b) {
+    const SymState& st = state_host[b];
+    memcpy(energy_out + 3 * b, st.e, 24);
+    contacts_out[b] = st.contacts;
+    if (wrench_out) memcpy(wrench_out + 6 * b, st.wrench, 48);
+    if (pose_out) memcpy(pose_out + 12 * b, st.pose, 96);
+    if (descent && step_io) step_io[b] = st.h;
+    if (accepted_out) accepted_out[b] = st.accepted;
+  }
+  if (dcoords_out) memcpy(dcoords_out, grad_host.data(), na * 8);
+  if (trace_out) memcpy(trace_out, trace_host.data(), trace_host.size() * 8);
+  return FD_OK;
+}
+
+extern "C" {
+
+int fd_symmetry_energy(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* order, const double* pose,
+                       const fd_symmetry_params* params, double* energy_out, int32_t* contacts_out, double* wrench_out,
+                       double* dcoords_out) {
+  return symmetry_run(device_id, coords, lens, B, L, order, pose, params, false, 0, nullptr, nullptr, energy_out, contacts_out, wrench_out,
+                      dcoords_out, nullptr, nullptr);
+}
+
+int fd_symmetry_dock(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* order, const double* pose,
+                     const fd_symmetry_params* params, int n_iter, double* step_io, double* pose_out, double* energy_out,
+                     int32_t* contacts_out, double* trace_out, int32_t* accepted_out) {
+  if (!pose_out || !accepted_out) return fail(FD_E_INVALID, "null argument");
+  return symmetry_run(device_id, coords, lens, B, L, order, pose, params, true, n_iter, step_io, pose_out, energy_out, contacts_out, nullptr,
+                      nullptr, trace_out, accepted_out);
 }
 
 int fd_internal_coords(int device_id, const float* xyz, const int32_t* chain_offsets, const int32_t* chain_lens, int n_chains,

@@ -346,9 +346,88 @@ struct ScaffoldWork {
 };
 // the statement up to G: shift, launch_nerf_scan, launch_restraint_energy, launch_soft_clash (clash.w > 0),
 // launch_template_energy (tpl not null) and, unless G is null, launch_nerf_vjp on the shifted rows -> G [B][L][F], unmasked
+struct SymGuide;
+// sym not null (symmetry.hip): launch_symmetry_guide runs behind the template line, before the derivative
 void launch_scaffold_energy(const float* x0, const float* known, const unsigned char* fixed, const int* lens, int B, int L, int F,
                             const SteerOffset& off, unsigned angle_mask, const NerfFeatures& fx, const Restraints& rs,
-                            const SoftClash& clash, const TemplateFit* tpl, const ScaffoldWork& wk, double* G, hipStream_t s);
+                            const SoftClash& clash, const TemplateFit* tpl, const ScaffoldWork& wk, double* G, hipStream_t s,
+                            const SymGuide* sym = nullptr);
+
+// ---- cyclic oligomers (symmetry.hip; the statements are in its header and in include/fdmi.h).  One 256-lane workgroup per chain
+// in the pair and place kernels, one lane per chain in the pose kernel; lens[b] <= kGuideMaxLen, order[b] in [1, kSymMaxOrder].
+constexpr int kSymMaxOrder = 12;
+// rot [(kSymMaxOrder + 1) * 12][2] <- (cos, sin) of 2 pi k / n at [n * 12 + k], evaluated in fp64 on the host
+void symmetry_rotations(double* rot);
+struct SymState;
+// one evaluation of the symmetry statement with chain b's pose at pose + b * pose_stride (doubles)
+struct SymPair {
+  const double* coords;        // [B][3L][3] in NeRF's frame
+  const int *lens, *order;     // [B]
+  const double* pose;          // 12 doubles per chain: Q row-major, then t
+  const double* rot;           // symmetry_rotations' table
+  double* energy;              // [B][3] clash | contact | radial
+  int* contacts;               // [B]
+  double* wrench;              // [B][6] F | tau, or null
+  double* dcoords;             // [B][3L][3] or null: Q^T g is ADDED on the atoms below 3 lens[b] of the chains with order >= 2
+                               // (store != 0: WRITTEN there instead)
+  // reuse != null: a chain whose reuse[b].reuse is set is not evaluated again -- its energies and contacts are reuse[b]'s, and
+  // spare [B][3L][3], the Q^T g an evaluation at that pose stored, is what is added to dcoords
+  const SymState* reuse;
+  const double* spare;
+  int L, pose_stride, store;
+  double clash_alpha, clash_margin, w_clash, w_contact, d_on, d_off, w_radial, r_max;
+};
+void launch_symmetry_pair(const SymPair& a, int B, hipStream_t s);
+// what the docking descent keeps of a chain between two launches
+struct SymState {
+  double pose[12], trial[12];  // the chain's pose and the pose under evaluation
+  double e[3], wrench[6];      // of the chain's pose
+  double e_total, h;
+  int contacts, accepted;
+  int reuse, pad;              // the launch with `last` set took its trial as the pose: that evaluation is the pose's
+};
+// one launch of symmetry_pose_kernel: closes the evaluation of state[b].trial (e_trial, contacts_trial, wrench_trial: what
+// launch_symmetry_pair wrote for it), then it == 0: the trial becomes the pose; it > 0: it does where its energy is not above the
+// pose's, and h grows or shrinks; !last: trial <- the next trial.  trace [.][B] or null.
+struct SymDock {
+  SymState* state;             // [B]
+  const int* order;            // [B]: a chain of order 1 keeps h and accepted
+  const double* e_trial;       // [B][3]
+  const int* contacts_trial;   // [B]
+  const double* wrench_trial;  // [B][6]
+  double* trace;
+  int B, it, last;
+  double lever, max_shift, grow, shrink;
+};
+void launch_symmetry_pose(const SymDock& a, hipStream_t s);
+// state[b].trial <- (R^T, -R^T t_fit) of launch_template_energy's transform fit[b] = (R | t_fit), where order[b] >= 2
+void launch_symmetry_fit_pose(const double* fit, const int* order, SymState* state, int B, hipStream_t s);
+// placed [B][3L][3] <- Q p + t on the atoms below 3 lens[b], by the pair kernel's own expression
+// (null: not written), and the same atoms packed at packed + 3 offsets[b] for the chains with offsets[b + 1] > offsets[b] (null: not)
+void launch_symmetry_place(const double* coords, const int* lens, int B, int L, const double* pose, int pose_stride, double* placed,
+                           const int* offsets, double* packed, hipStream_t s);
+// the symmetry lines of the scaffold-guide statement on coords [B][3L][3], every buffer on the device:
+//   fit.xyz (the placed coordinates of the visit before, with fit's all-atom lists) not null: state[b].trial <- the pose of the
+//   proper rigid fit of coords onto them (launch_template_energy as it is, then launch_symmetry_fit_pose); null: state[b].trial
+//   is the caller's;  1 + pose_iters evaluations of the descent (it = 0 takes the trial as the pose) with h = state[b].h, the
+//   last of which stores its Q^T g in g_spare;  one more launch that writes energy / contacts at the final pose and ADDS Q^T g
+//   to gc (null: no gradient) -- from g_spare and the state where the descent's last trial became the pose, by an evaluation of
+//   its own only for the chains whose last trial was dropped;  placed <- Q coords + t
+struct SymGuide {
+  SymPair pair;                // coords, lens, order, rot, L and the scalars; pose, energy, contacts, wrench, dcoords are set here
+  SymDock dock;                // state, B and the scalars; the trial buffers are set here
+  TemplateFit fit;             // offsets [B + 1] = 3 lens summed over the chains with order >= 2, atom = 0 .. 3 lens - 1, w = 1
+  double *fit_energy, *fit_rmsd, *fit_transform;  // [B], [B], [B][12] workspaces
+  double *e_trial, *wrench_trial;                 // [B][3], [B][6] workspaces
+  double* g_spare;                                // [B][3L][3] workspace
+  int* contacts_trial;                            // [B]
+  int pose_iters;
+  double* energy;              // [B][3] at the final pose
+  int* contacts;               // [B]
+  double* placed;              // [B][3L][3], or null
+  double* placed_packed;       // null, or the same atoms packed by fit.offsets: the next visit's fit targets
+};
+void launch_symmetry_guide(const SymGuide& g, double* gc, hipStream_t s);
 
 // *t_dev -= 1, or with a strided run open in `dyn` *t_dev = dyn->next_t[*t_dev]  (last node of the per-step graph)
 void launch_step_advance(int* t_dev, const UpdateDyn* dyn, hipStream_t s);

@@ -11,7 +11,8 @@
 // bits.  A fixed element keeps its bits and neither reads nor draws a z.
 //
 // launch_scaffold_energy.  shift, launch_nerf_scan, launch_restraint_energy, launch_soft_clash (only where w > 0),
-// launch_template_energy (template_fit.hip; only where a chain has a template entry) and, where a gradient is asked for,
+// launch_template_energy (template_fit.hip; only where a chain has a template entry), launch_symmetry_guide (symmetry.hip; only
+// where a chain has a symmetry order above 1) and, where a gradient is asked for,
 // launch_nerf_vjp on the shifted rows: the restraints before the clashes, relax.hip's order, so that with nothing fixed and no
 // template G is fd_relax_energy's gradient bit for bit.
 #include "block_sum.h"
@@ -87,13 +88,15 @@ void launch_scaffold_update(float* x, double* G, const unsigned char* fixed, con
 
 void launch_scaffold_energy(const float* x0, const float* known, const unsigned char* fixed, const int* lens, int B, int L, int F,
                             const SteerOffset& off, unsigned angle_mask, const NerfFeatures& fx, const Restraints& rs,
-                            const SoftClash& clash, const TemplateFit* tpl, const ScaffoldWork& wk, double* G, hipStream_t s) {
+                            const SoftClash& clash, const TemplateFit* tpl, const ScaffoldWork& wk, double* G, hipStream_t s,
+                            const SymGuide* sym) {
   const bool clashes = clash.w > 0.0;
   launch_scaffold_shift(x0, known, fixed, lens, B, L, F, off, angle_mask, wk.ang, s);
   launch_nerf_scan(wk.ang, lens, B, L, F, fx, 0, wk.coords, s);
   launch_restraint_energy(wk.coords, lens, B, L, rs, wk.e_rst, wk.max_violation, G || clashes ? wk.gc : nullptr, s);
   if (clashes) launch_soft_clash(wk.coords, lens, B, L, clash.alpha, clash.margin, clash.w, wk.e_clash, wk.gc, s);
   if (tpl) launch_template_energy(wk.coords, B, L, *tpl, wk.e_tpl, wk.rmsd_tpl, nullptr, G ? wk.gc : nullptr, s);
+  if (sym) launch_symmetry_guide(*sym, G ? wk.gc : nullptr, s);
   if (G) launch_nerf_vjp(wk.coords, lens, B, L, F, fx, 0, wk.gc, wk.ang, G, s);
 }
 

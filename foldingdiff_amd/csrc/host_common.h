@@ -364,4 +364,26 @@ inline int check_template(const TemplateLists& t, const int32_t* lens) {
   return FD_OK;
 }
 
+// ---- cyclic oligomers (fd_symmetry_energy, fd_symmetry_dock, fd_scaffold_guide_step_sym)
+// the statement's scalars, the orders (null: not looked at) and the poses (null: not looked at; only chains with order >= 2 are read)
+inline int check_symmetry(const fd_symmetry_params& p, const int32_t* order, const double* pose, int B) {
+  const struct { const char* name; double v; } nonneg[] = {{"clash_alpha", p.clash_alpha}, {"clash_margin", p.clash_margin}, {"w_clash", p.w_clash},
+                                                           {"w_contact", p.w_contact}, {"w_radial", p.w_radial}, {"r_max", p.r_max}};
+  for (const auto& w : nonneg)
+    if (!(w.v >= 0.0) || !std::isfinite(w.v)) return fail(FD_E_INVALID, "%s=%g must be >= 0 and finite", w.name, w.v);
+  if (!(p.d_on >= 0.0) || !(p.d_on < p.d_off) || !std::isfinite(p.d_off)) return fail(FD_E_INVALID, "d_on=%g, d_off=%g: 0 <= d_on < d_off, both finite", p.d_on, p.d_off);
+  const struct { const char* name; double v; } pos[] = {{"lever", p.lever}, {"max_shift", p.max_shift}, {"step0", p.step0}};
+  for (const auto& w : pos)
+    if (!(w.v > 0.0) || !std::isfinite(w.v)) return fail(FD_E_INVALID, "%s=%g must be > 0 and finite", w.name, w.v);
+  if (!(p.grow >= 1.0) || !std::isfinite(p.grow)) return fail(FD_E_INVALID, "grow=%g must be >= 1 and finite", p.grow);
+  if (!(p.shrink > 0.0 && p.shrink < 1.0)) return fail(FD_E_INVALID, "shrink=%g outside (0, 1)", p.shrink);
+  if (p.pose_iters < 0) return fail(FD_E_INVALID, "pose_iters=%d must be >= 0", p.pose_iters);
+  for (int b = 0; order && b < B; ++b)
+    if (order[b] < 1 || order[b] > 12) return fail(FD_E_INVALID, "order[%d]=%d outside [1, 12]", b, order[b]);
+  for (int b = 0; pose && b < B; ++b)
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(pose[(size_t)b * 12 + i])) return fail(FD_E_INVALID, "pose[%d][%d]=%g is not finite", b, i, pose[(size_t)b * 12 + i]);
+  return FD_OK;
+}
+
 }  // namespace fdmi

@@ -24,7 +24,7 @@ import ctypes as C
 import json
 import logging
 import os
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -1707,11 +1707,26 @@ def _run_fd_sample_guided_inpaint_tpl(h, x0: np.ndarray, lens: np.ndarray, visit
         _binding.ptr(worst), _binding.ptr(tpl_rmsd)))
 
 
+def _run_fd_sample_guided_inpaint_sym(h, x0: np.ndarray, lens: np.ndarray, visits: np.ndarray, coef: np.ndarray, known: np.ndarray,
+                                      fixed: np.ndarray, known_coef: np.ndarray, seed: int, guide_tab: np.ndarray, params, packed,
+                                      tpl_packed, order: np.ndarray, pose0: np.ndarray, sym_params, out: np.ndarray, energy: np.ndarray,
+                                      worst: np.ndarray, tpl_rmsd: np.ndarray, sym_energy: np.ndarray, sym_contacts: np.ndarray,
+                                      sym_pose: np.ndarray) -> None:
+    """The same for one subunit of a cyclic oligomer (fd_sample_guided_inpaint_sym): ``tpl_packed`` may be four ``None``."""
+    B, L, _ = x0.shape
+    _binding.check(_binding.load().fd_sample_guided_inpaint_sym(
+        h, _binding.ptr(x0), _binding.ptr(lens), B, L, _binding.ptr(visits), len(visits), _binding.ptr(coef), None, _binding.ptr(known),
+        _binding.ptr(fixed), _binding.ptr(known_coef), None, C.c_uint64(seed), C.c_int64(0), _binding.ptr(guide_tab), C.byref(params),
+        *(_binding.ptr(a) for a in packed), *(_binding.ptr(a) for a in tpl_packed), _binding.ptr(order), _binding.ptr(pose0),
+        C.byref(sym_params), _binding.ptr(out), _binding.ptr(energy), _binding.ptr(worst), _binding.ptr(tpl_rmsd),
+        _binding.ptr(sym_energy), _binding.ptr(sym_contacts), _binding.ptr(sym_pose)))
+
+
 @torch.no_grad()
 def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.ndarray], restraints, num_steps: Optional[int] = None,
                   eta: float = 1.0, scale: float = 1.0, max_norm: float = 1.0, guide_from: Optional[int] = None,
                   clash_weight: float = 0.0, clash_alpha: float = 0.63, clash_margin: float = 0.15, batch_size: int = 512,
-                  seed: Optional[int] = None, feature_key: str = "angles", templates=None):
+                  seed: Optional[int] = None, feature_key: str = "angles", templates=None, symmetry=None):
     """Restraint guidance combined with replacement (``fd_sample_guided_inpaint``): one backbone per item whose
     elements marked in ``fixed[i]`` are held to ``known[i]`` as in ``inpaint``, while the rest is steered toward distance
     restraints as in ``guide``.  The structure a visit is scored on carries the held elements exactly -- their known values,
@@ -1735,7 +1750,15 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
     the optimal fit by a proper rotation, which a mirror image cannot satisfy (``fd_sample_guided_inpaint_tpl``); ``info`` then
     also holds ``template_energy`` and ``template_rmsd`` (float64 ``[n]``) of the final states.  Without ``templates`` the call
     is the one made before the term existed.  How often a scaffold comes out in the wrong hand with a trained model -- like
-    designability -- is unmeasured: there are no trained weights here."""
+    designability -- is unmeasured: there are no trained weights here.
+
+    ``symmetry`` (a dict) makes every item one subunit of a cyclic oligomer (``fd_sample_guided_inpaint_sym``):
+    ``order`` (one for all or one per item, 1: not symmetric), optionally ``pose`` (``[n, 12]`` start poses; default
+    ``structures.start_pose(None, order, lengths=...)``) and ``params`` (``structures.symmetry_params()``).  Behind every visit
+    the chain is scored against its own copies about z -- soft clashes between copies, a CA contact reward, a pull to the axis --
+    after ``params.pose_iters`` rigid-body steps of its pose, and the gradient joins the one that is followed.  ``info`` then
+    holds ``symmetry_energy`` (``[n, 3]`` clash | contact | radial), ``symmetry_contacts`` and ``symmetry_pose`` (``[n, 12]``)
+    of the final states.  With ``None`` the call and its results are what they are without it."""
     from . import structures
     _check_few_step(None, "uniform", num_steps, eta)
     n = len(known)
@@ -1758,6 +1781,18 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
     if templates is not None:
         structures.pack_templates(templates, lengths)
         tpl_per_chain = [templates] * n if isinstance(templates, structures.Template) else list(templates)
+    if symmetry is not None:
+        unknown = set(symmetry) - {"order", "pose", "params"}
+        if unknown or "order" not in symmetry:
+            raise ValueError(f"symmetry takes 'order' and optionally 'pose' and 'params' (got {sorted(symmetry)})")
+        sym_orders = structures._orders(symmetry["order"], n)
+        sym_prm = symmetry.get("params") or structures.symmetry_params()
+        sym_pose0 = symmetry.get("pose")
+        sym_pose0 = (structures.start_pose(None, sym_orders, lengths=lengths) if sym_pose0 is None
+                     else np.ascontiguousarray(np.asarray(sym_pose0, dtype=np.float64).reshape(-1, 12)))
+        if len(sym_pose0) != n or not np.isfinite(sym_pose0).all():
+            raise ValueError(f"symmetry['pose']: {n} finite [12] poses")
+        sym_energies, sym_contacts, sym_poses = [], [], []
     T = dset.timesteps
     betas = dset.alpha_beta_terms["betas"]
     visits = _few_step_visits(betas, T if num_steps is None else int(num_steps), None, "uniform", -3.0)
@@ -1784,10 +1819,25 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
                 fb[i, :l] = fs[lo + i]
             philox_seed = _draw_philox_seed()
             out = np.empty((B, L, F), dtype=np.float32)
-            energy, worst = np.empty((B, 2 if templates is None else 3), dtype=np.float64), np.empty(B, dtype=np.float64)
+            energy = np.empty((B, 2 if templates is None and symmetry is None else 3), dtype=np.float64)
+            worst = np.empty(B, dtype=np.float64)
             packed = structures.pack_restraints(per_chain[lo: lo + B], these)
             with _packed_batch(model, these, on_gpu):   # positions beyond an item's length are cut away below, as in sample()
-                if templates is None:
+                if symmetry is not None:
+                    tpl_rmsd = np.empty(B, dtype=np.float64)
+                    tpl_packed = (None,) * 4 if templates is None else structures.pack_templates(tpl_per_chain[lo: lo + B], these)
+                    se, sc, sp = np.empty((B, 3), dtype=np.float64), np.empty(B, dtype=np.int32), np.empty((B, 12), dtype=np.float64)
+                    _run_fd_sample_guided_inpaint_sym(h, x0, _lens_array(these, B, L), visits, coef, kb, fb, known_coef, philox_seed,
+                                                      guide_tab, params, packed, tpl_packed, np.ascontiguousarray(sym_orders[lo: lo + B]),
+                                                      np.ascontiguousarray(sym_pose0[lo: lo + B]), sym_prm, out, energy, worst, tpl_rmsd,
+                                                      se, sc, sp)
+                    sym_energies.append(se)
+                    sym_contacts.append(sc)
+                    sym_poses.append(sp)
+                    if templates is not None:
+                        tpl_energies.append(energy[:, 2].copy())
+                        tpl_rmsds.append(tpl_rmsd)
+                elif templates is None:
                     _run_fd_sample_guided_inpaint(h, x0, _lens_array(these, B, L), visits, coef, kb, fb, known_coef, philox_seed, guide_tab,
                                                   params, packed, out, energy, worst)
                 else:
@@ -1805,10 +1855,53 @@ def guide_inpaint(model, dset, known: Sequence[np.ndarray], fixed: Sequence[np.n
             "visits": visits, "guide": guide_tab}
     if templates is not None:
         info["template_energy"], info["template_rmsd"] = np.concatenate(tpl_energies), np.concatenate(tpl_rmsds)
+    if symmetry is not None:
+        info["symmetry_energy"], info["symmetry_contacts"] = np.concatenate(sym_energies), np.concatenate(sym_contacts)
+        info["symmetry_pose"] = np.concatenate(sym_poses)
     return samples, info
 
 
 _run_fd_sample_guided_inpaint_default = _run_fd_sample_guided_inpaint
+
+
+class SymmetricSamples(NamedTuple):
+    """What ``sample_symmetric`` returns: per item the monomer's angles (``[len_i, F]``, data space), and arrays over the
+    items: the docked poses ``[n, 12]``, the symmetry energies clash | contact | radial ``[n, 3]`` and the contacts at those
+    poses, the orders, and ``info`` of the guided run (its own final poses and energies included)."""
+    angles: List[np.ndarray]
+    pose: np.ndarray
+    energy: np.ndarray
+    contacts: np.ndarray
+    order: np.ndarray
+    info: dict
+
+
+def sample_symmetric(model, dset, lengths: Sequence[int], order=3, num_steps: Optional[int] = None, scale: float = 1.0,
+                     clash_weight: float = 1.0, symmetry_params=None, dock_iters: int = 100, eta: float = 1.0, max_norm: float = 1.0,
+                     batch_size: int = 512, seed: Optional[int] = None, feature_key: str = "angles",
+                     device: Optional[int] = None) -> SymmetricSamples:
+    """Subunits of cyclic homo-oligomers: ``guide_inpaint`` with nothing held and no restraints, the intra-chain
+    clash term on (``clash_weight``) and ``symmetry={"order": order, "params": symmetry_params}``, followed by
+    ``structures.dock_cyclic`` (``dock_iters`` rigid-body steps) from the pose the run ends with, on the scan backbone of
+    each sample.  ``structures.cyclic_assembly(backbone, pose, order)`` is the oligomer.  Whether such assemblies are
+    designable, and what their interfaces are worth, is unmeasured: there are no trained weights here.  ``device``: the GPU the
+    backbones are built and docked on (default: the model's, 0 for a model that is not on one)."""
+    from . import nerf, structures
+    if device is None:
+        where = getattr(model, "device", None)
+        device = where.index or 0 if getattr(where, "type", "cpu") == "cuda" else 0
+    n = len(lengths)
+    F = model.n_inputs
+    prm = symmetry_params if symmetry_params is not None else structures.symmetry_params()
+    orders = structures._orders(order, n)
+    known = [np.full((int(l), F), np.nan, dtype=np.float32) for l in lengths]
+    fixed = [np.zeros((int(l), F), dtype=bool) for l in lengths]
+    angles, info = guide_inpaint(model, dset, known, fixed, None, num_steps=num_steps, eta=eta, scale=scale, max_norm=max_norm,
+                                 clash_weight=clash_weight, batch_size=batch_size, seed=seed, feature_key=feature_key,
+                                 symmetry={"order": orders, "params": prm})
+    backbones = nerf.build_backbones(angles, list(dset.feature_names[feature_key]), center_coords=False, device=int(device), method="scan")
+    docked = structures.dock_cyclic(backbones, orders, pose=info["symmetry_pose"], n_iter=int(dock_iters), params=prm, device=int(device))
+    return SymmetricSamples(angles, docked.pose, docked.energy, docked.contacts, orders, info)
 
 
 def scaffold_segments(model, dset, motif_angles: np.ndarray, motif_backbone: np.ndarray, segments: Sequence[Tuple[int, int, int]],

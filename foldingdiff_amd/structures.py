@@ -902,6 +902,154 @@ def relax_to_folder(angle_frames: Sequence[pd.DataFrame], names: Sequence[str], 
     return report
 
 
+# ---------------------------------------------------------------------------------------------------- cyclic oligomers
+def symmetry_params(alpha: float = 0.63, margin: float = 0.15, clash_weight: float = 1.0, contact_weight: float = 0.1,
+                    d_on: float = 8.0, d_off: float = 12.0, radial_weight: float = 0.01, r_max: float = 0.0, lever: float = 10.0,
+                    max_shift: float = 1.0, step0: float = 0.01, grow: float = 1.2, shrink: float = 0.5,
+                    pose_iters: int = 1) -> "_binding.FdSymmetryParams":
+    """``fd_symmetry_params`` (include/fdmi.h).  The defaults are choices, not fits: the clash term is
+    ``relax``' (``alpha``, ``margin``, ``clash_weight``); a CA-CA pair between copies earns up to ``contact_weight``, fully
+    below ``d_on`` and nothing beyond ``d_off`` (Angstrom); ``radial_weight`` with ``r_max = 0`` is a weak pull of the CA
+    centroid towards the axis, so that copies that start apart still meet.  ``lever`` (Angstrom) converts a torque into a turn,
+    ``max_shift`` bounds what one step moves the chain, ``step0`` / ``grow`` / ``shrink`` are ``relax``' step rule, and
+    ``pose_iters`` is how many rigid-body steps a guided visit takes.  Argument errors are left to the library."""
+    p = _binding.FdSymmetryParams()
+    p.clash_alpha, p.clash_margin, p.w_clash, p.w_contact = float(alpha), float(margin), float(clash_weight), float(contact_weight)
+    p.d_on, p.d_off, p.w_radial, p.r_max = float(d_on), float(d_off), float(radial_weight), float(r_max)
+    p.lever, p.max_shift, p.step0, p.grow, p.shrink = float(lever), float(max_shift), float(step0), float(grow), float(shrink)
+    p.pose_iters, p.reserved = int(pose_iters), 0
+    return p
+
+
+def _orders(order, B: int) -> np.ndarray:
+    """One int32 order per chain from a single order or one per chain."""
+    out = np.ascontiguousarray(np.broadcast_to(np.asarray(order, dtype=np.int32), (B,)))
+    if (out < 1).any() or (out > 12).any():
+        raise ValueError(f"order={order!r}: symmetry orders lie in [1, 12]")
+    return out
+
+
+def start_pose(coords, order, radius=None, lengths: Optional[Sequence[int]] = None) -> np.ndarray:
+    """Starting poses float64 ``[B, 12]`` (``Q`` row-major, then ``t``) for ``dock_cyclic`` and ``sample_symmetric``:
+    ``Q = I`` and the chain's CA centroid at ``(radius, 0, 0)``.  ``coords``: one ``[3 len_i, 3]`` array per chain, or None
+    with ``lengths`` when there is no structure yet.  ``radius`` defaults to ``Rg / sin(pi / n)`` with the chain's own CA
+    radius of gyration -- neighbouring copies' centroids are then ``2 Rg`` apart --, or with ``Rg = 2.2 len^0.38`` without
+    coordinates: NeRF's seed CA (``nerf.CA_INIT``, where every uncentred backbone has its first residue) then stands in for
+    the centroid, so the chain's first residue starts at the radius; an order of 1 gets radius 0."""
+    if coords is None:
+        if lengths is None:
+            raise ValueError("start_pose needs coords or lengths")
+        B = len(lengths)
+    else:
+        xs = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in coords]
+        B = len(xs)
+    orders = _orders(order, B)
+    radii = None if radius is None else np.broadcast_to(np.asarray(radius, dtype=np.float64), (B,))
+    pose = np.zeros((B, 12), dtype=np.float64)
+    pose[:, [0, 4, 8]] = 1.0
+    for b in range(B):
+        if coords is None:
+            centre, rg = nerf.CA_INIT, 2.2 * float(lengths[b]) ** 0.38
+        else:
+            ca = xs[b][1::3]
+            centre = ca.mean(axis=0)
+            rg = float(np.sqrt(((ca - centre) ** 2).sum(axis=1).mean()))
+        if radii is not None:
+            r = float(radii[b])
+        else:
+            r = rg / np.sin(np.pi / orders[b]) if orders[b] >= 2 else 0.0
+        pose[b, 9:] = np.array([r, 0.0, 0.0]) - centre
+    return pose
+
+
+def cyclic_assembly(coords, pose, order) -> np.ndarray:
+    """The explicit oligomer of one chain: float64 ``[n, 3 len, 3]``, copy ``k`` being ``R_k (Q p + t)`` with ``R_k`` the
+    rotation by ``2 pi k / n`` about z (copy 0 is the placed chain itself)."""
+    p = np.asarray(coords, dtype=np.float64).reshape(-1, 3)
+    pose = np.asarray(pose, dtype=np.float64).reshape(12)
+    n = int(order)
+    if not 1 <= n <= 12:
+        raise ValueError(f"order={order!r}: symmetry orders lie in [1, 12]")
+    y = p @ pose[:9].reshape(3, 3).T + pose[9:]
+    out = np.empty((n,) + y.shape)
+    for k in range(n):
+        c, s = np.cos(2.0 * np.pi * k / n), np.sin(2.0 * np.pi * k / n)
+        out[k] = y @ np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]).T
+    return out
+
+
+def _symmetry_inputs(coords, order, pose):
+    xs = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in coords]
+    if not xs or any(len(x) % 3 or not len(x) for x in xs):
+        raise ValueError("coords is a list of [3 len, 3] arrays")
+    lens = np.array([len(x) // 3 for x in xs], dtype=np.int32)
+    B, L = len(xs), int(lens.max())
+    xyz = np.zeros((B, 3 * L, 3), dtype=np.float64)
+    for b, x in enumerate(xs):
+        xyz[b, : len(x)] = x
+    poses = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(-1, 12))
+    if len(poses) != B:
+        raise ValueError(f"{len(poses)} poses for {B} chains")
+    return xyz, lens, B, L, _orders(order, B), poses
+
+
+def symmetry_energy(coords, order, pose, params=None, device: int = 0, return_wrench: bool = False, return_gradient: bool = False):
+    """A batch of chains scored against their own C_n copies about z, in one ``fd_symmetry_energy`` call.  ``coords``: one
+    ``[3 len_i, 3]`` array per chain; ``order``: one order for all or one per chain (1: not symmetric, zeros); ``pose``:
+    ``[B, 12]`` as from ``start_pose``; ``params``: ``symmetry_params()``.  Returns ``(energy [B, 3] clash | contact | radial,
+    contacts int32 [B])`` -- per subunit: ``n`` times clash + contact is the inter-chain energy of the explicit oligomer, and
+    ``contacts`` counts ordered (CA, copy, CA) triples closer than ``d_on`` --, then with ``return_wrench`` ``[B, 6]`` (the
+    force ``dE/dt`` and the torque about the origin) and with ``return_gradient`` the list of ``dE/dcoords`` ``[3 len_i, 3]``."""
+    xyz, lens, B, L, orders, poses = _symmetry_inputs(coords, order, pose)
+    prm = symmetry_params() if params is None else params
+    energy, contacts = np.empty((B, 3)), np.empty(B, dtype=np.int32)
+    wrench = np.empty((B, 6)) if return_wrench else None
+    grad = np.empty((B, 3 * L, 3)) if return_gradient else None
+    _binding.check(_binding.load().fd_symmetry_energy(device, ptr(xyz), ptr(lens), B, L, ptr(orders), ptr(poses), C.byref(prm), ptr(energy),
+                                                      ptr(contacts), ptr(wrench), ptr(grad)))
+    result = [energy, contacts]
+    if return_wrench:
+        result.append(wrench)
+    if return_gradient:
+        result.append([grad[b, : 3 * lens[b]].copy() for b in range(B)])
+    return tuple(result)
+
+
+class DockResult(NamedTuple):
+    """What ``dock_cyclic`` returns, arrays over the chains: the poses ``[B, 12]``, the energy terms clash | contact | radial
+    ``[B, 3]`` and the contacts there, the accepted steps, the step sizes to continue from, and with ``return_trace`` the total
+    energy after every iteration (``[n_iter + 1, B]``)."""
+    pose: np.ndarray
+    energy: np.ndarray
+    contacts: np.ndarray
+    accepted: np.ndarray
+    step: np.ndarray
+    trace: Optional[np.ndarray]
+
+
+def dock_cyclic(coords, order, pose=None, n_iter: int = 100, params=None, step=None, device: int = 0,
+                return_trace: bool = False) -> DockResult:
+    """Dock rigid chains into C_n assemblies on the device (``fd_symmetry_dock``): ``n_iter`` steps of a
+    descent with an adaptive step on the pose alone, whose energy never rises; the chains' internal coordinates do not
+    change.  ``pose`` defaults to ``start_pose(coords, order)``; ``step``: the step sizes of an earlier result to continue
+    from.  This is no docking program: backbone-only repulsion, a CA contact reward and a pull to the axis; what the
+    interfaces are worth is unmeasured."""
+    n_iter = int(n_iter)
+    if n_iter < 0:
+        raise ValueError(f"n_iter={n_iter} must be >= 0")
+    if pose is None:
+        pose = start_pose(coords, order)
+    xyz, lens, B, L, orders, poses = _symmetry_inputs(coords, order, pose)
+    prm = symmetry_params() if params is None else params
+    h = np.full(B, float(prm.step0)) if step is None else np.ascontiguousarray(np.asarray(step, dtype=np.float64).reshape(B)).copy()
+    out, energy, contacts = np.empty((B, 12)), np.empty((B, 3)), np.empty(B, dtype=np.int32)
+    accepted = np.zeros(B, dtype=np.int32)
+    trace = np.empty((n_iter + 1, B)) if return_trace else None
+    _binding.check(_binding.load().fd_symmetry_dock(device, ptr(xyz), ptr(lens), B, L, ptr(orders), ptr(poses), C.byref(prm), n_iter, ptr(h),
+                                                    ptr(out), ptr(energy), ptr(contacts), ptr(trace), ptr(accepted)))
+    return DockResult(out, energy, contacts, accepted.astype(np.int64), h, trace)
+
+
 class RmsdScorer:
     """A ``scorer=`` for ``sampling.get_reconstruction_error``: per item (RMSD of NeRF(reconstruction) to NeRF(truth),
     RMSD of NeRF(reconstruction) to the backbone of the item's PDB file), in Angstrom after optimal superposition --

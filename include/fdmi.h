@@ -62,6 +62,8 @@ extern "C" {
 /*    fd_nerf_scan, fd_relax_energy and fd_relax (relaxing backbones in torsion space) and the struct fd_relax_params are additive
  *    too */
 /*    fd_nerf_vjp_feats (the derivative of NeRF with the signs of the features the forward read) is additive too */
+/*    fd_symmetry_energy, fd_symmetry_dock, fd_scaffold_guide_step_sym and fd_sample_guided_inpaint_sym (cyclic oligomers: a chain
+ *    scored against its own symmetry copies) and the struct fd_symmetry_params are additive too */
 #define FDMI_ABI_VERSION 7
 
 enum {
@@ -936,6 +938,135 @@ int fd_sample_guided_inpaint_tpl(fd_model* m, const float* x_init, const int32_t
                                  const int32_t* rst_i, const int32_t* rst_j, const double* rst_d0, const double* rst_tol,
                                  const double* rst_w, const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz,
                                  const double* tpl_w, float* out, double* energy_out, double* max_violation_out, double* tpl_rmsd_out);
+
+/* ---- cyclic oligomers: a chain scored against its own C_n copies, and a rigid pose carried relative to the axis.
+ * Backbone-only repulsion and a CA contact reward are no force field; whether such assemblies are designable, and what their
+ * interfaces are worth, is unmeasured.
+ *
+ * The symmetry statement, per chain b.  n = order[b]; n == 1: the chain is not symmetric and every output is 0.  The pose
+ * (Q, t) is 12 doubles, Q row-major then t (fd_template_energy's transform_out layout); p_a are the fp64 coordinates of the atoms
+ * a < 3 lens[b], 3 i + {0 N, 1 CA, 2 C}:
+ *     y_a      = Q p_a + t                       the chain in the assembly frame; the axis is z through 0
+ *     R_k      = the rotation by 2 pi k / n about z, k = 1 .. n - 1 (cos and sin evaluated in fp64 on the host)
+ *     d(a,k,b) = |y_a - R_k y_b|                 ALL ordered atom pairs, a == b included, no |a - b| >= 2 exclusion: other chains
+ *     clash:   t_ab = clash_alpha (r_a + r_b) + clash_margin, r = 1.55 for N, 1.7 for CA and C (fd_relax_energy's numbers);
+ *              v = max(0, t_ab - d);  phi = w_clash v^2
+ *     contact: CA-CA pairs only;  u = clamp((d_off - d) / (d_off - d_on), 0, 1);  s = u^2 (3 - 2 u);  phi = -w_contact s
+ *     E_clash  = 1/2 sum_{k,a,b} phi_clash;   E_contact = 1/2 sum_{k,a,b} phi_contact
+ *              (per subunit: n (E_clash + E_contact) is the inter-chain energy of the explicit n-mer)
+ *     g_a      = sum_{k=1}^{n-1} sum_b phi'(d) (y_a - R_k y_b) / d,  terms with d == 0 dropped.  The 1/2 is gone: the triple
+ *              (b, n - k, a) has the same distance and gives y_a the same term.  One lane per atom owns g_a, k ascending and
+ *              the partners in index order within k; no atomics.
+ *     radial:  c = the mean of the CA y;  rho = sqrt(c_x^2 + c_y^2);  e = max(0, rho - r_max);  E_radial = w_radial e^2;
+ *              every CA's g gains 2 w_radial e (c_x, c_y, 0) / (rho lens[b]), nothing where rho == 0
+ *     contacts = the number of ordered triples (a CA, k, b CA) with d < d_on, an exact int32
+ *     F = sum_a g_a;   tau = sum_a y_a x g_a     (dE/dt, and dE/d(a rotation about the origin applied on the left))
+ *     dcoords_a = Q^T g_a
+ * F_z and tau_z vanish up to rounding: the energy does not change when the pose turns about z or shifts along it.  Every sum is in
+ * an order fixed by (length, order, lane); two calls give the same bits, and a chain's bits do not depend on the batch it is in.
+ *
+ * fd_symmetry_energy: the statement on host arrays, model-free and synchronous like fd_template_energy.
+ *   coords        float64 [B][3L][3] (host), finite on the atoms below 3 lens[b]; lens int32[B] in [1, min(L, 2048)]
+ *   order         int32[B], each in [1, 12];  pose double[B][12], every entry finite (Q is taken as given: not re-orthogonalised)
+ *   params        clash_alpha, clash_margin, w_clash, w_contact, w_radial, r_max finite and >= 0; 0 <= d_on < d_off, both finite;
+ *                 lever, max_shift, step0 > 0 and finite; grow >= 1; shrink in (0, 1); pose_iters >= 0 (read by
+ *                 fd_scaffold_guide_step_sym only)
+ *   energy_out    double[B][3] clash | contact | radial;  contacts_out int32[B]
+ *   wrench_out    double[B][6] F then tau, or NULL
+ *   dcoords_out   float64 [B][3L][3], or NULL: written everywhere, 0 where order[b] == 1 and at or beyond 3 lens[b]
+ * A bad call: FD_E_INVALID before any device call, the offending word in fd_last_error(), outputs untouched. */
+typedef struct fd_symmetry_params {
+  double clash_alpha, clash_margin, w_clash, w_contact, d_on, d_off, w_radial, r_max;
+  double lever, max_shift, step0, grow, shrink;
+  int32_t pose_iters, reserved;
+} fd_symmetry_params;
+int fd_symmetry_energy(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* order, const double* pose,
+                       const fd_symmetry_params* params, double* energy_out, int32_t* contacts_out, double* wrench_out,
+                       double* dcoords_out);
+
+/* fd_symmetry_dock: the docking descent, rigid body only -- fd_relax's scheme on the pose, per chain, chains independent, with
+ * E = E_clash + E_contact + E_radial and (E, F, tau) the statement's:
+ *     h = step_io ? step_io[b] : step0;   (E, F, tau) of the pose;   trace[0] = E
+ *     for it = 1 .. n_iter:
+ *         w = -h tau / lever^2;   dt = -h F;   m = max(|dt|, lever |w|);   k = m > max_shift ? max_shift / m : 1
+ *         Q' = Rot(k w) Q;   t' = Rot(k w) t + k dt        Rodrigues' formula in fp64; F == tau == 0 keeps the pose's bits
+ *         (E', F', tau') of the trial
+ *         if E' <= E (false for NaN):  the trial becomes the pose, h *= grow, accepted += 1;   else h *= shrink
+ *         trace[it] = E
+ *     pose_out = the pose;  energy_out, contacts_out = the statement's at it;  step_io[b] = h
+ * A chain of order 1 has nothing to descend: its pose, its h and accepted = 0 are returned as given.
+ * Nothing is asked of the host between the upload and the download; two launches per evaluation (the energy, then a
+ * one-lane-per-chain pose step).  fd_symmetry_dock(n_iter = N) equals N calls with n_iter = 1 chained through pose_out and
+ * step_io, bit for bit, and energy_out equals fd_symmetry_energy(pose_out) bit for bit.
+ *   n_iter        >= 0; 0 returns the input pose and its energy
+ *   step_io       double[B], each finite and > 0, or NULL
+ *   pose_out      double[B][12];  energy_out double[B][3];  contacts_out int32[B]
+ *   trace_out     double[n_iter + 1][B] or NULL;  accepted_out int32[B]
+ * Everything fd_symmetry_energy rejects, n_iter < 0, a step_io entry that is not finite and > 0, a NULL output other than
+ * trace_out: FD_E_INVALID before any device call, outputs untouched. */
+int fd_symmetry_dock(int device_id, const double* coords, const int32_t* lens, int B, int L, const int32_t* order, const double* pose,
+                     const fd_symmetry_params* params, int n_iter, double* step_io, double* pose_out, double* energy_out,
+                     int32_t* contacts_out, double* trace_out, int32_t* accepted_out);
+
+/* fd_scaffold_guide_step_sym: fd_scaffold_guide_step_tpl whose statement gains, after the template line, for the chains with
+ * sym_order[b] >= 2:
+ *     sym_placed_in given:  (Q, t) = the proper rigid fit of coords onto sym_placed_in[b], all atoms below 3 lens[b], unit weights:
+ *                           with (R, t_fit) = the template statement's transform for the targets sym_placed_in, Q = R^T, t = -R^T t_fit
+ *     sym_placed_in NULL:   (Q, t) = sym_pose_in[b]                                   (the first visit of a run)
+ *     pose_iters iterations of the docking descent from (Q, t), h carried in sym_step_io[b] (NULL: step0, not written back;
+ *         the entry of a chain of order 1 keeps its value)
+ *     E_clash_sym, E_contact, E_radial, contacts at the final pose;   gc += Q^T g
+ *     sym_pose_out[b] = (Q, t);   sym_placed_out[b] = Q coords + t
+ * The fit re-anchors the pose each visit: NeRF hangs the chain on residue 0, so a torsion change near the N-terminus swings the
+ * whole chain in NeRF's frame, and fitting onto where the last visit placed it removes that.  The angle gradient and the pose
+ * gradient are exact partial derivatives of one energy (block coordinate descent); no term is differentiated through the fit.
+ * Launches: the fit and its turn into a pose (with sym_placed_in), two per evaluation of the descent (1 + pose_iters
+ * evaluations), one evaluation at the final pose that writes the gradient, one placement.
+ *   tpl_*             as in fd_scaffold_guide_step_tpl, all four may be NULL
+ *   sym_order         int32[B] in [1, 12], or NULL.  NULL or all 1: none of these launches run and every output
+ *                     fd_scaffold_guide_step_tpl shares equals that entry's bit for bit; with all 1 the energies and contacts are
+ *                     0, sym_pose_out = sym_pose_in and sym_placed_out is not written; with NULL no sym_* argument is looked at
+ *   sym_pose_in       double[B][12], finite;  sym_placed_in double[B][3L][3] finite on the atoms below 3 lens[b], or NULL
+ *   sym_params        as in fd_symmetry_energy;  sym_step_io double[B] finite and > 0, or NULL
+ *   sym_energy_out    double[B][3] clash | contact | radial;  sym_contacts_out int32[B];  sym_pose_out double[B][12]
+ *   sym_placed_out    double[B][3L][3]: the atoms below 3 lens[b]; the others keep what they held.  A chain with order 1 among
+ *                     symmetric ones is placed by its sym_pose_in and scores 0
+ * Everything fd_scaffold_guide_step_tpl and fd_symmetry_energy reject, with sym_order given a NULL sym_pose_in, sym_params or
+ * sym_*_out: FD_E_INVALID before any device call, outputs untouched. */
+int fd_scaffold_guide_step_sym(int device_id, const float* x, const float* x0, const float* known, const uint8_t* fixed,
+                               const int32_t* lens, int B, int L, int F, const uint8_t* is_angle,
+                               const fd_scaffold_guide_params* params, const int32_t* rst_offsets, const int32_t* rst_i,
+                               const int32_t* rst_j, const double* rst_d0, const double* rst_tol, const double* rst_w,
+                               const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz, const double* tpl_w,
+                               const int32_t* sym_order, const double* sym_pose_in, const double* sym_placed_in,
+                               const fd_symmetry_params* sym_params, double* sym_step_io, float c, float s, const float* z, uint64_t seed,
+                               int t, int64_t seq_offset, float* x_out, double* energy_out, double* max_violation_out, double* gnorm_out,
+                               double* dfeats_out, double* tpl_rmsd_out, double* sym_energy_out, int32_t* sym_contacts_out,
+                               double* sym_pose_out, double* sym_placed_out);
+
+/* fd_sample_guided_inpaint_sym: fd_sample_guided_inpaint_tpl whose visits are followed by fd_scaffold_guide_step_sym's statement.
+ * The first visit takes sym_pose0 as the pose (no fit); every later visit, and the statement on the final state behind the last
+ * one, fits onto the placed atoms the statement before it left.  h starts at step0 and is carried; the pose, h and the placed atoms
+ * live on the device for the whole run.  The plain sampler's captured step graph is replayed, never captured again; only launches
+ * happen between the upload and the download.
+ *   tpl_*             as in fd_scaffold_guide_step_sym (all four may be NULL)
+ *   sym_order, sym_params   as in fd_scaffold_guide_step_sym;  sym_pose0 double[B][12], finite
+ *                     sym_order NULL or all 1: out, energy_out, max_violation_out and tpl_rmsd_out are fd_sample_guided_inpaint_tpl's
+ *                     bit for bit (all 1: the symmetry energies and contacts are 0 and sym_pose_out = sym_pose0)
+ *   sym_energy_out    double[B][3] clash | contact | radial, sym_contacts_out int32[B], sym_pose_out double[B][12]: the statement
+ *                     with p = the FINAL state (its fit and its pose_iters steps included)
+ * Everything fd_sample_guided_inpaint_tpl and fd_symmetry_energy reject, with sym_order given a NULL sym_pose0, sym_params or
+ * sym_*_out: FD_E_INVALID before any device call, outputs untouched.  Single device; not offered with jumps, the second-order
+ * solver, steering or ties. */
+int fd_sample_guided_inpaint_sym(fd_model* m, const float* x_init, const int32_t* lens, int B, int L, const int32_t* visits,
+                                 int n_visits, const float* coef, const float* noise, const float* known, const uint8_t* fixed,
+                                 const float* known_coef, const float* known_noise, uint64_t seed, int64_t seq_offset,
+                                 const float* guide, const fd_scaffold_guide_params* params, const int32_t* rst_offsets,
+                                 const int32_t* rst_i, const int32_t* rst_j, const double* rst_d0, const double* rst_tol,
+                                 const double* rst_w, const int32_t* tpl_offsets, const int32_t* tpl_atom, const double* tpl_xyz,
+                                 const double* tpl_w, const int32_t* sym_order, const double* sym_pose0,
+                                 const fd_symmetry_params* sym_params, float* out, double* energy_out, double* max_violation_out,
+                                 double* tpl_rmsd_out, double* sym_energy_out, int32_t* sym_contacts_out, double* sym_pose_out);
 
 /* ---- multi-GPU through the ABI: independent sequences are sharded across the GPUs of a node by the HOST (one
  * model per GPU, each sampling its slice with seq_offset = its first global sequence index; Philox noise is keyed by that
